@@ -283,3 +283,37 @@ def test_slab_graph_replay_matches_launches(rv):
     t3, s3 = bc.beam_search_prediction(host[0], W, L)
     assert (t2.numpy() == t3.numpy()).all() and np.array_equal(s2.numpy(), s3.numpy()) and not np.array_equal(s2.numpy(), ref[0][1])
     bc.close()
+
+
+def test_bench_plain_run_dumps_last_timed_step(rv, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (the plain run): one result line holding the headline fields
+    and nothing from the --full passes, K timed steps, and DIR/tokens.npy, DIR/scores.npy == a synchronous call on the bench's
+    seeded slab with its weights and recurrence form, bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], cwd=root, stdout=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0
+    lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["unit"] == "kbases/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 3
+    assert out["value"] > 0 and abs(out["value"] - 256 * 6 / out["ms_per_step"]) <= 1e-3 * out["value"]
+    assert not {"roofline", "verified", "steady_state", "synchronous", "read_level", "cpu_baseline"} & set(out)
+    tok, sc = np.load(tmp_path / "tokens.npy"), np.load(tmp_path / "scores.npy")
+    assert tok.dtype == np.float32 and sc.dtype == np.float32 and tok.shape == sc.shape and tok.shape[0] == 256
+    B, T_r, T_e, W, L = 256, 300, 30, 5, 48
+    bc = rv.Basecaller(128, 128, 128, rv.data_loader.nuc_tk, "joint", rv.data_loader.INPUT_PADDING,
+                       encoder_depth=2, decoder_depth=1, rnn_type="bilstm", attention_type="luong",
+                       beam_width=W, max_batch=B, max_raw_len=T_r, max_event_len=T_e, max_output_len=L)
+    bc.init_random_weights(seed=22)
+    bc.set_option("wide_recurrence", 1)
+    raw, ev, _ = rv.synthetic.make_slab(B, T_r, T_e, seed=0)
+    t, s = bc.beam_search_prediction((torch.from_numpy(raw).cuda(), torch.from_numpy(ev).cuda()), W, L)
+    assert tok.shape == tuple(t.shape)
+    assert np.array_equal(tok, t.cpu().numpy().astype(np.float32)) and np.array_equal(sc, s.cpu().numpy())
+    bc.close()
