@@ -141,8 +141,8 @@ __global__ __launch_bounds__(512) void k_dec_cell(DecState d, int layer, const f
       const float zf = zs[(1 * CELL_ROWS + row) * 17 + eun] + ew[p][1] + eb[1];
       const float zg = zs[(2 * CELL_ROWS + row) * 17 + eun] + ew[p][2] + eb[2];
       const float zo = zs[(3 * CELL_ROWS + row) * 17 + eun] + ew[p][3] + eb[3];
-      const float c2 = fmaf(rv_sigmoid(zf), ec[p], rv_sigmoid(zi) * rv_tanh(zg));
-      const float hh = rv_sigmoid(zo) * rv_tanh(c2);
+      const float c2 = fmaf(rv_sigmoid(zf), ec[p], rv_sigmoid(zi) * rv_tanh_abs(zg));
+      const float hh = rv_sigmoid(zo) * rv_tanh_abs(c2);
       cn_l[(size_t)en[p] * RV_U + ecol] = c2;
       hn_l[(size_t)en[p] * RV_U + ecol] = hh;
       if (xh_up) xh_up[(size_t)en[p] * RV_E + ecol] = hh;
@@ -1212,8 +1212,8 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         for (int it = 0; it < NITEM; ++it) {
           if (!ok[it]) continue;
           const int idx = tid + it * NT, w = idx >> 7, u = idx & 127;
-          const float c2 = fmaf(rv_sigmoid(z4[it][1]), cp[it], rv_sigmoid(z4[it][0]) * rv_tanh(z4[it][2]));
-          const float hh = rv_sigmoid(z4[it][3]) * rv_tanh(c2);
+          const float c2 = fmaf(rv_sigmoid(z4[it][1]), cp[it], rv_sigmoid(z4[it][0]) * rv_tanh_abs(z4[it][2]));
+          const float hh = rv_sigmoid(z4[it][3]) * rv_tanh_abs(c2);
           cst[(cb ^ 1) * W * RV_U + idx] = c2;
           {   // h as A fragments: h 2^14 in two f16 parts, k = 128 + u (top cell), 256 + u (cell 0 of two)
             const float sv = hh * 16384.f;
@@ -1274,8 +1274,8 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         z4[g] = (((part[(0 * W + pb) * RV_G + col] + part[(1 * W + pb) * RV_G + col]) + part[(2 * W + pb) * RV_G + col]) +
                    part[(3 * W + pb) * RV_G + col]) + zb[s_tok[w] * RV_G + col];
       }
-      const float c2 = fmaf(rv_sigmoid(z4[1]), cS[cb * W * RV_U + pb * RV_U + u], rv_sigmoid(z4[0]) * rv_tanh(z4[2]));
-      const float hh = rv_sigmoid(z4[3]) * rv_tanh(c2);
+      const float c2 = fmaf(rv_sigmoid(z4[1]), cS[cb * W * RV_U + pb * RV_U + u], rv_sigmoid(z4[0]) * rv_tanh_abs(z4[2]));
+      const float hh = rv_sigmoid(z4[3]) * rv_tanh_abs(c2);
       cS[(cb ^ 1) * W * RV_U + idx] = c2;
       if (D > 1) h0T[u * WB + w] = hh; else { hcT[u * WB + w] = hh; qp[idx] = hh * LOG2E; }
       if constexpr (MXS) {     // the score query as MFMA A fragments: [k-block u / 8][row mx_row(w) (+ 1: low part)][u % 8] f16 of h log2(e) 2^14
@@ -1330,8 +1330,8 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
           const float zrec = (partU[(0 * W + pb) * RV_G + col] + partU[(1 * W + pb) * RV_G + col]) + partU[(2 * W + pb) * RV_G + col];
           z4[g] = (zin + zrec) + b1s[col];
         }
-        const float c2 = fmaf(rv_sigmoid(z4[1]), cS1[cb * W * RV_U + pb * RV_U + u], rv_sigmoid(z4[0]) * rv_tanh(z4[2]));
-        const float hh = rv_sigmoid(z4[3]) * rv_tanh(c2);
+        const float c2 = fmaf(rv_sigmoid(z4[1]), cS1[cb * W * RV_U + pb * RV_U + u], rv_sigmoid(z4[0]) * rv_tanh_abs(z4[2]));
+        const float hh = rv_sigmoid(z4[3]) * rv_tanh_abs(c2);
         cS1[(cb ^ 1) * W * RV_U + idx] = c2; hcT[u * WB + w] = hh; qp[idx] = hh * LOG2E;
       }
       __syncthreads();

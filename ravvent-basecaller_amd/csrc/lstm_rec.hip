@@ -144,8 +144,7 @@ __global__ __launch_bounds__(512) void k_lstm_rec(RecArgs a) {
     // All rows sit in one basic block so their dependent chains interleave.
 #pragma unroll
     for (int r = 0; r < BT; ++r) {
-      const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-am * z[r]));
-      const float act = fmaf(sg, am, 1.0f - am);
+      const float act = am == 2.f ? rv_tanh(z[r]) : rv_sigmoid(z[r]);
       const float ig = quad_perm<0x00>(act), fg = quad_perm<0x55>(act);
       const float gg = quad_perm<0xAA>(act), og = quad_perm<0xFF>(act);
       c[r] = fmaf(fg, c[r], ig * gg);
@@ -663,8 +662,7 @@ __global__ __launch_bounds__(768) void k_lstm_rec_proj(RecArgs a) {
     }
 #pragma unroll
     for (int r = 0; r < BT; ++r) {
-      const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-am * z[r]));
-      const float act = fmaf(sg, am, 1.0f - am);
+      const float act = am == 2.f ? rv_tanh(z[r]) : rv_sigmoid(z[r]);
       const float ig = quad_perm<0x00>(act), fg = quad_perm<0x55>(act);
       const float gg = quad_perm<0xAA>(act), og = quad_perm<0xFF>(act);
       c[r] = fmaf(fg, c[r], ig * gg);
