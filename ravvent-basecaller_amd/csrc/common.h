@@ -131,6 +131,8 @@ struct DecState {
   float* step_scores;     // [L-1,B,W]
   float* step_logits;     // [L-1,B,W,V]   (greedy or debug) or nullptr
   float* step_align;      // [L-1,B,W,Tm]  (debug) or nullptr
+  float* persist_align;   // [L-1,B,W,Tm]  alignments of the persistent decode (option persist_taps) or nullptr; unlike step_align
+                          // it keeps the persistent decode, whose matrix-pipe forms record the f16 image the context product consumes
   int* nfin;              // [L] chunks-finished counter per step
   // optional fused post-processing of the best beam (basecaller.py:289-294 + utils.py:123-128)
   uint8_t* call_bases;    // [B,L-1] compacted base letters of tokens_to_nuc_sequences (or nullptr)
@@ -216,9 +218,9 @@ __device__ __forceinline__ float rv_tanh(float x) {
   const float small = fmaf(p * a2, a, a);
   return copysignf(a < 0.25f ? small : (a >= 9.0f ? 1.0f : big), x);
 }
-// 2 sigmoid(2x) - 1 (absolute error ~1e-7), kept for the decoder's cells only: rv_tanh in its place raises the scratch of the
-// persistent decode with the Luong scores on the matrix pipe (k_dec_persist<5,11,1,2>) from 20 to 36 B per lane, over that kernel's
-// bound in tests/test_build.py, for every relatively accurate form tried
+// 2 sigmoid(2x) - 1 (absolute error ~1e-7), kept for one site only: the g gate of the decode form with the Luong attention on the
+// matrix pipe and the cell product on packed FMAs (decode.hip, dec_gate_tanh), where rv_tanh pushes k_dec_persist<5,11,1,2> over its
+// scratch bound in tests/test_build.py
 __device__ __forceinline__ float rv_tanh_abs(float x) {
   return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)), -1.0f);
 }

@@ -141,8 +141,8 @@ __global__ __launch_bounds__(512) void k_dec_cell(DecState d, int layer, const f
       const float zf = zs[(1 * CELL_ROWS + row) * 17 + eun] + ew[p][1] + eb[1];
       const float zg = zs[(2 * CELL_ROWS + row) * 17 + eun] + ew[p][2] + eb[2];
       const float zo = zs[(3 * CELL_ROWS + row) * 17 + eun] + ew[p][3] + eb[3];
-      const float c2 = fmaf(rv_sigmoid(zf), ec[p], rv_sigmoid(zi) * rv_tanh_abs(zg));
-      const float hh = rv_sigmoid(zo) * rv_tanh_abs(c2);
+      const float c2 = fmaf(rv_sigmoid(zf), ec[p], rv_sigmoid(zi) * rv_tanh(zg));
+      const float hh = rv_sigmoid(zo) * rv_tanh(c2);
       cn_l[(size_t)en[p] * RV_U + ecol] = c2;
       hn_l[(size_t)en[p] * RV_U + ecol] = hh;
       if (xh_up) xh_up[(size_t)en[p] * RV_E + ecol] = hh;
@@ -953,6 +953,45 @@ struct PersistLds {
   }
 };
 
+// The decoder cells' tanh is rv_tanh, relatively accurate (a large recurrent gain multiplies an absolute error step after step).  One
+// exception: the g gate of the non-default form with the Luong scores and context on the matrix pipe and the cell product on packed
+// FMAs (ATT 2) keeps 2 sigmoid(2x) - 1 -- rv_tanh at both of that form's sites raises the scratch of k_dec_persist<5,11,1,2> from 20 to
+// 36 B per lane, over its bound in tests/test_build.py; at either one alone it stays at 20.  The cell-state site is the one that
+// holds an adversarial recurrent kernel closer to fp64, and that form is held to 1e-4 only (tests/test_bench_config_gpu.py, DESIGN.md
+// section 5)
+template <int ATT>
+__device__ __forceinline__ float dec_gate_tanh(float x) {
+  if constexpr (ATT == 2) return rv_tanh_abs(x);
+  else return rv_tanh(x);
+}
+
+// Tap (option persist_taps) of a matrix-pipe form's alignments: what the context product consumes, (hi + lo) 2^-14 read back from its
+// A image [k-block t / 8][row mx_row(beam) (+ 1: low part)][t % 8] in `part` (after the barrier that completes the image; a loop of its
+// own, away from the resident fragments' registers).  d.persist_align [L-1][B][W][T_m], steps t < T_m only.
+// The loop's shape is picked per form by what keeps each kernel within its scratch bound (tests/test_build.py): one flat loop over
+// (beam, step) for Bahdanau (ATT 4), a rolled loop over the beams for the Luong forms (ATT 2, 3)
+template <int W, bool FLAT>
+__device__ __forceinline__ void tap_align_image(const DecState& d, const float* part, int b, int step, int tid) {
+  const _Float16* aa = reinterpret_cast<const _Float16*>(part);
+  float* out = d.persist_align + ((size_t)step * d.B + b) * W * d.Tm;
+  int t0 = tid;
+  asm volatile("" : "+v"(t0));     // nothing of this loop is hoisted out of the step loop (no registers held while taps are off)
+  if constexpr (FLAT) {
+    for (int i = t0; i < W * d.Tm; i += 512) {
+      const int w = i / d.Tm, t = i - w * d.Tm;
+      const _Float16* q = aa + ((t >> 3) * 16 + mx_row(w)) * 8 + (t & 7);
+      out[i] = ((float)q[0] + (float)q[8]) * (1.0f / 16384.f);
+    }
+  } else {
+#pragma unroll 1
+    for (int w = 0; w < W; ++w)
+      for (int t = t0; t < d.Tm; t += 512) {
+        const _Float16* q = aa + ((t >> 3) * 16 + mx_row(w)) * 8 + (t & 7);
+        out[(unsigned)(w * d.Tm + t)] = ((float)q[0] + (float)q[8]) * (1.0f / 16384.f);
+      }
+  }
+}
+
 template <int W, int NIT, int D, int ATT = 0>
 __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __restrict__ Wcat /*[256,512] = [W_in rows of the attention input ; U]*/,
                                                       const float* __restrict__ Wtok /*[V,512]*/, const float* __restrict__ bdec /*[512]*/,
@@ -1212,8 +1251,8 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         for (int it = 0; it < NITEM; ++it) {
           if (!ok[it]) continue;
           const int idx = tid + it * NT, w = idx >> 7, u = idx & 127;
-          const float c2 = fmaf(rv_sigmoid(z4[it][1]), cp[it], rv_sigmoid(z4[it][0]) * rv_tanh_abs(z4[it][2]));
-          const float hh = rv_sigmoid(z4[it][3]) * rv_tanh_abs(c2);
+          const float c2 = fmaf(rv_sigmoid(z4[it][1]), cp[it], rv_sigmoid(z4[it][0]) * rv_tanh(z4[it][2]));
+          const float hh = rv_sigmoid(z4[it][3]) * rv_tanh(c2);
           cst[(cb ^ 1) * W * RV_U + idx] = c2;
           {   // h as A fragments: h 2^14 in two f16 parts, k = 128 + u (top cell), 256 + u (cell 0 of two)
             const float sv = hh * 16384.f;
@@ -1274,8 +1313,8 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         z4[g] = (((part[(0 * W + pb) * RV_G + col] + part[(1 * W + pb) * RV_G + col]) + part[(2 * W + pb) * RV_G + col]) +
                    part[(3 * W + pb) * RV_G + col]) + zb[s_tok[w] * RV_G + col];
       }
-      const float c2 = fmaf(rv_sigmoid(z4[1]), cS[cb * W * RV_U + pb * RV_U + u], rv_sigmoid(z4[0]) * rv_tanh_abs(z4[2]));
-      const float hh = rv_sigmoid(z4[3]) * rv_tanh_abs(c2);
+      const float c2 = fmaf(rv_sigmoid(z4[1]), cS[cb * W * RV_U + pb * RV_U + u], rv_sigmoid(z4[0]) * dec_gate_tanh<ATT>(z4[2]));
+      const float hh = rv_sigmoid(z4[3]) * rv_tanh(c2);
       cS[(cb ^ 1) * W * RV_U + idx] = c2;
       if (D > 1) h0T[u * WB + w] = hh; else { hcT[u * WB + w] = hh; qp[idx] = hh * LOG2E; }
       if constexpr (MXS) {     // the score query as MFMA A fragments: [k-block u / 8][row mx_row(w) (+ 1: low part)][u % 8] f16 of h log2(e) 2^14
@@ -1330,8 +1369,8 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
           const float zrec = (partU[(0 * W + pb) * RV_G + col] + partU[(1 * W + pb) * RV_G + col]) + partU[(2 * W + pb) * RV_G + col];
           z4[g] = (zin + zrec) + b1s[col];
         }
-        const float c2 = fmaf(rv_sigmoid(z4[1]), cS1[cb * W * RV_U + pb * RV_U + u], rv_sigmoid(z4[0]) * rv_tanh_abs(z4[2]));
-        const float hh = rv_sigmoid(z4[3]) * rv_tanh_abs(c2);
+        const float c2 = fmaf(rv_sigmoid(z4[1]), cS1[cb * W * RV_U + pb * RV_U + u], rv_sigmoid(z4[0]) * rv_tanh(z4[2]));
+        const float hh = rv_sigmoid(z4[3]) * rv_tanh(c2);
         cS1[(cb ^ 1) * W * RV_U + idx] = c2; hcT[u * WB + w] = hh; qp[idx] = hh * LOG2E;
       }
       __syncthreads();
@@ -1506,6 +1545,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         }
       }
       __syncthreads();
+      if (d.persist_align) tap_align_image<W, false>(d, part, b, step, tid);
       RV_STAMP(d, step, 5);
     } else {
     // ================= scores from the resident key rows: lane w keeps beam w's score of the even row of a pair, lane 8 + w
@@ -1612,6 +1652,18 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
       const float nanv = (s8 < W && mg[WB + s8] != mg[WB + s8]) ? mg[WB + s8] : 0.f;
 #pragma unroll
       for (int p = 0; p < NP; ++p) sc[p] = m == -INFINITY ? nanv : sc[p] * f;   // alignments of beam s8 on this half's rows
+      if constexpr (!MX) {
+        if (d.persist_align && s8 < W) {     // tap (option persist_taps): the fp32 alignments the context sum below consumes
+          int t0 = sid, w0 = s8;
+          asm volatile("" : "+v"(t0), "+v"(w0));   // nothing of the tap is hoisted out of the step loop (no registers held while taps are off)
+          float* out = d.persist_align + ((size_t)step * d.B + b) * W * Tm;   // (uniform base, 32-bit lane offset)
+#pragma unroll
+          for (int p = 0; p < NP; ++p) {
+            const int it = 2 * p + half, t = t0 + 32 * it;
+            if (it < NIT && t < Tm) out[(unsigned)(w0 * Tm + t)] = sc[p];
+          }
+        }
+      }
     }
     RV_STAMP(d, step, 5);
     if constexpr (MX) {
@@ -1632,6 +1684,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         }
       }
       __syncthreads();
+      if (d.persist_align) tap_align_image<W, true>(d, part, b, step, tid);
     } else {
     // ================= attention-layer context part = sum_t alpha_t * U'_t, one beam at a time (8-register accumulator)
     {

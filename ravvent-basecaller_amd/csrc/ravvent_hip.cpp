@@ -112,6 +112,7 @@ struct RvContext {
   // decoder buffers
   DecState dec_st{};
   float* step_align = nullptr; size_t step_align_cap = 0;
+  float* palign = nullptr; size_t palign_cap = 0;   // persist_taps: alignments of the persistent decode
   int32_t* out_tokens = nullptr;
   float* out2 = nullptr;
   // pinned host staging for the host-buffer entry points (pageable hipMemcpy is synchronous and slow)
@@ -638,6 +639,21 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     d.step_align = nullptr;
     if (!greedy && !h->opt_ptaps) d.step_logits = nullptr;
   }
+  d.persist_align = nullptr;
+  if (h->opt_ptaps) {
+    const size_t need = (size_t)steps * N * Tm;
+    if (need > h->palign_cap) {
+      if (h->palign) hipFree(h->palign);
+      h->palign = nullptr; h->palign_cap = 0;
+      for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // captured args hold the old pointer
+      h->graphs.clear();
+      HIPCHK(h, hipMalloc((void**)&h->palign, need * sizeof(float)));
+      h->palign_cap = need;
+    }
+    // NaN everywhere first: a step the kernel does not record is never read as a stale value of an earlier call
+    if (need) HIPCHK(h, hipMemsetAsync(h->palign, 0xff, need * sizeof(float), s));
+    d.persist_align = h->palign;
+  }
 
   // The slab decodes as `nsplit` independent sub-slabs on concurrent streams (inside one hipGraph):
   // while one sub-slab is in its HBM-bound attention sweep another runs its latency-bound cell /
@@ -679,6 +695,7 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     p.step_ids += (size_t)steps * Wd * b0; p.parent_ids += (size_t)steps * Wd * b0; p.step_scores += (size_t)steps * Wd * b0;
     if (p.step_logits) p.step_logits += (size_t)steps * Wd * V * b0;
     if (p.step_align) p.step_align += (size_t)steps * Wd * Tm * b0;
+    if (p.persist_align) p.persist_align += (size_t)steps * Wd * Tm * b0;
     p.nfin = d.nfin + g * (c.max_output_len + 1);
     parts.nfin[g] = p.nfin; parts.B[g] = p.B;
     if (!h->lpersist) launch_dec_init(p, s);
@@ -714,7 +731,7 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     launch_dec_persist(d, d.depth > 1 ? h->dec[0].W + (size_t)V * RV_G : h->d_Wcat2, h->dec[0].W, h->dec[0].b,
                        d.depth > 1 ? h->dec[1].W : nullptr, d.depth > 1 ? h->dec[1].b : nullptr, h->d_Nh, s);
   } else if (h->opt_graph && h->opt_profile != 2) {
-    GraphKey key{B, d.W, Tm, L, greedy ? 1 : 0, h->opt_taps * 2 + h->lflash + 4 * h->opt_att_nt + 4096 * (d.step_logits ? 1 : 0), nsplit};   // every captured pointer that can change is in the key
+    GraphKey key{B, d.W, Tm, L, greedy ? 1 : 0, h->opt_taps * 2 + h->lflash + 4 * h->opt_att_nt + 4096 * (d.step_logits ? 1 : 0) + 8192 * (d.persist_align ? 1 : 0), nsplit};   // every captured pointer that can change is in the key
     auto it = h->graphs.find(key);
     if (it == h->graphs.end()) {
       if (h->graphs.size() >= 32) {      // bound the cache (callers with ever-changing slab shapes)
@@ -1031,6 +1048,7 @@ void rv_destroy(rv_handle h) {
   for (int g = 0; g < 3; ++g) { if (h->side[g]) hipStreamDestroy(h->side[g]); if (h->ev_join[g]) hipEventDestroy(h->ev_join[g]); }
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
   if (h->step_align) hipFree(h->step_align);
+  if (h->palign) hipFree(h->palign);
   for (void* p : {(void*)h->pin_raw, (void*)h->pin_ev, (void*)h->pin_tok, (void*)h->pin_out2, (void*)h->pin_S, (void*)h->pin_bases, (void*)h->pin_probs, (void*)h->pin_clen, (void*)h->pin_ptab}) if (p) hipHostFree(p);
   for (void* p : h->allocs) hipFree(p);
   if (h->stream) hipStreamDestroy(h->stream);
@@ -1540,8 +1558,10 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     if (!h->ltaps && !h->lgreedy && !h->lptaps) return fail(h, RV_ESTATE, "step_logits needs option debug_taps=1 or persist_taps=1");
     src = d.step_logits; n = S * B * W * V;
   } else if (!strcmp(name, "step_alignments")) {
-    if (!h->ltaps) return fail(h, RV_ESTATE, "step_alignments needs option debug_taps=1");
-    src = h->step_align; n = S * B * W * Tm;
+    if (h->ltaps) src = h->step_align;
+    else if (h->lptaps && h->lpersist) src = h->palign;   // [S][B][W][T_m] as the per-step tap
+    else return fail(h, RV_ESTATE, "step_alignments needs option debug_taps=1, or persist_taps=1 on the persistent decode");
+    n = S * B * W * Tm;
   } else return fail(h, RV_EINVAL, "unknown tensor '%s'", name);
   *n_written = n;
   if (n == 0) return RV_OK;
@@ -1549,7 +1569,7 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (kind == 0) {
     HIPCHK(h, hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (!strcmp(name, "step_alignments") && h->lflash) {
+    if (src == h->step_align && h->lflash) {
       // the single-pass kernel taps raw log2-domain masked scores; normalise here (debug path only)
       for (size_t r = 0; r < n / Tm; ++r) {
         float* a = dst + r * Tm;

@@ -23,6 +23,25 @@ def _inputs(rv, mode, raw, ev):
     return {"joint": (raw, ev), "raw": raw, "event": ev}[mode]
 
 
+def _check_alignments(al, ref, mask, cs, tag, last=None):
+    """Alignments tapped from the persistent decode (option persist_taps), al [S, B, W, T_m], against the fp64 oracle's ref
+    [S', B, W, T_m], on every step each chunk ran (cs = chunk_steps; `last` caps the steps compared): within 1e-4, exactly 0.0 on
+    the masked memory steps, summing to 1 within 1e-5.  Returns the largest error."""
+    worst = 0.0
+    for b in range(al.shape[1]):
+        n = int(cs[b]) if last is None else min(int(cs[b]), int(last[b]))
+        if n == 0:
+            continue
+        a = al[:n, b]
+        assert np.isfinite(a).all(), (tag, b)
+        err = float(np.abs(a - ref[:n, b]).max())
+        worst = max(worst, err)
+        assert err < TOL, (tag, b, err)
+        assert (a[..., mask[b] == 0] == 0.0).all(), (tag, b, "masked step with a non-zero alignment")
+        assert np.abs(a.astype(np.float64).sum(-1) - 1.0).max() < 1e-5, (tag, b)
+    return worst
+
+
 @pytest.mark.parametrize("mode,attention,enc_depth", [
     ("joint", "luong", 2), ("raw", "luong", 2), ("event", "luong", 2),
     ("joint", "bahdanau", 2), ("joint", "luong", 1), ("joint", "luong", 3)])
@@ -66,16 +85,23 @@ def test_persistent_greedy_matches_per_step_and_oracle(rv, oracle, B, Tr, Te, L,
     bc.set_option("profile", 1)
     for persist in (1, 0):
         bc.set_option("persistent_decode", persist)
+        bc.set_option("persist_taps", persist)
         bc.reset_profile()
         tok, lg = bc.greedy_search_prediction(x, L)
         assert ("dec_persist" in bc.profile()) == bool(persist)
         out[persist] = (tok.numpy().copy(), lg.numpy().copy())
+        if persist:
+            al = bc.get_tensor("step_alignments").reshape(tok.shape[1], B, 1, -1)[:, :min(B, 12)].copy()
     assert out[1][0].shape == out[0][0].shape and (out[1][0] == out[0][0]).all()
     assert np.abs(out[1][1] - out[0][1]).max() < TOL
     nb = min(B, 12)
-    ot, olg = oracle.greedy_search(w, bc.cfg.oracle_cfg(), raw[:nb], ev[:nb] if mode == "joint" else None, L)
+    taps = {}
+    ot, olg = oracle.greedy_search(w, bc.cfg.oracle_cfg(), raw[:nb], ev[:nb] if mode == "joint" else None, L, taps=taps)
     S = min(ot.shape[1], out[1][0].shape[1])              # the oracle's sub-slab may stop earlier than the full slab
     assert (out[1][0][:nb, :S] == ot[:, :S]).all() and np.abs(out[1][1][:nb, :S] - olg[:, :S]).max() < TOL
+    # alignments of every step both ran (a greedy chunk runs on after its own first finished step, cs[b]: the slab's last step)
+    worst = _check_alignments(al, taps["step_alignments"][:, :, None], taps["mask"], np.full(nb, S), f"greedy D={dec_depth}")
+    print(f"greedy B={B} T_m={Tr + Te} D={dec_depth}: max |alpha - fp64| {worst:.2e}")
     bc.close()
 
 
@@ -149,21 +175,28 @@ def test_matrix_attention_matches_fp32_rows_and_oracle(rv, oracle, W, Tr, Te):
         cs = bc.get_tensor("chunk_steps").astype(int)
         S = tok.shape[1]
         got[mx] = (tok.numpy().copy(), sc.numpy().copy(), cs, bc.get_tensor("step_logits").reshape(S, B, W, 7).copy(),
-                   bc.get_tensor("step_ids").reshape(S, B, W).copy(), bc.get_tensor("parent_ids").reshape(S, B, W).copy())
+                   bc.get_tensor("step_ids").reshape(S, B, W).copy(), bc.get_tensor("parent_ids").reshape(S, B, W).copy(),
+                   bc.get_tensor("step_alignments").reshape(S, B, W, Tr + Te).copy())
     taps = {}
     otok, osc = oracle.beam_search(w, bc.cfg.oracle_cfg(), raw, ev, W, L, dtype=np.float64, taps=taps)
+    worst = {}
     for mx in (2, 1, 0):
-        tok, sc, cs, lg, ids, par = got[mx]
+        tok, sc, cs, lg, ids, par, al = got[mx]
         assert tok.shape == otok.shape and (tok == otok).all() and np.abs(sc - osc).max() < TOL, mx
         for b in range(B):
             n = cs[b]
             assert np.abs(lg[:n, b] - taps["step_logits"][:n, b]).max() < TOL, (mx, b)
             assert (ids[:n, b] == taps["step_ids"][:n, b]).all() and (par[:n, b] == taps["parent_ids"][:n, b]).all(), (mx, b)
+        # alignments: the f16 hi / lo image the context product consumes (mx 2, 1), the fp32 rows (mx 0)
+        worst[mx] = _check_alignments(al, taps["step_alignments"], taps["mask"], cs, f"matrix_attention form {mx}")
+    print(f"W={W} T_m={Tr + Te}: max |alpha - fp64| by form (2: ATT 3, 1: ATT 2, 0: ATT 0):", worst)
     assert (got[1][2] == got[0][2]).all() and (got[2][2] == got[0][2]).all()
     for b in range(B):
         n = got[1][2][b]
         assert np.abs(got[1][3][:n, b] - got[0][3][:n, b]).max() < 2e-5, b
         assert np.abs(got[2][3][:n, b] - got[0][3][:n, b]).max() < 2e-5, b
+        assert np.abs(got[1][6][:n, b] - got[0][6][:n, b]).max() < 2e-5, b
+        assert np.abs(got[2][6][:n, b] - got[0][6][:n, b]).max() < 2e-5, b
     bc.close()
 
 
@@ -181,21 +214,28 @@ def test_persistent_decode_step_logits(rv, oracle, W, dec_depth):
     raw, ev, _ = rv.synthetic.make_slab(B, 70, 14, seed=40 + W)
     bc.set_option("persist_taps", 1)
     bc.set_option("profile", 1)
-    tok, sc = bc.beam_search_prediction((raw, ev), W, L)
-    assert "dec_persist" in bc.profile()                     # the persistent kernel ran, not the per-step path
     taps = {}
     otok, osc = oracle.beam_search(w, bc.cfg.oracle_cfg(), raw, ev, W, L, dtype=np.float64, taps=taps)
     S = otok.shape[1]
-    assert tok.shape == otok.shape and (tok.numpy() == otok).all() and np.abs(sc.numpy() - osc).max() < TOL
-    cs = bc.get_tensor("chunk_steps").astype(int)
-    assert cs.max() == S and (cs >= 1).all()
-    lg = bc.get_tensor("step_logits").reshape(S, B, W, 7)
-    ids = bc.get_tensor("step_ids").reshape(S, B, W)
-    par = bc.get_tensor("parent_ids").reshape(S, B, W)
-    for b in range(B):
-        n = cs[b]
-        assert np.abs(lg[:n, b] - taps["step_logits"][:n, b]).max() < TOL, b
-        assert (ids[:n, b] == taps["step_ids"][:n, b]).all() and (par[:n, b] == taps["parent_ids"][:n, b]).all(), b
+    # the default form (all on the matrix pipe: ATT 3); with two cells also both cells on packed FMAs (ATT 0, matrix_cell = 0)
+    for mcell in ((1, 0) if dec_depth == 2 else (1,)):
+        bc.set_option("matrix_cell", mcell)
+        bc.reset_profile()
+        tok, sc = bc.beam_search_prediction((raw, ev), W, L)
+        assert "dec_persist" in bc.profile()                     # the persistent kernel ran, not the per-step path
+        assert tok.shape == otok.shape and (tok.numpy() == otok).all() and np.abs(sc.numpy() - osc).max() < TOL
+        cs = bc.get_tensor("chunk_steps").astype(int)
+        assert cs.max() == S and (cs >= 1).all()
+        lg = bc.get_tensor("step_logits").reshape(S, B, W, 7)
+        ids = bc.get_tensor("step_ids").reshape(S, B, W)
+        par = bc.get_tensor("parent_ids").reshape(S, B, W)
+        for b in range(B):
+            n = cs[b]
+            assert np.abs(lg[:n, b] - taps["step_logits"][:n, b]).max() < TOL, b
+            assert (ids[:n, b] == taps["step_ids"][:n, b]).all() and (par[:n, b] == taps["parent_ids"][:n, b]).all(), b
+        al = bc.get_tensor("step_alignments").reshape(S, B, W, 84)
+        worst = _check_alignments(al, taps["step_alignments"], taps["mask"], cs, f"W={W} D={dec_depth} matrix_cell={mcell}")
+        print(f"W={W} D={dec_depth} matrix_cell={mcell}: max |alpha - fp64| {worst:.2e}")
     bc.close()
 
 
@@ -1027,7 +1067,7 @@ def test_bahdanau_persistent_decode(rv, oracle, B, Tr, Te, W, L):
     raw, ev, _ = rv.synthetic.make_slab(B, Tr, max(Te, 1), seed=B + W)
     raw[1, Tr // 2:] = 0.0
     x = (raw, ev) if mode == "joint" else raw
-    out, lg, ids, par, cs = {}, {}, {}, {}, {}
+    out, lg, ids, par, cs, al = {}, {}, {}, {}, {}, {}
     bc.set_option("profile", 1)
     bc.set_option("persist_taps", 1)
     for form, (persist, mcell) in {"mx": (1, 1), "fma": (1, 0), "steps": (0, 1)}.items():
@@ -1043,6 +1083,7 @@ def test_bahdanau_persistent_decode(rv, oracle, B, Tr, Te, W, L):
             ids[form] = bc.get_tensor("step_ids").reshape(S, B, W).copy()
             par[form] = bc.get_tensor("parent_ids").reshape(S, B, W).copy()
             cs[form] = bc.get_tensor("chunk_steps").astype(int)
+            al[form] = bc.get_tensor("step_alignments").reshape(S, B, W, -1).copy()
     taps = {}
     ot, osc = oracle.beam_search(w, bc.cfg.oracle_cfg(), raw, ev if mode == "joint" else None, W, L, dtype=np.float64, taps=taps)
     for form in ("mx", "fma", "steps"):
@@ -1053,9 +1094,13 @@ def test_bahdanau_persistent_decode(rv, oracle, B, Tr, Te, W, L):
             n = cs[form][b]
             assert np.abs(lg[form][:n, b] - taps["step_logits"][:n, b]).max() < TOL, (form, b)
             assert (ids[form][:n, b] == taps["step_ids"][:n, b]).all() and (par[form][:n, b] == taps["parent_ids"][:n, b]).all(), (form, b)
+    # alignments: the f16 image the context product consumes (mx: ATT 4), the fp32 rows (fma: ATT 1)
+    worst = {form: _check_alignments(al[form], taps["step_alignments"], taps["mask"], cs[form], f"bahdanau {form}") for form in ("mx", "fma")}
+    print(f"Bahdanau W={W} T_m={Tr + Te}: max |alpha - fp64|", worst)
     for b in range(B):
         n = cs["mx"][b]
         assert np.abs(lg["mx"][:n, b] - lg["fma"][:n, b]).max() < 2e-5, b
+        assert np.abs(al["mx"][:n, b] - al["fma"][:n, b]).max() < 2e-5, b
     for mcell in (1, 0):
         bc.set_option("persistent_decode", 1); bc.set_option("matrix_cell", mcell)
         g, glg = bc.greedy_search_prediction(x, L)
