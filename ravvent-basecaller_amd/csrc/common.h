@@ -142,11 +142,12 @@ struct DecState {
   int* chunk_steps;       // persistent decode: [B] steps each chunk ran (nullptr on the per-step graph path)
   int* S_dev;             // [8]: [0] = S of the whole slab, [1+g] = S of sub-slab g
   int* S_host;            // device address of the host-mapped pinned word the call's S is left in (no copy launch for 4 bytes)
-  // persistent decode, Luong, one cell: scores and context as split-f16 MFMAs.  Scales: powers of two that bring the largest
+  // The form of the persistent decode this call runs (dec_persist_form: k_dec_persist's ATT), -1 on the per-step kernels.  Its
+  // matrix-pipe forms take the scores (Luong) and the context as split-f16 MFMAs.  Scales: powers of two that bring the largest
   // value a key / a U' element can take (from the weights; |enc_out| <= 1) into [2^13, 2^14); descale = 2^-14 / scale (the query
   // and the alignments are scaled by 2^14)
-  int mx_attention; float mx_kscale, mx_kdescale, mx_uscale, mx_udescale;
-  // ... and the cell product [ctx' | h] . Wcat2 too (mx_attention == 2): Wc16 = Wcat2 as MFMA B fragments of two f16 parts,
+  int persist_att; float mx_kscale, mx_kdescale, mx_uscale, mx_udescale;
+  // ... and the cell product [ctx' | h] . Wcat2 too (ATT 3, 4): Wc16 = Wcat2 as MFMA B fragments of two f16 parts,
   // [8 waves][32 (k-step, gate) pairs][2 parts][64 lanes][8 f16]; wave w owns units 16 w .. 16 w + 15 of all four gates; lane (n, kq)
   // of pair p = 4 ks + g holds T . Wcat2[k][128 g + 16 w + n] / xs[k], k = 32 ks + 8 kq + 0..7, with xs = mx_uscale for the ctx' rows
   // (k < 128) and 2^14 for the h rows -- the factors the inputs' f16 images carry -- and T the power of two that brings the largest
@@ -156,11 +157,11 @@ struct DecState {
   // [8 k-steps][2 parts][64 lanes][8 f16] (16 KB), rows divided like Wc16's, one power-of-two scale; mx_ldescale = its inverse.
   // Wave 0 takes the logits of all beams as 24 MFMAs on the [ctx' | h] image while the other waves already stream the cell product
   const uint16_t* Wl16; float mx_ldescale;
-  // Bahdanau on the matrix pipe (mx_attention == 2 with attention == 1): W_q [128][128] as B fragments of two f16 parts,
+  // Bahdanau on the matrix pipe (ATT 4): W_q [128][128] as B fragments of two f16 parts,
   // [8 waves][4 k-steps][2 parts][64 lanes][8 f16] (64 KB): wave w owns columns 16 w .. 16 w + 15, lane (n, kq) of k-step ks holds
   // T . W_q[32 ks + 8 kq + 0..7][16 w + n]; the A operand is the h half of the [ctx' | h] image (h 2^14): mx_qdescale = 2^-14 / T
   const uint16_t* Wq16; float mx_qdescale;
-  // Two decoder cells on the matrix pipe (depth == 2, mx_attention == 2).  Wc16 is then cell 0's product over [ctx' | h_1 | h_0]:
+  // Two decoder cells on the matrix pipe (depth == 2, ATT 3).  Wc16 is then cell 0's product over [ctx' | h_1 | h_0]:
   // [W_a ; A_h W_a ; U_0] [384][512] as [8 waves][48 (k-step, gate) pairs][2 parts][64 lanes][8 f16] (768 KB; rows divided by mx_uscale /
   // 2^14 / 2^14, one power-of-two scale, mx_cdescale its inverse); W1c16 = cell 1's two products, [8 waves][32 pairs][2][64][8] (512 KB):
   // pairs 0..15 = W_1 (input product on h_0), pairs 16..31 = U_1 (recurrent product on h_1), rows divided by 2^14, one scale (mx_c1descale)
@@ -181,8 +182,12 @@ void launch_dec_attend(const DecState& d, const float* WmemT, bool flash, int st
 // one launch, the chunk's attention memory resident in registers; also writes S_dev[0..1].  d.values must point at the
 // PROJECTED memory [B,Tm,256] = enc_output . [W_mem | A_c] (keys | attention-layer image of the values).
 // One cell: Wcat = [W_a ; U + A_h W_a] and Nh = A_h W_fc [128,V] (the attention layer's h part folded into the weights);
-// two cells: Wcat = [W_a ; U_0], Wcat1 / bdec1 = second cell ([W_1;U_1], b_1), Nh unused.
-bool dec_persist_supported(const DecState& d);
+// two cells: Wcat = [W_a ; U_0], Wcat1 / bdec1 = second cell ([W_1;U_1], b_1), Nh unused.  Launches the form d.persist_att.
+// dec_persist_form: the one place that picks that form from a call's options and shape -- k_dec_persist's ATT (PersistLds: Luong 0
+// on packed FMAs, 2 with the scores and context on the matrix pipe (option matrix_attention, one cell), 3 with the cell product and
+// the output layer there too (and matrix_cell); Bahdanau 1 on packed FMAs, 4 with all but the scores on the matrix pipe (both options,
+// one cell)), or -1 when no instantiation serves the call or its LDS does not fit.  W: the effective beam (1 for greedy search).
+int dec_persist_form(int attention, int depth, int W, int Tm, bool greedy, bool matrix_attention, bool matrix_cell);
 void launch_dec_persist(const DecState& d, const float* Wcat /*[256,512]*/, const float* Wtok /*[V,512]*/,
                         const float* bdec /*[512]*/, const float* Wcat1, const float* bdec1, const float* Nh, hipStream_t s);
 // ptab != null: the two output addresses are read from ptab[RV_PTAB_TOKENS] / ptab[RV_PTAB_OUT2] on the device instead

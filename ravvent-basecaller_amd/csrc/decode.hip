@@ -900,7 +900,9 @@ __host__ __device__ constexpr int part_floats(int W) { return 4 * W * RV_G > PER
 // and the last mxc_nc(W) pairs of each of the other seven waves (2 KB per pair and wave); the output layer's fragments (Wl16, 16 KB) sit in
 // LDS as well.  This form needs neither `qp` / `att` (fp32 copies of h and ctx') nor `attT` / `hcT` nor the fp32 output layer in static LDS
 __host__ __device__ constexpr int mxc_nc(int W) { return W <= 5 ? 2 : 1; }
-constexpr int MXC_STATIC_LDS = 1024;     // static LDS of the matrix-pipe instantiations (bias, beam bookkeeping): the others keep ~8.7 KB of output layer
+// static LDS (bytes, an upper bound) of a form: ~1 KB with the cell product on the matrix pipe (bias, beam bookkeeping), ~8.7 KB of output
+// layer in the others.  A form runs only where its dynamic LDS fits beside it (dec_persist_form) and opts in to no more than that
+constexpr int persist_static_lds(int ATT) { return ATT >= 3 ? 1024 : 10 * 1024; }
 __host__ __device__ constexpr int mxc_cache_floats(int W) { return (32 + 7 * mxc_nc(W)) * 512; }
 // two decoder cells on the matrix pipe: per step and wave 48 pairs of cell 0's product ([ctx' | h_1 | h_0] . [W_a ; A_h W_a ; U_0], K = 384) and
 // 16 of cell 1's recurrent product (h_1 . U_1) at the end of the step, 16 of cell 1's input product (h_0 . W_1) after cell 0's gates.  The
@@ -2222,46 +2224,60 @@ __global__ __launch_bounds__(64) void k_dec_reduce_steps(DecParts p) {
   if (lane == 0) { p.S_dev[0] = S; p.S_host[0] = S; }
 }
 
+// The instantiations of the decode kernels, each listed once: the dynamic-LDS opt-ins, the persistent decode's form check and the
+// launches walk these lists, so adding or removing a form is a change to its list only.  A list calls fn with each form in turn until
+// fn returns true, and says whether one did.  (Function templates rather than nested generic lambdas, whose instantiations the
+// compiler emits in reverse: a list's order is the order the kernels are emitted in, and the compiler's code for some of the
+// matrix-pipe persistent forms changes with that order)
+
+// k_dec_persist<W, NIT, D, ATT>: one decoder cell in each attention form (PersistLds) for every beam width, two cells (Luong: every
+// product on the matrix pipe, or packed FMAs) for W <= 5 (LDS).  NIT resident row groups serve T_m <= 32 NIT: the first form of
+// the list that serves a call has the fewest
+template <int W_, int NIT_, int D_, int ATT_> struct PersistForm { static constexpr int W = W_, NIT = NIT_, D = D_, ATT = ATT_; };
+template <int W, int D, int ATT, typename Fn> bool persist_nit(Fn& fn) {
+  return fn(PersistForm<W, 2, D, ATT>{}) || fn(PersistForm<W, 8, D, ATT>{}) || fn(PersistForm<W, 11, D, ATT>{});
+}
+template <int W, typename Fn> bool persist_w(Fn& fn) {
+  if constexpr (W <= 5)
+    if (persist_nit<W, 2, 3>(fn) || persist_nit<W, 2, 0>(fn)) return true;
+  return persist_nit<W, 1, 4>(fn) || persist_nit<W, 1, 1>(fn) || persist_nit<W, 1, 3>(fn) || persist_nit<W, 1, 2>(fn) || persist_nit<W, 1, 0>(fn);
+}
+template <typename Fn> bool for_each_persist_form(Fn&& fn) {
+  return persist_w<1>(fn) || persist_w<2>(fn) || persist_w<3>(fn) || persist_w<4>(fn) || persist_w<5>(fn) || persist_w<6>(fn) ||
+         persist_w<7>(fn) || persist_w<8>(fn);
+}
+template <typename F> bool persist_serves(int W, int D, int ATT, int Tm) { return F::W == W && F::D == D && F::ATT == ATT && Tm <= 32 * F::NIT; }
+
+// The per-step attend kernels: k_dec_attend_flash<W, NT> runs NT threads; k_dec_attend<W, TB, TD = 4 TB> serves T_m <= 32 TB (the
+// first of the list that serves a call has the shortest sweeps)
+template <int W_, int NT_> struct FlashForm { static constexpr bool FLASH = true; static constexpr int W = W_, NT = NT_; };
+template <int W_, int TB_> struct AttendForm { static constexpr bool FLASH = false; static constexpr int W = W_, TB = TB_, TD = 4 * TB_; };
+template <int W, typename Fn> bool attend_w(Fn& fn) {
+  return fn(FlashForm<W, 256>{}) || fn(FlashForm<W, 512>{}) || fn(AttendForm<W, 2>{}) || fn(AttendForm<W, 7>{}) || fn(AttendForm<W, 11>{});
+}
+template <typename Fn> bool for_each_attend_form(Fn&& fn) {
+  return attend_w<1>(fn) || attend_w<2>(fn) || attend_w<3>(fn) || attend_w<4>(fn) || attend_w<5>(fn) || attend_w<6>(fn) ||
+         attend_w<7>(fn) || attend_w<8>(fn);
+}
+
 }  // namespace
 
-template <int W, int D, int ATT>
-static void launch_persist_wd(const DecState& d, const float* Wcat, const float* Wtok, const float* bdec,
-                              const float* Wcat1, const float* bdec1, const float* Nh, hipStream_t s) {
-  const size_t shm = sizeof(float) * PersistLds(W, D, ATT).total;
-  if (d.Tm <= 64) hipLaunchKernelGGL((k_dec_persist<W, 2, D, ATT>), dim3(d.B), dim3(512), shm, s, d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh);
-  else if (d.Tm <= 256) hipLaunchKernelGGL((k_dec_persist<W, 8, D, ATT>), dim3(d.B), dim3(512), shm, s, d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh);
-  else hipLaunchKernelGGL((k_dec_persist<W, 11, D, ATT>), dim3(d.B), dim3(512), shm, s, d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh);
-}
-template <int W>
-static void launch_persist_w(const DecState& d, const float* Wcat, const float* Wtok, const float* bdec,
-                             const float* Wcat1, const float* bdec1, const float* Nh, hipStream_t s) {
-  if constexpr (W <= 5) {
-    if (d.depth > 1 && d.mx_attention == 2) { launch_persist_wd<W, 2, 3>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s); return; }   // two cells, everything on the matrix pipe
-    if (d.depth > 1) { launch_persist_wd<W, 2, 0>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s); return; }
-  }
-  if (d.attention == 1 && d.mx_attention == 2) launch_persist_wd<W, 1, 4>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s);   // Bahdanau: scores on the VALU, the rest on the matrix pipe
-  else if (d.attention == 1) launch_persist_wd<W, 1, 1>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s);     // Bahdanau: one decoder cell, packed FMAs
-  else if (d.mx_attention == 2) launch_persist_wd<W, 1, 3>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s);  // Luong, attention and cell product on the matrix pipe
-  else if (d.mx_attention) launch_persist_wd<W, 1, 2>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s);  // Luong, scores and context on the matrix pipe
-  else launch_persist_wd<W, 1, 0>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s);
-}
-bool dec_persist_supported(const DecState& d) {
-  const int att_form = d.attention == 1 ? (d.depth == 1 && d.mx_attention == 2 ? 4 : 1) : (d.depth <= 2 && d.mx_attention == 2 ? 3 : 0);
-  if (sizeof(float) * PersistLds(d.W, d.depth > 1 ? 2 : 1, att_form).total + (att_form >= 3 ? MXC_STATIC_LDS : 10 * 1024) > 160 * 1024) return false;   // dynamic + static LDS
-  return (d.attention == 0 || (d.attention == 1 && d.depth == 1)) && d.depth <= 2 && d.W <= (d.depth > 1 ? 5 : 8) && d.Tm <= 352 && !d.step_align && (!d.greedy || d.W == 1);
+int dec_persist_form(int attention, int depth, int W, int Tm, bool greedy, bool matrix_attention, bool matrix_cell) {
+  const bool mxc = matrix_attention && matrix_cell;
+  const int att = attention == 1 ? (mxc ? 4 : 1) : attention == 0 ? (mxc ? 3 : (matrix_attention && depth == 1 ? 2 : 0)) : -1;
+  if (greedy && W != 1) return -1;            // (greedy search decodes one beam)
+  if (!for_each_persist_form([&](auto f) { return persist_serves<decltype(f)>(W, depth, att, Tm); })) return -1;
+  return sizeof(float) * PersistLds(W, depth, att).total + persist_static_lds(att) <= 160 * 1024 ? att : -1;
 }
 void launch_dec_persist(const DecState& d, const float* Wcat, const float* Wtok, const float* bdec,
                         const float* Wcat1, const float* bdec1, const float* Nh, hipStream_t s) {
-  switch (d.W) {
-    case 1: launch_persist_w<1>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s); break;
-    case 2: launch_persist_w<2>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s); break;
-    case 3: launch_persist_w<3>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s); break;
-    case 4: launch_persist_w<4>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s); break;
-    case 5: launch_persist_w<5>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s); break;
-    case 6: launch_persist_w<6>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s); break;
-    case 7: launch_persist_w<7>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s); break;
-    default: launch_persist_w<8>(d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh, s); break;
-  }
+  for_each_persist_form([&](auto f) {
+    using F = decltype(f);
+    if (!persist_serves<F>(d.W, d.depth, d.persist_att, d.Tm)) return false;
+    hipLaunchKernelGGL((k_dec_persist<F::W, F::NIT, F::D, F::ATT>), dim3(d.B), dim3(512), sizeof(float) * PersistLds(F::W, F::D, F::ATT).total, s,
+                       d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh);
+    return true;
+  });
   // (S = max over chunk_steps is taken by k_dec_finalize)
 }
 
@@ -2284,91 +2300,46 @@ void launch_dec_cell(const DecState& d, int layer, const float* WcatT, const flo
   const size_t shm = sizeof(float) * CELL_LDS_FLOATS;
   hipLaunchKernelGGL(k_dec_cell, dim3(RV_U / 16, (N + CELL_ROWS - 1) / CELL_ROWS), dim3(512), shm, s, d, layer, WcatT, Wtok, bias, step);
 }
-template <int W, int TB, int TD>
-static void launch_attend_wt(const DecState& d, int step, hipStream_t s) {
-  const int TmP = (d.Tm + 3) & ~3;
-  const size_t shm = sizeof(float) * AttLds(W, TmP, false).total;
-  hipLaunchKernelGGL((k_dec_attend<W, TB, TD>), dim3(d.B), dim3(ATT_THREADS), shm, s, d, step);
-}
-template <int W>
-static void launch_attend_w(const DecState& d, const float* WmemT, bool flash, int step, hipStream_t s) {
-  if (flash) {
-    if (d.attend_threads ? d.attend_threads == 256 : d.B > 320) {     // more chunks than CUs: two 256-thread workgroups per CU overlap each other's phases
-      const size_t shm = sizeof(float) * AttLds(W, 0, true, 256).total;
-      hipLaunchKernelGGL((k_dec_attend_flash<W, 256>), dim3(d.B), dim3(256), shm, s, d, WmemT, step);
-    } else {
-      const size_t shm = sizeof(float) * AttLds(W, 0, true, 512).total;
-      hipLaunchKernelGGL((k_dec_attend_flash<W, 512>), dim3(d.B), dim3(512), shm, s, d, WmemT, step);
-    }
-    return;
-  }
-  if (d.Tm <= 64) launch_attend_wt<W, 2, 8>(d, step, s);
-  else if (d.Tm <= 224) launch_attend_wt<W, 7, 28>(d, step, s);
-  else launch_attend_wt<W, 11, 44>(d, step, s);
-}
 void launch_dec_attend(const DecState& d, const float* WmemT, bool flash, int step, hipStream_t s) {
-  switch (d.W) {
-    case 1: launch_attend_w<1>(d, WmemT, flash, step, s); break;
-    case 2: launch_attend_w<2>(d, WmemT, flash, step, s); break;
-    case 3: launch_attend_w<3>(d, WmemT, flash, step, s); break;
-    case 4: launch_attend_w<4>(d, WmemT, flash, step, s); break;
-    case 5: launch_attend_w<5>(d, WmemT, flash, step, s); break;
-    case 6: launch_attend_w<6>(d, WmemT, flash, step, s); break;
-    case 7: launch_attend_w<7>(d, WmemT, flash, step, s); break;
-    default: launch_attend_w<8>(d, WmemT, flash, step, s); break;
-  }
+  // flash: more chunks than CUs -> two 256-thread workgroups per CU overlap each other's phases
+  const int NT = (d.attend_threads ? d.attend_threads == 256 : d.B > 320) ? 256 : 512;
+  for_each_attend_form([&](auto f) {
+    using F = decltype(f);
+    if (F::W != d.W || F::FLASH != flash) return false;
+    if constexpr (F::FLASH) {
+      if (F::NT != NT) return false;
+      hipLaunchKernelGGL((k_dec_attend_flash<F::W, F::NT>), dim3(d.B), dim3(F::NT), sizeof(float) * AttLds(F::W, 0, true, F::NT).total, s, d, WmemT, step);
+    } else {
+      if (d.Tm > 32 * F::TB) return false;
+      hipLaunchKernelGGL((k_dec_attend<F::W, F::TB, F::TD>), dim3(d.B), dim3(ATT_THREADS), sizeof(float) * AttLds(F::W, (d.Tm + 3) & ~3, false).total, s, d, step);
+    }
+    return true;
+  });
 }
-// Kernels that use more than the default dynamic-LDS limit opt in once per device (called by rv_create
-// after hipSetDevice): sized for the largest shapes the library accepts (T_m <= 352).
-template <int W>
-static hipError_t configure_w() {
-  constexpr int cap = 160 * 1024 - 10 * 1024;    // leave room for the kernels' static LDS
-  hipError_t first = hipSuccess;
-  auto opt = [&](const void* f, size_t bytes) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes < (size_t)cap ? bytes : (size_t)cap));
-    if (e != hipSuccess && first == hipSuccess) first = e;
-  };
-  opt(reinterpret_cast<const void*>(&k_dec_attend<W, 2, 8>), sizeof(float) * AttLds(W, 64, false).total);
-  opt(reinterpret_cast<const void*>(&k_dec_attend<W, 7, 28>), sizeof(float) * AttLds(W, 224, false).total);
-  opt(reinterpret_cast<const void*>(&k_dec_attend<W, 11, 44>), sizeof(float) * AttLds(W, 352, false).total);
-  opt(reinterpret_cast<const void*>(&k_dec_attend_flash<W, 256>), sizeof(float) * AttLds(W, 0, true, 256).total);
-  opt(reinterpret_cast<const void*>(&k_dec_attend_flash<W, 512>), sizeof(float) * AttLds(W, 0, true, 512).total);
-  opt(reinterpret_cast<const void*>(&k_dec_persist<W, 2, 1>), sizeof(float) * PersistLds(W, 1).total);
-  opt(reinterpret_cast<const void*>(&k_dec_persist<W, 8, 1>), sizeof(float) * PersistLds(W, 1).total);
-  opt(reinterpret_cast<const void*>(&k_dec_persist<W, 11, 1>), sizeof(float) * PersistLds(W, 1).total);
-  opt(reinterpret_cast<const void*>(&k_dec_persist<W, 2, 1, 1>), sizeof(float) * PersistLds(W, 1, 1).total);
-  opt(reinterpret_cast<const void*>(&k_dec_persist<W, 8, 1, 1>), sizeof(float) * PersistLds(W, 1, 1).total);
-  opt(reinterpret_cast<const void*>(&k_dec_persist<W, 11, 1, 1>), sizeof(float) * PersistLds(W, 1, 1).total);
-  opt(reinterpret_cast<const void*>(&k_dec_persist<W, 2, 1, 2>), sizeof(float) * PersistLds(W, 1).total);
-  opt(reinterpret_cast<const void*>(&k_dec_persist<W, 8, 1, 2>), sizeof(float) * PersistLds(W, 1).total);
-  opt(reinterpret_cast<const void*>(&k_dec_persist<W, 11, 1, 2>), sizeof(float) * PersistLds(W, 1).total);
-  auto opt3 = [&](const void* f, size_t bytes) {       // (more dynamic LDS than `cap`: their static part is ~1 KB)
-    const size_t cap3 = 160 * 1024 - MXC_STATIC_LDS;
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes < cap3 ? bytes : cap3));
-    if (e != hipSuccess && first == hipSuccess) first = e;
-  };
-  opt3(reinterpret_cast<const void*>(&k_dec_persist<W, 2, 1, 3>), sizeof(float) * PersistLds(W, 1, 3).total);
-  opt3(reinterpret_cast<const void*>(&k_dec_persist<W, 8, 1, 3>), sizeof(float) * PersistLds(W, 1, 3).total);
-  opt3(reinterpret_cast<const void*>(&k_dec_persist<W, 11, 1, 3>), sizeof(float) * PersistLds(W, 1, 3).total);
-  opt3(reinterpret_cast<const void*>(&k_dec_persist<W, 2, 1, 4>), sizeof(float) * PersistLds(W, 1, 4).total);
-  opt3(reinterpret_cast<const void*>(&k_dec_persist<W, 8, 1, 4>), sizeof(float) * PersistLds(W, 1, 4).total);
-  opt3(reinterpret_cast<const void*>(&k_dec_persist<W, 11, 1, 4>), sizeof(float) * PersistLds(W, 1, 4).total);
-  if constexpr (W <= 5) {
-    opt3(reinterpret_cast<const void*>(&k_dec_persist<W, 2, 2, 3>), sizeof(float) * PersistLds(W, 2, 3).total);
-    opt3(reinterpret_cast<const void*>(&k_dec_persist<W, 8, 2, 3>), sizeof(float) * PersistLds(W, 2, 3).total);
-    opt3(reinterpret_cast<const void*>(&k_dec_persist<W, 11, 2, 3>), sizeof(float) * PersistLds(W, 2, 3).total);
-    opt(reinterpret_cast<const void*>(&k_dec_persist<W, 2, 2>), sizeof(float) * PersistLds(W, 2).total);
-    opt(reinterpret_cast<const void*>(&k_dec_persist<W, 8, 2>), sizeof(float) * PersistLds(W, 2).total);
-    opt(reinterpret_cast<const void*>(&k_dec_persist<W, 11, 2>), sizeof(float) * PersistLds(W, 2).total);
-  }
-  return first;
-}
+// Kernels that use more than the default dynamic-LDS limit opt in once per device (called by rv_create after hipSetDevice): sized
+// for the largest shapes the library accepts (T_m <= 352), up to what the kernel's static LDS leaves of the 160 KB (the attend
+// kernels' static part, like k_dec_persist's with packed-FMA cells, is under 10 KB)
 hipError_t configure_decode_kernels() {
   hipError_t first = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dec_cell), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)(sizeof(float) * CELL_LDS_FLOATS));
-  for (hipError_t e : {configure_w<1>(), configure_w<2>(), configure_w<3>(), configure_w<4>(),
-                       configure_w<5>(), configure_w<6>(), configure_w<7>(), configure_w<8>()})
+  auto opt = [&](const void* f, size_t bytes, int static_lds) {
+    const size_t cap = 160 * 1024 - static_lds;
+    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes < cap ? bytes : cap));
     if (e != hipSuccess && first == hipSuccess) first = e;
+    return false;
+  };
+  for_each_attend_form([&](auto f) {
+    using F = decltype(f);
+    if constexpr (F::FLASH)
+      return opt(reinterpret_cast<const void*>(&k_dec_attend_flash<F::W, F::NT>), sizeof(float) * AttLds(F::W, 0, true, F::NT).total, 10 * 1024);
+    else
+      return opt(reinterpret_cast<const void*>(&k_dec_attend<F::W, F::TB, F::TD>), sizeof(float) * AttLds(F::W, 32 * F::TB, false).total, 10 * 1024);
+  });
+  for_each_persist_form([&](auto f) {
+    using F = decltype(f);
+    return opt(reinterpret_cast<const void*>(&k_dec_persist<F::W, F::NIT, F::D, F::ATT>), sizeof(float) * PersistLds(F::W, F::D, F::ATT).total,
+               persist_static_lds(F::ATT));
+  });
   return first;
 }
 

@@ -693,92 +693,80 @@ __global__ __launch_bounds__(768) void k_lstm_rec_proj(RecArgs a) {
 constexpr size_t proj_lds_bytes(int bt, int split) {
   return sizeof(float) * (2 * bt * RV_U + 2 * 16 * RV_G + 2 * RV_G) + (split ? 2 * (split == 2 ? 2 : 3) * 32 * 272 : sizeof(float) * 2 * 16 * 260);
 }
-template <int BT>
-void launch_proj(const RecArgs& a, hipStream_t s) {
-  dim3 grid((a.B + BT - 1) / BT, 2);
-  if (a.Wh[0]) hipLaunchKernelGGL((k_lstm_rec_proj<BT, 2>), grid, dim3(768), proj_lds_bytes(BT, 2), s, a);
-  else if (a.Wsb[0]) hipLaunchKernelGGL((k_lstm_rec_proj<BT, 1>), grid, dim3(768), proj_lds_bytes(BT, 1), s, a);
-  else hipLaunchKernelGGL((k_lstm_rec_proj<BT, 0>), grid, dim3(768), proj_lds_bytes(BT, 0), s, a);
-}
-
 constexpr size_t REC_LDS_CAP = 160 * 1024;      // gfx950: 160 KB per workgroup (these kernels hold no static LDS)
 constexpr size_t one_lds_bytes(int bt, int F, int T) { return sizeof(float) * (2 * (size_t)bt * RV_U + (F > 0 ? (size_t)bt * T * F : 0)); }
 constexpr size_t tw_lds_bytes(int bt, int F, int T) { return sizeof(float) * ((size_t)bt * RV_U + (size_t)bt * RV_G + (size_t)bt * T * F); }
 
-template <int BT, int F>
-void launch_one(const RecArgs& a, hipStream_t s) {
-  dim3 grid((a.B + BT - 1) / BT, 2);
-  hipLaunchKernelGGL((k_lstm_rec<BT, F>), grid, dim3(512), one_lds_bytes(BT, F, a.T), s, a);
+// The instantiations, each listed once: the opt-ins and the launches walk these lists, calling fn with each form in turn until fn
+// returns true.  BT chunks per workgroup; F input features of layer 0 folded in (0: pre-projected inputs); SB the projection's weights:
+// 0 f32, 1 split-bf16, 2 split-f16
+template <int BT_, int F_> struct RecForm { static constexpr int BT = BT_, F = F_; };
+template <int BT_, int SB_> struct ProjForm { static constexpr int BT = BT_, SB = SB_; };
+template <typename Fn> bool for_each_rec_form(Fn&& fn) {     // k_lstm_rec<BT, F>
+  return fn(RecForm<1, 1>{}) || fn(RecForm<2, 1>{}) || fn(RecForm<4, 1>{}) || fn(RecForm<8, 1>{}) ||
+         fn(RecForm<1, 5>{}) || fn(RecForm<2, 5>{}) || fn(RecForm<4, 5>{}) || fn(RecForm<8, 5>{}) ||
+         fn(RecForm<1, 0>{}) || fn(RecForm<2, 0>{}) || fn(RecForm<4, 0>{}) || fn(RecForm<8, 0>{});
 }
-
-template <int BT, int F>
-void launch_tw(const RecArgs& a, hipStream_t s) {
-  dim3 grid((a.B + BT - 1) / BT, 2);
-  hipLaunchKernelGGL((k_lstm_rec_tw<BT, F>), grid, dim3(768), tw_lds_bytes(BT, F, a.T), s, a);
+template <typename Fn> bool for_each_tw_form(Fn&& fn) {      // k_lstm_rec_tw<BT, F>: layer 0 with two or more chunks per workgroup
+  return fn(RecForm<2, 1>{}) || fn(RecForm<4, 1>{}) || fn(RecForm<8, 1>{}) || fn(RecForm<2, 5>{}) || fn(RecForm<4, 5>{}) || fn(RecForm<8, 5>{});
 }
-
-template <int F>
-void launch_f(const RecArgs& a, int bt, hipStream_t s) {
-  if constexpr (F > 0) {
-    // (the tail-wave form stages 12 KB more per 8 rows than the 8-wave form: very long windows fall back to the latter)
-    if (a.tail_wave && bt >= 2 && tw_lds_bytes(bt, F, a.T) <= REC_LDS_CAP) {
-      switch (bt) {
-        case 2: launch_tw<2, F>(a, s); return;
-        case 4: launch_tw<4, F>(a, s); return;
-        default: launch_tw<8, F>(a, s); return;
-      }
-    }
-  }
-  switch (bt) {
-    case 1: launch_one<1, F>(a, s); break;
-    case 2: launch_one<2, F>(a, s); break;
-    case 4: launch_one<4, F>(a, s); break;
-    default: launch_one<8, F>(a, s); break;
-  }
+template <typename Fn> bool for_each_proj_form(Fn&& fn) {    // k_lstm_rec_proj<BT, SB>
+  return fn(ProjForm<1, 0>{}) || fn(ProjForm<2, 0>{}) || fn(ProjForm<4, 0>{}) || fn(ProjForm<8, 0>{}) ||
+         fn(ProjForm<1, 1>{}) || fn(ProjForm<2, 1>{}) || fn(ProjForm<4, 1>{}) || fn(ProjForm<8, 1>{}) ||
+         fn(ProjForm<1, 2>{}) || fn(ProjForm<2, 2>{}) || fn(ProjForm<4, 2>{}) || fn(ProjForm<8, 2>{});
 }
 
 }  // namespace
 
-void launch_lstm_rec_proj(const RecArgs& a, int rows_per_block, hipStream_t s) {
-  switch (rows_per_block) {
-    case 1: launch_proj<1>(a, s); break;
-    case 2: launch_proj<2>(a, s); break;
-    case 4: launch_proj<4>(a, s); break;
-    default: launch_proj<8>(a, s); break;
-  }
-}
-bool lstm_rec_window_fits(int F, int rows_per_block, int T) {
-  return one_lds_bytes(rows_per_block, F, T) <= REC_LDS_CAP;     // launch_f falls back to the 8-wave form when the tail-wave form does not fit
-}
 hipError_t configure_rec_kernels() {
-  const int shm = (int)proj_lds_bytes(8, 1);             // the largest of the three images
   hipError_t first = hipSuccess;
+  auto opt = [&](const void* f, size_t bytes) {
+    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess && first == hipSuccess) first = e;
+    return false;
+  };
   // layer-0 kernels stage the chunks' whole input windows: opt in to the full 160 KB (the 64 KB default is reached at
   // T_event > 281 / T_raw > 1408 with 8 rows per workgroup)
-  for (const void* f : {reinterpret_cast<const void*>(&k_lstm_rec<1, 1>), reinterpret_cast<const void*>(&k_lstm_rec<2, 1>),
-                        reinterpret_cast<const void*>(&k_lstm_rec<4, 1>), reinterpret_cast<const void*>(&k_lstm_rec<8, 1>),
-                        reinterpret_cast<const void*>(&k_lstm_rec<1, 5>), reinterpret_cast<const void*>(&k_lstm_rec<2, 5>),
-                        reinterpret_cast<const void*>(&k_lstm_rec<4, 5>), reinterpret_cast<const void*>(&k_lstm_rec<8, 5>),
-                        reinterpret_cast<const void*>(&k_lstm_rec_tw<2, 1>), reinterpret_cast<const void*>(&k_lstm_rec_tw<4, 1>),
-                        reinterpret_cast<const void*>(&k_lstm_rec_tw<8, 1>), reinterpret_cast<const void*>(&k_lstm_rec_tw<2, 5>),
-                        reinterpret_cast<const void*>(&k_lstm_rec_tw<4, 5>), reinterpret_cast<const void*>(&k_lstm_rec_tw<8, 5>)}) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)REC_LDS_CAP);
-    if (e != hipSuccess && first == hipSuccess) first = e;
-  }
-  for (const void* f : {reinterpret_cast<const void*>(&k_lstm_rec_proj<1, 0>), reinterpret_cast<const void*>(&k_lstm_rec_proj<2, 0>),
-                        reinterpret_cast<const void*>(&k_lstm_rec_proj<4, 0>), reinterpret_cast<const void*>(&k_lstm_rec_proj<8, 0>),
-                        reinterpret_cast<const void*>(&k_lstm_rec_proj<1, 1>), reinterpret_cast<const void*>(&k_lstm_rec_proj<2, 1>),
-                        reinterpret_cast<const void*>(&k_lstm_rec_proj<4, 1>), reinterpret_cast<const void*>(&k_lstm_rec_proj<8, 1>),
-                        reinterpret_cast<const void*>(&k_lstm_rec_proj<1, 2>), reinterpret_cast<const void*>(&k_lstm_rec_proj<2, 2>),
-                        reinterpret_cast<const void*>(&k_lstm_rec_proj<4, 2>), reinterpret_cast<const void*>(&k_lstm_rec_proj<8, 2>)}) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-    if (e != hipSuccess && first == hipSuccess) first = e;
-  }
+  for_each_rec_form([&](auto f) {
+    using R = decltype(f);
+    if constexpr (R::F > 0) opt(reinterpret_cast<const void*>(&k_lstm_rec<R::BT, R::F>), REC_LDS_CAP);
+    return false;
+  });
+  for_each_tw_form([&](auto f) { using R = decltype(f); return opt(reinterpret_cast<const void*>(&k_lstm_rec_tw<R::BT, R::F>), REC_LDS_CAP); });
+  for_each_proj_form([&](auto f) {     // (proj_lds_bytes(8, 1): the largest of the three images)
+    using P = decltype(f);
+    return opt(reinterpret_cast<const void*>(&k_lstm_rec_proj<P::BT, P::SB>), proj_lds_bytes(8, 1));
+  });
   return first;
 }
 
+void launch_lstm_rec_proj(const RecArgs& a, int rows_per_block, hipStream_t s) {
+  const int SB = a.Wh[0] ? 2 : (a.Wsb[0] ? 1 : 0);
+  const dim3 grid((a.B + rows_per_block - 1) / rows_per_block, 2);
+  for_each_proj_form([&](auto f) {
+    using P = decltype(f);
+    if (P::BT != rows_per_block || P::SB != SB) return false;
+    hipLaunchKernelGGL((k_lstm_rec_proj<P::BT, P::SB>), grid, dim3(768), proj_lds_bytes(P::BT, P::SB), s, a);
+    return true;
+  });
+}
+bool lstm_rec_window_fits(int F, int rows_per_block, int T) {
+  return one_lds_bytes(rows_per_block, F, T) <= REC_LDS_CAP;     // launch_lstm_rec falls back to the 8-wave form when the tail-wave form does not fit
+}
+
 void launch_lstm_rec(const RecArgs& a, int F, int rows_per_block, hipStream_t s) {
-  if (F == 0) launch_f<0>(a, rows_per_block, s);
-  else if (F == 1) launch_f<1>(a, rows_per_block, s);
-  else launch_f<5>(a, rows_per_block, s);
+  const dim3 grid((a.B + rows_per_block - 1) / rows_per_block, 2);
+  // the tail-wave form where there is one (a.tail_wave); it stages 12 KB more per 8 rows than the 8-wave form: very long windows fall back to the latter
+  const bool tw = a.tail_wave && tw_lds_bytes(rows_per_block, F, a.T) <= REC_LDS_CAP && for_each_tw_form([&](auto f) {
+    using R = decltype(f);
+    if (R::BT != rows_per_block || R::F != F) return false;
+    hipLaunchKernelGGL((k_lstm_rec_tw<R::BT, R::F>), grid, dim3(768), tw_lds_bytes(R::BT, R::F, a.T), s, a);
+    return true;
+  });
+  if (!tw) for_each_rec_form([&](auto f) {
+    using R = decltype(f);
+    if (R::BT != rows_per_block || R::F != F) return false;
+    hipLaunchKernelGGL((k_lstm_rec<R::BT, R::F>), grid, dim3(512), one_lds_bytes(R::BT, R::F, a.T), s, a);
+    return true;
+  });
 }

@@ -435,13 +435,11 @@ void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool pr
 
 struct CallsOut { const uint8_t* lut; uint8_t* bases; int32_t* lengths; float* probs; };
 
-// Does this call take the one-launch persistent decode (if the kernel has an instantiation for it: dec_persist_supported)?
-bool persist_wanted(const RvContext* h, bool greedy, int W, int Tm) {
+// The form of the one-launch persistent decode this call takes (dec_persist_form), or -1: the per-step kernels
+int persist_form(const RvContext* h, bool greedy, int W, int Tm) {
+  if (!h->opt_persist || !h->opt_flash || h->opt_taps) return -1;
   const RvConfig& c = h->cfg;
-  const int W_eff = greedy ? 1 : W;
-  return h->opt_persist && h->opt_flash && !h->opt_taps && c.dec_depth <= 2 &&
-         (c.attention == RV_ATT_LUONG || (c.attention == RV_ATT_BAHDANAU && c.dec_depth == 1)) &&
-         W_eff <= (c.dec_depth > 1 ? 5 : 8) && Tm <= 352;
+  return dec_persist_form(c.attention, c.dec_depth, greedy ? 1 : W, Tm, greedy, h->opt_mx_att, h->opt_mx_cell);
 }
 
 int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, int B, int T_r, int T_e, int W, int L, bool greedy,
@@ -502,7 +500,7 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
     h->slab_graphs.clear();
     h->graph_gen = root->opt_gen;
   }
-  const bool graphable = root->opt_slab_graph && h->lwide && !h->lrows8 && persist_wanted(h, greedy, W, T_r + T_e) && h->opt_profile == 0 && !h->opt_taps &&
+  const bool graphable = root->opt_slab_graph && h->lwide && !h->lrows8 && persist_form(h, greedy, W, T_r + T_e) >= 0 && h->opt_profile == 0 && !h->opt_taps &&
                          !h->opt_ptaps && !h->rec_ts && !h->dec_st.dbg_ts && h->d_ptab;
   if (!graphable) return record_slab(h, xr, xe, !dev_in, B, T_r, T_e, W, L, greedy, tk, o2, dev_out, lut, nullptr);
   h->pin_ptab[RV_PTAB_RAW] = xr; h->pin_ptab[RV_PTAB_EVENT] = xe; h->pin_ptab[RV_PTAB_TOKENS] = tk; h->pin_ptab[RV_PTAB_OUT2] = o2;
@@ -599,9 +597,9 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
   //      kernel and for the "keys" debug tap only.
   const int W_eff = greedy ? 1 : W;
   h->lflash = (c.attention == RV_ATT_LUONG && h->opt_flash && W_eff <= 5) ? 1 : 0;   // wider beams: register budget -> two-pass
-  // the persistent decode (decided below, once the decode state is set up) needs neither keys nor the per-step kernels
-  const bool persist_ok = persist_wanted(h, greedy, W, Tm);
-  h->lkeys = ((!h->lflash && !persist_ok) || h->opt_taps) ? 1 : 0;
+  // the persistent decode needs neither keys nor the per-step kernels
+  const int persist_att = persist_form(h, greedy, W, Tm);
+  h->lkeys = ((!h->lflash && persist_att < 0) || h->opt_taps) ? 1 : 0;
   if (h->lkeys) {
     GemmArgs g{};
     g.A = h->enc_out; g.lda = RV_E; g.Bm = h->W_mem; g.ldb = RV_U; g.C = h->keys; g.ldc = RV_U;
@@ -662,14 +660,10 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
   // keep sampling after their end token, so greedy decodes as one piece).
   int nsplit = (greedy || h->opt_taps || B < 64) ? 1 : std::min(std::max(h->opt_split, 1), 4);
   d.chunk_steps = nullptr;
-  // (sizes the decode's LDS)  Luong: 1 = scores and context on the matrix pipe, 2 = the cell product and the output layer too; Bahdanau: 2 = the
-  // context, the processed query, the cell product and the output layer on the matrix pipe (the tanh scores stay on the VALU), else packed FMAs
-  // Two cells (Luong): 2 = every product of both cells on the matrix pipe, else packed FMAs.
-  d.mx_attention = (h->opt_mx_att && d.depth <= 2) ? (h->opt_mx_cell ? 2 : (c.attention == RV_ATT_LUONG && d.depth == 1 ? 1 : 0)) : 0;
+  d.persist_att = persist_att;
   d.Wc16 = h->d_Wc16; d.mx_cdescale = h->mx_cdescale; d.Wl16 = h->d_Wl16; d.mx_ldescale = h->mx_ldescale;
   d.Wq16 = h->d_Wq16; d.mx_qdescale = h->mx_qdescale; d.W1c16 = h->d_W1c16; d.mx_c1descale = h->mx_c1descale;
-  h->lpersist = (persist_ok && dec_persist_supported(d)) ? 1 : 0;
-  if (persist_ok && !h->lpersist) return fail(h, RV_ESTATE, "internal: persistent decode predicate mismatch");
+  h->lpersist = persist_att >= 0 ? 1 : 0;
   if (h->lpersist) { nsplit = 1; d.chunk_steps = h->d_chunk_steps; }
   h->lsplit = nsplit;
   if (!h->lpersist) {
