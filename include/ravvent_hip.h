@@ -221,6 +221,13 @@ int rv_set_option(rv_handle h, const char* key, int32_t value);
  *   "chunk_steps"     [B]         steps each chunk ran in the persistent decode (its beams all finished there)
  *   "step_alignments" [S,B,W,T_m] (needs debug_taps)
  *   "step_ids" / "parent_ids" / "step_scores" [S,B,W]
+ *   "kernel_forms"    [n,5]       the kernel instantiations the handle's own context launched in its last call, each once, as rows
+ *                                 (kernel, p1, p2, p3, p4), unused parameters 0: kernel 0 k_dec_persist (W, NIT, D, ATT), 1 k_dec_attend_flash
+ *                                 (W, NT), 2 k_dec_attend (W, TB), 3 k_lstm_rec (BT, F), 4 k_lstm_rec_tw (BT, F), 5 k_lstm_rec_proj (BT, SB),
+ *                                 6 k_lstm_rec_mx (F, CH), 7 k_inproj_small (F).  Noted by the walk of each kernel's form list that launches
+ *                                 it; a per-step decode replayed from its captured hipGraph reports the forms of the capture.  After a call
+ *                                 that ran as a slab graph (option "slab_graph") it fails with RV_ESTATE
+ *   "kernel_form_list" [n,5]      every instantiation the form lists hold, in the same rows, whatever the last call was
  * n_written receives the element count; fails with RV_EINVAL if dst is too small. */
 int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, size_t* n_written);
 

@@ -12,6 +12,41 @@
 #define RV_MAX_BEAM 8
 #define RV_MAX_VOCAB 8
 
+// ---------------------------------------------------------------- kernel forms (rv_get_tensor "kernel_forms" / "kernel_form_list")
+// A launcher given a FormLog notes the instantiation it launches, from the same walk of its form list that launches it: one row
+// (kernel id, template parameters, zero-filled) per form, each row once.  Host code only.
+enum {
+  RV_K_DEC_PERSIST = 0,        // k_dec_persist<W, NIT, D, ATT>
+  RV_K_DEC_ATTEND_FLASH = 1,   // k_dec_attend_flash<W, NT>
+  RV_K_DEC_ATTEND = 2,         // k_dec_attend<W, TB, 4 TB>: (W, TB)
+  RV_K_LSTM_REC = 3,           // k_lstm_rec<BT, F>
+  RV_K_LSTM_REC_TW = 4,        // k_lstm_rec_tw<BT, F>
+  RV_K_LSTM_REC_PROJ = 5,      // k_lstm_rec_proj<BT, SB>
+  RV_K_LSTM_REC_MX = 6,        // k_lstm_rec_mx<F, CH>
+  RV_K_INPROJ_SMALL = 7,       // k_inproj_small<F>
+};
+#define RV_FORM_ROWS 512
+struct FormLog {
+  int n = 0;
+  bool full = false;           // a row did not fit (rv_get_tensor then fails rather than answer with a short table)
+  int row[RV_FORM_ROWS][5];
+  void add(int k, int p1, int p2 = 0, int p3 = 0, int p4 = 0) {
+    for (int i = 0; i < n; ++i)
+      if (row[i][0] == k && row[i][1] == p1 && row[i][2] == p2 && row[i][3] == p3 && row[i][4] == p4) return;
+    if (n == RV_FORM_ROWS) { full = true; return; }
+    int* r = row[n++];
+    r[0] = k; r[1] = p1; r[2] = p2; r[3] = p3; r[4] = p4;
+  }
+  void merge(const FormLog& o) {
+    for (int i = 0; i < o.n; ++i) add(o.row[i][0], o.row[i][1], o.row[i][2], o.row[i][3], o.row[i][4]);
+    full = full || o.full;
+  }
+};
+// every instantiation the form lists hold, whatever a call would pick (the lists are walked; no kernel is named)
+void list_rec_forms(FormLog& log);
+void list_mx_forms(FormLog& log);
+void list_decode_forms(FormLog& log);
+
 // ---------------------------------------------------------------- K1: BiLSTM recurrence
 struct RecArgs {
   const float* x;        // F>0: chunk input [B,T,F];  F==0: pre-projected xw [B,T,2,512] (bias folded)
@@ -44,22 +79,23 @@ struct RecArgs {
 // only addresses that change from call to call.
 enum { RV_PTAB_RAW = 0, RV_PTAB_EVENT = 1, RV_PTAB_TOKENS = 2, RV_PTAB_OUT2 = 3, RV_PTAB_N = 4 };
 // F in {0,1,5}; rows_per_block in {1,2,4,8}
-void launch_lstm_rec(const RecArgs& a, int F, int rows_per_block, hipStream_t s);
+void launch_lstm_rec(const RecArgs& a, int F, int rows_per_block, hipStream_t s, FormLog* log = nullptr);
 // layers >= 1 with x . W + b computed inside the kernel (MFMA waves beside the recurrence waves): a.x = [B,T,256] activations,
 // a.Wp / a.bias per direction
-void launch_lstm_rec_proj(const RecArgs& a, int rows_per_block, hipStream_t s);
+void launch_lstm_rec_proj(const RecArgs& a, int rows_per_block, hipStream_t s, FormLog* log = nullptr);
 // Matrix-pipe recurrence, RV_MX_ROWS chunks of one direction per workgroup (lstm_mx.hip).  F == 1: raw layer 0 (a.x = chunk inputs
 // [B,T,1], a.W / a.bias per direction); F == 0: a.x = pre-projected inputs xw [B,T,2,512] (bias folded).  Needs a.Ua.
 #define RV_MX_ROWS 16
 #define RV_UA_SLOT ((size_t)2 * RV_U * RV_G + 2 * RV_G)
-void launch_lstm_rec_mx(const RecArgs& a, int F, hipStream_t s, bool rows8 = false);   // rows8: eight chunks per workgroup (latency form)
+void launch_lstm_rec_mx(const RecArgs& a, int F, hipStream_t s, bool rows8 = false, FormLog* log = nullptr);   // rows8: eight chunks per workgroup (latency form)
 bool lstm_rec_mx_window_fits(int T, int F = 1);   // layer 0 with its input projection in the lane: do the input windows of a workgroup's chunks fit in LDS?
 hipError_t configure_mx_kernels();
 // xw [rows,2,512] = x [rows,F] . W_dir [F,512] + b_dir for a layer-0 encoder with F = 5 (or 1) input features, both directions
 // mask != null: also writes utils.input_mask of the rows, mask[(r / T) * mask_T + mask_t0 + r % T] = all(x[r, :] != pad)
 // xtab != null: x is read from xtab[RV_PTAB_EVENT] (F == 5) / xtab[RV_PTAB_RAW] (F == 1) on the device instead
 void launch_inproj_small(const float* x, int rows, int F, const float* W0, const float* b0, const float* W1, const float* b1, float* xw,
-                         uint8_t* mask, int T, int mask_T, int mask_t0, float pad, hipStream_t s, const void* const* xtab = nullptr);
+                         uint8_t* mask, int T, int mask_T, int mask_t0, float pad, hipStream_t s, const void* const* xtab = nullptr,
+                         FormLog* log = nullptr);
 hipError_t configure_rec_kernels();   // dynamic-LDS opt-in of the recurrence kernels; first error or hipSuccess
 // layer 0 stages its chunks' whole input windows in LDS: does a window of T steps x F features fit with that many rows per workgroup?
 bool lstm_rec_window_fits(int F, int rows_per_block, int T);
@@ -177,7 +213,7 @@ void launch_dec_init(const DecState& d, hipStream_t s);
 void launch_dec_cell(const DecState& d, int layer, const float* WcatT /*[512,256] = ([W_in;U])^T*/, const float* Wtok /*[V,512]*/,
                      const float* bias /*[512]*/, int step, hipStream_t s);
 // flash: single-pass Luong attend over `values` only (WmemT = W_mem^T [128,256]); else the two-pass kernel
-void launch_dec_attend(const DecState& d, const float* WmemT, bool flash, int step, hipStream_t s);
+void launch_dec_attend(const DecState& d, const float* WmemT, bool flash, int step, hipStream_t s, FormLog* log = nullptr);
 // Persistent decode (Luong beam search with W <= 8, W <= 5 with two stacked cells; greedy search; no taps): the whole loop in
 // one launch, the chunk's attention memory resident in registers; also writes S_dev[0..1].  d.values must point at the
 // PROJECTED memory [B,Tm,256] = enc_output . [W_mem | A_c] (keys | attention-layer image of the values).
@@ -189,7 +225,8 @@ void launch_dec_attend(const DecState& d, const float* WmemT, bool flash, int st
 // one cell)), or -1 when no instantiation serves the call or its LDS does not fit.  W: the effective beam (1 for greedy search).
 int dec_persist_form(int attention, int depth, int W, int Tm, bool greedy, bool matrix_attention, bool matrix_cell);
 void launch_dec_persist(const DecState& d, const float* Wcat /*[256,512]*/, const float* Wtok /*[V,512]*/,
-                        const float* bdec /*[512]*/, const float* Wcat1, const float* bdec1, const float* Nh, hipStream_t s);
+                        const float* bdec /*[512]*/, const float* Wcat1, const float* bdec1, const float* Nh, hipStream_t s,
+                        FormLog* log = nullptr);
 // ptab != null: the two output addresses are read from ptab[RV_PTAB_TOKENS] / ptab[RV_PTAB_OUT2] on the device instead
 void launch_dec_finalize(const DecState& d, int32_t* tokens /*[B,L-1]*/, float* scores_or_logits, hipStream_t s, const void* const* ptab = nullptr);
 struct DecParts { const int* nfin[4]; int B[4]; int n; int steps; int* S_dev; int* S_host; };

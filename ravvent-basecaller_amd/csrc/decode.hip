@@ -2259,8 +2259,24 @@ template <typename Fn> bool for_each_attend_form(Fn&& fn) {
   return attend_w<1>(fn) || attend_w<2>(fn) || attend_w<3>(fn) || attend_w<4>(fn) || attend_w<5>(fn) || attend_w<6>(fn) ||
          attend_w<7>(fn) || attend_w<8>(fn);
 }
+// (the flash forms of W 6-8 are listed and opted in, but a call only takes the single-pass attend with an effective beam <= 5:
+// ravvent_hip.cpp, record_slab, lflash)
+template <typename F> bool attend_serves(int W, bool flash, int NT, int Tm) {
+  if constexpr (F::FLASH) return F::W == W && flash && F::NT == NT;
+  else return F::W == W && !flash && Tm <= 32 * F::TB;
+}
 
 }  // namespace
+
+void list_decode_forms(FormLog& log) {
+  for_each_persist_form([&](auto f) { using F = decltype(f); log.add(RV_K_DEC_PERSIST, F::W, F::NIT, F::D, F::ATT); return false; });
+  for_each_attend_form([&](auto f) {
+    using F = decltype(f);
+    if constexpr (F::FLASH) log.add(RV_K_DEC_ATTEND_FLASH, F::W, F::NT);
+    else log.add(RV_K_DEC_ATTEND, F::W, F::TB);
+    return false;
+  });
+}
 
 int dec_persist_form(int attention, int depth, int W, int Tm, bool greedy, bool matrix_attention, bool matrix_cell) {
   const bool mxc = matrix_attention && matrix_cell;
@@ -2270,12 +2286,13 @@ int dec_persist_form(int attention, int depth, int W, int Tm, bool greedy, bool 
   return sizeof(float) * PersistLds(W, depth, att).total + persist_static_lds(att) <= 160 * 1024 ? att : -1;
 }
 void launch_dec_persist(const DecState& d, const float* Wcat, const float* Wtok, const float* bdec,
-                        const float* Wcat1, const float* bdec1, const float* Nh, hipStream_t s) {
+                        const float* Wcat1, const float* bdec1, const float* Nh, hipStream_t s, FormLog* log) {
   for_each_persist_form([&](auto f) {
     using F = decltype(f);
     if (!persist_serves<F>(d.W, d.depth, d.persist_att, d.Tm)) return false;
     hipLaunchKernelGGL((k_dec_persist<F::W, F::NIT, F::D, F::ATT>), dim3(d.B), dim3(512), sizeof(float) * PersistLds(F::W, F::D, F::ATT).total, s,
                        d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh);
+    if (log) log->add(RV_K_DEC_PERSIST, F::W, F::NIT, F::D, F::ATT);
     return true;
   });
   // (S = max over chunk_steps is taken by k_dec_finalize)
@@ -2300,18 +2317,18 @@ void launch_dec_cell(const DecState& d, int layer, const float* WcatT, const flo
   const size_t shm = sizeof(float) * CELL_LDS_FLOATS;
   hipLaunchKernelGGL(k_dec_cell, dim3(RV_U / 16, (N + CELL_ROWS - 1) / CELL_ROWS), dim3(512), shm, s, d, layer, WcatT, Wtok, bias, step);
 }
-void launch_dec_attend(const DecState& d, const float* WmemT, bool flash, int step, hipStream_t s) {
+void launch_dec_attend(const DecState& d, const float* WmemT, bool flash, int step, hipStream_t s, FormLog* log) {
   // flash: more chunks than CUs -> two 256-thread workgroups per CU overlap each other's phases
   const int NT = (d.attend_threads ? d.attend_threads == 256 : d.B > 320) ? 256 : 512;
   for_each_attend_form([&](auto f) {
     using F = decltype(f);
-    if (F::W != d.W || F::FLASH != flash) return false;
+    if (!attend_serves<F>(d.W, flash, NT, d.Tm)) return false;
     if constexpr (F::FLASH) {
-      if (F::NT != NT) return false;
       hipLaunchKernelGGL((k_dec_attend_flash<F::W, F::NT>), dim3(d.B), dim3(F::NT), sizeof(float) * AttLds(F::W, 0, true, F::NT).total, s, d, WmemT, step);
+      if (log) log->add(RV_K_DEC_ATTEND_FLASH, F::W, F::NT);
     } else {
-      if (d.Tm > 32 * F::TB) return false;
       hipLaunchKernelGGL((k_dec_attend<F::W, F::TB, F::TD>), dim3(d.B), dim3(ATT_THREADS), sizeof(float) * AttLds(F::W, (d.Tm + 3) & ~3, false).total, s, d, step);
+      if (log) log->add(RV_K_DEC_ATTEND, F::W, F::TB);
     }
     return true;
   });

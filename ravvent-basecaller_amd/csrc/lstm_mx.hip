@@ -292,10 +292,19 @@ __global__ __launch_bounds__(256) void k_inproj_small(const float* __restrict__ 
 // the instantiations of k_lstm_rec_mx, (F, CH): adding or removing a form is this one line
 template <int F_, int CH_> struct MxForm { static constexpr int F = F_, CH = CH_; };
 template <typename Fn> void for_each_mx_form(Fn&& fn) { fn(MxForm<0, 16>{}); fn(MxForm<1, 16>{}); fn(MxForm<5, 16>{}); fn(MxForm<0, 8>{}); fn(MxForm<1, 8>{}); fn(MxForm<5, 8>{}); }
+template <typename M> bool mx_serves(int F, int CH) { return M::F == F && M::CH == CH; }
+// ... and of k_inproj_small<F>: fn with each form in turn until it returns true
+template <int F_> struct InprojForm { static constexpr int F = F_; };
+template <typename Fn> bool for_each_inproj_form(Fn&& fn) { return fn(InprojForm<5>{}) || fn(InprojForm<1>{}); }
 
 constexpr size_t mx_lds_bytes(int F, int T) { return 16384 + sizeof(float) * ((size_t)RV_G + (F > 0 ? (size_t)(F + 1) * RV_G + (size_t)RV_MX_ROWS * T * F : 2 * RV_G)); }
 
 }  // namespace
+
+void list_mx_forms(FormLog& log) {
+  for_each_mx_form([&](auto form) { using M = decltype(form); log.add(RV_K_LSTM_REC_MX, M::F, M::CH); });
+  for_each_inproj_form([&](auto form) { log.add(RV_K_INPROJ_SMALL, decltype(form)::F); return false; });
+}
 
 bool lstm_rec_mx_window_fits(int T, int F) { return mx_lds_bytes(F, T) <= 160 * 1024; }
 
@@ -309,18 +318,25 @@ hipError_t configure_mx_kernels() {
   return first;
 }
 
-void launch_lstm_rec_mx(const RecArgs& a, int F, hipStream_t s, bool rows8) {
+void launch_lstm_rec_mx(const RecArgs& a, int F, hipStream_t s, bool rows8, FormLog* log) {
   const int CH = rows8 ? 8 : RV_MX_ROWS;                         // eight chunks per workgroup: the latency form (see the head of this file)
   for_each_mx_form([&](auto form) {
     using M = decltype(form);
-    if (M::F == F && M::CH == CH)
+    if (mx_serves<M>(F, CH)) {
       hipLaunchKernelGGL((k_lstm_rec_mx<M::F, M::CH>), dim3((a.B + CH - 1) / CH, 2), dim3(512), mx_lds_bytes(M::F, a.T), s, a);
+      if (log) log->add(RV_K_LSTM_REC_MX, M::F, M::CH);
+    }
   });
 }
 
 void launch_inproj_small(const float* x, int rows, int F, const float* W0, const float* b0, const float* W1, const float* b1, float* xw,
-                         uint8_t* mask, int T, int mask_T, int mask_t0, float pad, hipStream_t s, const void* const* xtab) {
+                         uint8_t* mask, int T, int mask_T, int mask_t0, float pad, hipStream_t s, const void* const* xtab, FormLog* log) {
   const int grid = rows < 4096 ? rows : 4096;
-  if (F == 5) hipLaunchKernelGGL((k_inproj_small<5>), dim3(grid), dim3(256), 0, s, x, rows, W0, b0, W1, b1, xw, mask, T, mask_T, mask_t0, pad, xtab);
-  else hipLaunchKernelGGL((k_inproj_small<1>), dim3(grid), dim3(256), 0, s, x, rows, W0, b0, W1, b1, xw, mask, T, mask_T, mask_t0, pad, xtab);
+  for_each_inproj_form([&](auto form) {
+    using P = decltype(form);
+    if (P::F != F) return false;
+    hipLaunchKernelGGL((k_inproj_small<P::F>), dim3(grid), dim3(256), 0, s, x, rows, W0, b0, W1, b1, xw, mask, T, mask_T, mask_t0, pad, xtab);
+    if (log) log->add(RV_K_INPROJ_SMALL, P::F);
+    return true;
+  });
 }

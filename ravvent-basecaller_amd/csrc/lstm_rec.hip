@@ -715,8 +715,17 @@ template <typename Fn> bool for_each_proj_form(Fn&& fn) {    // k_lstm_rec_proj<
          fn(ProjForm<1, 1>{}) || fn(ProjForm<2, 1>{}) || fn(ProjForm<4, 1>{}) || fn(ProjForm<8, 1>{}) ||
          fn(ProjForm<1, 2>{}) || fn(ProjForm<2, 2>{}) || fn(ProjForm<4, 2>{}) || fn(ProjForm<8, 2>{});
 }
+// the form of a list that a launch with BT chunks per workgroup and F input features (RecForm) / projection weights SB (ProjForm) takes
+template <typename R> bool rec_serves(int BT, int F) { return R::BT == BT && R::F == F; }
+template <typename P> bool proj_serves(int BT, int SB) { return P::BT == BT && P::SB == SB; }
 
 }  // namespace
+
+void list_rec_forms(FormLog& log) {
+  for_each_rec_form([&](auto f) { using R = decltype(f); log.add(RV_K_LSTM_REC, R::BT, R::F); return false; });
+  for_each_tw_form([&](auto f) { using R = decltype(f); log.add(RV_K_LSTM_REC_TW, R::BT, R::F); return false; });
+  for_each_proj_form([&](auto f) { using P = decltype(f); log.add(RV_K_LSTM_REC_PROJ, P::BT, P::SB); return false; });
+}
 
 hipError_t configure_rec_kernels() {
   hipError_t first = hipSuccess;
@@ -740,13 +749,14 @@ hipError_t configure_rec_kernels() {
   return first;
 }
 
-void launch_lstm_rec_proj(const RecArgs& a, int rows_per_block, hipStream_t s) {
+void launch_lstm_rec_proj(const RecArgs& a, int rows_per_block, hipStream_t s, FormLog* log) {
   const int SB = a.Wh[0] ? 2 : (a.Wsb[0] ? 1 : 0);
   const dim3 grid((a.B + rows_per_block - 1) / rows_per_block, 2);
   for_each_proj_form([&](auto f) {
     using P = decltype(f);
-    if (P::BT != rows_per_block || P::SB != SB) return false;
+    if (!proj_serves<P>(rows_per_block, SB)) return false;
     hipLaunchKernelGGL((k_lstm_rec_proj<P::BT, P::SB>), grid, dim3(768), proj_lds_bytes(P::BT, P::SB), s, a);
+    if (log) log->add(RV_K_LSTM_REC_PROJ, P::BT, P::SB);
     return true;
   });
 }
@@ -754,19 +764,21 @@ bool lstm_rec_window_fits(int F, int rows_per_block, int T) {
   return one_lds_bytes(rows_per_block, F, T) <= REC_LDS_CAP;     // launch_lstm_rec falls back to the 8-wave form when the tail-wave form does not fit
 }
 
-void launch_lstm_rec(const RecArgs& a, int F, int rows_per_block, hipStream_t s) {
+void launch_lstm_rec(const RecArgs& a, int F, int rows_per_block, hipStream_t s, FormLog* log) {
   const dim3 grid((a.B + rows_per_block - 1) / rows_per_block, 2);
   // the tail-wave form where there is one (a.tail_wave); it stages 12 KB more per 8 rows than the 8-wave form: very long windows fall back to the latter
   const bool tw = a.tail_wave && tw_lds_bytes(rows_per_block, F, a.T) <= REC_LDS_CAP && for_each_tw_form([&](auto f) {
     using R = decltype(f);
-    if (R::BT != rows_per_block || R::F != F) return false;
+    if (!rec_serves<R>(rows_per_block, F)) return false;
     hipLaunchKernelGGL((k_lstm_rec_tw<R::BT, R::F>), grid, dim3(768), tw_lds_bytes(R::BT, R::F, a.T), s, a);
+    if (log) log->add(RV_K_LSTM_REC_TW, R::BT, R::F);
     return true;
   });
   if (!tw) for_each_rec_form([&](auto f) {
     using R = decltype(f);
-    if (R::BT != rows_per_block || R::F != F) return false;
+    if (!rec_serves<R>(rows_per_block, F)) return false;
     hipLaunchKernelGGL((k_lstm_rec<R::BT, R::F>), grid, dim3(512), one_lds_bytes(R::BT, R::F, a.T), s, a);
+    if (log) log->add(RV_K_LSTM_REC, R::BT, R::F);
     return true;
   });
 }

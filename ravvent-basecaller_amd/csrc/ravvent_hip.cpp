@@ -147,6 +147,9 @@ struct RvContext {
 
   // last call
   int lB = 0, lW = 0, lTm = 0, lL = 0, lS = 0, lgreedy = 0, ltaps = 0;
+  FormLog lforms;                           // the kernel instantiations it launched ("kernel_forms"); lforms_ok = 0: it ran as a slab graph
+  int lforms_ok = 1;
+  std::map<GraphKey, FormLog> graph_forms;  // ... those a captured decode graph of `graphs` launches (recorded at its capture)
 
   // asynchronous calls (rv_beam_search_submit* / rv_beam_search_collect*): the handle owns `kids` more slab contexts -- own stream,
   // own buffers, the PARENT's weights and derived images -- so that several slabs are in flight on the GPU at once
@@ -352,14 +355,14 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
         a.ptab = ptab;
         a.dbg_ts = (e == 0 && h->rec_ts_layer == 0) ? h->rec_ts : nullptr;     // (RV_REC_STAMPS=1: phase cycle sums of workgroup (0, 0))
         Scope sc(h, F == 1 ? "lstm_rec_raw_l0" : "lstm_rec_event_l0", s);
-        launch_lstm_rec_mx(a, F, s, h->lrows8 != 0);
+        launch_lstm_rec_mx(a, F, s, h->lrows8 != 0, &h->lforms);
         a.dbg_ts = nullptr; a.ptab = nullptr; a.mask = nullptr;
         continue;
       }
       if (l == 0) {
         Scope sc(h, e == 0 ? "inproj_raw_l0" : "inproj_event_l0", s);
         launch_inproj_small(x, B * T, F, h->enc[e][0][0].W, h->enc[e][0][0].b, h->enc[e][0][1].W, h->enc[e][0][1].b, h->xw[e],
-                            h->mask, T, Tm, t_off, h->cfg.padding_value, s, ptab);
+                            h->mask, T, Tm, t_off, h->cfg.padding_value, s, ptab, &h->lforms);
       } else {
         Scope sc(h, e == 0 ? "gemm_inproj_raw" : "gemm_inproj_event", s);
         launch_gemm_split_blocks(h->act[e][(l - 1) & 1], B * T, h->d_Wx16 + (size_t)(e * (depth - 1) + (l - 1)) * RV_WX16_SLOT, 4,
@@ -368,7 +371,7 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
       a.x = h->xw[e];
       a.dbg_ts = (e == 0 && l == 1 && h->rec_ts_layer == 1) ? h->rec_ts : nullptr;    // (RV_REC_STAMPS=2)
       Scope sc(h, l == 0 ? "lstm_rec_event_l0" : (e == 0 ? "lstm_rec_raw_l1p" : "lstm_rec_event_l1p"), s);
-      launch_lstm_rec_mx(a, 0, s, h->lrows8 != 0);
+      launch_lstm_rec_mx(a, 0, s, h->lrows8 != 0, &h->lforms);
       a.dbg_ts = nullptr;
       continue;
     }
@@ -378,7 +381,7 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
       Scope sc(h, e == 0 ? "lstm_rec_raw_l0" : "lstm_rec_event_l0", s);
       a.tail_wave = h->opt_tail_wave;
       a.dbg_ts = (e == 0 && h->rec_ts_layer == 0) ? h->rec_ts : nullptr;
-      launch_lstm_rec(a, F, bt, s);
+      launch_lstm_rec(a, F, bt, s, &h->lforms);
       a.dbg_ts = nullptr;
     } else {
       const float* in = h->act[e][(l - 1) & 1];
@@ -393,7 +396,7 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
         }
         a.dbg_ts = (e == 0 && l == 1 && h->rec_ts_layer == 1) ? h->rec_ts : nullptr;
         Scope sc(h, e == 0 ? "lstm_rec_raw_l1p" : "lstm_rec_event_l1p", s);
-        launch_lstm_rec_proj(a, bt, s);
+        launch_lstm_rec_proj(a, bt, s, &h->lforms);
         continue;
       }
       {   // both directions in ONE launch (same A): 2x the workgroups -> less round quantisation
@@ -408,12 +411,12 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
       }
       a.x = h->xw[e];
       Scope sc(h, e == 0 ? "lstm_rec_raw_l1p" : "lstm_rec_event_l1p", s);
-      launch_lstm_rec(a, 0, bt, s);
+      launch_lstm_rec(a, 0, bt, s, &h->lforms);
     }
   }
 }
 
-void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool profiled) {
+void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool profiled, FormLog* log) {
   const bool flash = h->lflash != 0;
   auto cells = [&](int step, bool prof) {
     for (int k = 0; k < d.depth; ++k) {
@@ -425,10 +428,10 @@ void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool pr
   for (int step = 0; step < d.L - 1; ++step) {
     if (profiled) {
       cells(step, true);
-      { Scope sc(h, "dec_attend"); launch_dec_attend(d, h->d_WmemT, flash, step, s); }
+      { Scope sc(h, "dec_attend"); launch_dec_attend(d, h->d_WmemT, flash, step, s, log); }
     } else {
       cells(step, false);
-      launch_dec_attend(d, h->d_WmemT, flash, step, s);
+      launch_dec_attend(d, h->d_WmemT, flash, step, s, log);
     }
   }
 }
@@ -469,6 +472,7 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
   if (dev_out && B > 0 && L > 1 && (!tokens || !out2)) return fail(h, RV_EINVAL, "null output pointer");
   HIPCHK(h, hipSetDevice(c.device));
   h->lB = B; h->lW = W; h->lL = L; h->lS = 0; h->lgreedy = greedy; h->lTm = T_r + T_e; h->ltaps = h->opt_taps; h->lptaps = h->opt_ptaps;
+  h->lforms.n = 0; h->lforms.full = false; h->lforms_ok = 1;
   h->pend = RvContext::PendingCall{};
   h->pend.busy = true; h->pend.greedy = greedy; h->pend.dev_out = dev_out; h->pend.calls = calls;
   h->pend.B = B; h->pend.steps = std::max(L - 1, 0); h->pend.V = c.vocab; h->pend.Wd = greedy ? 1 : W;
@@ -503,6 +507,7 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
   const bool graphable = root->opt_slab_graph && h->lwide && !h->lrows8 && persist_form(h, greedy, W, T_r + T_e) >= 0 && h->opt_profile == 0 && !h->opt_taps &&
                          !h->opt_ptaps && !h->rec_ts && !h->dec_st.dbg_ts && h->d_ptab;
   if (!graphable) return record_slab(h, xr, xe, !dev_in, B, T_r, T_e, W, L, greedy, tk, o2, dev_out, lut, nullptr);
+  h->lforms_ok = 0;                             // (a slab graph replays without the host launchers: "kernel_forms" answers RV_ESTATE)
   h->pin_ptab[RV_PTAB_RAW] = xr; h->pin_ptab[RV_PTAB_EVENT] = xe; h->pin_ptab[RV_PTAB_TOKENS] = tk; h->pin_ptab[RV_PTAB_OUT2] = o2;
   SlabKey key{B, T_r, T_e, W, L, (greedy ? 1 : 0) | (calls ? 2 : 0) | (dev_in ? 0 : 4) | (dev_out ? 0 : 8), 0};
   if (calls) memcpy(&key.lut, lut, std::min<size_t>(sizeof key.lut, (size_t)c.vocab));
@@ -694,12 +699,12 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     parts.nfin[g] = p.nfin; parts.B[g] = p.B;
     if (!h->lpersist) launch_dec_init(p, s);
   }
-  auto enqueue_steps = [&](bool profiled) -> int {
+  auto enqueue_steps = [&](bool profiled, FormLog* log) -> int {
     for (int g = 1; g < nsplit; ++g) {
       HIPCHK(h, hipEventRecord(h->ev_fork, s));
       HIPCHK(h, hipStreamWaitEvent(side_stream(h, g - 1), h->ev_fork, 0));
     }
-    for (int g = 0; g < nsplit; ++g) launch_decode_steps(h, part[g], g == 0 ? s : side_stream(h, g - 1), profiled && nsplit == 1);
+    for (int g = 0; g < nsplit; ++g) launch_decode_steps(h, part[g], g == 0 ? s : side_stream(h, g - 1), profiled && nsplit == 1, log);
     for (int g = 1; g < nsplit; ++g) {
       HIPCHK(h, hipEventRecord(h->ev_join[g - 1], side_stream(h, g - 1)));
       HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[g - 1], 0));
@@ -723,7 +728,7 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     d.mx_uscale = h->mx_uscale; d.mx_udescale = std::ldexp(1.0f, -14) / h->mx_uscale;
     Scope sc(h, "dec_persist", nullptr, true);
     launch_dec_persist(d, d.depth > 1 ? h->dec[0].W + (size_t)V * RV_G : h->d_Wcat2, h->dec[0].W, h->dec[0].b,
-                       d.depth > 1 ? h->dec[1].W : nullptr, d.depth > 1 ? h->dec[1].b : nullptr, h->d_Nh, s);
+                       d.depth > 1 ? h->dec[1].W : nullptr, d.depth > 1 ? h->dec[1].b : nullptr, h->d_Nh, s, &h->lforms);
   } else if (h->opt_graph && h->opt_profile != 2) {
     GraphKey key{B, d.W, Tm, L, greedy ? 1 : 0, h->opt_taps * 2 + h->lflash + 4 * h->opt_att_nt + 4096 * (d.step_logits ? 1 : 0) + 8192 * (d.persist_align ? 1 : 0), nsplit};   // every captured pointer that can change is in the key
     auto it = h->graphs.find(key);
@@ -731,10 +736,13 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
       if (h->graphs.size() >= 32) {      // bound the cache (callers with ever-changing slab shapes)
         for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
         h->graphs.clear();
+        h->graph_forms.clear();
       }
+      FormLog& gforms = h->graph_forms[key];
+      gforms.n = 0; gforms.full = false;
       hipGraph_t graph = nullptr;
       HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      const int rc = enqueue_steps(false);
+      const int rc = enqueue_steps(false, &gforms);
       hipError_t ce = hipStreamEndCapture(s, &graph);
       if (rc != RV_OK) return rc;
       HIPCHK(h, ce);
@@ -743,12 +751,13 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
       hipGraphDestroy(graph);
       it = h->graphs.emplace(key, exec).first;
     }
+    h->lforms.merge(h->graph_forms[key]);      // the launches of the graph's capture: it replays those
     Scope sc(h, "decode_graph", nullptr, true);
     HIPCHK(h, hipGraphLaunch(it->second, s));
   } else {
     if (h->opt_profile == 2) nsplit = 1, parts.n = 1;     // per-kernel events need one stream
     if (nsplit == 1) { part[0] = d; part[0].part = 0; part[0].nfin = d.nfin; parts.nfin[0] = d.nfin; parts.B[0] = B; launch_dec_init(part[0], s); }
-    const int rc = enqueue_steps(h->opt_profile == 2);
+    const int rc = enqueue_steps(h->opt_profile == 2, &h->lforms);
     if (rc != RV_OK) return rc;
   }
 
@@ -1528,6 +1537,22 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     *n_written = 24;
     if (!dst || dst_floats < 24) return fail(h, RV_EINVAL, "rec_stamps needs 24 floats");
     for (int i = 0; i < 24; ++i) dst[i] = (float)ts[i];
+    return RV_OK;
+  }
+  else if (!strcmp(name, "kernel_forms") || !strcmp(name, "kernel_form_list")) {
+    FormLog all;
+    const FormLog* f = &h->lforms;
+    if (!strcmp(name, "kernel_form_list")) {
+      list_rec_forms(all); list_mx_forms(all); list_decode_forms(all);
+      f = &all;
+    } else if (!h->lforms_ok) {
+      return fail(h, RV_ESTATE, "kernel_forms: the last call replayed a slab graph (option slab_graph), which launches nothing on the host");
+    }
+    if (f->full) return fail(h, RV_EUNSUPPORTED, "%s: more than %d forms (raise RV_FORM_ROWS)", name, RV_FORM_ROWS);
+    *n_written = (size_t)5 * f->n;
+    if (*n_written && (!dst || dst_floats < *n_written)) return fail(h, RV_EINVAL, "%s needs %zu floats", name, *n_written);
+    for (int i = 0; i < f->n; ++i)
+      for (int j = 0; j < 5; ++j) dst[5 * i + j] = (float)f->row[i][j];
     return RV_OK;
   }
   else if (!strcmp(name, "dbg_stamps")) {
