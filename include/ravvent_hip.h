@@ -59,7 +59,7 @@ typedef struct RvConfig {
   int32_t dec_depth;      /* StackedRNNCells depth                       basecaller.py:85-91 */
   int32_t mode;           /* RV_MODE_*                                                    */
   int32_t attention;      /* RV_ATT_*                                                     */
-  int32_t vocab;          /* len(tokenizer.word_index) = 7               basecaller.py:189 */
+  int32_t vocab;          /* len(tokenizer.word_index) = 7 (2..8; the ids below may coincide)  basecaller.py:189 */
   int32_t start_token;    /* '$' = 2   basecaller.py:204 */
   int32_t end_token;      /* '^' = 1   basecaller.py:205 */
   int32_t pad_token;      /* ''  = 0   basecaller.py:206 */
@@ -68,7 +68,7 @@ typedef struct RvConfig {
   int32_t max_raw_len;    /* T_r upper bound */
   int32_t max_event_len;  /* T_e upper bound */
   int32_t max_output_len; /* L upper bound (decode runs at most L-1 steps) */
-  int32_t max_beam;       /* beam width upper bound (<= 8) */
+  int32_t max_beam;       /* beam width upper bound (1..8; Basecaller(max_beam=...), default 8): wider calls fail with RV_EINVAL */
   int32_t device;         /* HIP device ordinal */
 } RvConfig;
 
@@ -108,7 +108,7 @@ int rv_beam_search_dev(rv_handle h, const float* d_raw, const float* d_event, in
  *   lut[vocab]: token id -> upper-case ASCII letter, 0 for ids the string form drops ('', '^', '$');
  *   bases [B, L-1] u8: the chunk's letters compacted to the front (zero-filled tail);
  *   lengths [B] i32: letters per chunk;  probs [B, L-1] f32: exp(score_t - score_{t-1}), score_{-1} = 0
- *   (the reference pairs a chunk's string with probs[:len(string)]).  Host buffers. */
+ *   (the reference pairs a chunk's string with probs[:len(string)]); columns >= S of probs are 0.  Host buffers. */
 int rv_beam_search_calls(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r,
                          int32_t T_e, int32_t W, int32_t L, const uint8_t* lut, uint8_t* bases,
                          int32_t* lengths, float* probs, int32_t* S_out);

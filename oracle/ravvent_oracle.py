@@ -291,11 +291,13 @@ def greedy_search(weights, cfg, raw, event, max_output_len, dtype=np.float64, ta
 INDEX_WORD = {0: "", 1: "^", 2: "$", 3: "a", 4: "c", 5: "g", 6: "t"}  # data_loader.py:20-22
 
 
-def tokens_to_nuc_sequences(tokens):
-    """Basecaller.tokens_to_nuc_sequences (/root/reference/basecaller.py:289-294)."""
+def tokens_to_nuc_sequences(tokens, index_word=None):
+    """Basecaller.tokens_to_nuc_sequences (/root/reference/basecaller.py:289-294); ``index_word``: the tokenizer's own map
+    (default: the reference's hand-set vocabulary)."""
+    index_word = INDEX_WORD if index_word is None else index_word
     out = []
     for row in np.asarray(tokens):
-        text = " ".join(INDEX_WORD[int(t)] for t in row if int(t) in INDEX_WORD)
+        text = " ".join(index_word[int(t)] for t in row if int(t) in index_word)
         out.append(text.replace(" ", "").replace("^", "").replace("$", "").upper())
     return out
 

@@ -18,7 +18,7 @@ import torch
 
 from . import _capi, weights as _weights
 from .config import RvConfig, RAW_FEATURES, EVENT_FEATURES
-from .data_loader import tokens_to_strings
+from .data_loader import nuc_tk, tokens_to_strings
 
 
 def _as_int(x) -> int:
@@ -34,9 +34,10 @@ class Basecaller:
                  rnn_type: str = "bilstm", teacher_forcing=True, attention_type: str = "luong",
                  beam_width: int = 5, *, device: int | None = None, max_batch: int = 1024,
                  max_raw_len: int = 300, max_event_len: int = 45, max_output_len: int = 64,
-                 honor_attention_type: bool = False):
+                 honor_attention_type: bool = False, max_beam: int = 8):
         """Positional / keyword arguments are those of the reference constructor
-        (basecaller.py:158).  Keyword-only extras size device memory.
+        (basecaller.py:158).  Keyword-only extras size device memory (``max_beam``: the widest beam
+        the handle will be asked for, 1..8).
 
         The reference hard-codes Luong attention when it builds its Decoder
         (basecaller.py:194) and only stores ``attention_type`` (:201); that behaviour is kept
@@ -66,11 +67,11 @@ class Basecaller:
             enc_units=enc_units, dec_units=dec_units, enc_depth=encoder_depth, dec_depth=decoder_depth,
             mode=input_data_type,
             attention=attention_type if honor_attention_type else "luong",
-            vocab=len(tokenizer.word_index),
+            vocab=len(set(tokenizer.word_index.values())),      # = len(word_index) unless two of '' ^ $ share an id
             start_token=int(self.output_start_token), end_token=int(self.output_end_token),
             pad_token=int(self.output_padding_token), padding_value=float(input_padding_value),
             max_batch=max_batch, max_raw_len=max_raw_len, max_event_len=max_event_len,
-            max_output_len=max_output_len, max_beam=8, device=device)
+            max_output_len=max_output_len, max_beam=int(max_beam), device=device)
         self.device = torch.device("cuda", device)
         self._lib = _capi.load_library()
         self._h = ctypes.c_void_p()
@@ -417,7 +418,11 @@ class Basecaller:
         """basecaller.py:289-294"""
         if isinstance(result_tokens, torch.Tensor):
             result_tokens = result_tokens.detach().cpu().numpy()
-        return tokens_to_strings(result_tokens)
+        if self.tokenizer.word_index == nuc_tk.word_index:
+            return tokens_to_strings(result_tokens)
+        table = np.zeros(256, np.uint8)
+        table[:8] = self._call_lut()                 # a custom tokenizer: its own letters, its own '' ^ $ dropped
+        return tokens_to_strings(result_tokens, table)
 
     # ------------------------------------------------------------------ debug taps / profile
     def get_tensor(self, name: str) -> np.ndarray:

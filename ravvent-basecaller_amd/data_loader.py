@@ -45,13 +45,14 @@ _ASCII = np.zeros(256, np.uint8)
 _ASCII[3:7] = np.frombuffer(b"ACGT", np.uint8)
 
 
-def tokens_to_strings(tokens) -> list:
+def tokens_to_strings(tokens, table=None) -> list:
     """Vectorised equivalent of Basecaller.tokens_to_nuc_sequences
-    (/root/reference/basecaller.py:289-294): map ids to chars, drop '' ^ $, upper-case."""
+    (/root/reference/basecaller.py:289-294): map ids to chars, drop '' ^ $, upper-case.
+    ``table`` (u8[256], 0 = dropped): the id -> ASCII map of another tokenizer than `nuc_tk`."""
     t = np.asarray(tokens)
     if t.ndim == 1:
         t = t[None]
-    codes = _ASCII[np.clip(t, 0, 255).astype(np.uint8)]
+    codes = (_ASCII if table is None else table)[np.clip(t, 0, 255).astype(np.uint8)]
     keep = codes != 0
     flat = codes[keep].tobytes().decode("ascii")          # one decode for the whole slab
     ends = np.cumsum(keep.sum(axis=1)).tolist()

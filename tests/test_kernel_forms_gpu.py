@@ -78,32 +78,35 @@ def _assert_family_ran(bc, fam, ran):
           "".join(f"; excluded {r}: {EXCLUDED[r]}" for r in sorted(excluded)))
 
 
-def _slab(mode, Tr, Te, seed):
+def _slab(mode, Tr, Te, seed, pad=0.0):
     """B chunks over T_m = T_r + T_e memory steps: 0 unpadded; 1 suffix padding in both parts; 2 padding after its first step up to the
-    events (in joint mode the row groups after the first hold no live step until the events begin); 3 interior padding: zeros at the
-    row-group boundaries 31 / 32 / 63 / 64 and at T_r - 1, one event with exactly one feature 0.0, one with a -0.0 feature
-    (utils.input_mask: a step is padding when ANY feature equals the padding value, and -0.0 == 0.0); 4 live at T_m - 1 only; 5 unpadded."""
+    events (in joint mode the row groups after the first hold no live step until the events begin); 3 interior padding: padding at the
+    row-group boundaries 31 / 32 / 63 / 64 and at T_r - 1, one event with exactly one feature equal to the padding value, and -- when
+    the padding value is 0.0 -- one with a -0.0 feature (utils.input_mask: a step is padding when ANY feature equals the padding
+    value, and -0.0 == 0.0); 4 live at T_m - 1 only; 5 unpadded.  `pad` is the handle's input padding value."""
     rng = np.random.default_rng(seed)
     raw = rng.standard_normal((B, Tr, 1)).astype(np.float32)
     ev = rng.standard_normal((B, Te, 5)).astype(np.float32)
+    pad = np.float32(pad)
     if Tr:
-        raw[1, Tr - max(Tr // 3, 1):] = 0.0
+        raw[1, Tr - max(Tr // 3, 1):] = pad
     if Te:
-        ev[1, Te - max(Te // 3, 1):] = 0.0
-    (raw if Tr else ev)[2, 1:] = 0.0
+        ev[1, Te - max(Te // 3, 1):] = pad
+    (raw if Tr else ev)[2, 1:] = pad
     for t in (31, 32, 63, 64):
         if t < Tr:
-            raw[3, t] = 0.0
+            raw[3, t] = pad
         elif not Tr and t < Te:
-            ev[3, t, t % 5] = 0.0
+            ev[3, t, t % 5] = pad
     if Tr:
-        raw[3, Tr - 1] = 0.0
+        raw[3, Tr - 1] = pad
     if Te:
-        ev[3, Te // 2, 2] = 0.0
-        ev[3, Te - 1, 4] = -0.0
+        ev[3, Te // 2, 2] = pad
+        if pad == 0.0:
+            ev[3, Te - 1, 4] = -0.0
     last = (ev if Te else raw)[4, -1].copy()
-    raw[4] = 0.0
-    ev[4] = 0.0
+    raw[4] = pad
+    ev[4] = pad
     (ev if Te else raw)[4, -1] = last
     return raw, ev
 
@@ -116,11 +119,12 @@ def _oracle_inputs(mode, raw, ev):
     return (raw if mode != "event" else None), (ev if mode != "raw" else None)
 
 
-def _handle(rv, mode, attention, D, seed, Tr_max=308, Te_max=90, L=16, max_batch=B):
-    bc = rv.Basecaller(128, 128, 128, rv.data_loader.nuc_tk, mode, 0.0, decoder_depth=D, attention_type=attention,
-                       honor_attention_type=True, max_batch=max_batch, max_raw_len=Tr_max, max_event_len=Te_max, max_output_len=L)
+def _handle(rv, mode, attention, D, seed, Tr_max=308, Te_max=90, L=16, max_batch=B, tokenizer=None, pad=0.0, enc_depth=2, end_bias=0.05):
+    bc = rv.Basecaller(128, 128, 128, tokenizer or rv.data_loader.nuc_tk, mode, pad, encoder_depth=enc_depth, decoder_depth=D,
+                       attention_type=attention, honor_attention_type=True, max_batch=max_batch, max_raw_len=Tr_max,
+                       max_event_len=Te_max, max_output_len=L)
     flat = rv.weights.init_weights(bc.cfg, seed=seed, gain=1.5)
-    flat["b_fc"][bc.cfg.end_token] = 0.05                # chunks finish at different steps, some run all L - 1
+    flat["b_fc"][bc.cfg.end_token] = end_bias            # chunks finish at different steps, some run all L - 1
     bc.set_weights_flat(flat)
     return bc, rv.weights.flat_to_nested(bc.cfg, flat)
 
@@ -134,8 +138,8 @@ def _decode_forms(bc):
     return {r for r in _rows(bc, "kernel_forms") if r[0] in DECODE}
 
 
-def _beam(bc, x, W, L, Tm, persist):
-    """One beam search and its taps."""
+def _beam(bc, x, W, L, Tm, persist, V=V, B=B):
+    """One beam search and its taps (V: the handle's vocabulary, B: the slab's chunks)."""
     tok, sc = bc.beam_search_prediction(x, W, L)
     tok, sc = tok.numpy().copy(), sc.numpy().copy()
     S = tok.shape[1]
@@ -145,7 +149,7 @@ def _beam(bc, x, W, L, Tm, persist):
                 al=t("step_alignments", S, B, W, Tm), mask=t("mask", B, Tm))
 
 
-def _check_beam(oracle, r, o, otok, osc, W, end, tag):
+def _check_beam(oracle, r, o, otok, osc, W, end, tag, B=B):
     """A beam search against the fp64 decode of its slab: the mask exact; on every step where the beams still agree (_agreeing_steps)
     logits within 1e-4 and alignments by _check_alignments; a chunk whose beam ids or parents leave the fp64 decode sits on a genuine
     near-tie; the other chunks' tokens equal the oracle's and their scores are within 1e-4.  Returns the agreeing steps and the chunks

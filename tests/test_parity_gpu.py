@@ -351,7 +351,8 @@ def _emitting_flat(rv, cfg, seed=22, end_bias=-1.0):
     """Random weights biased to call bases (gain 3, base letters + 1.5, end token lowered): at Keras-default weights nearly every
     best hypothesis at BASELINE sizes is a row of end tokens, and "tokens identical" is then nearly free."""
     flat = rv.weights.init_weights(cfg, seed=seed, gain=3.0)
-    flat["b_fc"][3:7] += 1.5
+    letters = [t for t in range(cfg.vocab) if t not in (cfg.start_token, cfg.end_token, cfg.pad_token)]   # a c g t = 3..6 of nuc_tk
+    flat["b_fc"][letters] += 1.5
     flat["b_fc"][cfg.end_token] += end_bias
     return flat
 
