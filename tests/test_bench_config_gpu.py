@@ -17,7 +17,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
-TWIN_K, TWIN_C = 2.0, 5e-6   # adversarial recurrent kernels: max |enc_output - fp64| <= TWIN_K x the numpy fp32 twin's + TWIN_C
+TWIN_K, TWIN_C = 2.0, 5e-6   # max |tensor - fp64| <= TWIN_K x the numpy fp32 twin's + TWIN_C: the adversarial tests here, and every
+                             # fp64 comparison of a tapped tensor in the form / configuration / parity tests (test_parity_gpu._assert_twin)
 
 
 def _same(got, want):

@@ -1,4 +1,4 @@
-"""Every configuration the C-ABI accepts, held to the fp64 oracle.
+"""Every configuration the C-ABI accepts, held to the fp64 oracle (1e-4, and the twin-relative bound of test_parity_gpu._assert_twin).
 
 rv_create takes a vocabulary of 2..8 tokens, any start / end / pad id inside it, any input padding value, 1..8 encoder layers, 1..4
 decoder cells and a widest beam of 1..8; the other GPU modules run 7 tokens, ids 2 / 1 / 0, padding 0.0 and depths 1-3.  Here the
@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from test_parity_gpu import _emitting_flat
+from test_parity_gpu import _assert_twin, _emitting_flat, _memory_errors, _twin_beam, _twin_greedy
 from test_kernel_forms_gpu import (ATTEND, B, FLASH, FORM_TOL, PERSIST, REC, REC_MX, REC_PROJ, TOL, _beam, _check_beam,
                                    _check_forms_agree, _check_greedy, _f, _handle, _rows, _set, _slab, ENCODER)
 
@@ -165,13 +165,14 @@ def test_configuration_against_fp64(rv, oracle, name, fam):
         taps = {}
         otok, osc = oracle.beam_search(w, cfg, raw, ev, W, L, dtype=np.float64, taps=taps)
         fin = _well_chosen(taps, V, f"{name} {fam} W={W}")
+        twin = _twin_beam(oracle, w, cfg, raw, ev, W, L, taps, osc, f"config {name} {fam} W={W}")
         got, worst_lg, worst_al, ran = {}, 0.0, 0.0, []
         for label, opts, want, persist in _runs(attention, D, W):
-            tag = f"{name} {fam} W={W} {label}"
+            tag = f"config {name} {fam} W={W} {label}"
             _set(bc, opts)
             r = _beam(bc, (raw, ev), W, L, TM, persist=persist, V=V)
             assert r["forms"] == {want}, (tag, sorted(r["forms"]))
-            n, left = _check_beam(oracle, r, taps, otok, osc, W, end, tag)
+            n, left = _check_beam(oracle, r, taps, otok, osc, W, end, tag, twin)
             assert len(left) <= 1, (tag, "badly chosen: chunks that left the fp64 decode", sorted(left))
             lg, al = _worst(r, taps, n)
             worst_lg, worst_al = max(worst_lg, lg), max(worst_al, al)
@@ -189,9 +190,10 @@ def test_configuration_against_fp64(rv, oracle, name, fam):
         og, olg = oracle.greedy_search(w, cfg, raw, ev, L, dtype=np.float64, taps=gtaps)
         ends = [int(np.argmax(row == end)) if (row == end).any() else og.shape[1] for row in og]
         assert len(set(ends)) >= 2, (name, "badly chosen: greedy chunks end at", ends)
+        gtwin = _twin_greedy(oracle, w, cfg, raw, ev, L, og, olg, gtaps, f"config {name} greedy")
         for a, m, c in ((3, 1, 1), (0, 0, 0)):
             _set(bc, dict(PERSIST_ON, matrix_attention=m, matrix_cell=c))
-            forms = _check_greedy(bc, (raw, ev), L, TM, og, olg, gtaps, f"{name} greedy ATT {a}")
+            forms = _check_greedy(bc, (raw, ev), L, TM, og, olg, gtaps, f"config {name} greedy ATT {a}", gtwin)
             assert forms == {_f(PERSIST, 1, 8, 1, a)}, (name, a, sorted(forms))
         print(f"config {name} greedy: ATT 3 and 0, chunks end at {ends}")
     bc.close()
@@ -244,9 +246,8 @@ def test_deep_encoders_against_fp64(rv, oracle, enc_depth, name, mode):
     r_, e_ = (raw, ev) if mode == "joint" else (None, ev)
     taps = {}
     otok, osc = oracle.beam_search(w, cfg, r_, e_, W, L, dtype=np.float64, taps=taps)
-    t32 = {}
-    oracle.beam_search(w, cfg, r_, e_, W, L, dtype=np.float32, taps=t32)
-    twin = float(np.abs(t32["enc_output"] - taps["enc_output"]).max())
+    twins = _twin_beam(oracle, w, cfg, r_, e_, W, L, taps, osc, f"enc_depth {enc_depth} {mode} config {name}")
+    twin = twins["enc_output"]
     ref = None
     for opts in ENC_FORMS:
         tag = f"enc_depth {enc_depth} {mode} config {name} {opts}"
@@ -257,12 +258,13 @@ def test_deep_encoders_against_fp64(rv, oracle, enc_depth, name, mode):
         enc = bc.get_tensor("enc_output").reshape(Bn, Tm, 256)
         keys = bc.get_tensor("keys").reshape(Bn, Tm, 128)
         e_enc, e_keys = float(np.abs(enc - taps["enc_output"]).max()), float(np.abs(keys - taps["keys"]).max())
-        n, left = _check_beam(oracle, r, taps, otok, osc, W, end, tag, B=Bn)
+        n, left = _check_beam(oracle, r, taps, otok, osc, W, end, tag, twins, B=Bn)
         lg = max((float(np.abs(r["lg"][:k, b] - taps["step_logits"][:k, b]).max()) for b, k in enumerate(n) if k), default=0.0)
         print(f"{tag}: |enc_output - fp64| {e_enc:.2e} (numpy fp32 twin {twin:.2e}), |keys - fp64| {e_keys:.2e}, |logits - fp64| {lg:.2e}, "
               f"chunks that left at a near-tie {sorted(left)}; forms {sorted(f[:3] for f in forms)}")
         assert e_enc < TOL, (tag, "enc_output vs fp64", e_enc)
         assert e_keys < TOL, (tag, "keys vs fp64", e_keys)
+        _assert_twin(_memory_errors(enc, keys, taps), twins, tag)
         if ref is None:
             ref = enc
         else:
@@ -270,7 +272,7 @@ def test_deep_encoders_against_fp64(rv, oracle, enc_depth, name, mode):
     _set(bc, dict(PERSIST_ON, matrix_attention=1, matrix_cell=1, wide_recurrence=1, fused_projection=1, split_projection=2))
     r = _beam(bc, x, W, L, Tm, persist=True, V=V, B=Bn)
     assert r["forms"] == {_f(PERSIST, W, min(k for k in (2, 8, 11) if Tm <= 32 * k), 1, 3)}, sorted(r["forms"])
-    _check_beam(oracle, r, taps, otok, osc, W, end, f"enc_depth {enc_depth} {mode} persistent", B=Bn)
+    _check_beam(oracle, r, taps, otok, osc, W, end, f"enc_depth {enc_depth} {mode} persistent", twins, B=Bn)
     bc.close()
 
 
@@ -496,7 +498,7 @@ def test_max_beam_bounds_the_calls(rv, oracle):
     bc.set_option("persist_taps", 1)
     r = _beam(bc, (raw, ev), 3, L, TM, persist=True, V=V)
     assert r["forms"] == {_f(PERSIST, 3, 8, 1, 3)}, sorted(r["forms"])
-    _check_beam(oracle, r, taps, otok, osc, 3, end, "max_beam 3, W 3")
+    _check_beam(oracle, r, taps, otok, osc, 3, end, "max_beam 3, W 3", _twin_beam(oracle, w, cfg, raw, ev, 3, L, taps, osc, "max_beam 3, W 3"))
     for call in (lambda: bc.beam_search_prediction((raw, ev), 4, L), lambda: bc.submit_beam_search((raw, ev), 4, L),
                  lambda: bc.beam_search_calls((raw, ev), 4, L), lambda: bc.submit_calls((raw, ev), 4, L)):
         with pytest.raises(rv._capi.RavventHipError, match=r"beam width 4 outside \[1,3\]"):

@@ -3,7 +3,8 @@
 Each kernel family keeps its instantiations in one list (decode.hip: for_each_persist_form, for_each_attend_form; lstm_rec.hip:
 for_each_rec_form / _tw_form / _proj_form; lstm_mx.hip: for_each_mx_form, for_each_inproj_form), and the launchers pick from those
 lists.  rv_get_tensor("kernel_forms") names the forms the last call launched, "kernel_form_list" every form the lists hold.  Every
-call here is checked against the fp64 oracle and for the form it was meant to run; each test then asserts that the forms its calls
+call here is checked against the fp64 oracle -- within 1e-4, and no further from it than twice the oracle's numpy fp32 twin plus 5e-6
+(test_parity_gpu._assert_twin) -- and for the form it was meant to run; each test then asserts that the forms its calls
 ran are exactly its family's part of the list, so a form added to a list without a case here fails by name.  Forms no call can
 reach are named in EXCLUDED with the rule that keeps them out.
 
@@ -14,7 +15,8 @@ import numpy as np
 import pytest
 
 from test_bench_config_gpu import _agreeing_steps
-from test_parity_gpu import _check_alignments, _near_tie_gap
+from test_parity_gpu import (_assert_twin, _beam_errors, _check_alignments, _greedy_errors, _near_tie_gap, _twin_beam,
+                             _twin_greedy)
 
 pytestmark = pytest.mark.gpu
 
@@ -149,11 +151,12 @@ def _beam(bc, x, W, L, Tm, persist, V=V, B=B):
                 al=t("step_alignments", S, B, W, Tm), mask=t("mask", B, Tm))
 
 
-def _check_beam(oracle, r, o, otok, osc, W, end, tag, B=B):
+def _check_beam(oracle, r, o, otok, osc, W, end, tag, twin, B=B):
     """A beam search against the fp64 decode of its slab: the mask exact; on every step where the beams still agree (_agreeing_steps)
     logits within 1e-4 and alignments by _check_alignments; a chunk whose beam ids or parents leave the fp64 decode sits on a genuine
-    near-tie; the other chunks' tokens equal the oracle's and their scores are within 1e-4.  Returns the agreeing steps and the chunks
-    that left."""
+    near-tie; the other chunks' tokens equal the oracle's and their scores are within 1e-4; and logits, alignments and scores no
+    further from fp64 than the numpy fp32 twin's (`twin`: test_parity_gpu._twin_beam of the same oracle pass; _assert_twin).  Returns
+    the agreeing steps and the chunks that left."""
     assert (r["mask"] == o["mask"]).all(), (tag, "mask")
     So = o["step_ids"].shape[0]
     n = _agreeing_steps(r["ids"], r["par"], o["step_ids"], o["parent_ids"], r["cs"])
@@ -173,6 +176,9 @@ def _check_beam(oracle, r, o, otok, osc, W, end, tag, B=B):
     S = min(r["tok"].shape[1], otok.shape[1])
     assert (r["tok"][stay, :S] == otok[stay, :S]).all(), (tag, "tokens")
     assert np.abs(r["sc"][stay, :S] - osc[stay, :S]).max(initial=0.0) < TOL, (tag, "scores")
+    err, left_ = _beam_errors(r["lg"], r["al"], r["ids"], r["par"], r["cs"], r["sc"], o, osc)
+    assert set(left_) == left, (tag, left_, left)
+    _assert_twin(err, twin, tag)
     return n, left
 
 
@@ -189,9 +195,10 @@ def _check_forms_agree(ref, r, tag):
             assert np.abs(a["al"][:k, b] - b_["al"][:k, b]).max() < FORM_TOL, (tag, b, "alignments between forms")
 
 
-def _check_greedy(bc, x, L, Tm, og, olg, gtaps, tag):
+def _check_greedy(bc, x, L, Tm, og, olg, gtaps, tag, twin):
     """A greedy search against the fp64 greedy decode: logits within 1e-4 and alignments by _check_alignments up to a chunk's first
-    token that differs, which must sit on a genuine near-tie of the fp64 logits; tokens equal otherwise.  Returns the decode forms."""
+    token that differs, which must sit on a genuine near-tie of the fp64 logits; tokens equal otherwise; both no further from fp64
+    than the numpy fp32 twin's (`twin`: test_parity_gpu._twin_greedy of the same oracle pass).  Returns the decode forms."""
     tok, lg = bc.greedy_search_prediction(x, L)
     tok, lg = tok.numpy(), lg.numpy()
     S = tok.shape[1]
@@ -209,6 +216,7 @@ def _check_greedy(bc, x, L, Tm, og, olg, gtaps, tag):
     if not flipped:
         assert tok.shape == og.shape, (tag, tok.shape, og.shape)
     _check_alignments(al, gtaps["step_alignments"][:, :, None], gtaps["mask"], np.full(B, S), tag, last=n)
+    _assert_twin(_greedy_errors(tok, lg, al[:, :, 0], og, olg, gtaps)[0], twin, tag)
     return _decode_forms(bc)
 
 
@@ -244,9 +252,11 @@ def test_persistent_decode_forms(rv, oracle, fam):
         nit = min(k for k in PERSIST_BANDS if Tm <= 32 * k)
         taps = {}
         otok, osc = oracle.beam_search(w, cfg, r_, e_, W, L, dtype=np.float64, taps=taps)
+        twin = _twin_beam(oracle, w, cfg, r_, e_, W, L, taps, osc, f"{fam} {mode} W={W} T_m={Tm}")
         if W == 1:
             gtaps = {}
             og, olg = oracle.greedy_search(w, cfg, r_, e_, L, dtype=np.float64, taps=gtaps)
+            gtwin = _twin_greedy(oracle, w, cfg, r_, e_, L, og, olg, gtaps, f"{fam} {mode} T_m={Tm} greedy")
         got = {}
         for att, opts in atts.items():
             tag = f"{fam} {mode} W={W} T_m={Tm} ATT={att}"
@@ -255,10 +265,10 @@ def test_persistent_decode_forms(rv, oracle, fam):
             r = _beam(bc, x, W, L, Tm, persist=True)
             assert r["forms"] == {want}, (tag, sorted(r["forms"]))
             ran.add(want)
-            n, left = _check_beam(oracle, r, taps, otok, osc, W, end, tag)
+            n, left = _check_beam(oracle, r, taps, otok, osc, W, end, tag, twin)
             got[att] = (r, n, left)
             if W == 1:
-                assert _check_greedy(bc, x, L, Tm, og, olg, gtaps, tag + " greedy") == {want}, tag
+                assert _check_greedy(bc, x, L, Tm, og, olg, gtaps, tag + " greedy", gtwin) == {want}, tag
         ref = next(iter(atts))
         for att in atts:
             if att != ref:
@@ -302,13 +312,14 @@ def test_per_step_attend_forms(rv, oracle, kind):
         L = 14 + W % 3
         taps = {}
         otok, osc = oracle.beam_search(w, cfg, raw, ev, W, L, dtype=np.float64, taps=taps)
+        twin = _twin_beam(oracle, w, cfg, raw, ev, W, L, taps, osc, f"{kind} W={W} T_m={Tm}")
         for opts, want in runs:
             tag = f"{kind} W={W} T_m={Tm} {opts}"
             _set(bc, opts)
             r = _beam(bc, (raw, ev), W, L, Tm, persist=False)
             assert r["forms"] == {want}, (tag, sorted(r["forms"]))
             ran.add(want)
-            _check_beam(oracle, r, taps, otok, osc, W, end, tag)
+            _check_beam(oracle, r, taps, otok, osc, W, end, tag, twin)
             if W == fast_path:
                 _taps_off_identical(bc, (raw, ev), W, L, r, tag)
                 fast_path = None
@@ -341,7 +352,8 @@ def test_per_step_decode_of_what_the_persistent_decode_hands_over(rv, oracle, at
         if W == "greedy":
             gtaps = {}
             og, olg = oracle.greedy_search(w, cfg, raw, ev, L, dtype=np.float64, taps=gtaps)
-            assert _check_greedy(bc, (raw, ev), L, Tm, og, olg, gtaps, tag) == {want}, tag
+            gtwin = _twin_greedy(oracle, w, cfg, raw, ev, L, og, olg, gtaps, tag)
+            assert _check_greedy(bc, (raw, ev), L, Tm, og, olg, gtaps, tag, gtwin) == {want}, tag
             tok, lg = bc.greedy_search_prediction((raw, ev), L)
             bc.set_option("debug_taps", 0)
             tok2, lg2 = bc.greedy_search_prediction((raw, ev), L)
@@ -352,7 +364,7 @@ def test_per_step_decode_of_what_the_persistent_decode_hands_over(rv, oracle, at
         otok, osc = oracle.beam_search(w, cfg, raw, ev, W, L, dtype=np.float64, taps=taps)
         r = _beam(bc, (raw, ev), W, L, Tm, persist=False)
         assert r["forms"] == {want}, (tag, sorted(r["forms"]))
-        _check_beam(oracle, r, taps, otok, osc, W, end, tag)
+        _check_beam(oracle, r, taps, otok, osc, W, end, tag, _twin_beam(oracle, w, cfg, raw, ev, W, L, taps, osc, tag))
         _taps_off_identical(bc, (raw, ev), W, L, r, tag)
     bc.close()
 
@@ -417,6 +429,8 @@ def test_encoder_recurrence_forms(rv, oracle):
             sample |= {g * G, min(g * G + G - 1, Bn - 1)}
         sample = sorted(sample)
         o_enc, _ = oracle.encode_input(w, raw[sample], ev[sample], "joint", 0.0, np.float64)
+        t_enc, _ = oracle.encode_input(w, raw[sample], ev[sample], "joint", 0.0, np.float32)
+        twin = dict(enc_output=float(np.abs(t_enc - o_enc).max()))
         ref = None
         for opts in configs:
             tag = f"B={Bn} {opts}"
@@ -429,6 +443,7 @@ def test_encoder_recurrence_forms(rv, oracle):
             enc = bc.get_tensor("enc_output").reshape(Bn, Tm, 256)
             err = float(np.abs(enc[sample] - o_enc).max())
             assert err < TOL, (tag, "enc_output vs fp64", err)
+            _assert_twin(dict(enc_output=err), twin, "recurrence " + tag)
             if ref is None:
                 ref = enc
             else:

@@ -2,9 +2,12 @@
 `Basecaller` API, against the CPU oracle on the same seeded inputs.
 
 Tolerances (BASELINE.json north_star): base-call strings bit-exact at beam=1, attention /
-logit tensors within 1e-4 (fp32) of the fp64 oracle."""
+logit tensors within 1e-4 (fp32) of the fp64 oracle; and, beside that acceptance bar, every tapped tensor no further from fp64 than
+TWIN_K x the oracle's numpy fp32 twin + TWIN_C (_assert_twin below)."""
 import numpy as np
 import pytest
+
+from test_bench_config_gpu import TWIN_C, TWIN_K, _agreeing_steps
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +45,112 @@ def _check_alignments(al, ref, mask, cs, tag, last=None):
     return worst
 
 
+# ----------------------------------------------------------------------------------------------
+# The twin-relative bound.  1e-4 is the acceptance bar, not what fp32 arithmetic gives: the oracle's own numpy fp32 twin sits at
+# 1e-9 (alignments) to 3e-7 (logits) from its fp64 pass on these cases, so a kernel a hundred times less precise than it is would
+# still pass `< TOL`.  Beside every fp64 comparison of a tapped tensor the tests therefore run the oracle once more with
+# dtype = np.float32 on the same weights and inputs and hold the GPU to
+#     max |gpu - fp64| <= TWIN_K x max |twin - fp64| + TWIN_C
+# per tensor, each side over the steps on which IT still agrees with the fp64 decode.  TWIN_K and TWIN_C are the constants of the
+# adversarial tests (test_bench_config_gpu): "no further from fp64 than an honest fp32 evaluation"; they come from the reference
+# side only and do not move towards what the kernels measure (measured values: DESIGN.md section 5).
+def _beam_errors(lg, al, ids, par, cs, sc, o, osc):
+    """{tensor: max |x - fp64|} of one beam search against the fp64 pass (taps o, top-1 scores osc), and the chunks that left it.
+    Step logits lg [S, B, W, V] and alignments al [S, B, W, T_m] (None: not tapped) over every step up to the first one whose beam
+    ids or parents differ (_agreeing_steps; cs: the steps each chunk ran), alignments on the unmasked memory steps; the top-1 scores
+    sc [B, S] (None: not compared) on the chunks that never left."""
+    So, nB = o["step_ids"].shape[0], ids.shape[1]
+    n = _agreeing_steps(ids, par, o["step_ids"], o["parent_ids"], cs)
+    live = np.asarray(o["mask"]) != 0
+    err = dict(step_logits=0.0)
+    if al is not None:
+        err["step_alignments"] = 0.0
+    if sc is not None:
+        err["scores"] = 0.0
+    left = []
+    for b in range(nB):
+        m = min(int(cs[b]), So)
+        if ((ids[:m, b] != o["step_ids"][:m, b]) | (par[:m, b] != o["parent_ids"][:m, b])).any():
+            left.append(b)
+        elif sc is not None:
+            S = min(sc.shape[1], osc.shape[1])
+            err["scores"] = max(err["scores"], float(np.abs(sc[b, :S] - osc[b, :S]).max(initial=0.0)))
+        k = int(n[b])
+        if k:
+            err["step_logits"] = max(err["step_logits"], float(np.abs(lg[:k, b] - o["step_logits"][:k, b]).max()))
+            if al is not None:
+                d = np.abs(al[:k, b][..., live[b]] - o["step_alignments"][:k, b][..., live[b]])
+                err["step_alignments"] = max(err["step_alignments"], float(d.max(initial=0.0)))
+    return err, left
+
+
+def _greedy_errors(tok, lg, al, og, olg, o):
+    """The same for a greedy search: logits lg [B, S, V] and alignments al [S, B, T_m] (None: not tapped) up to and including each
+    chunk's first token that differs from the fp64 decode's (og, olg, taps o)."""
+    S = min(tok.shape[1], og.shape[1])
+    live = np.asarray(o["mask"]) != 0
+    err = dict(step_logits=0.0)
+    if al is not None:
+        err["step_alignments"] = 0.0
+    left = []
+    for b in range(tok.shape[0]):
+        diff = np.nonzero(tok[b, :S] != og[b, :S])[0]
+        k = int(diff[0]) + 1 if diff.size else S
+        if diff.size:
+            left.append(b)
+        if k:
+            err["step_logits"] = max(err["step_logits"], float(np.abs(lg[b, :k] - olg[b, :k]).max()))
+            if al is not None:
+                d = np.abs(al[:k, b][..., live[b]] - o["step_alignments"][:k, b][..., live[b]])
+                err["step_alignments"] = max(err["step_alignments"], float(d.max(initial=0.0)))
+    return err, left
+
+
+def _memory_errors(enc, keys, o, rows=slice(None)):
+    """{enc_output, keys: max |x - fp64|} of the encoder output [B, T_m, 2u] and the attention keys [B, T_m, d] (None: left out)."""
+    err = {}
+    if enc is not None:
+        err["enc_output"] = float(np.abs(enc - o["enc_output"][rows]).max())
+    if keys is not None:
+        err["keys"] = float(np.abs(keys - o["keys"][rows]).max())
+    return err
+
+
+def _stays(left, nB, tag):
+    """A case only probes the decode while the fp32 twin itself stays on the fp64 decode: on at least three quarters of the chunks
+    (the cap the adversarial tests put on near-tie chunks), else its inputs must change."""
+    assert len(left) <= nB // 4, (tag, "a poor probe: the numpy fp32 twin leaves the fp64 decode on chunks", left)
+
+
+def _twin_beam(oracle, w, cfg, raw, ev, W, L, o, osc, tag):
+    """One pass of the oracle's numpy fp32 twin over a beam search whose fp64 pass gave (o, osc): its error dict against fp64."""
+    t = {}
+    _, tsc = oracle.beam_search(w, cfg, raw, ev, W, L, dtype=np.float32, taps=t)
+    S, nB = t["step_ids"].shape[:2]
+    err, left = _beam_errors(t["step_logits"], t["step_alignments"], t["step_ids"], t["parent_ids"], np.full(nB, S), tsc, o, osc)
+    _stays(left, nB, tag)
+    err.update(_memory_errors(t["enc_output"], t["keys"], o))
+    return err
+
+
+def _twin_greedy(oracle, w, cfg, raw, ev, L, og, olg, o, tag):
+    """The same for a greedy search whose fp64 pass gave (og, olg, taps o)."""
+    t = {}
+    tg, tlg = oracle.greedy_search(w, cfg, raw, ev, L, dtype=np.float32, taps=t)
+    err, left = _greedy_errors(tg, tlg, t["step_alignments"], og, olg, o)
+    _stays(left, tg.shape[0], tag)
+    err.update(_memory_errors(t["enc_output"], t["keys"], o))
+    return err
+
+
+def _assert_twin(err, twin, tag):
+    """Every tensor of err (the GPU's {tensor: max |x - fp64|}) no further from fp64 than TWIN_K x the numpy fp32 twin's error on
+    the same tensor + TWIN_C.  Prints one line per case -- tensor, GPU error, twin error, ratio -- before it asserts."""
+    print(f"twin-relative [{tag}]: " + "; ".join(f"{k} {e:.2e} / {twin[k]:.2e} = {e / max(twin[k], 1e-300):.2f}x" for k, e in err.items()))
+    for k, e in err.items():
+        assert e <= TWIN_K * twin[k] + TWIN_C, (tag, k, "further from fp64 than an fp32 evaluation is", e, twin[k])
+
+
 @pytest.mark.parametrize("mode,attention,enc_depth", [
     ("joint", "luong", 2), ("raw", "luong", 2), ("event", "luong", 2),
     ("joint", "bahdanau", 2), ("joint", "luong", 1), ("joint", "luong", 3)])
@@ -65,6 +174,10 @@ def test_greedy_tensors_and_strings(rv, oracle, mode, attention, enc_depth):
     assert np.abs(logits.numpy() - ologits).max() < TOL
     assert (tok.numpy() == otok).all()                      # beam=1 strings bit-exact
     assert bc.tokens_to_nuc_sequences(tok) == oracle.tokens_to_nuc_sequences(otok)
+    tag = f"greedy per-step {mode} {attention} enc_depth {enc_depth}"
+    err, _ = _greedy_errors(tok.numpy(), logits.numpy(), al, otok, ologits, taps)
+    err.update(_memory_errors(enc, bc.get_tensor("keys").reshape(B, Tm, 128), taps))
+    _assert_twin(err, _twin_greedy(oracle, w, bc.cfg.oracle_cfg(), raw, ev, L, otok, ologits, taps, tag), tag)
     bc.close()
 
 
@@ -179,6 +292,7 @@ def test_matrix_attention_matches_fp32_rows_and_oracle(rv, oracle, W, Tr, Te):
                    bc.get_tensor("step_alignments").reshape(S, B, W, Tr + Te).copy())
     taps = {}
     otok, osc = oracle.beam_search(w, bc.cfg.oracle_cfg(), raw, ev, W, L, dtype=np.float64, taps=taps)
+    twin = _twin_beam(oracle, w, bc.cfg.oracle_cfg(), raw, ev, W, L, taps, osc, f"matrix_attention W={W} T_m={Tr + Te}")
     worst = {}
     for mx in (2, 1, 0):
         tok, sc, cs, lg, ids, par, al = got[mx]
@@ -189,6 +303,7 @@ def test_matrix_attention_matches_fp32_rows_and_oracle(rv, oracle, W, Tr, Te):
             assert (ids[:n, b] == taps["step_ids"][:n, b]).all() and (par[:n, b] == taps["parent_ids"][:n, b]).all(), (mx, b)
         # alignments: the f16 hi / lo image the context product consumes (mx 2, 1), the fp32 rows (mx 0)
         worst[mx] = _check_alignments(al, taps["step_alignments"], taps["mask"], cs, f"matrix_attention form {mx}")
+        _assert_twin(_beam_errors(lg, al, ids, par, cs, sc, taps, osc)[0], twin, f"matrix_attention W={W} T_m={Tr + Te} form {mx}")
     print(f"W={W} T_m={Tr + Te}: max |alpha - fp64| by form (2: ATT 3, 1: ATT 2, 0: ATT 0):", worst)
     assert (got[1][2] == got[0][2]).all() and (got[2][2] == got[0][2]).all()
     for b in range(B):
@@ -217,6 +332,7 @@ def test_persistent_decode_step_logits(rv, oracle, W, dec_depth):
     taps = {}
     otok, osc = oracle.beam_search(w, bc.cfg.oracle_cfg(), raw, ev, W, L, dtype=np.float64, taps=taps)
     S = otok.shape[1]
+    twin = _twin_beam(oracle, w, bc.cfg.oracle_cfg(), raw, ev, W, L, taps, osc, f"persistent W={W} D={dec_depth}")
     # the default form (all on the matrix pipe: ATT 3); with two cells also both cells on packed FMAs (ATT 0, matrix_cell = 0)
     for mcell in ((1, 0) if dec_depth == 2 else (1,)):
         bc.set_option("matrix_cell", mcell)
@@ -236,6 +352,7 @@ def test_persistent_decode_step_logits(rv, oracle, W, dec_depth):
         al = bc.get_tensor("step_alignments").reshape(S, B, W, 84)
         worst = _check_alignments(al, taps["step_alignments"], taps["mask"], cs, f"W={W} D={dec_depth} matrix_cell={mcell}")
         print(f"W={W} D={dec_depth} matrix_cell={mcell}: max |alpha - fp64| {worst:.2e}")
+        _assert_twin(_beam_errors(lg, al, ids, par, cs, sc.numpy(), taps, osc)[0], twin, f"persistent W={W} D={dec_depth} matrix_cell={mcell}")
     bc.close()
 
 
@@ -466,9 +583,15 @@ def test_fused_projection_matches_gemm_path_and_oracle(rv, oracle, mode, B, Tr, 
         enc[fuse] = (bc.get_tensor("enc_output").copy(), tok.numpy().copy())
     assert np.abs(enc[1][0] - enc[0][0]).max() < 1e-5 and (enc[1][1] == enc[0][1]).all()
     nb = min(B, 6)
-    o_enc, _ = oracle.encode_input(w, raw[:nb] if mode != "event" else None, ev[:nb] if mode != "raw" else None, mode)
+    r_, e_ = raw[:nb] if mode != "event" else None, ev[:nb] if mode != "raw" else None
+    o_enc, _ = oracle.encode_input(w, r_, e_, mode)
+    t_enc, _ = oracle.encode_input(w, r_, e_, mode, 0.0, np.float32)
+    twin = dict(enc_output=float(np.abs(t_enc - o_enc).max()))
     got = enc[1][0].reshape(B, -1, 256)[:nb]
     assert np.abs(got - o_enc).max() < TOL
+    for fuse in (1, 0):
+        got = enc[fuse][0].reshape(B, -1, 256)[:nb]
+        _assert_twin(dict(enc_output=float(np.abs(got - o_enc).max())), twin, f"packed FMA {mode} B={B} depth={depth} fused_projection={fuse}")
     bc.close()
 
 
@@ -497,9 +620,14 @@ def test_matrix_pipe_recurrence_matches_fma_path_and_oracle(rv, oracle, mode, B,
         out[wide] = (tok.numpy().copy(), sc.numpy().copy())
         enc[wide] = bc.get_tensor("enc_output").reshape(B, -1, 256)
     nb = min(B, 24)
-    e64, _ = oracle.encode_input(w, raw[:nb] if mode != "event" else None, ev[:nb] if mode != "raw" else None, mode, 0.0, np.float64)
+    r_, e_ = raw[:nb] if mode != "event" else None, ev[:nb] if mode != "raw" else None
+    e64, _ = oracle.encode_input(w, r_, e_, mode, 0.0, np.float64)
+    e32, _ = oracle.encode_input(w, r_, e_, mode, 0.0, np.float32)
+    twin = dict(enc_output=float(np.abs(e32 - e64).max()))
     err = {k: float(np.abs(enc[k][:nb] - e64).max()) for k in enc}
     print(f"{mode} B={B} depth={depth}: max |enc_output - fp64| matrix pipe {err[1]:.2e}, its 8-chunk form {err[2]:.2e}, packed FMA {err[0]:.2e}")
+    for k in (1, 2, 0):
+        _assert_twin(dict(enc_output=err[k]), twin, f"recurrence {mode} B={B} depth={depth} wide_recurrence={k}")
     for k in (1, 2):
         assert err[k] < TOL and err[k] <= 2.0 * err[0] + 1e-6, err
         assert np.abs(enc[k] - enc[0]).max() < TOL
@@ -798,8 +926,11 @@ def test_two_decoder_cells_on_the_matrix_pipe(rv, oracle, W, Tr, Te):
                           bc.get_tensor("step_ids").reshape(S, B, W).copy(), bc.get_tensor("parent_ids").reshape(S, B, W).copy()]
     taps = {}
     otok, osc = oracle.beam_search(w, bc.cfg.oracle_cfg(), raw, ev, W, L, dtype=np.float64, taps=taps)
+    tag = f"two cells W={W} T_m={Tr + Te}"
+    twin = _twin_beam(oracle, w, bc.cfg.oracle_cfg(), raw, ev, W, L, taps, osc, tag)
     for form in ("mx", "fma", "steps"):
         assert got[form][0].shape == otok.shape and (got[form][0] == otok).all() and np.abs(got[form][1] - osc).max() < TOL, form
+    _assert_twin(dict(scores=float(np.abs(got["steps"][1] - osc).max())), twin, f"{tag} steps")    # (tokens equal: no chunk left)
     assert (got["mx"][2] == got["fma"][2]).all()
     for form in ("mx", "fma"):
         tok, sc, cs, lg, ids, par = got[form]
@@ -807,14 +938,18 @@ def test_two_decoder_cells_on_the_matrix_pipe(rv, oracle, W, Tr, Te):
             n = cs[b]
             assert np.abs(lg[:n, b] - taps["step_logits"][:n, b]).max() < TOL, (form, b)
             assert (ids[:n, b] == taps["step_ids"][:n, b]).all() and (par[:n, b] == taps["parent_ids"][:n, b]).all(), (form, b)
+        _assert_twin(_beam_errors(lg, None, ids, par, cs, sc, taps, osc)[0], twin, f"{tag} {form}")
     for b in range(B):
         n = got["mx"][2][b]
         assert np.abs(got["mx"][3][:n, b] - got["fma"][3][:n, b]).max() < 2e-5, b
+    gtaps = {}
+    og, olg = oracle.greedy_search(w, bc.cfg.oracle_cfg(), raw, ev, L, taps=gtaps)
+    gtwin = _twin_greedy(oracle, w, bc.cfg.oracle_cfg(), raw, ev, L, og, olg, gtaps, f"{tag} greedy")
     for mcell in (1, 0):
         bc.set_option("persistent_decode", 1); bc.set_option("matrix_cell", mcell)
         g, glg = bc.greedy_search_prediction((raw, ev), L)
-        og, olg = oracle.greedy_search(w, bc.cfg.oracle_cfg(), raw, ev, L)
         assert g.shape == og.shape and (g.numpy() == og).all() and np.abs(glg.numpy() - olg).max() < TOL, mcell
+        _assert_twin(_greedy_errors(g.numpy(), glg.numpy(), None, og, olg, gtaps)[0], gtwin, f"{tag} greedy matrix_cell={mcell}")
     bc.close()
 
 
@@ -828,8 +963,12 @@ def test_stacked_decoder_cells(rv, oracle, dec_depth, enc_depth):
     raw, ev, _ = rv.synthetic.make_slab(7, 44, 9, seed=dec_depth)
     bc.set_option("debug_taps", 1)
     g, lg = bc.greedy_search_prediction((raw, ev), 12)
-    og, olg = oracle.greedy_search(w, bc.cfg.oracle_cfg(), raw, ev, 12)
+    gtaps = {}
+    og, olg = oracle.greedy_search(w, bc.cfg.oracle_cfg(), raw, ev, 12, taps=gtaps)
     assert g.shape == og.shape and (g.numpy() == og).all() and np.abs(lg.numpy() - olg).max() < TOL
+    tag = f"stacked cells D={dec_depth} enc_depth {enc_depth}"
+    _assert_twin(_greedy_errors(g.numpy(), lg.numpy(), None, og, olg, gtaps)[0],
+                 _twin_greedy(oracle, w, bc.cfg.oracle_cfg(), raw, ev, 12, og, olg, gtaps, f"{tag} greedy"), f"{tag} greedy")
     for W, flash, nt in ((5, 1, 512), (3, 0, 0), (8, 1, 0), (4, 1, 256)):
         bc.set_option("flash_attend", flash)
         bc.set_option("attend_threads", nt)
@@ -847,6 +986,10 @@ def test_stacked_decoder_cells(rv, oracle, dec_depth, enc_depth):
             else:
                 gap = _near_tie_gap(oracle, taps["step_logits"][:, b], W, bc.cfg.oracle_cfg()["end_token"])
                 assert gap < 1e-6, f"chunk {b}, beam {W}: beam order differs from fp64 with no near-tie (smallest gap {gap:.3e})"
+        # (a chunk whose parents differ is compared up to that step; the scores of every chunk, as above: the tokens are equal)
+        err, _ = _beam_errors(lgt, None, bc.get_tensor("step_ids").reshape(S, 7, W), pid, np.full(7, S), None, taps, osc)
+        err["scores"] = float(np.abs(sc.numpy() - osc).max())
+        _assert_twin(err, _twin_beam(oracle, w, bc.cfg.oracle_cfg(), raw, ev, W, 12, taps, osc, f"{tag} W={W}"), f"{tag} W={W} flash {flash}/{nt}")
     bc.close()
 
 
@@ -1087,8 +1230,12 @@ def test_bahdanau_persistent_decode(rv, oracle, B, Tr, Te, W, L):
             al[form] = bc.get_tensor("step_alignments").reshape(S, B, W, -1).copy()
     taps = {}
     ot, osc = oracle.beam_search(w, bc.cfg.oracle_cfg(), raw, ev if mode == "joint" else None, W, L, dtype=np.float64, taps=taps)
+    r_, e_ = raw, ev if mode == "joint" else None
+    tag = f"Bahdanau W={W} T_m={Tr + Te}"
+    twin = _twin_beam(oracle, w, bc.cfg.oracle_cfg(), r_, e_, W, L, taps, osc, tag)
     for form in ("mx", "fma", "steps"):
         assert out[form][0].shape == ot.shape and (out[form][0] == ot).all() and np.abs(out[form][1] - osc).max() < TOL, form
+    _assert_twin(dict(scores=float(np.abs(out["steps"][1] - osc).max())), twin, f"{tag} steps")    # (tokens equal: no chunk left)
     assert (cs["mx"] == cs["fma"]).all()
     for form in ("mx", "fma"):
         for b in range(B):
@@ -1098,15 +1245,20 @@ def test_bahdanau_persistent_decode(rv, oracle, B, Tr, Te, W, L):
     # alignments: the f16 image the context product consumes (mx: ATT 4), the fp32 rows (fma: ATT 1)
     worst = {form: _check_alignments(al[form], taps["step_alignments"], taps["mask"], cs[form], f"bahdanau {form}") for form in ("mx", "fma")}
     print(f"Bahdanau W={W} T_m={Tr + Te}: max |alpha - fp64|", worst)
+    for form in ("mx", "fma"):
+        _assert_twin(_beam_errors(lg[form], al[form], ids[form], par[form], cs[form], out[form][1], taps, osc)[0], twin, f"{tag} {form}")
     for b in range(B):
         n = cs["mx"][b]
         assert np.abs(lg["mx"][:n, b] - lg["fma"][:n, b]).max() < 2e-5, b
         assert np.abs(al["mx"][:n, b] - al["fma"][:n, b]).max() < 2e-5, b
+    gtaps = {}
+    og, olg = oracle.greedy_search(w, bc.cfg.oracle_cfg(), r_, e_, L, taps=gtaps)
+    gtwin = _twin_greedy(oracle, w, bc.cfg.oracle_cfg(), r_, e_, L, og, olg, gtaps, f"{tag} greedy")
     for mcell in (1, 0):
         bc.set_option("persistent_decode", 1); bc.set_option("matrix_cell", mcell)
         g, glg = bc.greedy_search_prediction(x, L)
-        og, olg = oracle.greedy_search(w, bc.cfg.oracle_cfg(), raw, ev if mode == "joint" else None, L)
         assert g.shape == og.shape and (g.numpy() == og).all() and np.abs(glg.numpy() - olg).max() < TOL, mcell
+        _assert_twin(_greedy_errors(g.numpy(), glg.numpy(), None, og, olg, gtaps)[0], gtwin, f"{tag} greedy matrix_cell={mcell}")
     bc.close()
 
 
