@@ -4,6 +4,7 @@
 // (/root/reference/basecaller.py:296-330).  No CPU compute path exists in this library.
 #include "../../include/ravvent_hip.h"
 #include "common.h"
+#include "split_image.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -1132,30 +1133,13 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
       for (int l = 1; l < h->cfg.enc_depth; ++l) {
         std::vector<uint16_t> img(RV_WX16_SLOT);
         std::vector<float> b2(2 * RV_G);
+        size_t off[2];
         for (int dr = 0; dr < 2; ++dr) {
-          const size_t off = (size_t)(h->enc[e][l][dr].W - h->d_w), boff = (size_t)(h->enc[e][l][dr].b - h->d_w);
+          const size_t boff = (size_t)(h->enc[e][l][dr].b - h->d_w);
+          off[dr] = (size_t)(h->enc[e][l][dr].W - h->d_w);
           for (int n = 0; n < RV_G; ++n) b2[(size_t)dr * RV_G + n] = blob[boff + n];
-          for (int n = 0; n < RV_G; ++n) {
-            float mx = 0.f;
-            for (int k = 0; k < RV_E; ++k) mx = std::max(mx, std::fabs(blob[off + (size_t)k * RV_G + n]));
-            int ex = 0;
-            if (mx > 0.f && std::isfinite(mx)) std::frexp(mx, &ex);
-            const float sc = std::ldexp(1.0f, 14 - ex);
-            const int cb = 2 * dr + n / RV_E, nn = n % RV_E;
-            const float f = std::ldexp(1.0f, -14) / sc;
-            memcpy(&img[(size_t)4 * 2 * RV_E * RV_E + 2 * ((size_t)cb * RV_E + nn)], &f, 4);
-            for (int k = 0; k < RV_E; ++k) {
-              const float v = blob[off + (size_t)k * RV_G + n] * sc;
-              const _Float16 hi = (_Float16)v;
-              const _Float16 lo = (_Float16)(v - (float)hi);
-              uint16_t hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
-              const int ks = k / 32, ln = 16 * ((k % 32) / 8) + (nn % 16), j = k % 8, nt = nn / 16;
-              const size_t base = (size_t)cb * 2 * RV_E * RV_E + ((((size_t)ks * 16 + nt) * 2) * 64) * 8;
-              img[base + (size_t)ln * 8 + j] = hb;
-              img[base + 64 * 8 + (size_t)ln * 8 + j] = lb;
-            }
-          }
         }
+        rv_pack_split_image(blob, RV_G, 4, [&](int c) { return off[c / RV_G] + (size_t)(c % RV_G); }, img.data());
         const size_t slot = (size_t)(e * (h->cfg.enc_depth - 1) + (l - 1));
         HIPCHK(h, hipMemcpy(h->d_Wx16 + slot * RV_WX16_SLOT, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         HIPCHK(h, hipMemcpy(h->d_bx2 + slot * 2 * RV_G, b2.data(), b2.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1234,27 +1218,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
         h->mx_kscale = pow2_scale(bk); h->mx_uscale = pow2_scale(bu);
       }
       std::vector<uint16_t> img(RV_WMP16_SLOT);
-      float cs[RV_E];
-      for (int n = 0; n < RV_E; ++n) {
-        float mx = 0.f;
-        for (int kk = 0; kk < RV_E; ++kk) mx = std::max(mx, std::fabs(wmp[(size_t)kk * RV_E + n]));
-        int ex = 0;
-        if (mx > 0.f && std::isfinite(mx)) std::frexp(mx, &ex);
-        cs[n] = std::ldexp(1.0f, 14 - ex);
-      }
-      for (int ks = 0; ks < 8; ++ks)
-        for (int nt = 0; nt < 16; ++nt)
-          for (int ln = 0; ln < 64; ++ln)
-            for (int j = 0; j < 8; ++j) {
-              const int n = 16 * nt + (ln & 15);
-              const float v = wmp[(size_t)(32 * ks + 8 * (ln >> 4) + j) * RV_E + n] * cs[n];
-              const _Float16 hi = (_Float16)v;
-              const _Float16 lo = (_Float16)(v - (float)hi);
-              uint16_t hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
-              img[((((size_t)ks * 16 + nt) * 2 + 0) * 64 + ln) * 8 + j] = hb;
-              img[((((size_t)ks * 16 + nt) * 2 + 1) * 64 + ln) * 8 + j] = lb;
-            }
-      for (int n = 0; n < RV_E; ++n) { const float f = std::ldexp(1.0f, -14) / cs[n]; memcpy(&img[(size_t)2 * RV_E * RV_E + 2 * n], &f, 4); }
+      rv_pack_split_image(wmp.data(), RV_E, 1, [](int c) { return (size_t)c; }, img.data());
       HIPCHK(h, hipMemcpy(h->d_Wmp16, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     }
     if (h->cfg.dec_depth <= 2) {
