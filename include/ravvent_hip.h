@@ -186,7 +186,7 @@ int rv_greedy_search_dev(rv_handle h, const float* d_raw, const float* d_event, 
  *                       option is set -- when the value exceeds GPU_MAX_HW_QUEUES as found in the environment, see "Hardware queues" above),
  *          "slab_graph" (0/1, default 0: a call on the default path -- matrix-pipe recurrences, persistent decode, no profiling, no taps --
  *                       replays as ONE hipGraphLaunch per slab (captured per slab context and call shape; the caller's input / output
- *                       addresses reach the kernels through a table in mapped pinned memory) instead of nine kernel launches (ten with "lane_projection" 0): half the
+ *                       addresses reach the kernels through a table in mapped pinned memory) instead of eight kernel launches (nine with "fused_memory" 0, one more with "lane_projection" 0): half the
  *                       host time per call (24 us against 46), but the replayed slabs stream 1.5-3 % slower on ROCm 7.2, so it is off
  *                       unless a caller's host thread is the bottleneck; results are identical),
  *          "persistent_decode" (0/1, default 1: Luong beam search (beam <= 8; <= 5 with two decoder cells) and greedy search, no
@@ -205,6 +205,11 @@ int rv_greedy_search_dev(rv_handle h, const float* d_raw, const float* d_event, 
  *                       cell product and the output layer to the matrix pipe; the tanh scores stay on the vector ALU),
  *          "persist_taps" (0/1, default 0: the persistent decode also records every step's logits [S,B,W,V] for
  *                       rv_get_tensor("step_logits"); rows of a chunk beyond its own last step ("chunk_steps") are not written),
+ *          "fused_memory" (0/1, default 1: the default persistent decode -- Luong attention, one decoder cell, "matrix_attention" and
+ *                       "matrix_cell" on, "split_projection" on -- computes each chunk's projected memory enc_output . [W_mem | A_c] in the
+ *                       prologue of its own workgroup, with the arithmetic of the split GEMM, straight into the resident fragments: no
+ *                       `gemm_memory` launch and no [B,T_m,2u] tensor written and read back.  0 = the GEMM launch in front of the decode,
+ *                       which every other form of the decode keeps in either case.  Results are identical bit for bit),
  *          "profile"    (0 off; 1: hipEvents around every launch outside the decode graph and around
  *                       the graph as a whole; 2: no graph, events around every kernel; 3: events around the decode
  *                       launch only -- the persistent decode kernel or the decode graph). */
@@ -216,7 +221,9 @@ int rv_set_option(rv_handle h, const char* key, int32_t value);
  *   "keys"       [B,T_m,d]    attention keys after setup_memory   basecaller.py:303
  *   "projected_memory" [B,T_m,2u] enc_output . [W_mem | A_c]: keys (columns 0..u-1) and the attention layer's image of the values
  *                              (A_c = rows u..3u-1 of the attention layer), what the persistent decode keeps on chip (last call
- *                              must have run the persistent decode)
+ *                              must have run the persistent decode).  After a call that projected the memory inside the decode ("fused_memory")
+ *                              the tensor is what that decode's workgroups computed if "persist_taps" was on; otherwise the GEMM is run
+ *                              on the call's enc_output when the tensor is asked for
  *   "step_logits"     [S,B,W,V]   (needs debug_taps, or persist_taps on the persistent decode)
  *   "chunk_steps"     [B]         steps each chunk ran in the persistent decode (its beams all finished there)
  *   "step_alignments" [S,B,W,T_m] (needs debug_taps)

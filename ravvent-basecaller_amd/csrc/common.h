@@ -120,6 +120,7 @@ void launch_gemm_f32(const GemmArgs& a, bool small_tile, hipStream_t s);
 // kernel, then 256 floats 2^-14 / s_n (RV_WMP16_SLOT uint16).  Precondition: |A| <= 1 (rows of an LSTM layer's output).
 #define RV_WMP16_SLOT ((size_t)2 * RV_E * RV_E + 2 * RV_E)
 void launch_gemm_mem_split(const float* A, int M, const uint16_t* img, float* C, hipStream_t s);
+#define RV_WKP16_SLOT ((size_t)2 * RV_E * RV_U)      // DecState::Wkp16
 // The same kernel over `ncb` column blocks of 256: C[M, ldc] (columns 256 cb ..) = A[M,256] . W_cb[256,256] (+ bias[256 cb ..]);
 // img = [ncb][8 k-steps][16 tiles][2 parts][64 lanes][8 f16], then 256 ncb floats 2^-14 / s_n.  A workgroup takes the ncb blocks of a
 // row tile one after the other, so A comes from HBM once.  The input projection of encoder layers >= 1 for the matrix-pipe
@@ -183,6 +184,13 @@ struct DecState {
   // value a key / a U' element can take (from the weights; |enc_out| <= 1) into [2^13, 2^14); descale = 2^-14 / scale (the query
   // and the alignments are scaled by 2^14)
   int persist_att; float mx_kscale, mx_kdescale, mx_uscale, mx_udescale;
+  // Option fused_memory: the default form (Luong, one cell, ATT 3) projects its chunk's [keys | U'] itself (decode.hip,
+  // persist_project_memory) when enc_rows is set: the encoder output [B,Tm,256] (`values` is not read then).  Wmp16 = the split GEMM's
+  // image of [W_mem | A_c] with its column factors (RV_WMP16_SLOT; the A_c tiles feed the U' product as they are); Wkp16 = the W_mem
+  // half of the same f16 parts with the columns permuted into the rows of the key tiles, [8 k-steps][8 tiles][2 parts][64 lanes][8 f16]:
+  // lane (i, kq) of tile 2 ks + y holds column 32 ks + 8 (i / 4) + 4 y + i % 4 (RV_WKP16_SLOT uint16).  mem_tap (option persist_taps):
+  // [B,Tm,256] that the workgroups also store their fp32 values to, or nullptr
+  const float* enc_rows; const uint16_t* Wmp16; const uint16_t* Wkp16; float* mem_tap;
   // ... and the cell product [ctx' | h] . Wcat2 too (ATT 3, 4): Wc16 = Wcat2 as MFMA B fragments of two f16 parts,
   // [8 waves][32 (k-step, gate) pairs][2 parts][64 lanes][8 f16]; wave w owns units 16 w .. 16 w + 15 of all four gates; lane (n, kq)
   // of pair p = 4 ks + g holds T . Wcat2[k][128 g + 16 w + n] / xs[k], k = 32 ks + 8 kq + 0..7, with xs = mx_uscale for the ctx' rows

@@ -994,6 +994,165 @@ __device__ __forceinline__ void tap_align_image(const DecState& d, const float* 
   }
 }
 
+// The default form's own memory projection (option fused_memory; DecState::enc_rows): the chunk's [keys | U'] = enc_out . [W_mem | A_c]
+// computed by its decode workgroup straight into the resident fragments, instead of a GEMM launch that writes [B,T_m,256] floats
+// which this prologue would read back.  Every element keeps the chain of k_gemm_mem_split3 (gemm_f32.hip): k in eight steps of 32,
+// per step w_lo . a_hi, w_hi . a_lo, w_hi . a_hi into one f32 accumulator, a' = 2^14 a, w' from the same host-packed parts, then
+// fma(acc, 2^-14 / s_n, +0) -- so the fp32 value that split_f16x8 cuts is the GEMM's, bit for bit.
+// No transposition: an MFMA's C/D registers give lane (n, q) rows 4 q + i, both resident layouts give lane (n, kq) 8 consecutive
+// indices; a tile's rows are free to choose, so each 32 indices are TWO tiles, X with row 4 q + i <-> index 8 q + i and Y with + 4,
+// and a lane's X and Y accumulators are its fragment.
+//   U' first.  Its fragments belong to the wave that owns the UNITS, over all of time, but a wave computes what it can feed from
+//   its own rows of enc_out: (32-step block, X | Y) unit wv + 8 r against all 8 unit tiles of A_c (the A_c half of Wmp16, 128 KB, in
+//   LDS).  The accumulators then cross to the owning waves through LDS, lane to the same lane, in two rounds of (NIT + 1) / 2 blocks
+//   (96 KB at most, over the weights that are dead by then).  Every wave reads in both rounds: fragments defined under a per-wave
+//   branch made k_dec_persist<5,11,1,3> spill one of them across the whole step loop.
+//   Keys second: wave wv owns the 16-step tiles wv + 8 c as in the step loop; the permuted rows are weight columns, a second
+//   host-packed image (Wkp16, 128 KB, in LDS).  All of a wave's tiles advance together, so each weight fragment is read once per wave;
+//   the accumulators of both phases turn into the resident fragments in place (8 floats -> two f16 parts of 8).
+// Rows t >= T_m are clamped to row T_m - 1 and livebits is built as in the GEMM-fed prologue.  d.mem_tap (option persist_taps): the
+// fp32 values are also stored where the GEMM would have put them.  Uses the first 128 KB of the dynamic LDS, which the caller
+// initialises only afterwards; ends with a barrier.
+template <int NIT>
+__device__ __forceinline__ void persist_project_memory(const DecState& d, int b, float* dsm, float4 (&kb)[(2 * NIT + 7) / 8][4][2],
+                                                       float4 (&ub)[NIT][2], unsigned& livebits) {
+  constexpr int NTT = (2 * NIT + 7) / 8;     // a wave's 16-step key tiles, and as many (block, X | Y) units of U'
+  const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, kq = lane >> 4, Tm = d.Tm;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform: what depends on the wave alone stays on the scalar side)
+  const float* enc = d.enc_rows + (size_t)b * Tm * RV_E + 8 * kq;
+  const float* css = reinterpret_cast<const float*>(d.Wmp16 + (size_t)2 * RV_E * RV_E);    // 2^-14 / s_n
+  uint4* wls = reinterpret_cast<uint4*>(dsm);           // [8 k-steps][8 tiles][2 parts][64 lanes] uint4 (128 KB)
+  f4v* xb = reinterpret_cast<f4v*>(dsm);                // exchange: [8 unit tiles][2 HB units of a round][64 lanes] float4
+  float* tap = d.mem_tap ? d.mem_tap + (size_t)b * Tm * RV_E : nullptr;
+  f4v acc[NTT][8];
+  int trow[NTT];
+  // one pass over a wave's NTT row tiles: SWAP = false: D = a . w (rows = steps: U'), true: D = w . a (rows = weight columns: keys)
+  auto product = [&](auto swap) {
+    constexpr bool SWAP = decltype(swap)::value;
+#pragma unroll
+    for (int r = 0; r < NTT; ++r)
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc[r][u] = f4v{0.f, 0.f, 0.f, 0.f};
+    float4 nx[NTT][2];
+#pragma unroll
+    for (int r = 0; r < NTT; ++r) {
+      nx[r][0] = *reinterpret_cast<const float4*>(enc + (size_t)trow[r] * RV_E);
+      nx[r][1] = *reinterpret_cast<const float4*>(enc + (size_t)trow[r] * RV_E + 4);
+    }
+#pragma unroll 1
+    for (int ks = 0; ks < 8; ++ks) {
+      h8 ah[NTT], al[NTT];
+#pragma unroll
+      for (int r = 0; r < NTT; ++r) {
+        const float v[8] = {nx[r][0].x, nx[r][0].y, nx[r][0].z, nx[r][0].w, nx[r][1].x, nx[r][1].y, nx[r][1].z, nx[r][1].w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float sv = v[j] * 16384.f;
+          ah[r][j] = (_Float16)sv;
+          al[r][j] = (_Float16)(sv - (float)ah[r][j]);
+        }
+      }
+      const int kn = min(ks + 1, 7);         // the next k-step's floats travel under this one's MFMAs (the last step re-reads its own)
+#pragma unroll
+      for (int r = 0; r < NTT; ++r) {
+        nx[r][0] = *reinterpret_cast<const float4*>(enc + (size_t)trow[r] * RV_E + 32 * kn);
+        nx[r][1] = *reinterpret_cast<const float4*>(enc + (size_t)trow[r] * RV_E + 32 * kn + 4);
+      }
+      const uint4* wp = wls + ks * 1024 + lane;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const h8 wh = __builtin_bit_cast(h8, wp[u * 128]), wl = __builtin_bit_cast(h8, wp[u * 128 + 64]);
+#pragma unroll
+        for (int r = 0; r < NTT; ++r) {
+          if constexpr (SWAP) {
+            acc[r][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, ah[r], acc[r][u], 0, 0, 0);
+            acc[r][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, al[r], acc[r][u], 0, 0, 0);
+            acc[r][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, ah[r], acc[r][u], 0, 0, 0);
+          } else {
+            acc[r][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[r], wl, acc[r][u], 0, 0, 0);
+            acc[r][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[r], wh, acc[r][u], 0, 0, 0);
+            acc[r][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[r], wh, acc[r][u], 0, 0, 0);
+          }
+        }
+      }
+    }
+  };
+
+  // ---- U': the A_c tiles (nt = 8..15) of every k-step of the GEMM's image -> LDS
+  {
+    const uint4* img = reinterpret_cast<const uint4*>(d.Wmp16);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { const int x = tid + 512 * i; wls[x] = img[(x >> 10) * 2048 + 1024 + (x & 1023)]; }
+  }
+#pragma unroll
+  for (int r = 0; r < NTT; ++r) {            // unit wv + 8 r = (block, X | Y): tile row i <-> step 32 block + 8 (i / 4) + 4 (X | Y) + i % 4
+    const int un = wv + 8 * r;
+    trow[r] = min(32 * (un >> 1) + 8 * (l16 >> 2) + 4 * (un & 1) + (l16 & 3), Tm - 1);
+  }
+  __syncthreads();
+  product(std::false_type{});
+  __syncthreads();                           // the weights are dead: the accumulators cross over them
+  constexpr int HB = (NIT + 1) / 2;          // blocks per round
+  const int col = RV_U + 16 * wv + l16;      // lane (n = unit, kq) of wave wv: U'[32 ks + 8 kq + 0..7][16 wv + n]
+  const float cf = css[col];
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf) {
+#pragma unroll
+    for (int r = 0; r < NTT; ++r) {
+      const int un = wv + 8 * r - 2 * HB * hf;
+      if (un >= 0 && un < 2 * HB && un + 2 * HB * hf < 2 * NIT)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) xb[(u * 2 * HB + un) * 64 + lane] = acc[r][u];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kl = 0; kl < HB; ++kl) {
+      const int ks = HB * hf + kl;
+      if (ks < NIT) {
+        const f4v x = xb[(wv * 2 * HB + 2 * kl) * 64 + lane], y = xb[(wv * 2 * HB + 2 * kl + 1) * 64 + lane];
+        const float v[8] = {fmaf(x[0], cf, 0.f), fmaf(x[1], cf, 0.f), fmaf(x[2], cf, 0.f), fmaf(x[3], cf, 0.f),
+                            fmaf(y[0], cf, 0.f), fmaf(y[1], cf, 0.f), fmaf(y[2], cf, 0.f), fmaf(y[3], cf, 0.f)};
+        if (tap)
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (32 * ks + 8 * kq + j < Tm) tap[(size_t)(32 * ks + 8 * kq + j) * RV_E + col] = v[j];
+        split_f16x8(v, d.mx_uscale, ub[ks][0], ub[ks][1]);
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- keys: the permuted image of W_mem -> LDS
+  {
+    const uint4* img = reinterpret_cast<const uint4*>(d.Wkp16);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) wls[tid + 512 * i] = img[tid + 512 * i];
+  }
+#pragma unroll
+  for (int c = 0; c < NTT; ++c) trow[c] = min(16 * (wv + 8 * c) + l16, Tm - 1);
+  __syncthreads();
+  product(std::true_type{});
+  const uint8_t* mrow = d.mask + (size_t)b * Tm;
+#pragma unroll
+  for (int c = 0; c < NTT; ++c) {            // lane (n = step, kq): key[t][32 ks + 8 kq + 0..7] = X and Y accumulators of tiles 2 ks, 2 ks + 1
+    const int t = 16 * (wv + 8 * c) + l16;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const float4 f0 = *reinterpret_cast<const float4*>(css + 32 * ks + 8 * kq), f1 = *reinterpret_cast<const float4*>(css + 32 * ks + 8 * kq + 4);
+      const f4v x = acc[c][2 * ks], y = acc[c][2 * ks + 1];
+      const float v[8] = {fmaf(x[0], f0.x, 0.f), fmaf(x[1], f0.y, 0.f), fmaf(x[2], f0.z, 0.f), fmaf(x[3], f0.w, 0.f),
+                          fmaf(y[0], f1.x, 0.f), fmaf(y[1], f1.y, 0.f), fmaf(y[2], f1.z, 0.f), fmaf(y[3], f1.w, 0.f)};
+      if (tap && t < Tm) {
+        *reinterpret_cast<float4*>(tap + (size_t)t * RV_E + 32 * ks + 8 * kq) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(tap + (size_t)t * RV_E + 32 * ks + 8 * kq + 4) = make_float4(v[4], v[5], v[6], v[7]);
+      }
+      split_f16x8(v, d.mx_kscale, kb[c][ks][0], kb[c][ks][1]);
+    }
+    if (t < Tm && mrow[trow[c]]) livebits |= 1u << c;      // _maybe_mask_score: padded steps never score
+  }
+  __syncthreads();
+}
+
 template <int W, int NIT, int D, int ATT = 0>
 __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __restrict__ Wcat /*[256,512] = [W_in rows of the attention input ; U]*/,
                                                       const float* __restrict__ Wtok /*[V,512]*/, const float* __restrict__ bdec /*[512]*/,
@@ -1050,6 +1209,14 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
   constexpr int NTT = (2 * NIT + 7) / 8;
   float4 kb[MXS ? NTT : 1][4][2], ub[MX ? NIT : 1][2];
   unsigned livebits = 0;
+  // the default form projects its chunk's memory itself when the call hands it enc_out (persist_project_memory); d.values is unused then
+  constexpr bool FUSE = ATT == 3 && D == 1;
+  bool fused = false;
+  if constexpr (FUSE) {
+    fused = d.enc_rows != nullptr;
+    if (fused) persist_project_memory<NIT>(d, b, dsm, kb, ub, livebits);
+  }
+  if (!fused) {
   if constexpr (MXS) {
     const float* cbase = d.values + (size_t)b * Tm * RV_E;
     const uint8_t* mrow = d.mask + (size_t)b * Tm;
@@ -1078,6 +1245,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
       split_f16x8(v, d.mx_uscale, ub[ks][0], ub[ks][1]);
     }
   }
+  }   // !fused
   if constexpr (!MXS) {
     const float* cbase = d.values + (size_t)b * Tm * RV_E;
     const uint8_t* mrow = d.mask + (size_t)b * Tm;

@@ -99,6 +99,9 @@ struct RvContext {
   float* d_Nh = nullptr;                    // derived (one decoder cell): A_h W_fc [128][V]
   uint16_t* d_Wc16 = nullptr;               // derived (one decoder cell): Wcat2 as two f16 parts in MFMA B-fragment order (DecState::Wc16)
   uint16_t* d_Wmp16 = nullptr;              // derived: Wmp as two f16 parts in MFMA fragment order + column factors (launch_gemm_mem_split)
+  uint16_t* d_Wkp16 = nullptr;              // derived: the W_mem half of those parts, columns permuted into key-tile rows (DecState::Wkp16)
+  int opt_fused_mem = 1;                    // option "fused_memory": the default decode form projects its own attention memory (no gemm_memory launch)
+  int lmem2_stale = 0;                      // the last call did so without persist_taps: mem2 is built when "projected_memory" is asked for
   float* mem2 = nullptr;                    // [B,Tm,256] = enc_out . Wmp: keys | attention-layer image of the values
   float* d_WcatT = nullptr;                 // derived: ([W_dec[V:] ; U_dec])^T, [512][256]
   const float *W_mem = nullptr, *W_q = nullptr, *v_att = nullptr, *W_att = nullptr, *W_fc = nullptr, *b_fc = nullptr;
@@ -136,7 +139,7 @@ struct RvContext {
   // one hipGraph per slab context and call shape: the whole slab (ten launches on the default path) replays as ONE hipGraphLaunch.
   // Every kernel argument is frozen at capture; the addresses that change from call to call (caller inputs and outputs) reach the
   // kernels through a 4-entry table in mapped pinned memory (common.h: RV_PTAB_*), rewritten by the host before each replay
-  struct SlabGraph { hipGraphExec_t exec = nullptr; int lflash = 0, lkeys = 0, lpersist = 0, lsplit = 1, lW = 0; };
+  struct SlabGraph { hipGraphExec_t exec = nullptr; int lflash = 0, lkeys = 0, lpersist = 0, lsplit = 1, lW = 0, lmem2_stale = 0; };
   std::map<SlabKey, SlabGraph> slab_graphs;
   const void** d_ptab = nullptr;
   const void** pin_ptab = nullptr;
@@ -528,11 +531,11 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
     const hipError_t ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
     HIPCHK(h, ie);
-    g.lflash = h->lflash; g.lkeys = h->lkeys; g.lpersist = h->lpersist; g.lsplit = h->lsplit; g.lW = h->lW;
+    g.lflash = h->lflash; g.lkeys = h->lkeys; g.lpersist = h->lpersist; g.lsplit = h->lsplit; g.lW = h->lW; g.lmem2_stale = h->lmem2_stale;
     it = h->slab_graphs.emplace(key, g).first;
   }
   const RvContext::SlabGraph& g = it->second;
-  h->lflash = g.lflash; h->lkeys = g.lkeys; h->lpersist = g.lpersist; h->lsplit = g.lsplit; h->lW = g.lW;
+  h->lflash = g.lflash; h->lkeys = g.lkeys; h->lpersist = g.lpersist; h->lsplit = g.lsplit; h->lW = g.lW; h->lmem2_stale = g.lmem2_stale;
   HIPCHK(h, hipGraphLaunch(g.exec, s));
   return RV_OK;
 }
@@ -670,6 +673,7 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
   d.Wc16 = h->d_Wc16; d.mx_cdescale = h->mx_cdescale; d.Wl16 = h->d_Wl16; d.mx_ldescale = h->mx_ldescale;
   d.Wq16 = h->d_Wq16; d.mx_qdescale = h->mx_qdescale; d.W1c16 = h->d_W1c16; d.mx_c1descale = h->mx_c1descale;
   h->lpersist = persist_att >= 0 ? 1 : 0;
+  h->lmem2_stale = 0;
   if (h->lpersist) { nsplit = 1; d.chunk_steps = h->d_chunk_steps; }
   h->lsplit = nsplit;
   if (!h->lpersist) {
@@ -715,7 +719,14 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
   if (h->lpersist) {
     part[0] = d; part[0].part = 0; parts.n = 1;
     if (greedy) HIPCHK(h, hipMemsetAsync(d.nfin, 0, 2 * sizeof(int), s));   // chunks-finished count and latest first-finish step
-    {   // attention memory in the form the persistent decode keeps on chip: [keys | U'] = enc_out . [W_mem | A_c]
+    // The default form (Luong, one cell, everything on the matrix pipe) takes enc_out and projects each chunk's rows in its own
+    // prologue, with the split GEMM's arithmetic (decode.hip, persist_project_memory); every other form reads the GEMM's mem2
+    const bool fused_mem = h->opt_fused_mem && h->opt_split_proj && persist_att == 3 && d.depth == 1;
+    h->lmem2_stale = fused_mem && !h->opt_ptaps;
+    d.enc_rows = nullptr; d.Wmp16 = h->d_Wmp16; d.Wkp16 = h->d_Wkp16; d.mem_tap = nullptr;
+    if (fused_mem) {
+      d.enc_rows = h->enc_out; d.mem_tap = h->opt_ptaps ? h->mem2 : nullptr;
+    } else {   // attention memory in the form the persistent decode keeps on chip: [keys | U'] = enc_out . [W_mem | A_c]
       GemmArgs g{};
       g.A = h->enc_out; g.lda = RV_E; g.Bm = h->d_Wmp; g.ldb = RV_E; g.C = h->mem2; g.ldc = RV_E;
       g.M = B * Tm; g.N = RV_E; g.K = RV_E;
@@ -933,7 +944,7 @@ int create_child(RvContext* p, RvContext** out) {
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return fail(p, RV_EHIP, "hipStreamCreate failed for an asynchronous context"); }
   h->d_w = p->d_w; h->n_w = p->n_w;
   h->d_WmemT = p->d_WmemT; h->d_Up = p->d_Up; h->d_Wp = p->d_Wp; h->d_Wsb = p->d_Wsb; h->d_Wh = p->d_Wh; h->d_Ua = p->d_Ua;
-  h->d_Wx16 = p->d_Wx16; h->d_bx2 = p->d_bx2; h->d_Wmp = p->d_Wmp; h->d_Wcat2 = p->d_Wcat2; h->d_Nh = p->d_Nh; h->d_Wmp16 = p->d_Wmp16; h->d_Wc16 = p->d_Wc16; h->d_Wl16 = p->d_Wl16;
+  h->d_Wx16 = p->d_Wx16; h->d_bx2 = p->d_bx2; h->d_Wmp = p->d_Wmp; h->d_Wcat2 = p->d_Wcat2; h->d_Nh = p->d_Nh; h->d_Wmp16 = p->d_Wmp16; h->d_Wkp16 = p->d_Wkp16; h->d_Wc16 = p->d_Wc16; h->d_Wl16 = p->d_Wl16;
   h->d_Wq16 = p->d_Wq16; h->d_W1c16 = p->d_W1c16;
   h->d_WcatT = p->d_WcatT;
   bind_weights(h);
@@ -949,7 +960,7 @@ void sync_child(RvContext* k, const RvContext* p) {
   k->opt_split = p->opt_split; k->opt_att_nt = p->opt_att_nt; k->opt_side_ev = p->opt_side_ev; k->opt_lane_inproj = p->opt_lane_inproj; k->opt_persist = p->opt_persist;
   k->opt_flash = p->opt_flash; k->opt_split_proj = p->opt_split_proj; k->opt_mx_att = p->opt_mx_att; k->opt_mx_cell = p->opt_mx_cell; k->mx_cdescale = p->mx_cdescale; k->mx_ldescale = p->mx_ldescale; k->opt_tail_wave = p->opt_tail_wave;
   k->mx_qdescale = p->mx_qdescale; k->mx_c1descale = p->mx_c1descale;
-  k->opt_fuse = p->opt_fuse; k->opt_wide = p->opt_wide; k->opt_graph = p->opt_graph; k->opt_profile = p->opt_profile;
+  k->opt_fuse = p->opt_fuse; k->opt_fused_mem = p->opt_fused_mem; k->opt_wide = p->opt_wide; k->opt_graph = p->opt_graph; k->opt_profile = p->opt_profile;
   k->opt_taps = 0; k->opt_ptaps = 0;      // debug taps belong to the synchronous calls
   k->inflight_hint = p->inflight_hint;
 }
@@ -1014,6 +1025,7 @@ int rv_create(const RvConfig* cfg, rv_handle* out) {
   TRY(dalloc(h, &h->d_WcatT, (size_t)c.dec_depth * RV_G * RV_E));
   TRY(dalloc(h, &h->d_Wmp, (size_t)RV_E * RV_E));
   TRY(dalloc(h, &h->d_Wmp16, RV_WMP16_SLOT));
+  TRY(dalloc(h, &h->d_Wkp16, RV_WKP16_SLOT));
   TRY(dalloc(h, &h->d_Wc16, (size_t)2 * 3 * RV_U * RV_G));      // (two cells: 384 rows)
   if (c.dec_depth == 2) TRY(dalloc(h, &h->d_W1c16, (size_t)2 * RV_E * RV_G));
   TRY(dalloc(h, &h->d_Wl16, (size_t)2 * RV_E * 16));
@@ -1220,6 +1232,18 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
       std::vector<uint16_t> img(RV_WMP16_SLOT);
       rv_pack_split_image(wmp.data(), RV_E, 1, [](int c) { return (size_t)c; }, img.data());
       HIPCHK(h, hipMemcpy(h->d_Wmp16, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+      // the same f16 parts of the W_mem half, for the decode's own projection (DecState::Wkp16): lane (i, kq) of key tile 2 ks + y
+      // takes what lane (c % 16, kq) of column tile c / 16 holds, c = 32 ks + 8 (i / 4) + 4 y + i % 4
+      std::vector<uint16_t> kimg(RV_WKP16_SLOT);
+      for (int st = 0; st < 8; ++st)
+        for (int t8 = 0; t8 < 8; ++t8)
+          for (int part = 0; part < 2; ++part)
+            for (int ln = 0; ln < 64; ++ln) {
+              const int i = ln & 15, q = ln >> 4, c = 32 * (t8 >> 1) + 8 * (i >> 2) + 4 * (t8 & 1) + (i & 3);
+              memcpy(&kimg[((((size_t)st * 8 + t8) * 2 + part) * 64 + ln) * 8],
+                     &img[((((size_t)st * 16 + c / 16) * 2 + part) * 64 + 16 * q + c % 16) * 8], 8 * sizeof(uint16_t));
+            }
+      HIPCHK(h, hipMemcpy(h->d_Wkp16, kimg.data(), kimg.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     }
     if (h->cfg.dec_depth <= 2) {
       // attention = h . A_h + ctx' (h = the top cell's output); its h part is folded into what consumes the attention vector (products in double):
@@ -1446,6 +1470,7 @@ int rv_set_option(rv_handle h, const char* key, int32_t value) {
   if (!strcmp(key, "debug_taps")) h->opt_taps = value != 0;
   else if (!strcmp(key, "slab_graph")) h->opt_slab_graph = value != 0;
   else if (!strcmp(key, "persist_taps")) h->opt_ptaps = value != 0;
+  else if (!strcmp(key, "fused_memory")) h->opt_fused_mem = value != 0;
   else if (!strcmp(key, "use_graph")) h->opt_graph = value != 0;
   else if (!strcmp(key, "flash_attend")) h->opt_flash = value != 0;
   else if (!strcmp(key, "persistent_decode")) h->opt_persist = value != 0;
@@ -1492,6 +1517,12 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
   }
   else if (!strcmp(name, "projected_memory")) {
     if (!h->lpersist) return fail(h, RV_ESTATE, "the projected memory is built for the persistent decode only (the last call ran the per-step kernels)");
+    if (h->lmem2_stale) {   // the decode projected its chunks itself and stored nothing: the same product of that call's enc_out, now
+      HIPCHK(h, hipSetDevice(h->cfg.device));
+      launch_gemm_mem_split(h->enc_out, (int)(B * Tm), h->d_Wmp16, h->mem2, h->stream);
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      h->lmem2_stale = 0;
+    }
     src = h->mem2; n = B * Tm * RV_E;
   }
   else if (!strcmp(name, "rec_stamps")) {

@@ -14,5 +14,5 @@ for L in (2, 3, 5, 9, 17, 48):
     bc.set_option("profile", 1); bc.reset_profile()
     for _ in range(20): bc.beam_search_prediction(x, W, L)
     p = {k: v[0] / max(v[1], 1) for k, v in bc.profile().items()}
-    print(f"L={L:3d} ({L - 1} steps at most): dec_persist {p['dec_persist']:.4f} ms, dec_finalize {p['dec_finalize']:.4f}, gemm_memory {p['gemm_memory']:.4f}", flush=True)
+    print(f"L={L:3d} ({L - 1} steps at most): dec_persist {p['dec_persist']:.4f} ms, dec_finalize {p['dec_finalize']:.4f}, gemm_memory {p.get('gemm_memory', 0.0):.4f} (0: projected in the decode's prologue, option fused_memory)", flush=True)
     bc.close()
