@@ -15,10 +15,11 @@
  * rv_greedy_search_dev, rv_load_weights, rv_get_tensor: results are complete when the call
  * returns, so a caller's wall-clock timers mean what they mean around the reference's methods.
  * Asynchronous calls -- rv_beam_search_submit, _submit_dev, _submit_calls: they return once the
- * slab is queued; the matching rv_beam_search_collect* waits for it.  A synchronous call may be
+ * slab is queued, or held for its group until one of the events listed at rv_beam_search_flush
+ * (option "coalesce"); the matching rv_beam_search_collect* waits for it.  A synchronous call may be
  * made while tickets are in flight: it runs on an idle slab context of the handle (its own when
  * that one is idle) and fails with RV_ESTATE, touching nothing, when every context holds an
- * uncollected ticket.  rv_get_tensor and the debug-tap options refer to the handle's OWN context:
+ * uncollected ticket (with coalesced slabs: when async_depth tickets are uncollected).  rv_get_tensor and the debug-tap options refer to the handle's OWN context:
  * with taps on, a synchronous call needs that context idle.
  *
  * Hardware queues: every slab context is one HIP stream, and the HIP runtime multiplexes a
@@ -26,7 +27,8 @@
  * otherwise when the runtime starts, i.e. at the process's first HIP call).  Loading this
  * library sets GPU_MAX_HW_QUEUES=16 if the variable is unset (RAVVENT_KEEP_ENV=1 opts out): load
  * it before the first HIP call, or export the variable yourself.  rv_set_option("async_depth", n)
- * returns the warning RV_WQUEUES when n exceeds the setting it finds.
+ * returns the warning RV_WQUEUES when n exceeds the setting it finds.  With fewer queues than
+ * contexts the handle decodes consecutive slabs as one wide call instead (option "coalesce").
  *
  * Host-buffer entry points copy inputs H2D / outputs D2H themselves.  The *_dev variants
  * take device addresses valid on the handle's device (e.g. torch tensor data_ptr()) and move
@@ -135,6 +137,20 @@ int rv_beam_search_submit_calls(rv_handle h, const float* raw, const float* even
                                 int32_t W, int32_t L, const uint8_t* lut, int32_t* ticket);
 int rv_beam_search_collect_calls(rv_handle h, int32_t ticket, uint8_t* bases, int32_t* lengths, float* probs, int32_t* S_out);
 
+/* Coalesced slabs (option "coalesce" = n >= 2, or its default when it chooses so): up to n consecutively submitted slabs of the default
+ * streamed path -- beam search, persistent decode, matrix-pipe recurrences, "profile" 0, no taps, "slab_graph" 0 -- are decoded as ONE
+ * internal call of sum(B) chunks on a group context (buffers for n x max_batch chunks; ceil(async_depth / n) of them in ordinary use, one
+ * more whenever none is idle), so that the encoder recurrences launch n times as many workgroups and the handle fills the chip from a few
+ * hardware queues.  Tickets, results, S and the padding of the columns >= S stay per slab and byte-identical to the synchronous call's;
+ * submit still succeeds whenever fewer than async_depth tickets are uncollected; host inputs are staged, and device inputs copied into the
+ * group's input buffer by a stream-ordered copy, when submit is called.  A group is launched when it has n members, and early on:
+ *   a submit whose T_r, T_e, W, L, input / output kind or lut differs from the group's, or that takes another path (that slab then
+ *   runs alone); a collect of any of its tickets; a synchronous call; rv_set_option; rv_load_weights (which still refuses while
+ *   tickets are uncollected); rv_destroy; rv_beam_search_flush.
+ * A caller that submits a slab and then waits for something else than its ticket calls rv_beam_search_flush, which launches the group
+ * that is still filling and returns at once (RV_OK also when there is none).  A launch that fails is reported by its tickets' collects. */
+int rv_beam_search_flush(rv_handle h);
+
 /* Basecaller.greedy_search_prediction (basecaller.py:317-330): tokens = sample_id [B, L-1],
  * logits = rnn_output [B, L-1, vocab]; columns >= S are pad_token / 0. */
 int rv_greedy_search(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r,
@@ -184,6 +200,13 @@ int rv_greedy_search_dev(rv_handle h, const float* d_raw, const float* d_event, 
  *                       the slab or shard it travels in),
  *          "async_depth" (1..16, default 2: contexts the rv_beam_search_submit* calls rotate through; returns the warning RV_WQUEUES -- the
  *                       option is set -- when the value exceeds GPU_MAX_HW_QUEUES as found in the environment, see "Hardware queues" above),
+ *          "coalesce"   (-1 / 0 / 1 / 2..8, default -1: slabs of the asynchronous calls decoded as one internal call, see rv_beam_search_flush.
+ *                       0 or 1 = none: one context and one stream per slab.  -1 = chosen from "async_depth" and the hardware queues found in
+ *                       the environment: 1 for depths up to 3 (a slab is never held back from a caller that submits one and then works on
+ *                       the CPU) and wherever the queues are at least as many as the contexts; else 2 below depth 8 and min(depth / 2, 5) from there, so that one group
+ *                       runs while the next fills.  An explicit value is capped by the depth.  Greedy search, the per-step decode, tapped or
+ *                       profiled calls and the fma recurrence form are never coalesced.  With "wide_recurrence" -1 a group takes the form its
+ *                       first member would have got alone.  rv_get_tensor("coalesce_stats") counts what was coalesced),
  *          "slab_graph" (0/1, default 0: a call on the default path -- matrix-pipe recurrences, persistent decode, no profiling, no taps --
  *                       replays as ONE hipGraphLaunch per slab (captured per slab context and call shape; the caller's input / output
  *                       addresses reach the kernels through a table in mapped pinned memory) instead of eight kernel launches (nine with "fused_memory" 0, one more with "lane_projection" 0): half the
@@ -235,6 +258,8 @@ int rv_set_option(rv_handle h, const char* key, int32_t value);
  *                                 it; a per-step decode replayed from its captured hipGraph reports the forms of the capture.  After a call
  *                                 that ran as a slab graph (option "slab_graph") it fails with RV_ESTATE
  *   "kernel_form_list" [n,5]      every instantiation the form lists hold, in the same rows, whatever the last call was
+ *   "coalesce_stats"  [4]         of the handle since it was created: groups launched (option "coalesce"), slabs they held, members of the
+ *                                 largest one, and the slabs per group the options and the environment give right now (1 = none)
  * n_written receives the element count; fails with RV_EINVAL if dst is too small. */
 int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, size_t* n_written);
 

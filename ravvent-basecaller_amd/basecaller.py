@@ -223,6 +223,15 @@ class Basecaller:
         self.set_option("async_depth", int(depth))
         self.async_depth = int(depth)
 
+    def set_coalesce(self, n: int):
+        """Slabs of the submit_* calls decoded as one internal call (option coalesce): 0 / 1 none, 2..8 that many, -1 (default) chosen
+        from the asynchronous depth.  A slab may then wait for its group: until it is full, a ticket of it is collected, `flush()`, ..."""
+        self.set_option("coalesce", int(n))
+
+    def flush(self):
+        """Launch the group of submitted slabs that is still filling (rv_beam_search_flush); nothing to do without one."""
+        self._check(self._lib.rv_beam_search_flush(self._h), "rv_beam_search_flush")
+
     supports_out = True       # submit_beam_search / beam_search_stream take caller-provided device outputs
 
     def submit_beam_search(self, input_data, beam_width, max_output_len, out=None, out_ptrs=None):

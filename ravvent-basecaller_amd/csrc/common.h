@@ -178,7 +178,8 @@ struct DecState {
   uint8_t lut[RV_MAX_VOCAB];   // token id -> upper-case letter, 0 for tokens the string form drops
   int* chunk_steps;       // persistent decode: [B] steps each chunk ran (nullptr on the per-step graph path)
   int* S_dev;             // [8]: [0] = S of the whole slab, [1+g] = S of sub-slab g
-  int* S_host;            // device address of the host-mapped pinned word the call's S is left in (no copy launch for 4 bytes)
+  int* S_host;            // device address of the host-mapped pinned words the call's S is left in (no copy launch for 4 bytes): [RV_MAX_MEMBERS],
+                          // one per member of a coalesced call (DecMembers), word 0 for every other call
   // The form of the persistent decode this call runs (dec_persist_form: k_dec_persist's ATT), -1 on the per-step kernels.  Its
   // matrix-pipe forms take the scores (Luong) and the context as split-f16 MFMAs.  Scales: powers of two that bring the largest
   // value a key / a U' element can take (from the weights; |enc_out| <= 1) into [2^13, 2^14); descale = 2^-14 / scale (the query
@@ -236,7 +237,13 @@ void launch_dec_persist(const DecState& d, const float* Wcat /*[256,512]*/, cons
                         const float* bdec /*[512]*/, const float* Wcat1, const float* bdec1, const float* Nh, hipStream_t s,
                         FormLog* log = nullptr);
 // ptab != null: the two output addresses are read from ptab[RV_PTAB_TOKENS] / ptab[RV_PTAB_OUT2] on the device instead
-void launch_dec_finalize(const DecState& d, int32_t* tokens /*[B,L-1]*/, float* scores_or_logits, hipStream_t s, const void* const* ptab = nullptr);
+// Members (persistent beam-search decode only): the slab is n slabs of the asynchronous calls decoded as one, back to back.  Member m
+// owns rows row0[m] .. row0[m] + rows[m] - 1: its S is the maximum of chunk_steps over those rows alone, goes to S_host[m], and its rows
+// are written through tokens[m] / out2[m] at the member's own row index.  n = 0: one member, the whole slab, the launcher's two pointers.
+#define RV_MAX_MEMBERS 8
+struct DecMembers { int n; int row0[RV_MAX_MEMBERS]; int rows[RV_MAX_MEMBERS]; int32_t* tokens[RV_MAX_MEMBERS]; float* out2[RV_MAX_MEMBERS]; };
+void launch_dec_finalize(const DecState& d, int32_t* tokens /*[B,L-1]*/, float* scores_or_logits, hipStream_t s, const void* const* ptab = nullptr,
+                         const DecMembers* members = nullptr);
 struct DecParts { const int* nfin[4]; int B[4]; int n; int steps; int* S_dev; int* S_host; };
 void launch_dec_reduce_steps(const DecParts& p, hipStream_t s);   // S_dev[0] = max_g S_g, S_dev[1+g] = S_g
 

@@ -2300,7 +2300,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
 
 // One 64-thread workgroup per chunk: the chunk's [S,W] ids/parents are staged in LDS so the
 // serial gather_tree back-trace runs on LDS latency, not on dependent global loads.
-__global__ __launch_bounds__(64) void k_dec_finalize(DecState d, int32_t* tokens, float* out2, const void* const* ptab) {
+__global__ __launch_bounds__(64) void k_dec_finalize(DecState d, int32_t* tokens, float* out2, const void* const* ptab, DecMembers mem) {
   __shared__ int s_ids[64 * RV_MAX_BEAM], s_par[64 * RV_MAX_BEAM], s_tok[64];
   __shared__ int s_S;
   if (ptab) {      // graph replay: this call's output addresses (the kernel arguments are the capture's)
@@ -2309,6 +2309,12 @@ __global__ __launch_bounds__(64) void k_dec_finalize(DecState d, int32_t* tokens
   }
   const int b = blockIdx.x, tid = threadIdx.x;
   const int steps = d.L - 1, W = d.W, V = d.V;
+  // the member of a coalesced call this chunk belongs to: its rows, its outputs, its word for S (one member = the whole slab otherwise)
+  int r0 = 0, nr = d.B, mi = 0;
+#pragma unroll
+  for (int m = 0; m < RV_MAX_MEMBERS; ++m)
+    if (m < mem.n && b >= mem.row0[m] && b < mem.row0[m] + mem.rows[m]) { r0 = mem.row0[m]; nr = mem.rows[m]; mi = m; tokens = mem.tokens[m]; out2 = mem.out2[m]; }
+  const int br = b - r0;      // the chunk's row in its member's outputs
   // S: steps the reference loop runs for the WHOLE slab (until every row is finished); So: steps this
   // sub-slab actually ran.  For s in [So, S) all of its beams are finished: the reference emits the
   // end token at an unchanged top-1 score there, which is what is written below.
@@ -2316,18 +2322,18 @@ __global__ __launch_bounds__(64) void k_dec_finalize(DecState d, int32_t* tokens
   // from L2) instead of in a launch of its own; workgroup 0 leaves it in S_dev for the host
   if (d.chunk_steps) {
     int m = 0;
-    for (int i = tid; i < d.B; i += 64) m = max(m, d.chunk_steps[i]);
+    for (int i = tid; i < nr; i += 64) m = max(m, d.chunk_steps[r0 + i]);
     for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
-    if (tid == 0) { s_S = m; if (b == 0) { d.S_dev[0] = m; d.S_dev[1] = m; d.S_host[0] = m; } }
+    if (tid == 0) { s_S = m; if (br == 0) { d.S_host[mi] = m; if (b == 0) { d.S_dev[0] = m; d.S_dev[1] = m; } } }
     __syncthreads();
   }
   const int S = d.chunk_steps ? s_S : d.S_dev[0], So = d.chunk_steps ? d.chunk_steps[b] : d.S_dev[1 + d.part];
-  int32_t* tk = tokens + (size_t)b * steps;
+  int32_t* tk = tokens + (size_t)br * steps;
   if (d.greedy) {
     for (int s = tid; s < steps; s += 64) {
       tk[s] = s < S ? d.step_ids[(size_t)s * d.B + b] : d.pad_token;
       for (int v = 0; v < V; ++v)
-        out2[((size_t)b * steps + s) * V + v] = s < S ? d.step_logits[((size_t)s * d.B + b) * V + v] : 0.f;
+        out2[((size_t)br * steps + s) * V + v] = s < S ? d.step_logits[((size_t)s * d.B + b) * V + v] : 0.f;
     }
     return;
   }
@@ -2361,7 +2367,7 @@ __global__ __launch_bounds__(64) void k_dec_finalize(DecState d, int32_t* tokens
   const int s = tid;
   const int tokv = s < S ? s_tok[s] : d.pad_token;
   const float scv = s < S ? d.step_scores[((size_t)min(s, So - 1) * d.B + b) * W] : 0.f;
-  if (s < steps) { tk[s] = tokv; out2[(size_t)b * steps + s] = scv; }
+  if (s < steps) { tk[s] = tokv; out2[(size_t)br * steps + s] = scv; }
   if (d.call_bases) {
     // fused tokens_to_nuc_sequences + calc_prob_logits_beam_search_scores for this chunk
     const float prev = __shfl_up(scv, 1);
@@ -2528,6 +2534,8 @@ hipError_t configure_decode_kernels() {
   return first;
 }
 
-void launch_dec_finalize(const DecState& d, int32_t* tokens, float* out2, hipStream_t s, const void* const* ptab) {
-  hipLaunchKernelGGL(k_dec_finalize, dim3(d.B), dim3(64), 0, s, d, tokens, out2, ptab);
+void launch_dec_finalize(const DecState& d, int32_t* tokens, float* out2, hipStream_t s, const void* const* ptab, const DecMembers* members) {
+  DecMembers mem{};
+  if (members) mem = *members;
+  hipLaunchKernelGGL(k_dec_finalize, dim3(d.B), dim3(64), 0, s, d, tokens, out2, ptab, mem);
 }

@@ -163,6 +163,23 @@ struct RvContext {
   int inflight_hint = 1;                    // slabs the caller keeps in flight (1 for the synchronous entry points): sizes the workgroups
   int next_slot = 0, generation = 0;
   struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
+
+  // coalesced asynchronous calls (option "coalesce"): up to n consecutively submitted slabs of the default streamed path are decoded as ONE
+  // internal call of sum(B) chunks on a GROUP context -- a child context whose buffers hold n x max_batch chunks -- so that the narrow
+  // recurrence launches are n times as wide and a handle fills the chip from few hardware queues.  Tickets stay per slab (`ticks`).
+  int opt_coalesce = -1;                    // 0 / 1 off, n >= 2 slabs per group, -1 chosen from async_depth (coalesce_n)
+  std::vector<RvContext*> groups;           // (root) group contexts, created when a slab finds none idle
+  RvContext* open_grp = nullptr;            // (root) the group that still takes members: filled, not launched
+  struct Tick { bool busy = false, done = false, dev_out = false, calls = false; int ticket = -1, member = 0, B = 0, row0 = 0, steps = 0, S = 0; RvContext* grp = nullptr; };
+  Tick ticks[RV_MAX_ASYNC];                 // (root) one per uncollected slab of a group; `done`: its group has run, S is final
+  long long co_groups = 0, co_slabs = 0, co_largest = 0;     // (root) "coalesce_stats": groups launched, slabs in them, members of the largest
+  // ... of a group context
+  int g_cap = 0, g_n = 0, g_rows = 0, g_staged = 0, g_failed = RV_OK;     // members it takes / holds, chunks they add up to, members whose results wait in its staging
+  bool g_launched = false, g_synced = false, g_dev_in = false, g_dev_out = false, g_calls = false, group_call = false;
+  int g_Tr = 0, g_Te = 0, g_W = 0, g_L = 0, g_formB = 0;
+  uint8_t g_lut[RV_MAX_VOCAB] = {};
+  int g_tslot[RV_MAX_MEMBERS] = {};
+  DecMembers lmem{};                        // the member table of the call being recorded (n = 0: an ordinary call)
 };
 
 namespace {
@@ -455,12 +472,10 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
 // Everything of a call up to (not including) the wait for the stream: launches and the D2H copies into pinned staging.
 // dev_out: tokens / out2 are device pointers written by the finalize kernel; else the results wait in pinned memory for finish().
 // lut != nullptr: the fused post-processing (rv_beam_search_calls) instead of tokens / scores.
-int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W,
-            int L, bool greedy, int32_t* tokens, float* out2, bool dev_out, const uint8_t* lut) {
-  if (!h) return RV_EINVAL;
+// The checks every call passes before anything is queued (T_r / T_e of an unused encoder become 0)
+int validate_call(RvContext* h, const float* raw, const float* ev, int B, int& T_r, int& T_e, int W, int L, const int32_t* tokens,
+                  const float* out2, bool dev_out) {
   const RvConfig& c = h->cfg;
-  const bool calls = lut != nullptr;
-  if (h->pend.busy) return fail(h, RV_ESTATE, "this context still holds an uncollected call");
   if (!h->loaded) return fail(h, RV_ESTATE, "no weights loaded (call rv_load_weights first)");
   const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
   if (!use_raw) T_r = 0;
@@ -470,10 +485,22 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
   if (use_ev && (T_e < 1 || T_e > c.max_event_len)) return fail(h, RV_EINVAL, "T_e=%d outside [1,%d]", T_e, c.max_event_len);
   if (W < 1 || W > c.max_beam || W > RV_MAX_BEAM) return fail(h, RV_EINVAL, "beam width %d outside [1,%d]", W, std::min(c.max_beam, RV_MAX_BEAM));
   if (L < 1 || L > c.max_output_len) return fail(h, RV_EINVAL, "max_output_len=%d outside [1,%d]", L, c.max_output_len);
-  if ((use_raw && !raw) || (use_ev && !ev)) return fail(h, RV_EINVAL, "missing input pointer for this mode");
+  if (B > 0 && ((use_raw && !raw) || (use_ev && !ev))) return fail(h, RV_EINVAL, "missing input pointer for this mode");   // (an empty device tensor has no address)
   if (T_r + T_e > 352) return fail(h, RV_EUNSUPPORTED, "attention memory of %d steps exceeds the 352 the decode kernel is built for", T_r + T_e);
   if (L > 64) return fail(h, RV_EUNSUPPORTED, "max_output_len %d exceeds 64", L);
   if (dev_out && B > 0 && L > 1 && (!tokens || !out2)) return fail(h, RV_EINVAL, "null output pointer");
+  return RV_OK;
+}
+
+int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W,
+            int L, bool greedy, int32_t* tokens, float* out2, bool dev_out, const uint8_t* lut) {
+  if (!h) return RV_EINVAL;
+  const RvConfig& c = h->cfg;
+  const bool calls = lut != nullptr;
+  if (h->pend.busy) return fail(h, RV_ESTATE, "this context still holds an uncollected call");
+  const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
+  { const int rc = validate_call(h, raw, ev, B, T_r, T_e, W, L, tokens, out2, dev_out); if (rc != RV_OK) return rc; }
+  if (!h->group_call) h->lmem.n = 0;
   HIPCHK(h, hipSetDevice(c.device));
   h->lB = B; h->lW = W; h->lL = L; h->lS = 0; h->lgreedy = greedy; h->lTm = T_r + T_e; h->ltaps = h->opt_taps; h->lptaps = h->opt_ptaps;
   h->lforms.n = 0; h->lforms.full = false; h->lforms_ok = 1;
@@ -489,8 +516,9 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
     if (use_ev) { memcpy(h->pin_ev, ev, sizeof(float) * B * T_e * 5); xe = h->d_ev; }
   }
 
-  h->lwide = wide_recurrence(h, B, T_r) ? 1 : 0;
-  h->lrows8 = h->lwide && rows8_wanted(h, B) ? 1 : 0;
+  const int form_B = h->group_call ? h->g_formB : B;      // a group takes the forms its first member would have got alone
+  h->lwide = wide_recurrence(h, form_B, T_r) ? 1 : 0;
+  h->lrows8 = h->lwide && rows8_wanted(h, form_B) ? 1 : 0;
   if ((!h->opt_fuse && c.enc_depth > 1) || h->lwide) {   // pre-projected tensors [max_batch, T_max, 2, 512]: allocated with the context (alloc_slab_buffers); this is a safety net
     if (use_raw && c.enc_depth > 1 && !h->xw[0]) { const int rc = dalloc(h, &h->xw[0], (size_t)c.max_batch * c.max_raw_len * 2 * RV_G); if (rc != RV_OK) return rc; }
     if (use_ev && !h->xw[1]) { const int rc = dalloc(h, &h->xw[1], (size_t)c.max_batch * c.max_event_len * 2 * RV_G); if (rc != RV_OK) return rc; }
@@ -778,7 +806,8 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     if (!h->lpersist) launch_dec_reduce_steps(parts, s);
     for (int g = 0; g < parts.n; ++g) {
       const size_t b0 = parts.n == 1 ? 0 : (size_t)B * g / parts.n;
-      launch_dec_finalize(part[g], tk + b0 * steps, o2 + b0 * steps * (greedy ? V : 1), s, ptab);     // (ptab: persistent decode only, one part)
+      launch_dec_finalize(part[g], tk + b0 * steps, o2 + b0 * steps * (greedy ? V : 1), s, ptab,      // (ptab: persistent decode only, one part)
+                          h->lpersist && h->lmem.n ? &h->lmem : nullptr);
     }
   }
   // (S reaches the host through d.S_host: the finalize / reduce kernel stores it straight into the mapped pinned word)
@@ -826,6 +855,8 @@ int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, in
 }
 
 void sync_child(RvContext* k, const RvContext* p);
+int flush_open_group(RvContext* h);
+int uncollected(const RvContext* h);
 
 int run(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W,
         int L, bool greedy, int32_t* tokens, float* out2, bool dev_out, int32_t* S_out, const CallsOut* calls = nullptr) {
@@ -833,6 +864,14 @@ int run(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int
   if (!S_out || (B > 0 && L > 1 && !calls && (!tokens || !out2))) return fail(h, RV_EINVAL, "null output pointer");
   if (calls && (!calls->lut || !calls->bases || !calls->lengths || !calls->probs)) return fail(h, RV_EINVAL, "null calls output pointer");
   *S_out = 0;
+  {   // coalesced tickets hold the handle's slots as the slab contexts' tickets do: with async_depth of them uncollected a synchronous
+      // call is refused, touching nothing (the handle's own context is idle then, but the contract does not depend on the path)
+    bool ticks_out = false;
+    for (const auto& t : h->ticks) ticks_out = ticks_out || t.busy;
+    if (ticks_out && uncollected(h) >= std::min(std::max(h->opt_async_depth, 1), RV_MAX_ASYNC))
+      return fail(h, RV_ESTATE, "every slab context of this handle holds an uncollected asynchronous call: collect one before a synchronous call");
+  }
+  flush_open_group(h);      // (a group still filling goes first; a failure there is its tickets')
   // A synchronous call between asynchronous ones: it runs on the handle's own context when that one is idle, else on any idle
   // context of the handle -- never on one that still holds an uncollected ticket (its stream work and output pointers are live).
   // Debug taps and rv_get_tensor belong to the handle's own context, so with taps on that context must be the idle one.
@@ -917,7 +956,7 @@ int alloc_slab_buffers(RvContext* h) {
   HIPTRY(hipHostMalloc((void**)&h->pin_ev, std::max<size_t>(B * Te * 5, 1) * sizeof(float), hipHostMallocDefault));
   HIPTRY(hipHostMalloc((void**)&h->pin_tok, B * L * sizeof(int32_t), hipHostMallocDefault));
   HIPTRY(hipHostMalloc((void**)&h->pin_out2, B * L * V * sizeof(float), hipHostMallocDefault));
-  HIPTRY(hipHostMalloc((void**)&h->pin_S, sizeof(int), hipHostMallocMapped));
+  HIPTRY(hipHostMalloc((void**)&h->pin_S, sizeof(int) * RV_MAX_MEMBERS, hipHostMallocMapped));
   HIPTRY(hipHostGetDevicePointer((void**)&d.S_host, h->pin_S, 0));
   TRY(dalloc(h, &h->d_bases, B * L));
   TRY(dalloc(h, &h->d_probs, B * L));
@@ -935,9 +974,10 @@ int alloc_slab_buffers(RvContext* h) {
 }
 
 // A further slab context of handle p for the asynchronous calls: own stream and buffers, p's weights.
-int create_child(RvContext* p, RvContext** out) {
+int create_child(RvContext* p, RvContext** out, int slabs = 1) {
   RvContext* h = new RvContext();
   h->cfg = p->cfg;
+  h->cfg.max_batch *= slabs;                // (a group context of the coalesced calls: room for `slabs` slabs back to back)
   h->parent = p;
   // (stream priorities -- the contexts at the runtime's three levels in turn, so that slabs submitted together leave lockstep -- measured
   //  no gain at the driver's 20 steps and 4 % less once the stream has settled: tools/stream_ab.py, round 4)
@@ -963,6 +1003,180 @@ void sync_child(RvContext* k, const RvContext* p) {
   k->opt_fuse = p->opt_fuse; k->opt_fused_mem = p->opt_fused_mem; k->opt_wide = p->opt_wide; k->opt_graph = p->opt_graph; k->opt_profile = p->opt_profile;
   k->opt_taps = 0; k->opt_ptaps = 0;      // debug taps belong to the synchronous calls
   k->inflight_hint = p->inflight_hint;
+}
+
+// ---- coalesced asynchronous calls
+int hw_queues() {       // what the runtime was (or will be) started with: rv_set_option("async_depth") warns from the same reading
+  const char* q = getenv("GPU_MAX_HW_QUEUES");
+  const int nq = q ? atoi(q) : 4;
+  return nq > 0 ? nq : 4;
+}
+
+// Slabs per group.  An explicit option value holds (up to the depth and the member table).  The default never holds back the slab of a
+// caller that submits one and then works on the CPU (depth <= 3), never exceeds depth / 2 (one group runs while the next fills), and
+// coalesces only where the contexts outnumber the hardware queues -- with a queue per context the slabs overlap by themselves
+// (profiles/coalesce.md has the sweep behind the numbers).
+int coalesce_n(const RvContext* h, int depth) {
+  if (h->opt_coalesce >= 0) return std::max(1, std::min({h->opt_coalesce, depth, RV_MAX_MEMBERS}));
+  if (depth <= 3 || hw_queues() >= depth) return 1;
+  return depth < 8 ? 2 : std::min(depth / 2, 5);      // (C3 on 4 queues: depth 4 and 6 stream fastest with 2, depth 10 with 5)
+}
+
+int uncollected(const RvContext* h) {
+  int n = h->pend.busy ? 1 : 0;
+  for (const RvContext* k : h->kids) n += k->pend.busy ? 1 : 0;
+  for (const auto& t : h->ticks) n += t.busy ? 1 : 0;
+  return n;
+}
+
+// Does this (validated) slab take the default streamed path, the only one that is coalesced?
+bool coalescible(const RvContext* h, int B, int T_r, int T_e, int W, int L) {
+  if (h->opt_profile != 0 || h->opt_taps || h->opt_ptaps || h->rec_ts || h->dec_st.dbg_ts || h->opt_slab_graph || L <= 1) return false;
+  return wide_recurrence(h, B, T_r) && persist_form(h, false, W, T_r + T_e) >= 0;
+}
+
+void reset_group(RvContext* g) {
+  g->g_n = 0; g->g_rows = 0; g->g_staged = 0; g->g_launched = false; g->g_synced = false; g->g_failed = RV_OK;
+}
+
+// Queue a group's internal call: its members' inputs are in d_raw / d_ev already (submit_group), back to back.
+int launch_group(RvContext* root, RvContext* g) {
+  if (root->open_grp == g) root->open_grp = nullptr;
+  if (g->g_launched) return g->g_failed;
+  g->g_launched = true;
+  root->co_groups += 1; root->co_slabs += g->g_n; root->co_largest = std::max<long long>(root->co_largest, g->g_n);
+  if (g->g_rows == 0) return RV_OK;          // empty slabs only: nothing to run, S = 0
+  sync_child(g, root);
+  const size_t steps = (size_t)g->g_L - 1;
+  DecMembers& m = g->lmem;
+  m.n = g->g_n;
+  for (int i = 0; i < g->g_n; ++i) {
+    const RvContext::Tick& t = root->ticks[g->g_tslot[i]];
+    m.row0[i] = t.row0; m.rows[i] = t.B;
+    if (!g->g_dev_out) { m.tokens[i] = g->out_tokens + (size_t)t.row0 * steps; m.out2[i] = g->out2 + (size_t)t.row0 * steps; }
+  }
+  g->group_call = true;
+  int rc = enqueue(g, g->d_raw, g->d_ev, true, g->g_rows, g->g_Tr, g->g_Te, g->g_W, g->g_L, false, g->out_tokens, g->out2, g->g_dev_out,
+                   g->g_calls ? g->g_lut : nullptr);
+  g->group_call = false;
+  g->pend.busy = false;                      // (the tickets live in the root's table)
+  if (rc != RV_OK) { root->err = g->err; g->g_failed = rc; }
+  return rc;
+}
+
+int flush_open_group(RvContext* h) { return h->open_grp ? launch_group(h, h->open_grp) : RV_OK; }
+
+int submit_group(RvContext* h, int n, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W, int L,
+                 int32_t* tokens, float* out2, bool dev_out, const uint8_t* lut, int32_t* ticket) {
+  const RvConfig& c = h->cfg;
+  const bool calls = lut != nullptr;
+  HIPCHK(h, hipSetDevice(c.device));
+  RvContext* g = h->open_grp;
+  if (g && (g->g_cap != n || g->g_Tr != T_r || g->g_Te != T_e || g->g_W != W || g->g_L != L || g->g_dev_in != dev_in || g->g_dev_out != dev_out ||
+            g->g_calls != calls || (calls && memcmp(g->g_lut, lut, (size_t)c.vocab)))) {
+    launch_group(h, g);                      // another shape or kind: the group goes as it is (a failure is its members' to collect)
+    g = nullptr;
+  }
+  if (!g) {
+    for (size_t i = 0; i < h->groups.size() && !g; ++i) {
+      RvContext* cand = h->groups[i];
+      if (cand->g_n != 0) continue;
+      if (cand->g_cap == n) { g = cand; break; }
+      rv_destroy(cand);                      // idle, sized for another group size (the option changed)
+      h->groups.erase(h->groups.begin() + i); --i;
+    }
+    // the group contexts an in-order stream needs, ceil(depth / n), exist from the first coalesced submit on, as the slab contexts do from the
+    // first submit: none is allocated (gigabytes of hipMalloc at C3 sizes) in the middle of a stream.  One more only when none is idle
+    const int depth = std::min(std::max(h->opt_async_depth, 1), RV_MAX_ASYNC);
+    while (!g || (int)h->groups.size() < (depth + n - 1) / n) {
+      RvContext* k = nullptr;
+      const int rc = create_child(h, &k, n);
+      if (rc != RV_OK) return rc;
+      k->g_cap = n;
+      reset_group(k);
+      h->groups.push_back(k);
+      if (!g) g = k;
+    }
+    reset_group(g);
+    g->g_Tr = T_r; g->g_Te = T_e; g->g_W = W; g->g_L = L; g->g_dev_in = dev_in; g->g_dev_out = dev_out; g->g_calls = calls; g->g_formB = B;
+    memset(g->g_lut, 0, sizeof g->g_lut);
+    if (calls) memcpy(g->g_lut, lut, (size_t)c.vocab);
+    h->open_grp = g;
+  }
+  int slot = -1;
+  for (int i = 0; i < RV_MAX_ASYNC && slot < 0; ++i) if (!h->ticks[i].busy) slot = i;
+  if (slot < 0) return fail(h, RV_ESTATE, "no free ticket");      // (unreachable: at most async_depth <= RV_MAX_ASYNC are uncollected)
+  const size_t row0 = (size_t)g->g_rows;
+  if (B > 0) {    // the member's inputs go to its rows of the group's input buffers now: the caller's host buffers are free on return
+    const size_t nr = (size_t)B * T_r, ne = (size_t)B * T_e * 5;
+    if (!dev_in) {
+      if (nr) { memcpy(g->pin_raw + row0 * T_r, raw, sizeof(float) * nr); HIPCHK(h, hipMemcpyAsync(g->d_raw + row0 * T_r, g->pin_raw + row0 * T_r, sizeof(float) * nr, hipMemcpyHostToDevice, g->stream)); }
+      if (ne) { memcpy(g->pin_ev + row0 * T_e * 5, ev, sizeof(float) * ne); HIPCHK(h, hipMemcpyAsync(g->d_ev + row0 * T_e * 5, g->pin_ev + row0 * T_e * 5, sizeof(float) * ne, hipMemcpyHostToDevice, g->stream)); }
+    } else {
+      if (nr) HIPCHK(h, hipMemcpyAsync(g->d_raw + row0 * T_r, raw, sizeof(float) * nr, hipMemcpyDeviceToDevice, g->stream));
+      if (ne) HIPCHK(h, hipMemcpyAsync(g->d_ev + row0 * T_e * 5, ev, sizeof(float) * ne, hipMemcpyDeviceToDevice, g->stream));
+    }
+  }
+  const int i = g->g_n++;
+  g->g_rows += B;
+  g->g_tslot[i] = slot;
+  if (dev_out) { g->lmem.tokens[i] = tokens; g->lmem.out2[i] = out2; } else g->g_staged += 1;
+  RvContext::Tick& t = h->ticks[slot];
+  t = RvContext::Tick{};
+  t.busy = true; t.dev_out = dev_out; t.calls = calls; t.member = i; t.B = B; t.row0 = (int)row0; t.steps = L - 1; t.grp = g;
+  h->generation = (h->generation + 1) & 0xFFFFF;
+  t.ticket = (h->generation << 4) | slot;
+  *ticket = t.ticket;
+  if (g->g_n == g->g_cap) launch_group(h, g);      // (a failed launch is reported when its tickets are collected)
+  return RV_OK;
+}
+
+int collect_group(RvContext* h, int slot, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out) {
+  RvContext::Tick& t = h->ticks[slot];
+  *S_out = 0;
+  if (!t.done) {          // the first collect of a group's ticket launches it if need be, waits for it and settles every member's S
+    RvContext* g = t.grp;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = launch_group(h, g);
+    if (rc == RV_OK && g->g_rows > 0) {
+      hipError_t e = hipStreamSynchronize(g->stream);
+      if (e == hipSuccess) e = hipGetLastError();
+      if (e != hipSuccess) rc = fail(h, RV_EHIP, "a coalesced call failed: %s", hipGetErrorString(e));
+    }
+    g->g_synced = true;
+    for (int i = 0; i < g->g_n; ++i) {
+      RvContext::Tick& u = h->ticks[g->g_tslot[i]];
+      u.done = true; u.S = (rc == RV_OK && u.B > 0) ? g->pin_S[i] : 0;
+      if (rc != RV_OK) u.S = -1;
+    }
+    if (rc != RV_OK || g->g_staged == 0) {   // results in the callers' device memory: the context takes the next group now
+      for (int i = 0; i < g->g_n; ++i) h->ticks[g->g_tslot[i]].grp = nullptr;
+      reset_group(g);
+    }
+  }
+  const RvContext::Tick u = t;
+  t.busy = false;
+  if (u.S < 0) return fail(h, RV_EHIP, "ticket %d: its coalesced call failed", u.ticket);
+  if (u.B > 0 && !u.dev_out) {
+    RvContext* g = u.grp;
+    const size_t B = u.B, steps = u.steps, r0 = u.row0;
+    int rc = RV_OK;
+    if (!u.calls && (!tokens || !out2)) rc = fail(h, RV_EINVAL, "null output pointer");
+    else if (u.calls && (!calls || !calls->bases || !calls->lengths || !calls->probs)) rc = fail(h, RV_EINVAL, "null calls output pointer");
+    else if (!u.calls) {
+      memcpy(tokens, g->pin_tok + r0 * steps, sizeof(int32_t) * B * steps);
+      memcpy(out2, g->pin_out2 + r0 * steps, sizeof(float) * B * steps);
+    } else {
+      memcpy(calls->bases, g->pin_bases + r0 * steps, B * steps);
+      memcpy(calls->probs, g->pin_probs + r0 * steps, sizeof(float) * B * steps);
+      memcpy(calls->lengths, g->pin_clen + r0, sizeof(int) * B);
+    }
+    if (rc != RV_OK) { if (--g->g_staged == 0) reset_group(g); return rc; }
+  }
+  if (!u.dev_out && u.grp && --u.grp->g_staged == 0) reset_group(u.grp);
+  *S_out = u.S;
+  h->lS = u.S;
+  return RV_OK;
 }
 
 }  // namespace
@@ -1055,6 +1269,9 @@ void rv_destroy(rv_handle h) {
   if (!h) return;
   for (RvContext* k : h->kids) rv_destroy(k);
   h->kids.clear();
+  for (RvContext* g : h->groups) rv_destroy(g);      // (launched or still filling: their streams drain in there)
+  h->groups.clear();
+  h->open_grp = nullptr;
   hipSetDevice(h->cfg.device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
@@ -1077,7 +1294,8 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
   if (!h) return RV_EINVAL;
   if (!blob) return fail(h, RV_EINVAL, "null weight blob");
   if (n_floats != h->n_w) return fail(h, RV_EINVAL, "weight blob has %zu floats, config needs %zu", n_floats, h->n_w);
-  if (h->pend.busy) return fail(h, RV_ESTATE, "collect the calls in flight before loading weights");
+  flush_open_group(h);
+  if (uncollected(h)) return fail(h, RV_ESTATE, "collect the calls in flight before loading weights");
   for (RvContext* k : h->kids) if (k->pend.busy) return fail(h, RV_ESTATE, "collect the calls in flight before loading weights");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   h->opt_gen++;                      // (weight-derived scalars travel by value in the decode's kernel arguments)
@@ -1407,6 +1625,20 @@ static int submit(rv_handle h, const float* raw, const float* ev, bool dev_in, i
   if (!h || !ticket) return RV_EINVAL;
   *ticket = -1;
   const int depth = std::min(std::max(h->opt_async_depth, 1), RV_MAX_ASYNC);
+  const int n_co = coalesce_n(h, depth);
+  bool ticks_out = false;
+  for (const auto& t : h->ticks) ticks_out = ticks_out || t.busy;
+  if (n_co >= 2 || ticks_out) {            // (neither: the path below, one context per slab, as it always was)
+    int tr = T_r, te = T_e;
+    const int rv = validate_call(h, raw, ev, B, tr, te, W, L, tokens, out2, dev_out);
+    if (rv != RV_OK) return rv;
+    if (uncollected(h) >= depth)
+      return fail(h, RV_ESTATE, "all %d asynchronous slots hold uncollected calls (option async_depth): collect one first", depth);
+    h->inflight_hint = depth;
+    if (n_co >= 2 && coalescible(h, B, tr, te, W, L))
+      return submit_group(h, n_co, raw, ev, dev_in, B, tr, te, W, L, tokens, out2, dev_out, lut, ticket);
+    flush_open_group(h);      // a slab of another path: the group goes as it is, this slab on a context of its own
+  }
   while ((int)h->kids.size() < depth - 1) {
     RvContext* k = nullptr;
     const int rc = create_child(h, &k);
@@ -1433,6 +1665,7 @@ static int submit(rv_handle h, const float* raw, const float* ev, bool dev_in, i
 static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out) {
   if (!h || !S_out) return RV_EINVAL;
   const int slot = ticket & 15;
+  if (ticket >= 0 && h->ticks[slot].busy && h->ticks[slot].ticket == ticket) return collect_group(h, slot, tokens, out2, calls, S_out);
   if (ticket < 0 || slot > (int)h->kids.size()) return fail(h, RV_EINVAL, "unknown ticket %d", ticket);
   RvContext* ctx = slot == 0 ? h : h->kids[slot - 1];
   if (!ctx->pend.busy || ctx->pend.ticket != ticket) return fail(h, RV_ESTATE, "ticket %d is not in flight (collected already?)", ticket);
@@ -1464,11 +1697,21 @@ int rv_beam_search_collect_calls(rv_handle h, int32_t ticket, uint8_t* bases, in
   return collect(h, ticket, nullptr, nullptr, &c, S_out);
 }
 
+int rv_beam_search_flush(rv_handle h) {
+  if (!h) return RV_EINVAL;
+  return flush_open_group(h);
+}
+
 int rv_set_option(rv_handle h, const char* key, int32_t value) {
   if (!h || !key) return RV_EINVAL;
+  flush_open_group(h);               // a group still filling was submitted under the options as they were
   h->opt_gen++;                      // slab graphs captured under the old options are rebuilt on their next use
   if (!strcmp(key, "debug_taps")) h->opt_taps = value != 0;
   else if (!strcmp(key, "slab_graph")) h->opt_slab_graph = value != 0;
+  else if (!strcmp(key, "coalesce")) {
+    if (value < -1 || value > RV_MAX_MEMBERS) return fail(h, RV_EINVAL, "coalesce must be -1 (chosen from async_depth), 0, 1 or 2..%d", RV_MAX_MEMBERS);
+    h->opt_coalesce = value;
+  }
   else if (!strcmp(key, "persist_taps")) h->opt_ptaps = value != 0;
   else if (!strcmp(key, "fused_memory")) h->opt_fused_mem = value != 0;
   else if (!strcmp(key, "use_graph")) h->opt_graph = value != 0;
@@ -1524,6 +1767,13 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
       h->lmem2_stale = 0;
     }
     src = h->mem2; n = B * Tm * RV_E;
+  }
+  else if (!strcmp(name, "coalesce_stats")) {   // groups launched, slabs they held, members of the largest, slabs per group in force
+    *n_written = 4;
+    if (!dst || dst_floats < 4) return fail(h, RV_EINVAL, "coalesce_stats needs 4 floats");
+    dst[0] = (float)h->co_groups; dst[1] = (float)h->co_slabs; dst[2] = (float)h->co_largest;
+    dst[3] = (float)coalesce_n(h, std::min(std::max(h->opt_async_depth, 1), RV_MAX_ASYNC));
+    return RV_OK;
   }
   else if (!strcmp(name, "rec_stamps")) {
     if (!h->rec_ts) return fail(h, RV_ESTATE, "set RV_REC_STAMPS=1 before rv_create (and load a -DRV_REC_STAMPS build)");
