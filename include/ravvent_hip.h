@@ -11,10 +11,10 @@
  * is NOT thread-safe (the reference is single-threaded and synchronous:
  * ravvent_performance_evaluator.py:51-55); use one handle per GPU / per process.
  *
- * Synchronous calls -- rv_beam_search, rv_beam_search_dev, rv_beam_search_calls, rv_greedy_search,
- * rv_greedy_search_dev, rv_load_weights, rv_get_tensor: results are complete when the call
+ * Synchronous calls -- rv_beam_search, rv_beam_search_dev, rv_beam_search_calls, rv_beam_search_all, rv_beam_search_all_dev,
+ * rv_greedy_search, rv_greedy_search_dev, rv_load_weights, rv_get_tensor: results are complete when the call
  * returns, so a caller's wall-clock timers mean what they mean around the reference's methods.
- * Asynchronous calls -- rv_beam_search_submit, _submit_dev, _submit_calls: they return once the
+ * Asynchronous calls -- rv_beam_search_submit, _submit_dev, _submit_calls, _submit_all, _submit_all_dev: they return once the
  * slab is queued, or held for its group until one of the events listed at rv_beam_search_flush
  * (option "coalesce"); the matching rv_beam_search_collect* waits for it.  A synchronous call may be
  * made while tickets are in flight: it runs on an idle slab context of the handle (its own when
@@ -136,6 +136,41 @@ int rv_beam_search_collect_dev(rv_handle h, int32_t ticket, int32_t* S_out);
 int rv_beam_search_submit_calls(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e,
                                 int32_t W, int32_t L, const uint8_t* lut, int32_t* ticket);
 int rv_beam_search_collect_calls(rv_handle h, int32_t ticket, uint8_t* bases, int32_t* lengths, float* probs, int32_t* S_out);
+
+/* The whole beam: what TFA's BeamSearchDecoder returns and Basecaller.beam_search_prediction drops (basecaller.py:313-315 keeps
+ * predicted_ids[:,:,0] / scores[:,:,0] and discards the final state's log_probs and lengths).  Same inputs, limits and messages as
+ * rv_beam_search; the five outputs, beam innermost, row stride (L-1) W for the first three:
+ *   tokens      [B, L-1, W] i32  predicted_ids: hypothesis w back-traced through parent_ids from its slot w at the chunk's last step
+ *                                (TFA gather_tree with the chunk's max_sequence_lengths, then end_token after a hypothesis's first
+ *                                end_token); end_token up to column S, pad_token in the columns >= S
+ *   scores      [B, L-1, W] f32  beam_search_decoder_output.scores: the cumulative log-probability in SLOT w after each step, NOT
+ *                                back-traced (column s may belong to another hypothesis than tokens[:, s, w]); 0 in the columns >= S
+ *   path_scores [B, L-1, W] f32  the cumulative log-probability of hypothesis w ITSELF after each step: scores in the slot its
+ *                                back-trace passes through; the value of its last step repeats up to column S; 0 in the columns >= S.
+ *                                exp(path_scores[:, s, w] - path_scores[:, s-1, w]) is the probability of tokens[:, s, w]
+ *   log_probs   [B, W]      f32  the final state's log_probs: the hypotheses' total scores, descending in w
+ *   lengths     [B, W]      i32  the final state's lengths: steps of each hypothesis up to and including its end_token
+ * tokens[:, :, 0] and scores[:, :, 0] are rv_beam_search's outputs byte for byte.  tokens and scores are required; path_scores,
+ * log_probs and lengths may be NULL and are then not produced.  A call with B == 0 or L == 1 launches nothing: S = 0, log_probs is
+ * the initial state (0 in slot 0, -inf in the others), lengths 0.
+ *   rv_beam_search_all             host inputs and outputs (staging buffers of max_batch x max_output_len x max_beam are allocated
+ *                                  on a slab context's first such call: a handle that never asks allocates nothing)
+ *   rv_beam_search_all_dev         device inputs and outputs (`d_out` is a host struct of device addresses)
+ *   rv_beam_search_submit_all / rv_beam_search_collect_all          asynchronous, host buffers (collect takes the RvBeams)
+ *   rv_beam_search_submit_all_dev / rv_beam_search_collect_dev      asynchronous, device buffers, given at submit
+ * An all-beams slab takes another finalize kernel than the slabs of rv_beam_search*: it is never coalesced (it launches the group
+ * that is filling and runs alone, on a slab context of its own) and never replayed as a "slab_graph".  Profile scope
+ * "dec_finalize_beams" (in place of "dec_finalize"). */
+typedef struct RvBeams { int32_t* tokens; float* scores; float* path_scores; float* log_probs; int32_t* lengths; } RvBeams;
+int rv_beam_search_all(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                       const RvBeams* out, int32_t* S_out);
+int rv_beam_search_all_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
+                           int32_t L, const RvBeams* d_out, int32_t* S_out);
+int rv_beam_search_submit_all(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
+                              int32_t L, int32_t* ticket);
+int rv_beam_search_collect_all(rv_handle h, int32_t ticket, const RvBeams* out, int32_t* S_out);
+int rv_beam_search_submit_all_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e,
+                                  int32_t W, int32_t L, const RvBeams* d_out, int32_t* ticket);
 
 /* Coalesced slabs (option "coalesce" = n >= 2, or its default when it chooses so): up to n consecutively submitted slabs of the default
  * streamed path -- beam search, persistent decode, matrix-pipe recurrences, "profile" 0, no taps, "slab_graph" 0 -- are decoded as ONE

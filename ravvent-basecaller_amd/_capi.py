@@ -14,8 +14,16 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libravvent_hip.so")
 RV_OK = 0
 ERROR_NAMES = {-1: "RV_EINVAL", -2: "RV_ENOMEM", -3: "RV_EHIP", -4: "RV_ESTATE", -5: "RV_EUNSUPPORTED"}
 
+
+
+class CRvBeams(ctypes.Structure):
+    """RvBeams (include/ravvent_hip.h): the five outputs of the rv_beam_search_all* calls; the last three may be None."""
+    _fields_ = [("tokens", c_void_p), ("scores", c_void_p), ("path_scores", c_void_p), ("log_probs", c_void_p), ("lengths", c_void_p)]
+
+
 # every symbol include/ravvent_hip.h declares: (name, restype, argtypes)
 _F, _I = POINTER(c_float), POINTER(c_int32)
+_B = POINTER(CRvBeams)
 SYMBOLS = [
     ("rv_abi_version", c_int32, []),
     ("rv_create", c_int32, [POINTER(CRvConfig), POINTER(c_void_p)]),
@@ -32,6 +40,11 @@ SYMBOLS = [
     ("rv_beam_search_collect_dev", c_int32, [c_void_p, c_int32, _I]),
     ("rv_beam_search_submit_calls", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, _I]),
     ("rv_beam_search_collect_calls", c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, _I]),
+    ("rv_beam_search_all", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _B, _I]),
+    ("rv_beam_search_all_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _B, _I]),
+    ("rv_beam_search_submit_all", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _I]),
+    ("rv_beam_search_collect_all", c_int32, [c_void_p, c_int32, _B, _I]),
+    ("rv_beam_search_submit_all_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _B, _I]),
     ("rv_beam_search_flush", c_int32, [c_void_p]),
     ("rv_greedy_search", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
     ("rv_greedy_search_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),

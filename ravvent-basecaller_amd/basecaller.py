@@ -10,6 +10,7 @@ through the host-buffer C entry points (PCIe copies included), CUDA/HIP tensors 
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 
@@ -19,6 +20,12 @@ import torch
 from . import _capi, weights as _weights
 from .config import RvConfig, RAW_FEATURES, EVENT_FEATURES
 from .data_loader import nuc_tk, tokens_to_strings
+
+
+# What TFA's BeamSearchDecoder returns for a slab (rv_beam_search_all*, include/ravvent_hip.h): tokens [B,S,W] int32 the W
+# back-traced hypotheses, scores [B,S,W] the per-slot cumulative log-probabilities (not back-traced), path_scores [B,S,W] each
+# hypothesis's own cumulative log-probability, log_probs [B,W] / lengths [B,W] the final state's
+BeamHypotheses = collections.namedtuple("BeamHypotheses", "tokens scores path_scores log_probs lengths")
 
 
 def _as_int(x) -> int:
@@ -216,6 +223,57 @@ class Basecaller:
         self.last_steps = S.value
         return tokens[:, :S.value], scores[:, :S.value]
 
+    # ------------------------------------------------------------------ the whole beam
+    def _beams_dev(self, B, steps, W):
+        i32, f32 = torch.int32, torch.float32
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        return BeamHypotheses(mk((B, steps, W), i32), mk((B, steps, W), f32), mk((B, steps, W), f32), mk((B, W), f32), mk((B, W), i32))
+
+    @staticmethod
+    def _beams_host(B, steps, W):
+        return BeamHypotheses(np.empty((B, steps, W), np.int32), np.empty((B, steps, W), np.float32), np.empty((B, steps, W), np.float32),
+                              np.empty((B, W), np.float32), np.empty((B, W), np.int32))
+
+    @staticmethod
+    def _beams_struct(bufs):
+        ptr = lambda a: None if a is None else ctypes.c_void_p(a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data)
+        return _capi.CRvBeams(*[ptr(a) for a in bufs])
+
+    @staticmethod
+    def _beams_cut(bufs, S):
+        t = [a if isinstance(a, torch.Tensor) else torch.from_numpy(a) for a in bufs]
+        return BeamHypotheses(t[0][:, :S], t[1][:, :S], t[2][:, :S], t[3], t[4])
+
+    def _check_beams_out(self, out, B, steps, W):
+        want = (((B, steps, W), torch.int32), ((B, steps, W), torch.float32), ((B, steps, W), torch.float32), ((B, W), torch.float32),
+                ((B, W), torch.int32))
+        if len(out) != 5 or any(tuple(a.shape) != sh or a.dtype != dt or not a.is_contiguous() or a.device != self.device
+                                for a, (sh, dt) in zip(out, want)):
+            raise ValueError(f"out: five contiguous tensors on {self.device}: int32 / float32 / float32 {(B, steps, W)}, float32 / int32 {(B, W)}")
+        return BeamHypotheses(*out)
+
+    def beam_search_hypotheses(self, input_data, beam_width, max_output_len):
+        """All `beam_width` hypotheses of every chunk (rv_beam_search_all / _all_dev): what tfa's BeamSearchDecoder returns before
+        basecaller.py:313-315 keeps slot 0 -> BeamHypotheses(tokens [B,S,W] int32, scores [B,S,W] f32, path_scores [B,S,W] f32,
+        log_probs [B,W] f32, lengths [B,W] int32).  tokens[:, :, 0] / scores[:, :, 0] are `beam_search_prediction`'s results;
+        `utils.calc_prob_path_scores(path_scores)` gives each hypothesis's per-base probabilities."""
+        keep, pr, pe, B, Tr, Te, on_dev = self._gather_inputs(input_data)
+        L, W = _as_int(max_output_len), int(beam_width)
+        steps = max(L - 1, 0)
+        S = ctypes.c_int32(0)
+        if on_dev:
+            torch.cuda.current_stream(self.device).synchronize()   # inputs ready before the library's stream reads them
+            bufs = self._beams_dev(B, steps, max(W, 0))
+            st = self._beams_struct(bufs)
+            rc = self._lib.rv_beam_search_all_dev(self._h, pr, pe, B, Tr, Te, W, L, ctypes.byref(st), ctypes.byref(S))
+        else:
+            bufs = self._beams_host(B, steps, max(W, 0))
+            st = self._beams_struct(bufs)
+            rc = self._lib.rv_beam_search_all(self._h, pr, pe, B, Tr, Te, W, L, ctypes.byref(st), ctypes.byref(S))
+        self._check(rc, "rv_beam_search_all")
+        self.last_steps = S.value
+        return self._beams_cut(bufs, S.value)
+
     # ------------------------------------------------------------------ the hot path, several slabs in flight
     def set_async_depth(self, depth: int):
         """Slab contexts the submit_* calls rotate through (1..16; default 2).  With several slabs in flight the GPU never idles
@@ -234,17 +292,37 @@ class Basecaller:
 
     supports_out = True       # submit_beam_search / beam_search_stream take caller-provided device outputs
 
-    def submit_beam_search(self, input_data, beam_width, max_output_len, out=None, out_ptrs=None):
+    def submit_beam_search(self, input_data, beam_width, max_output_len, out=None, out_ptrs=None, all_beams=False):
         """Queue `beam_search_prediction(input_data, ...)` without waiting for the GPU (rv_beam_search_submit / _submit_dev);
         returns a ticket for `collect`.  Results are byte-identical to the synchronous call.  Device inputs must stay untouched
         until the ticket is collected (the ticket keeps them alive).  `out` (device inputs only): a pair of contiguous device
         tensors (int32 [B, L-1], float32 [B, L-1]) the library writes into instead of fresh ones -- e.g. views into a gather buffer.
         `out_ptrs` (device inputs only): the same as two raw device addresses (the caller vouches for room, type and lifetime; `collect`
-        then returns only the step count) -- a loop that submits thousands of slabs into one buffer saves the per-slab tensor views."""
+        then returns only the step count) -- a loop that submits thousands of slabs into one buffer saves the per-slab tensor views.
+        `all_beams`: queue `beam_search_hypotheses` instead (rv_beam_search_submit_all / _submit_all_dev); `out` is then its five
+        device tensors (tokens, scores, path_scores [B, L-1, W], log_probs, lengths [B, W]) and `collect` returns a BeamHypotheses.
+        Such a slab is never coalesced with others."""
         keep, pr, pe, B, Tr, Te, on_dev = self._gather_inputs(input_data)
         L, W = _as_int(max_output_len), int(beam_width)
         steps = max(L - 1, 0)
         t = ctypes.c_int32(-1)
+        if all_beams:
+            if out_ptrs is not None:
+                raise ValueError("all_beams takes its outputs as tensors (out=)")
+            call = {"kind": "all_dev" if on_dev else "all_host", "keep": keep, "B": B, "steps": steps, "W": max(W, 0)}
+            if on_dev:
+                torch.cuda.current_stream(self.device).synchronize()
+                bufs = self._check_beams_out(out, B, steps, W) if out is not None else self._beams_dev(B, steps, max(W, 0))
+                call["out"] = bufs
+                st = self._beams_struct(bufs)
+                rc = self._lib.rv_beam_search_submit_all_dev(self._h, pr, pe, B, Tr, Te, W, L, ctypes.byref(st), ctypes.byref(t))
+            else:
+                if out is not None:
+                    raise ValueError("out= needs device inputs")
+                rc = self._lib.rv_beam_search_submit_all(self._h, pr, pe, B, Tr, Te, W, L, ctypes.byref(t))
+            self._check(rc, "rv_beam_search_submit_all")
+            call["ticket"] = t.value
+            return call
         call = {"kind": "dev" if on_dev else "host", "keep": keep, "B": B, "steps": steps}
         if on_dev:
             torch.cuda.current_stream(self.device).synchronize()
@@ -273,8 +351,21 @@ class Basecaller:
         return call
 
     def collect(self, call):
-        """Wait for a `submit_beam_search` ticket -> (predicted_ids[:,:,0] [B,S] int32, scores[:,:,0] [B,S] f32)."""
+        """Wait for a `submit_beam_search` ticket -> (predicted_ids[:,:,0] [B,S] int32, scores[:,:,0] [B,S] f32), or the
+        BeamHypotheses of an `all_beams` ticket."""
         S = ctypes.c_int32(0)
+        if call["kind"] in ("all_dev", "all_host"):
+            if call["kind"] == "all_dev":
+                self._check(self._lib.rv_beam_search_collect_dev(self._h, call["ticket"], ctypes.byref(S)), "rv_beam_search_collect_dev")
+                bufs = call["out"]
+            else:
+                bufs = self._beams_host(call["B"], call["steps"], call["W"])
+                st = self._beams_struct(bufs)
+                self._check(self._lib.rv_beam_search_collect_all(self._h, call["ticket"], ctypes.byref(st), ctypes.byref(S)),
+                            "rv_beam_search_collect_all")
+            call["keep"] = None
+            self.last_steps = S.value
+            return self._beams_cut(bufs, S.value)
         if call["kind"] == "dev_ptrs":     # results went to the caller's addresses: only the step count comes back
             self._check(self._lib.rv_beam_search_collect_dev(self._h, call["ticket"], ctypes.byref(S)), "rv_beam_search_collect_dev")
             call["keep"] = None
@@ -424,9 +515,14 @@ class Basecaller:
         return self.beam_search_calls(input_data, beam_width, max_output_len, arrays=True)
 
     def tokens_to_nuc_sequences(self, result_tokens):
-        """basecaller.py:289-294"""
+        """basecaller.py:289-294.  [B,S,W] tokens (BeamHypotheses.tokens): a list of W strings per chunk."""
         if isinstance(result_tokens, torch.Tensor):
             result_tokens = result_tokens.detach().cpu().numpy()
+        result_tokens = np.asarray(result_tokens)
+        if result_tokens.ndim == 3:
+            Bn, Sn, Wn = result_tokens.shape
+            flat = self.tokens_to_nuc_sequences(np.ascontiguousarray(result_tokens.transpose(0, 2, 1)).reshape(Bn * Wn, Sn)) if Bn * Wn else []
+            return [flat[b * Wn:(b + 1) * Wn] for b in range(Bn)]
         if self.tokenizer.word_index == nuc_tk.word_index:
             return tokens_to_strings(result_tokens)
         table = np.zeros(256, np.uint8)

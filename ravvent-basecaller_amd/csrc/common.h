@@ -246,6 +246,11 @@ void launch_dec_finalize(const DecState& d, int32_t* tokens /*[B,L-1]*/, float* 
                          const DecMembers* members = nullptr);
 struct DecParts { const int* nfin[4]; int B[4]; int n; int steps; int* S_dev; int* S_host; };
 void launch_dec_reduce_steps(const DecParts& p, hipStream_t s);   // S_dev[0] = max_g S_g, S_dev[1+g] = S_g
+// The whole beam of a call (beams.hip, rv_beam_search_all*): k_dec_finalize_beams takes k_dec_finalize's place for such a call, one
+// launch per decode part.  Row stride (L-1) W, beam innermost; tokens / scores / path_scores [B,L-1,W], log_probs / lengths [B,W]
+// (include/ravvent_hip.h: RvBeams).  path_scores, log_probs and lengths may be null: the kernel skips a null output.
+struct BeamsOut { int32_t* tokens; float* scores; float* path_scores; float* log_probs; int32_t* lengths; };
+void launch_dec_finalize_beams(const DecState& d, const BeamsOut& o, hipStream_t s);
 
 // ---------------------------------------------------------------- device math helpers
 #ifdef __HIPCC__

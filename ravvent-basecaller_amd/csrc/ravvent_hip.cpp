@@ -126,6 +126,11 @@ struct RvContext {
   uint8_t *d_bases = nullptr, *pin_bases = nullptr;
   float *d_probs = nullptr, *pin_probs = nullptr;
   int *d_clen = nullptr, *pin_clen = nullptr;
+  // the whole beam (rv_beam_search_all*): device outputs and pinned staging of the host variants, [max_batch, max_output_len, max_beam]
+  // and [max_batch, max_beam], allocated on this context's first such call (ensure_beam_buffers)
+  BeamsOut d_beams{}, pin_beams{};
+  bool all_beams = false;                   // the call being recorded hands out the whole beam, through ...
+  BeamsOut lbeams{};                        // ... these device addresses (the caller's, or d_beams)
 
   int opt_taps = 0, opt_graph = 1, opt_profile = 0;
   long long* rec_ts = nullptr;              // diagnostic: per-wave cycle sums of the raw layer-0 recurrence (RV_REC_STAMPS=1) or of its fused layer 1 (=2)
@@ -162,7 +167,7 @@ struct RvContext {
   int opt_async_depth = 2;                  // contexts the asynchronous entry points rotate through (1..RV_MAX_ASYNC)
   int inflight_hint = 1;                    // slabs the caller keeps in flight (1 for the synchronous entry points): sizes the workgroups
   int next_slot = 0, generation = 0;
-  struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
+  struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false, all = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
 
   // coalesced asynchronous calls (option "coalesce"): up to n consecutively submitted slabs of the default streamed path are decoded as ONE
   // internal call of sum(B) chunks on a GROUP context -- a child context whose buffers hold n x max_batch chunks -- so that the narrow
@@ -505,9 +510,18 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
   h->lB = B; h->lW = W; h->lL = L; h->lS = 0; h->lgreedy = greedy; h->lTm = T_r + T_e; h->ltaps = h->opt_taps; h->lptaps = h->opt_ptaps;
   h->lforms.n = 0; h->lforms.full = false; h->lforms_ok = 1;
   h->pend = RvContext::PendingCall{};
-  h->pend.busy = true; h->pend.greedy = greedy; h->pend.dev_out = dev_out; h->pend.calls = calls;
+  h->pend.busy = true; h->pend.greedy = greedy; h->pend.dev_out = dev_out; h->pend.calls = calls; h->pend.all = h->all_beams;
   h->pend.B = B; h->pend.steps = std::max(L - 1, 0); h->pend.V = c.vocab; h->pend.Wd = greedy ? 1 : W;
-  if (B == 0 || L <= 1) { h->pend.trivial = true; return RV_OK; }
+  if (B == 0 || L <= 1) {
+    h->pend.trivial = true;
+    if (h->all_beams && dev_out && B > 0) {      // nothing is launched: the initial state goes to the caller's device buffers by plain copies
+      std::vector<float> lp((size_t)B * W, -INFINITY);
+      for (int b = 0; b < B; ++b) lp[(size_t)b * W] = 0.f;
+      if (h->lbeams.log_probs) HIPCHK(h, hipMemcpy(h->lbeams.log_probs, lp.data(), sizeof(float) * lp.size(), hipMemcpyHostToDevice));
+      if (h->lbeams.lengths) HIPCHK(h, hipMemset(h->lbeams.lengths, 0, sizeof(int32_t) * (size_t)B * W));
+    }
+    return RV_OK;
+  }
 
   hipStream_t s = h->stream;
   const float *xr = raw, *xe = ev;
@@ -537,7 +551,7 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
     h->graph_gen = root->opt_gen;
   }
   const bool graphable = root->opt_slab_graph && h->lwide && !h->lrows8 && persist_form(h, greedy, W, T_r + T_e) >= 0 && h->opt_profile == 0 && !h->opt_taps &&
-                         !h->opt_ptaps && !h->rec_ts && !h->dec_st.dbg_ts && h->d_ptab;
+                         !h->all_beams && !h->opt_ptaps && !h->rec_ts && !h->dec_st.dbg_ts && h->d_ptab;
   if (!graphable) return record_slab(h, xr, xe, !dev_in, B, T_r, T_e, W, L, greedy, tk, o2, dev_out, lut, nullptr);
   h->lforms_ok = 0;                             // (a slab graph replays without the host launchers: "kernel_forms" answers RV_ESTATE)
   h->pin_ptab[RV_PTAB_RAW] = xr; h->pin_ptab[RV_PTAB_EVENT] = xe; h->pin_ptab[RV_PTAB_TOKENS] = tk; h->pin_ptab[RV_PTAB_OUT2] = o2;
@@ -801,7 +815,19 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     if (rc != RV_OK) return rc;
   }
 
-  {
+  if (h->all_beams) {      // the whole beam: k_dec_finalize_beams in k_dec_finalize's place (never a group, never captured)
+    Scope sc(h, "dec_finalize_beams");
+    if (!h->lpersist) launch_dec_reduce_steps(parts, s);
+    for (int g = 0; g < parts.n; ++g) {
+      const size_t b0 = parts.n == 1 ? 0 : (size_t)B * g / parts.n;
+      BeamsOut o = h->lbeams;
+      o.tokens += b0 * steps * Wd; o.scores += b0 * steps * Wd;
+      if (o.path_scores) o.path_scores += b0 * steps * Wd;
+      if (o.log_probs) o.log_probs += b0 * Wd;
+      if (o.lengths) o.lengths += b0 * Wd;
+      launch_dec_finalize_beams(part[g], o, s);
+    }
+  } else {
     Scope sc(h, "dec_finalize");
     if (!h->lpersist) launch_dec_reduce_steps(parts, s);
     for (int g = 0; g < parts.n; ++g) {
@@ -811,7 +837,15 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     }
   }
   // (S reaches the host through d.S_host: the finalize / reduce kernel stores it straight into the mapped pinned word)
-  if (!dev_out && !calls) {
+  if (h->all_beams && !dev_out) {
+    const BeamsOut &o = h->lbeams, &p = h->pin_beams;
+    const size_t n = (size_t)B * steps * Wd, nb = (size_t)B * Wd;
+    HIPCHK(h, hipMemcpyAsync(p.tokens, o.tokens, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(p.scores, o.scores, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+    if (o.path_scores) HIPCHK(h, hipMemcpyAsync(p.path_scores, o.path_scores, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+    if (o.log_probs) HIPCHK(h, hipMemcpyAsync(p.log_probs, o.log_probs, sizeof(float) * nb, hipMemcpyDeviceToHost, s));
+    if (o.lengths) HIPCHK(h, hipMemcpyAsync(p.lengths, o.lengths, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, s));
+  } else if (!dev_out && !calls) {
     HIPCHK(h, hipMemcpyAsync(h->pin_tok, tk, sizeof(int32_t) * B * steps, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(h->pin_out2, o2, sizeof(float) * B * steps * (greedy ? V : 1), hipMemcpyDeviceToHost, s));
   }
@@ -825,21 +859,41 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
 }
 
 // The rest of a call: wait for the context's stream, hand the staged results to the caller's host buffers.
-int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out) {
+int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr) {
   if (!h || !S_out) return RV_EINVAL;
   if (!h->pend.busy) return fail(h, RV_ESTATE, "no call to collect on this context");
   const RvContext::PendingCall p = h->pend;
-  h->pend.busy = false;
   *S_out = 0;
-  if (p.trivial) return RV_OK;
-  if (!p.dev_out && !p.calls && (!tokens || !out2)) return fail(h, RV_EINVAL, "null output pointer");
+  if (p.all != (beams != nullptr) && !(p.all && p.dev_out))      // (the ticket stays in flight)
+    return fail(h, RV_EINVAL, p.all ? "this call hands out the whole beam: collect it with rv_beam_search_collect_all"
+                                    : "rv_beam_search_collect_all takes the tickets of rv_beam_search_submit_all");
+  h->pend.busy = false;
+  if (p.trivial) {
+    if (p.all && !p.dev_out && beams) {      // the initial state
+      for (size_t i = 0; i < (size_t)p.B * p.Wd; ++i) {
+        if (beams->log_probs) beams->log_probs[i] = i % p.Wd == 0 ? 0.f : -INFINITY;
+        if (beams->lengths) beams->lengths[i] = 0;
+      }
+    }
+    return RV_OK;
+  }
+  if (p.all && !p.dev_out && (!beams->tokens || !beams->scores)) return fail(h, RV_EINVAL, "null output pointer");
+  if (!p.all && !p.dev_out && !p.calls && (!tokens || !out2)) return fail(h, RV_EINVAL, "null output pointer");
   if (p.calls && (!calls || !calls->bases || !calls->lengths || !calls->probs)) return fail(h, RV_EINVAL, "null calls output pointer");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipGetLastError());
   const int S = *h->pin_S;
   const size_t B = p.B, steps = p.steps;
-  if (!p.dev_out && !p.calls) {
+  if (p.all && !p.dev_out) {
+    const BeamsOut& q = h->pin_beams;
+    const size_t n = B * steps * p.Wd, nb = B * p.Wd;
+    memcpy(beams->tokens, q.tokens, sizeof(int32_t) * n);
+    memcpy(beams->scores, q.scores, sizeof(float) * n);
+    if (beams->path_scores) memcpy(beams->path_scores, q.path_scores, sizeof(float) * n);
+    if (beams->log_probs) memcpy(beams->log_probs, q.log_probs, sizeof(float) * nb);
+    if (beams->lengths) memcpy(beams->lengths, q.lengths, sizeof(int32_t) * nb);
+  } else if (!p.dev_out && !p.calls) {
     memcpy(tokens, h->pin_tok, sizeof(int32_t) * B * steps);
     memcpy(out2, h->pin_out2, sizeof(float) * B * steps * (p.greedy ? p.V : 1));
   }
@@ -858,8 +912,46 @@ void sync_child(RvContext* k, const RvContext* p);
 int flush_open_group(RvContext* h);
 int uncollected(const RvContext* h);
 
+// The whole beam's device buffers and pinned staging of a context, for the host variants of rv_beam_search_all*
+int ensure_beam_buffers(RvContext* h) {
+  if (h->pin_beams.tokens) return RV_OK;
+  const RvConfig& c = h->cfg;
+  const size_t n = (size_t)c.max_batch * c.max_output_len * c.max_beam, nb = (size_t)c.max_batch * c.max_beam;
+  HIPCHK(h, hipSetDevice(c.device));
+  BeamsOut& d = h->d_beams;
+  BeamsOut& p = h->pin_beams;
+#define TRY(x) do { int r_ = (x); if (r_ != RV_OK) return r_; } while (0)
+  TRY(dalloc(h, &d.tokens, n)); TRY(dalloc(h, &d.scores, n)); TRY(dalloc(h, &d.path_scores, n));
+  TRY(dalloc(h, &d.log_probs, nb)); TRY(dalloc(h, &d.lengths, nb));
+#undef TRY
+  HIPCHK(h, hipHostMalloc((void**)&p.scores, n * sizeof(float), hipHostMallocDefault));
+  HIPCHK(h, hipHostMalloc((void**)&p.path_scores, n * sizeof(float), hipHostMallocDefault));
+  HIPCHK(h, hipHostMalloc((void**)&p.log_probs, nb * sizeof(float), hipHostMallocDefault));
+  HIPCHK(h, hipHostMalloc((void**)&p.lengths, nb * sizeof(int32_t), hipHostMallocDefault));
+  HIPCHK(h, hipHostMalloc((void**)&p.tokens, n * sizeof(int32_t), hipHostMallocDefault));      // (last: its address says the set is complete)
+  return RV_OK;
+}
+
+// Before enqueue() of an all-beams call on `ctx`: where its finalize kernel writes.  `ab` null = every output, to the context's
+// own buffers (an asynchronous call with host outputs: what is asked for is known at its collect); dev_out = the caller's addresses
+int begin_all_beams(RvContext* ctx, const RvBeams* ab, bool dev_out) {
+  if (dev_out) {
+    ctx->lbeams = BeamsOut{ab->tokens, ab->scores, ab->path_scores, ab->log_probs, ab->lengths};
+  } else {
+    const int rc = ensure_beam_buffers(ctx);
+    if (rc != RV_OK) return rc;
+    ctx->lbeams = ctx->d_beams;
+    if (ab && !ab->path_scores) ctx->lbeams.path_scores = nullptr;
+    if (ab && !ab->log_probs) ctx->lbeams.log_probs = nullptr;
+    if (ab && !ab->lengths) ctx->lbeams.lengths = nullptr;
+  }
+  ctx->all_beams = true;
+  return RV_OK;
+}
+
 int run(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W,
-        int L, bool greedy, int32_t* tokens, float* out2, bool dev_out, int32_t* S_out, const CallsOut* calls = nullptr) {
+        int L, bool greedy, int32_t* tokens, float* out2, bool dev_out, int32_t* S_out, const CallsOut* calls = nullptr,
+        const RvBeams* ab = nullptr) {
   if (!h) return RV_EINVAL;
   if (!S_out || (B > 0 && L > 1 && !calls && (!tokens || !out2))) return fail(h, RV_EINVAL, "null output pointer");
   if (calls && (!calls->lut || !calls->bases || !calls->lengths || !calls->probs)) return fail(h, RV_EINVAL, "null calls output pointer");
@@ -885,9 +977,11 @@ int run(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int
   }
   h->inflight_hint = 1;
   if (ctx != h) sync_child(ctx, h);
+  if (ab) { const int rb = begin_all_beams(ctx, ab, dev_out); if (rb != RV_OK) { if (ctx != h) h->err = ctx->err; return rb; } }
   const int rc = enqueue(ctx, raw, ev, dev_in, B, T_r, T_e, W, L, greedy, tokens, out2, dev_out, calls ? calls->lut : nullptr);
+  ctx->all_beams = false;
   if (rc != RV_OK) { ctx->pend.busy = false; if (ctx != h) h->err = ctx->err; return rc; }   // (ctx was idle on entry: the flag is this call's)
-  const int rf = finish(ctx, tokens, out2, calls, S_out);
+  const int rf = finish(ctx, tokens, out2, calls, S_out, ab);
   if (ctx != h) { if (rf != RV_OK) h->err = ctx->err; h->lS = ctx->lS; }
   return rf;
 }
@@ -1282,7 +1376,8 @@ void rv_destroy(rv_handle h) {
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
   if (h->step_align) hipFree(h->step_align);
   if (h->palign) hipFree(h->palign);
-  for (void* p : {(void*)h->pin_raw, (void*)h->pin_ev, (void*)h->pin_tok, (void*)h->pin_out2, (void*)h->pin_S, (void*)h->pin_bases, (void*)h->pin_probs, (void*)h->pin_clen, (void*)h->pin_ptab}) if (p) hipHostFree(p);
+  for (void* p : {(void*)h->pin_raw, (void*)h->pin_ev, (void*)h->pin_tok, (void*)h->pin_out2, (void*)h->pin_S, (void*)h->pin_bases, (void*)h->pin_probs, (void*)h->pin_clen, (void*)h->pin_ptab,
+                  (void*)h->pin_beams.tokens, (void*)h->pin_beams.scores, (void*)h->pin_beams.path_scores, (void*)h->pin_beams.log_probs, (void*)h->pin_beams.lengths}) if (p) hipHostFree(p);
   for (void* p : h->allocs) hipFree(p);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
@@ -1621,7 +1716,7 @@ int rv_greedy_search_dev(rv_handle h, const float* raw, const float* event, int3
 
 // ---- asynchronous calls: submit returns once the slab's work is queued on one of the handle's contexts; collect waits for it.
 static int submit(rv_handle h, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W, int L,
-                  int32_t* tokens, float* out2, bool dev_out, const uint8_t* lut, int32_t* ticket) {
+                  int32_t* tokens, float* out2, bool dev_out, const uint8_t* lut, int32_t* ticket, bool all = false, const RvBeams* ab = nullptr) {
   if (!h || !ticket) return RV_EINVAL;
   *ticket = -1;
   const int depth = std::min(std::max(h->opt_async_depth, 1), RV_MAX_ASYNC);
@@ -1635,7 +1730,7 @@ static int submit(rv_handle h, const float* raw, const float* ev, bool dev_in, i
     if (uncollected(h) >= depth)
       return fail(h, RV_ESTATE, "all %d asynchronous slots hold uncollected calls (option async_depth): collect one first", depth);
     h->inflight_hint = depth;
-    if (n_co >= 2 && coalescible(h, B, tr, te, W, L))
+    if (n_co >= 2 && !all && coalescible(h, B, tr, te, W, L))
       return submit_group(h, n_co, raw, ev, dev_in, B, tr, te, W, L, tokens, out2, dev_out, lut, ticket);
     flush_open_group(h);      // a slab of another path: the group goes as it is, this slab on a context of its own
   }
@@ -1654,7 +1749,9 @@ static int submit(rv_handle h, const float* raw, const float* ev, bool dev_in, i
   if (!ctx) return fail(h, RV_ESTATE, "all %d asynchronous contexts hold uncollected calls (option async_depth): collect one first", depth);
   h->inflight_hint = depth;
   if (ctx != h) sync_child(ctx, h);
+  if (all) { const int rb = begin_all_beams(ctx, ab, dev_out); if (rb != RV_OK) { if (ctx != h) h->err = ctx->err; return rb; } }
   const int rc = enqueue(ctx, raw, ev, dev_in, B, T_r, T_e, W, L, false, tokens, out2, dev_out, lut);
+  ctx->all_beams = false;
   if (rc != RV_OK) { ctx->pend.busy = false; if (ctx != h) h->err = ctx->err; return rc; }
   h->next_slot = (slot + 1) % depth;
   h->generation = (h->generation + 1) & 0xFFFFF;
@@ -1662,14 +1759,17 @@ static int submit(rv_handle h, const float* raw, const float* ev, bool dev_in, i
   *ticket = ctx->pend.ticket;
   return RV_OK;
 }
-static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out) {
+static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr) {
   if (!h || !S_out) return RV_EINVAL;
   const int slot = ticket & 15;
-  if (ticket >= 0 && h->ticks[slot].busy && h->ticks[slot].ticket == ticket) return collect_group(h, slot, tokens, out2, calls, S_out);
+  if (ticket >= 0 && h->ticks[slot].busy && h->ticks[slot].ticket == ticket) {
+    if (beams) return fail(h, RV_EINVAL, "rv_beam_search_collect_all takes the tickets of rv_beam_search_submit_all");      // (a group never holds one)
+    return collect_group(h, slot, tokens, out2, calls, S_out);
+  }
   if (ticket < 0 || slot > (int)h->kids.size()) return fail(h, RV_EINVAL, "unknown ticket %d", ticket);
   RvContext* ctx = slot == 0 ? h : h->kids[slot - 1];
   if (!ctx->pend.busy || ctx->pend.ticket != ticket) return fail(h, RV_ESTATE, "ticket %d is not in flight (collected already?)", ticket);
-  const int rc = finish(ctx, tokens, out2, calls, S_out);
+  const int rc = finish(ctx, tokens, out2, calls, S_out, beams);
   if (rc != RV_OK && ctx != h) h->err = ctx->err;
   return rc;
 }
@@ -1695,6 +1795,36 @@ int rv_beam_search_submit_calls(rv_handle h, const float* raw, const float* even
 int rv_beam_search_collect_calls(rv_handle h, int32_t ticket, uint8_t* bases, int32_t* lengths, float* probs, int32_t* S_out) {
   const CallsOut c{nullptr, bases, lengths, probs};
   return collect(h, ticket, nullptr, nullptr, &c, S_out);
+}
+
+// ---- the whole beam (k_dec_finalize_beams): tokens and scores are required, the other three outputs may be null
+static bool beams_missing(const RvBeams* o, int B, int L) { return !o || (B > 0 && L > 1 && (!o->tokens || !o->scores)); }
+int rv_beam_search_all(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                       const RvBeams* out, int32_t* S_out) {
+  if (!h) return RV_EINVAL;
+  if (beams_missing(out, B, L)) return fail(h, RV_EINVAL, "null output pointer");
+  return run(h, raw, event, false, B, T_r, T_e, W, L, false, out->tokens, out->scores, false, S_out, nullptr, out);
+}
+int rv_beam_search_all_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
+                           int32_t L, const RvBeams* d_out, int32_t* S_out) {
+  if (!h) return RV_EINVAL;
+  if (beams_missing(d_out, B, L)) return fail(h, RV_EINVAL, "null output pointer");
+  return run(h, d_raw, d_event, true, B, T_r, T_e, W, L, false, d_out->tokens, d_out->scores, true, S_out, nullptr, d_out);
+}
+int rv_beam_search_submit_all(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
+                              int32_t L, int32_t* ticket) {
+  return submit(h, raw, event, false, B, T_r, T_e, W, L, nullptr, nullptr, false, nullptr, ticket, true, nullptr);
+}
+int rv_beam_search_collect_all(rv_handle h, int32_t ticket, const RvBeams* out, int32_t* S_out) {
+  if (!h) return RV_EINVAL;
+  if (!out) return fail(h, RV_EINVAL, "null output pointer");
+  return collect(h, ticket, nullptr, nullptr, nullptr, S_out, out);
+}
+int rv_beam_search_submit_all_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e,
+                                  int32_t W, int32_t L, const RvBeams* d_out, int32_t* ticket) {
+  if (!h) return RV_EINVAL;
+  if (beams_missing(d_out, B, L)) return fail(h, RV_EINVAL, "null output pointer");
+  return submit(h, d_raw, d_event, true, B, T_r, T_e, W, L, d_out->tokens, d_out->scores, true, nullptr, ticket, true, d_out);
 }
 
 int rv_beam_search_flush(rv_handle h) {

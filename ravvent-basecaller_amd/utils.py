@@ -39,3 +39,22 @@ def calc_prob_logits_beam_search_scores(beam_scores):
     prev = np.zeros_like(s)
     prev[..., 1:] = s[..., :-1]
     return np.exp(s - prev)
+
+
+def calc_prob_path_scores(path_scores):
+    """Per-base probabilities of every hypothesis of a beam: exp(p_t - p_{t-1}), p_{-1} = 0, along axis 1 of
+    `BeamHypotheses.path_scores` [B,S,W] (Basecaller.beam_search_hypotheses) -- the probability of tokens[b, t, w] given that
+    hypothesis's own prefix.  (calc_prob_logits_beam_search_scores on scores[:, :, 0] takes slot 0's score at every step, which is
+    another hypothesis's wherever the best path did not sit in slot 0.)  Accepts numpy arrays or torch tensors; returns the same kind."""
+    try:
+        import torch
+        if isinstance(path_scores, torch.Tensor):
+            prev = torch.zeros_like(path_scores)
+            prev[:, 1:] = path_scores[:, :-1]
+            return torch.exp(path_scores - prev)
+    except ImportError:  # pragma: no cover
+        pass
+    s = np.asarray(path_scores)
+    prev = np.zeros_like(s)
+    prev[:, 1:] = s[:, :-1]
+    return np.exp(s - prev)
