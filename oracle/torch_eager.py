@@ -53,8 +53,10 @@ def _encoder(x, layers):
     return x
 
 
-def beam_search(weights, cfg, raw, event, beam_width, max_output_len):
-    """Basecaller.beam_search_prediction (basecaller.py:296-315) -> (tokens [B,S] i32, scores [B,S] f32), numpy."""
+def beam_search(weights, cfg, raw, event, beam_width, max_output_len, taps=None):
+    """Basecaller.beam_search_prediction (basecaller.py:296-315) -> (tokens [B,S] i32, scores [B,S] f32), numpy.
+    ``taps`` (dict) receives the records of ravvent_oracle.beam_search: step_ids, parent_ids [S,B,W], lengths, finished [B,W]
+    (left untouched by a call that runs no step: max_output_len <= 1)."""
     W = int(beam_width)
     end, start, pad = cfg["end_token"], cfg["start_token"], cfg.get("padding_value", 0.0)
     outs, masks = [], []
@@ -124,6 +126,8 @@ def beam_search(weights, cfg, raw, event, beam_width, max_output_len):
             return np.zeros((B, 0), np.int32), np.zeros((B, 0), np.float32)
         step_ids = torch.stack(ids).numpy(); parent_ids = torch.stack(parents).numpy()
         maxlen = lengths.max(1).values.numpy()
+        if taps is not None:
+            taps.update(step_ids=step_ids, parent_ids=parent_ids, lengths=lengths.numpy(), finished=finished.numpy())
     # gather_tree, beam 0 only (basecaller.py:315)
     S = step_ids.shape[0]
     out = np.full((B, S), end, np.int32)
