@@ -12,7 +12,7 @@
  * ravvent_performance_evaluator.py:51-55); use one handle per GPU / per process.
  *
  * Synchronous calls -- rv_beam_search, rv_beam_search_dev, rv_beam_search_calls, rv_beam_search_all, rv_beam_search_all_dev,
- * rv_greedy_search, rv_greedy_search_dev, rv_load_weights, rv_get_tensor: results are complete when the call
+ * rv_greedy_search, rv_greedy_search_dev, rv_teacher_forced, rv_teacher_forced_dev, rv_score_logits, rv_load_weights, rv_get_tensor: results are complete when the call
  * returns, so a caller's wall-clock timers mean what they mean around the reference's methods.
  * Asynchronous calls -- rv_beam_search_submit, _submit_dev, _submit_calls, _submit_all, _submit_all_dev: they return once the
  * slab is queued, or held for its group until one of the events listed at rv_beam_search_flush
@@ -192,6 +192,40 @@ int rv_greedy_search(rv_handle h, const float* raw, const float* event, int32_t 
                      int32_t T_e, int32_t L, int32_t* tokens, float* logits, int32_t* S_out);
 int rv_greedy_search_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r,
                          int32_t T_e, int32_t L, int32_t* d_tokens, float* d_logits, int32_t* S_out);
+
+/* Scoring given label sequences.  These entry points were added without changing an existing one: RV_ABI_VERSION stays at 1.
+ *
+ * RvScore: the terms of Basecaller.loss_function (basecaller.py:212-220) and of utils.masked_accuracy (utils.py:15-24) for label rows
+ * [B, S] against logits [B, S, vocab].  Every member may be NULL and is then not produced.
+ *   nll       [B, S] f32  logsumexp(logits) - logits[label] (max-subtracted), 0 where label == pad_token: loss_function's mask * loss
+ *   nll_sum   [B]    f32  the row's nll added in column order by one lane: never depends on the slab.  -nll_sum is the label row's log-likelihood
+ *   n_labels  [B]    i32  labels != pad_token
+ *   n_counted [B]    i32  labels outside the omit set; n_match [B] i32: those of them that equal the argmax of the logits (first maximum on ties)
+ * omit_mask: bit t set = label id t is left out of n_counted / n_match (masked_accuracy's omit_vals): pad | start | end in _train_step
+ * (basecaller.py:247), start | end in _val_step (:277).  The caller forms loss = sum(nll_sum) / sum(n_labels) and acc = sum(n_match) /
+ * sum(n_counted); with no label counted the quotient is 0 / 0 = NaN, as the reference's division gives.
+ *
+ * rv_teacher_forced: Decoder.call as _train_step uses it (basecaller.py:142-152, :234-244), without the gradient.  The decoder is fed
+ *   targets[:, :-1] (TrainingSampler) instead of its own argmax -- column 0 is fed as it is, it need not be start_token -- and every chunk runs
+ *   all L - 1 steps (sequence_length = L - 1 for every row): sample_id [B, L-1] i32 is the argmax of rnn_output = logits [B, L-1, vocab] f32,
+ *   and `out` scores targets[:, 1:] against those logits.  targets [B, L] i32, row stride L.  Same limits and messages as rv_greedy_search.
+ *   Synchronous, under the rules at the head of this file; never coalesced (it launches the group that is filling) and never replayed as a
+ *   "slab_graph"; on the per-step decode its steps are launched without the captured hipGraph.  B == 0 or L == 1 launches nothing:
+ *   the per-chunk members of `out` are 0.  Host buffers: a target id outside [0, vocab) fails with RV_EINVAL before anything is queued.
+ * rv_teacher_forced_dev: device addresses for inputs, targets, outputs and the members of `out` (a host struct).  The ids must lie in
+ *   [0, vocab): they are not read by the host.  The kernels never index memory with an id unchecked: an id outside the range adds no input
+ *   row to the decoder cell (tf.one_hot gives zeros) and, as a label, has nll = NaN.  Such a call with vocab == 8 takes the per-step decode.
+ * rv_score_logits: loss_function / masked_accuracy on logits the caller holds -- _val_step (basecaller.py:264-279) scores the zero-padded
+ *   greedy logits.  Host buffers; S <= max_output_len; labels [B, S]; pred [B, S] i32 (the argmax) may be NULL.  A label outside
+ *   [0, vocab) fails with RV_EINVAL.  Synchronous; one launch of a few microseconds.
+ * Profile scope "score_tokens". */
+typedef struct RvScore { float* nll; float* nll_sum; int32_t* n_labels; int32_t* n_match; int32_t* n_counted; } RvScore;
+int rv_teacher_forced(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t L,
+                      const int32_t* targets, uint32_t omit_mask, int32_t* sample_id, float* logits, const RvScore* out);
+int rv_teacher_forced_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e, int32_t L,
+                          const int32_t* d_targets, uint32_t omit_mask, int32_t* d_sample_id, float* d_logits, const RvScore* d_out);
+int rv_score_logits(rv_handle h, const float* logits, const int32_t* labels, int32_t B, int32_t S, uint32_t omit_mask, int32_t* pred,
+                    const RvScore* out);
 
 /* Options.  The DEFAULT path is: matrix-pipe recurrences ("wide_recurrence" 1) + split-f16 GEMMs + the one-launch persistent decode with
  * attention and cell product on the matrix pipe ("persistent_decode", "matrix_attention", "matrix_cell" 1).  Options marked [fma form] only

@@ -21,9 +21,15 @@ class CRvBeams(ctypes.Structure):
     _fields_ = [("tokens", c_void_p), ("scores", c_void_p), ("path_scores", c_void_p), ("log_probs", c_void_p), ("lengths", c_void_p)]
 
 
+class CRvScore(ctypes.Structure):
+    """RvScore (include/ravvent_hip.h): the outputs of rv_teacher_forced* / rv_score_logits; each may be None."""
+    _fields_ = [("nll", c_void_p), ("nll_sum", c_void_p), ("n_labels", c_void_p), ("n_match", c_void_p), ("n_counted", c_void_p)]
+
+
 # every symbol include/ravvent_hip.h declares: (name, restype, argtypes)
 _F, _I = POINTER(c_float), POINTER(c_int32)
 _B = POINTER(CRvBeams)
+_S = POINTER(CRvScore)
 SYMBOLS = [
     ("rv_abi_version", c_int32, []),
     ("rv_create", c_int32, [POINTER(CRvConfig), POINTER(c_void_p)]),
@@ -48,6 +54,9 @@ SYMBOLS = [
     ("rv_beam_search_flush", c_int32, [c_void_p]),
     ("rv_greedy_search", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
     ("rv_greedy_search_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
+    ("rv_teacher_forced", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, _S]),
+    ("rv_teacher_forced_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, _S]),
+    ("rv_score_logits", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_uint32, c_void_p, _S]),
     ("rv_set_option", c_int32, [c_void_p, c_char_p, c_int32]),
     ("rv_get_tensor", c_int32, [c_void_p, c_char_p, c_void_p, c_size_t, POINTER(c_size_t)]),
     ("rv_get_profile", c_int32, [c_void_p, c_char_p, POINTER(c_double), POINTER(c_int64)]),

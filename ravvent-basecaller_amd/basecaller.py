@@ -27,6 +27,10 @@ from .data_loader import nuc_tk, tokens_to_strings
 # hypothesis's own cumulative log-probability, log_probs [B,W] / lengths [B,W] the final state's
 BeamHypotheses = collections.namedtuple("BeamHypotheses", "tokens scores path_scores log_probs lengths")
 
+# What a forced decode or a scoring call leaves (rv_teacher_forced*, rv_score_logits; include/ravvent_hip.h: RvScore): sample_id [B,S]
+# int32 the argmax of logits [B,S,V]; nll [B,S] f32 the masked cross-entropy terms; nll_sum [B] f32, n_labels / n_match / n_counted [B] int32
+ForcedScores = collections.namedtuple("ForcedScores", "sample_id logits nll nll_sum n_labels n_match n_counted")
+
 
 def _as_int(x) -> int:
     """max_output_len arrives as tf.shape(target)[1] in the reference (a 0-d tensor)."""
@@ -466,6 +470,116 @@ class Basecaller:
         self._check(rc, "rv_greedy_search")
         self.last_steps = S.value
         return tokens[:, :S.value], logits[:, :S.value]
+
+    # ------------------------------------------------------------------ scoring given label sequences
+    def _omit_mask(self, tokens):
+        """masked_accuracy's omit_vals (utils.py:15-24) as the bit mask over token ids the C-ABI takes."""
+        m = 0
+        for t in tokens:
+            m |= 1 << int(t)
+        return m
+
+    @property
+    def _train_omit(self):      # basecaller.py:247
+        return (self.output_padding_token, self.output_start_token, self.output_end_token)
+
+    @property
+    def _val_omit(self):        # basecaller.py:277
+        return (self.output_start_token, self.output_end_token)
+
+    @staticmethod
+    def _quotients(sc):
+        """loss = sum(mask * loss) / sum(mask) in float32 (basecaller.py:218-219), acc = count / total in float64 (utils.py:22-24);
+        NaN when nothing is counted, as the reference's divisions give."""
+        t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
+        loss = t(sc.nll_sum).sum(dtype=torch.float32) / t(sc.n_labels).sum().to(torch.float32)
+        acc = t(sc.n_match).sum().to(torch.float64) / t(sc.n_counted).sum().to(torch.float64)
+        return {"loss": loss.cpu(), "acc": acc.cpu()}
+
+    def _teacher_forced(self, input_data, target_tokens, omit):
+        """One rv_teacher_forced / _dev call -> ForcedScores over the L - 1 positions of every chunk.  Host inputs take host labels
+        (checked by the library: an id outside the vocabulary is RV_EINVAL); device inputs take the labels to the device unchecked
+        (the kernels never index with such an id: it adds no input row, and as a label its nll is NaN)."""
+        keep, pr, pe, B, Tr, Te, on_dev = self._gather_inputs(input_data)
+        V = self.cfg.vocab
+        if isinstance(target_tokens, torch.Tensor) and not on_dev:
+            target_tokens = target_tokens.detach().cpu().numpy()
+        if on_dev:
+            tg = torch.as_tensor(target_tokens).to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            tg = np.ascontiguousarray(np.asarray(target_tokens), dtype=np.int32)
+        if tg.ndim != 2 or tg.shape[0] != B:
+            raise ValueError(f"target_tokens: expected [{B},L], got {tuple(tg.shape)}")
+        L = int(tg.shape[1])
+        steps = max(L - 1, 0)
+        shapes = (((B, steps), "i"), ((B, steps, V), "f"), ((B, steps), "f"), ((B,), "f"), ((B,), "i"), ((B,), "i"), ((B,), "i"))
+        if on_dev:
+            torch.cuda.current_stream(self.device).synchronize()
+            bufs = [torch.empty(sh, dtype=torch.int32 if k == "i" else torch.float32, device=self.device) for sh, k in shapes]
+            ptr = lambda a: ctypes.c_void_p(a.data_ptr())
+            fn, what = self._lib.rv_teacher_forced_dev, "rv_teacher_forced_dev"
+        else:
+            bufs = [np.empty(sh, np.int32 if k == "i" else np.float32) for sh, k in shapes]
+            ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+            fn, what = self._lib.rv_teacher_forced, "rv_teacher_forced"
+        st = _capi.CRvScore(*[ptr(a) for a in bufs[2:]])
+        self._check(fn(self._h, pr, pe, B, Tr, Te, L, ptr(tg), self._omit_mask(omit), ptr(bufs[0]), ptr(bufs[1]), ctypes.byref(st)), what)
+        self.last_steps = steps
+        return ForcedScores(*[a if isinstance(a, torch.Tensor) else torch.from_numpy(a) for a in bufs])
+
+    def teacher_forced_prediction(self, input_data, target_tokens):
+        """Decoder.call as _train_step uses it (basecaller.py:142-152, :234-244): the decoder is fed target_tokens[:, :-1] instead of
+        its own argmax -> (sample_id [B,L-1] int32, rnn_output logits [B,L-1,V] f32), all L - 1 positions of every chunk."""
+        r = self._teacher_forced(input_data, target_tokens, self._train_omit)
+        return r.sample_id, r.logits
+
+    def sequence_nll(self, input_data, target_tokens):
+        """-> (nll [B,L-1] f32, nll_sum [B] f32): the cross-entropy of target_tokens[:, 1:] under the forced decode, 0 at the padding
+        token; -nll_sum is each label row's log-likelihood given its chunk."""
+        r = self._teacher_forced(input_data, target_tokens, self._train_omit)
+        return r.nll, r.nll_sum
+
+    def score_logits(self, real, pred, omit):
+        """rv_score_logits: labels `real` [B,S] against logits `pred` [B,S,V] -> ForcedScores (sample_id = argmax of pred)."""
+        t = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        lg = np.ascontiguousarray(t(pred), dtype=np.float32)
+        lb = np.ascontiguousarray(t(real), dtype=np.int32)
+        if lg.ndim != 3 or lg.shape[2] != self.cfg.vocab or lb.shape != lg.shape[:2]:
+            raise ValueError(f"expected labels [B,S] and logits [B,S,{self.cfg.vocab}], got {lb.shape} and {lg.shape}")
+        B, S = lb.shape
+        ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+        pred_ids = np.empty((B, S), np.int32)
+        outs = [np.empty((B, S), np.float32), np.empty(B, np.float32), np.empty(B, np.int32), np.empty(B, np.int32), np.empty(B, np.int32)]
+        st = _capi.CRvScore(*[ptr(a) for a in outs])
+        self._check(self._lib.rv_score_logits(self._h, ptr(lg), ptr(lb), B, S, self._omit_mask(omit), ptr(pred_ids), ctypes.byref(st)),
+                    "rv_score_logits")
+        return ForcedScores(*[torch.from_numpy(a) for a in [pred_ids, lg] + outs])
+
+    def loss_function(self, real, pred):
+        """basecaller.py:212-220: masked sparse cross-entropy of logits `pred` [B,S,V] at labels `real` [B,S] -> 0-d float32 tensor."""
+        return self._quotients(self.score_logits(real, pred, ()))["loss"]
+
+    def evaluate_step(self, data):
+        """The forward half of _train_step (basecaller.py:225-253), no gradient: data = (raw, events, target) -> {'loss', 'acc'}
+        of the forced decode, accuracy over the labels that are not padding, start or end token."""
+        from .utils import unpack_data_to_input_target
+        input_data, target_tokens = unpack_data_to_input_target(data, self.input_data_type)
+        return self._quotients(self._teacher_forced(input_data, target_tokens, self._train_omit))
+
+    def test_step(self, data):
+        """_val_step (basecaller.py:264-279), what Keras evaluate() calls: greedy search, its logits and ids padded with zeros to
+        L - 1 columns (tf.pad), then loss_function and masked_accuracy with [start, end] omitted -> {'loss', 'acc'}."""
+        from .utils import unpack_data_to_input_target
+        input_data, target_tokens = unpack_data_to_input_target(data, self.input_data_type)
+        tg = target_tokens.detach().cpu().numpy() if isinstance(target_tokens, torch.Tensor) else np.asarray(target_tokens)
+        L = int(tg.shape[1])
+        tok, lg = self.greedy_search_prediction(input_data, L)
+        B, S = tok.shape
+        logits = np.zeros((B, max(L - 1, 0), self.cfg.vocab), np.float32)
+        logits[:, :S] = lg.cpu().numpy()
+        # masked_accuracy compares the padded ids; the library's pred is the argmax of the padded logits, which is the same thing: the greedy
+        # ids are the argmax of their logits and a row of zero logits has its first maximum at id 0, tf.pad's fill
+        return self._quotients(self.score_logits(tg[:, 1:], logits, self._val_omit))
 
     def _out_buffers(self, kind, B, steps, V):
         """Device outputs of the `*_dev` entry points.  Default: FRESH tensors per call, like the reference's return

@@ -215,6 +215,12 @@ struct DecState {
   int part;               // sub-slab index (decode of one slab may run as up to 4 concurrent sub-slabs)
   long long* dbg_ts;      // diagnostic: [16] s_memtime stamps of block 0 at the phase boundaries of step 3
   int dbg_stop;           // diagnostic builds only: leave k_dec_attend after phase N (0 = run everything)
+  // Forced decode (rv_teacher_forced*: Decoder.call with TrainingSampler, basecaller.py:142-152): label rows [B,L], row stride L, or
+  // nullptr (every other call).  Set only with greedy and W == 1: step s feeds forced[b*L + s] instead of the previous argmax, step_ids
+  // still records the argmax (sample_id), and every chunk runs exactly L - 1 steps -- nothing is added to nfin, chunk_steps[b] = L - 1.
+  // An id outside [0, V) adds no input row (tf.one_hot gives zeros); the persistent decode takes such calls only with V < RV_MAX_VOCAB
+  // (last: the kernel-argument offsets of the members above are those of every earlier build)
+  const int* forced;
 };
 hipError_t configure_decode_kernels();   // per-device dynamic-LDS opt-in; call after hipSetDevice; first error or hipSuccess
 void launch_dec_init(const DecState& d, hipStream_t s);
@@ -251,6 +257,26 @@ void launch_dec_reduce_steps(const DecParts& p, hipStream_t s);   // S_dev[0] = 
 // (include/ravvent_hip.h: RvBeams).  path_scores, log_probs and lengths may be null: the kernel skips a null output.
 struct BeamsOut { int32_t* tokens; float* scores; float* path_scores; float* log_probs; int32_t* lengths; };
 void launch_dec_finalize_beams(const DecState& d, const BeamsOut& o, hipStream_t s);
+
+// ---------------------------------------------------------------- scoring (score.hip)
+// Masked sparse cross-entropy and masked token accuracy of label rows against logits (Basecaller.loss_function, basecaller.py:212-220;
+// utils.masked_accuracy, utils.py:15-24), per position and per chunk; the caller forms the two scalar quotients.  One wave per chunk,
+// lane = position: S <= 64, 2 <= V <= RV_MAX_VOCAB.  Every output may be null.
+struct ScoreArgs {
+  const float* logits;      // [B,S,V]
+  const int* labels;        // row b at labels + b * label_stride, S ids
+  int label_stride;
+  int B, S, V;
+  int pad_token;            // nll is 0 and n_labels does not count where label == pad_token (the mask of loss_function)
+  uint32_t omit_mask;       // bit t set: label id t is left out of n_counted / n_match (masked_accuracy's omit_vals)
+  float* nll;               // [B,S]  logsumexp(logits) - logits[label], max-subtracted; NaN for a non-pad label outside [0, V)
+  int* pred;                // [B,S]  argmax, first maximum on ties
+  float* nll_sum;           // [B]    nll summed over the row in column order by one lane
+  int* n_labels;            // [B]    labels != pad_token
+  int* n_match;             // [B]    counted labels that equal pred
+  int* n_counted;           // [B]    labels outside the omit set
+};
+void launch_score_tokens(const ScoreArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- device math helpers
 #ifdef __HIPCC__

@@ -40,7 +40,7 @@ __global__ void k_dec_init(DecState d) {
   const int N = d.B * d.W;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx < N) {
-    d.tok[idx] = d.start_token;
+    d.tok[idx] = d.forced ? d.forced[(size_t)idx * d.L] : d.start_token;   // forced decode (W == 1): TrainingSampler feeds the label row's own first token
     d.log_probs[idx] = (idx % d.W) == 0 ? 0.f : -INFINITY;   // one_hot(0, W, on=0, off=-inf)
     d.finished[idx] = 0;
     d.lengths[idx] = 0;
@@ -110,7 +110,8 @@ __global__ __launch_bounds__(512) void k_dec_cell(DecState d, int layer, const f
 #pragma unroll
   for (int p = 0; p < 2; ++p)       // one-hot row gather; lands while the MFMAs run
 #pragma unroll
-    for (int gg = 0; gg < 4; ++gg) ew[p][gg] = Wtok ? Wtok[(size_t)etok[p] * RV_G + gg * RV_U + ecol] : 0.f;
+    for (int gg = 0; gg < 4; ++gg)      // (an id outside the vocabulary -- a forced decode's device labels -- adds no row: tf.one_hot gives zeros)
+      ew[p][gg] = (Wtok && (unsigned)etok[p] < (unsigned)d.V) ? Wtok[(size_t)etok[p] * RV_G + gg * RV_U + ecol] : 0.f;
   __syncthreads();
   const int rq = wv & 3, gh = wv >> 2;            // wave = 16-row quarter x gate pair
   const int li = lane & 15, kq = lane >> 4;       // lane group kq supplies k in [64kq, 64kq+64)
@@ -370,6 +371,7 @@ __device__ __forceinline__ void att_tail(const DecState& d, AttShared& S, const 
     const int lane = tid, w = lane / V, v = lane % V;
     const bool cand = lane < W * V;
     const size_t o = ((size_t)step * d.B + b) * W;
+    const bool forced = W == 1 && d.forced;      // (a forced decode has one beam: the wider instantiations compile the test away)
     float val = -INFINITY;
     if (d.greedy) {
       if (cand) val = lg[v];
@@ -397,7 +399,7 @@ __device__ __forceinline__ void att_tail(const DecState& d, AttShared& S, const 
     bool nf = false; int nl = 0;
     if (lane < W) {
       if (d.greedy) {
-        nf = S.fin[0] != 0 || my_word == d.end_token;
+        nf = !forced && (S.fin[0] != 0 || my_word == d.end_token);      // forced decode: every chunk runs all L - 1 steps, nfin stays 0
       } else {
         const bool pf = S.fin[my_par] != 0;
         nf = pf || my_word == d.end_token;
@@ -407,7 +409,7 @@ __device__ __forceinline__ void att_tail(const DecState& d, AttShared& S, const 
     const unsigned long long fmask = __ballot(lane < W && nf);
     if (lane < W) {
       d.step_ids[o + lane] = my_word; d.parent_ids[o + lane] = my_par; d.step_scores[o + lane] = my_val;
-      d.tok[row0 + lane] = my_word;
+      d.tok[row0 + lane] = forced ? d.forced[(size_t)b * d.L + step + 1] : my_word;   // forced: the next label, whatever the argmax was
       d.finished[row0 + lane] = nf;
       if (!d.greedy) { d.log_probs[row0 + lane] = my_val; d.lengths[row0 + lane] = nl; }
       S.parent[lane] = my_par;
@@ -1153,6 +1155,13 @@ __device__ __forceinline__ void persist_project_memory(const DecState& d, int b,
   __syncthreads();
 }
 
+// Forced decode (DecState::forced): chunk b's input token of step s, as the row of the resident zb table it selects.  An id outside
+// the vocabulary selects row V, which holds the bias alone -- no input row, as tf.one_hot gives zeros -- so an id never indexes LDS unchecked
+__device__ __forceinline__ int persist_forced_tok(const DecState& d, int b, int s) {
+  const int t = d.forced[(size_t)b * d.L + s];
+  return (unsigned)t < (unsigned)d.V ? t : d.V;
+}
+
 template <int W, int NIT, int D, int ATT = 0>
 __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __restrict__ Wcat /*[256,512] = [W_in rows of the attention input ; U]*/,
                                                       const float* __restrict__ Wtok /*[V,512]*/, const float* __restrict__ bdec /*[512]*/,
@@ -1343,11 +1352,12 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
   }
   if (BAH && tid < RV_U) vat[tid] = d.v_att[tid] * (-2.0f * LOG2E);   // score = sum_j v_j tanh(.) = const - 2 sum_j v_j / (1 + exp(.)): softmax drops the constant
   if (tid < WB) {
-    s_tok[tid] = d.start_token; s_lprob[tid] = tid == 0 ? 0.f : -INFINITY;
+    s_tok[tid] = (W == 1 && d.forced) ? persist_forced_tok(d, b, 0) : d.start_token; s_lprob[tid] = tid == 0 ? 0.f : -INFINITY;
     s_fin[tid] = 0; s_len[tid] = 0; s_parent[tid] = tid;
   }
   if (tid == 0) s_allfin = 0;
   for (int i = tid; i < V * RV_G; i += NT) zb[i] = Wtok[i] + bdec[i & (RV_G - 1)];   // W_dec[one_hot(v)] + b, resident
+  if (W == 1 && d.forced) for (int i = tid; i < RV_G; i += NT) zb[V * RV_G + i] = bdec[i];      // row V (V < RV_MAX_VOCAB: ravvent_hip.cpp, persist_form): no input row, persist_forced_tok
   __syncthreads();
 
   uint4 rbh[NR > 0 ? NR : 1], rbl[NR > 0 ? NR : 1];       // pairs 32 - NC - NR .. 32 - NC - 1 of this wave, resident for the whole decode
@@ -2047,7 +2057,14 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         nl = s_len[my_par] + (pf ? 0 : 1);
       }
       const unsigned long long fmask = __ballot(lane < W && nf);
-      if (d.greedy) {
+      if (W == 1 && d.forced) {      // (one beam: the wider instantiations compile this branch away)
+        // TrainingSampler with sequence_length = L - 1 for every row: the next input is the next label, sample_id is still the argmax of
+        // the raw logits, and no chunk waits for or reports to another -- every chunk runs exactly L - 1 steps (s_fin, s_allfin stay 0)
+        if (lane == 0) {
+          d.step_ids[(size_t)step * d.B + b] = my_word;
+          s_tok[0] = persist_forced_tok(d, b, step + 1); s_parent[0] = 0;
+        }
+      } else if (d.greedy) {
         // BasicDecoder without impute_finished: a finished row keeps sampling and the loop runs until EVERY row of the
         // slab has finished, so a chunk may only stop once all chunks have reported their first finished step
         // (nfin[0] = how many have, nfin[1] = the latest of those steps + 1) and it has itself recorded that many steps.

@@ -131,6 +131,12 @@ struct RvContext {
   BeamsOut d_beams{}, pin_beams{};
   bool all_beams = false;                   // the call being recorded hands out the whole beam, through ...
   BeamsOut lbeams{};                        // ... these device addresses (the caller's, or d_beams)
+  // forced decode and scoring (rv_teacher_forced*, rv_score_logits)
+  const int* lforced = nullptr;             // the call being recorded feeds these label rows [B,L] (device: the caller's, or d_forced) instead of its argmax
+  ScoreArgs lscore{};                       // ... and scores them: omit_mask and the output addresses (device: the caller's, or the d_sc_* below; null = not asked for)
+  int32_t* d_forced = nullptr;              // host variants: labels [max_batch, max_output_len] and the score outputs, allocated on this context's
+  float *d_sc_nll = nullptr, *d_sc_sum = nullptr;   //   first such call (ensure_score_buffers): nll [max_batch, max_output_len], nll_sum [max_batch],
+  int32_t* d_sc_cnt = nullptr;              //   n_labels | n_match | n_counted [3][max_batch]
 
   int opt_taps = 0, opt_graph = 1, opt_profile = 0;
   long long* rec_ts = nullptr;              // diagnostic: per-wave cycle sums of the raw layer-0 recurrence (RV_REC_STAMPS=1) or of its fused layer 1 (=2)
@@ -468,6 +474,7 @@ struct CallsOut { const uint8_t* lut; uint8_t* bases; int32_t* lengths; float* p
 int persist_form(const RvContext* h, bool greedy, int W, int Tm) {
   if (!h->opt_persist || !h->opt_flash || h->opt_taps) return -1;
   const RvConfig& c = h->cfg;
+  if (h->lforced && c.vocab >= RV_MAX_VOCAB) return -1;      // (a forced decode keeps a bias-only row behind the vocabulary's in the resident token table)
   return dec_persist_form(c.attention, c.dec_depth, greedy ? 1 : W, Tm, greedy, h->opt_mx_att, h->opt_mx_cell);
 }
 
@@ -551,7 +558,7 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
     h->graph_gen = root->opt_gen;
   }
   const bool graphable = root->opt_slab_graph && h->lwide && !h->lrows8 && persist_form(h, greedy, W, T_r + T_e) >= 0 && h->opt_profile == 0 && !h->opt_taps &&
-                         !h->all_beams && !h->opt_ptaps && !h->rec_ts && !h->dec_st.dbg_ts && h->d_ptab;
+                         !h->all_beams && !h->lforced && !h->opt_ptaps && !h->rec_ts && !h->dec_st.dbg_ts && h->d_ptab;
   if (!graphable) return record_slab(h, xr, xe, !dev_in, B, T_r, T_e, W, L, greedy, tk, o2, dev_out, lut, nullptr);
   h->lforms_ok = 0;                             // (a slab graph replays without the host launchers: "kernel_forms" answers RV_ESTATE)
   h->pin_ptab[RV_PTAB_RAW] = xr; h->pin_ptab[RV_PTAB_EVENT] = xe; h->pin_ptab[RV_PTAB_TOKENS] = tk; h->pin_ptab[RV_PTAB_OUT2] = o2;
@@ -663,6 +670,7 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
   DecState d = h->dec_st;
   d.B = B; d.W = greedy ? 1 : W; d.Tm = Tm; d.V = V; d.L = L;
   d.greedy = greedy; d.attention = c.attention;
+  d.forced = h->lforced;
   d.start_token = c.start_token; d.end_token = c.end_token; d.pad_token = c.pad_token;
   d.attend_threads = h->opt_att_nt;
   d.keys = h->keys; d.values = h->enc_out; d.mask = h->mask;
@@ -783,7 +791,7 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     Scope sc(h, "dec_persist", nullptr, true);
     launch_dec_persist(d, d.depth > 1 ? h->dec[0].W + (size_t)V * RV_G : h->d_Wcat2, h->dec[0].W, h->dec[0].b,
                        d.depth > 1 ? h->dec[1].W : nullptr, d.depth > 1 ? h->dec[1].b : nullptr, h->d_Nh, s, &h->lforms);
-  } else if (h->opt_graph && h->opt_profile != 2) {
+  } else if (h->opt_graph && h->opt_profile != 2 && !d.forced) {      // (a forced decode launches its steps without replay: the label pointer is no part of the key)
     GraphKey key{B, d.W, Tm, L, greedy ? 1 : 0, h->opt_taps * 2 + h->lflash + 4 * h->opt_att_nt + 4096 * (d.step_logits ? 1 : 0) + 8192 * (d.persist_align ? 1 : 0), nsplit};   // every captured pointer that can change is in the key
     auto it = h->graphs.find(key);
     if (it == h->graphs.end()) {
@@ -835,6 +843,12 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
       launch_dec_finalize(part[g], tk + b0 * steps, o2 + b0 * steps * (greedy ? V : 1), s, ptab,      // (ptab: persistent decode only, one part)
                           h->lpersist && h->lmem.n ? &h->lmem : nullptr);
     }
+  }
+  if (d.forced) {      // the forced decode's labels target[:, 1:] against the logits the finalize kernel just wrote
+    ScoreArgs a = h->lscore;
+    a.logits = o2; a.labels = d.forced + 1; a.label_stride = L; a.B = B; a.S = steps; a.V = V; a.pad_token = c.pad_token; a.pred = nullptr;
+    Scope sc(h, "score_tokens");
+    launch_score_tokens(a, s);
   }
   // (S reaches the host through d.S_host: the finalize / reduce kernel stores it straight into the mapped pinned word)
   if (h->all_beams && !dev_out) {
@@ -949,13 +963,89 @@ int begin_all_beams(RvContext* ctx, const RvBeams* ab, bool dev_out) {
   return RV_OK;
 }
 
-int run(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W,
-        int L, bool greedy, int32_t* tokens, float* out2, bool dev_out, int32_t* S_out, const CallsOut* calls = nullptr,
-        const RvBeams* ab = nullptr) {
-  if (!h) return RV_EINVAL;
-  if (!S_out || (B > 0 && L > 1 && !calls && (!tokens || !out2))) return fail(h, RV_EINVAL, "null output pointer");
-  if (calls && (!calls->lut || !calls->bases || !calls->lengths || !calls->probs)) return fail(h, RV_EINVAL, "null calls output pointer");
-  *S_out = 0;
+// The labels and score outputs of a forced decode (rv_teacher_forced*) or of rv_score_logits
+struct ForcedCall { const int32_t* targets; uint32_t omit_mask; const RvScore* out; };
+
+// Labels and score outputs of a context on the device, for the host variants of rv_teacher_forced and for rv_score_logits
+int ensure_score_buffers(RvContext* h) {
+  if (h->d_sc_cnt) return RV_OK;
+  const RvConfig& c = h->cfg;
+  const size_t n = (size_t)c.max_batch * c.max_output_len, nb = (size_t)c.max_batch;
+  HIPCHK(h, hipSetDevice(c.device));
+#define TRY(x) do { int r_ = (x); if (r_ != RV_OK) return r_; } while (0)
+  TRY(dalloc(h, &h->d_forced, n)); TRY(dalloc(h, &h->d_sc_nll, n)); TRY(dalloc(h, &h->d_sc_sum, nb));
+  TRY(dalloc(h, &h->d_sc_cnt, 3 * nb));      // (last: its address says the set is complete)
+#undef TRY
+  return RV_OK;
+}
+
+// Where a call's k_score_tokens writes: the caller's device addresses, or the context's buffers for the outputs a host caller asked for
+void set_score_outputs(RvContext* ctx, const ForcedCall* fc, bool dev_out) {
+  const RvScore none{};
+  const RvScore& o = fc->out ? *fc->out : none;
+  const size_t nb = (size_t)ctx->cfg.max_batch;
+  ScoreArgs& a = ctx->lscore;
+  a = ScoreArgs{};
+  a.omit_mask = fc->omit_mask;
+  a.nll = dev_out ? o.nll : (o.nll ? ctx->d_sc_nll : nullptr);
+  a.nll_sum = dev_out ? o.nll_sum : (o.nll_sum ? ctx->d_sc_sum : nullptr);
+  a.n_labels = dev_out ? o.n_labels : (o.n_labels ? ctx->d_sc_cnt : nullptr);
+  a.n_match = dev_out ? o.n_match : (o.n_match ? ctx->d_sc_cnt + nb : nullptr);
+  a.n_counted = dev_out ? o.n_counted : (o.n_counted ? ctx->d_sc_cnt + 2 * nb : nullptr);
+}
+
+// ids [n] all inside [0, vocab)?  (host labels: an id never reaches a kernel unchecked)
+int check_token_ids(RvContext* h, const int32_t* ids, size_t n, int row_len, const char* what) {
+  const int V = h->cfg.vocab;
+  for (size_t i = 0; i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= V)
+      return fail(h, RV_EINVAL, "%s id %d at [%zu,%zu] outside [0,%d)", what, (int)ids[i], i / row_len, i % row_len, V);
+  return RV_OK;
+}
+
+// Before enqueue() of a forced decode on the idle context `ctx`: the call's own checks, then its labels and score outputs
+int begin_forced(RvContext* ctx, const ForcedCall* fc, const float* raw, const float* ev, bool dev, int B, int T_r, int T_e, int L,
+                 const int32_t* tokens, const float* out2) {
+  { const int rc = validate_call(ctx, raw, ev, B, T_r, T_e, 1, L, tokens, out2, dev); if (rc != RV_OK) return rc; }
+  if (B > 0 && !fc->targets) return fail(ctx, RV_EINVAL, "null target pointer");
+  if (dev) {
+    ctx->lforced = fc->targets;
+  } else {
+    { const int rc = check_token_ids(ctx, fc->targets, (size_t)B * L, L, "target"); if (rc != RV_OK) return rc; }
+    { const int rc = ensure_score_buffers(ctx); if (rc != RV_OK) return rc; }
+    if (B > 0) HIPCHK(ctx, hipMemcpy(ctx->d_forced, fc->targets, sizeof(int32_t) * (size_t)B * L, hipMemcpyHostToDevice));
+    ctx->lforced = ctx->d_forced;
+  }
+  set_score_outputs(ctx, fc, dev);
+  return RV_OK;
+}
+
+// After the stream of `ctx` has drained: the scores of B chunks x S positions to a host caller's buffers (zeros when nothing was launched)
+int fetch_scores(RvContext* ctx, const RvScore* out, bool dev_out, int B, int S) {
+  if (!out || B <= 0) return RV_OK;
+  const ScoreArgs& a = ctx->lscore;
+  const size_t nb = (size_t)B, n = nb * (size_t)std::max(S, 0);
+  if (S <= 0) {      // nothing ran: every per-chunk sum is zero
+    if (dev_out) {
+      if (out->nll_sum) HIPCHK(ctx, hipMemset(out->nll_sum, 0, sizeof(float) * nb));
+      for (int32_t* p : {out->n_labels, out->n_match, out->n_counted}) if (p) HIPCHK(ctx, hipMemset(p, 0, sizeof(int32_t) * nb));
+    } else {
+      if (out->nll_sum) memset(out->nll_sum, 0, sizeof(float) * nb);
+      for (int32_t* p : {out->n_labels, out->n_match, out->n_counted}) if (p) memset(p, 0, sizeof(int32_t) * nb);
+    }
+    return RV_OK;
+  }
+  if (dev_out) return RV_OK;
+  if (out->nll) HIPCHK(ctx, hipMemcpy(out->nll, a.nll, sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (out->nll_sum) HIPCHK(ctx, hipMemcpy(out->nll_sum, a.nll_sum, sizeof(float) * nb, hipMemcpyDeviceToHost));
+  if (out->n_labels) HIPCHK(ctx, hipMemcpy(out->n_labels, a.n_labels, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+  if (out->n_match) HIPCHK(ctx, hipMemcpy(out->n_match, a.n_match, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+  if (out->n_counted) HIPCHK(ctx, hipMemcpy(out->n_counted, a.n_counted, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+  return RV_OK;
+}
+
+// The slab context a synchronous call runs on.  A group of coalesced slabs that is still filling is launched first.
+int sync_context(RvContext* h, RvContext** out) {
   {   // coalesced tickets hold the handle's slots as the slab contexts' tickets do: with async_depth of them uncollected a synchronous
       // call is refused, touching nothing (the handle's own context is idle then, but the contract does not depend on the path)
     bool ticks_out = false;
@@ -977,11 +1067,30 @@ int run(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int
   }
   h->inflight_hint = 1;
   if (ctx != h) sync_child(ctx, h);
+  *out = ctx;
+  return RV_OK;
+}
+
+int run(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W,
+        int L, bool greedy, int32_t* tokens, float* out2, bool dev_out, int32_t* S_out, const CallsOut* calls = nullptr,
+        const RvBeams* ab = nullptr, const ForcedCall* fc = nullptr) {
+  if (!h) return RV_EINVAL;
+  if (!S_out || (B > 0 && L > 1 && !calls && (!tokens || !out2))) return fail(h, RV_EINVAL, "null output pointer");
+  if (calls && (!calls->lut || !calls->bases || !calls->lengths || !calls->probs)) return fail(h, RV_EINVAL, "null calls output pointer");
+  *S_out = 0;
+  RvContext* ctx = nullptr;
+  { const int rc = sync_context(h, &ctx); if (rc != RV_OK) return rc; }
   if (ab) { const int rb = begin_all_beams(ctx, ab, dev_out); if (rb != RV_OK) { if (ctx != h) h->err = ctx->err; return rb; } }
+  if (fc) {
+    const int rb = begin_forced(ctx, fc, raw, ev, dev_in, B, T_r, T_e, L, tokens, out2);
+    if (rb != RV_OK) { ctx->lforced = nullptr; if (ctx != h) h->err = ctx->err; return rb; }
+  }
   const int rc = enqueue(ctx, raw, ev, dev_in, B, T_r, T_e, W, L, greedy, tokens, out2, dev_out, calls ? calls->lut : nullptr);
   ctx->all_beams = false;
+  ctx->lforced = nullptr;
   if (rc != RV_OK) { ctx->pend.busy = false; if (ctx != h) h->err = ctx->err; return rc; }   // (ctx was idle on entry: the flag is this call's)
-  const int rf = finish(ctx, tokens, out2, calls, S_out, ab);
+  int rf = finish(ctx, tokens, out2, calls, S_out, ab);
+  if (fc && rf == RV_OK) rf = fetch_scores(ctx, fc->out, dev_out, B, L - 1);
   if (ctx != h) { if (rf != RV_OK) h->err = ctx->err; h->lS = ctx->lS; }
   return rf;
 }
@@ -1712,6 +1821,54 @@ int rv_greedy_search(rv_handle h, const float* raw, const float* event, int32_t 
 int rv_greedy_search_dev(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e,
                          int32_t L, int32_t* tokens, float* logits, int32_t* S_out) {
   return run(h, raw, event, true, B, T_r, T_e, 1, L, true, tokens, logits, true, S_out);
+}
+
+// Decoder.call under TrainingSampler, as _train_step drives it: greedy decode's launches with the labels fed in, then k_score_tokens
+int rv_teacher_forced(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t L,
+                      const int32_t* targets, uint32_t omit_mask, int32_t* sample_id, float* logits, const RvScore* out) {
+  const ForcedCall fc{targets, omit_mask, out};
+  int32_t S = 0;
+  return run(h, raw, event, false, B, T_r, T_e, 1, L, true, sample_id, logits, false, &S, nullptr, nullptr, &fc);
+}
+int rv_teacher_forced_dev(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t L,
+                          const int32_t* targets, uint32_t omit_mask, int32_t* sample_id, float* logits, const RvScore* out) {
+  const ForcedCall fc{targets, omit_mask, out};
+  int32_t S = 0;
+  return run(h, raw, event, true, B, T_r, T_e, 1, L, true, sample_id, logits, true, &S, nullptr, nullptr, &fc);
+}
+
+// loss_function / masked_accuracy on logits the caller holds (test_step: the zero-padded greedy logits); host buffers
+int rv_score_logits(rv_handle h, const float* logits, const int32_t* labels, int32_t B, int32_t S, uint32_t omit_mask, int32_t* pred,
+                    const RvScore* out) {
+  if (!h) return RV_EINVAL;
+  const RvConfig& c = h->cfg;
+  if (B < 0 || B > c.max_batch) return fail(h, RV_EINVAL, "B=%d outside [0,%d]", B, c.max_batch);
+  if (S < 0 || S > c.max_output_len || S > 64) return fail(h, RV_EINVAL, "S=%d outside [0,%d]", S, std::min(c.max_output_len, 64));
+  if (B > 0 && S > 0 && (!logits || !labels)) return fail(h, RV_EINVAL, "null input pointer");
+  const size_t n = (size_t)B * S;
+  { const int rc = check_token_ids(h, labels, n, std::max(S, 1), "label"); if (rc != RV_OK) return rc; }
+  RvContext* ctx = nullptr;
+  { const int rc = sync_context(h, &ctx); if (rc != RV_OK) return rc; }
+  auto body = [&]() -> int {
+    if (n == 0) return fetch_scores(ctx, out, false, B, 0);
+    HIPCHK(ctx, hipSetDevice(c.device));
+    { const int rc = ensure_score_buffers(ctx); if (rc != RV_OK) return rc; }
+    const ForcedCall fc{labels, omit_mask, out};
+    set_score_outputs(ctx, &fc, false);
+    HIPCHK(ctx, hipMemcpy(ctx->out2, logits, sizeof(float) * n * c.vocab, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->d_forced, labels, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    ScoreArgs a = ctx->lscore;
+    a.logits = ctx->out2; a.labels = ctx->d_forced; a.label_stride = S; a.B = B; a.S = S; a.V = c.vocab; a.pad_token = c.pad_token;
+    a.pred = pred ? ctx->out_tokens : nullptr;
+    launch_score_tokens(a, ctx->stream);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    if (pred) HIPCHK(ctx, hipMemcpy(pred, ctx->out_tokens, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return fetch_scores(ctx, out, false, B, S);
+  };
+  const int rc = body();
+  if (rc != RV_OK && ctx != h) h->err = ctx->err;
+  return rc;
 }
 
 // ---- asynchronous calls: submit returns once the slab's work is queued on one of the handle's contexts; collect waits for it.

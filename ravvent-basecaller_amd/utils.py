@@ -24,6 +24,17 @@ def unpack_data_to_input_target(data, input_data_type):
     raise ValueError(f"input_data_type {input_data_type!r}")
 
 
+def masked_accuracy(y_true, y_pred, omit_vals):
+    """/root/reference/utils.py:15-24 -- the share of the labels outside `omit_vals` that `y_pred` equals (NaN when there is none).
+    Host form; Basecaller.evaluate_step / test_step take the same counts from the GPU (rv_teacher_forced, rv_score_logits)."""
+    y_true, y_pred = np.asarray(y_true), np.asarray(y_pred)
+    mask = np.ones(y_true.shape, bool)
+    for ov in omit_vals:
+        mask &= y_true != ov
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.float64((mask & (y_true == y_pred)).sum()) / np.float64(mask.sum())
+
+
 def calc_prob_logits_beam_search_scores(beam_scores):
     """/root/reference/utils.py:123-128 -- exp(score_t - score_{t-1}), score_{-1} = 0, along the
     last axis.  Accepts numpy arrays or torch tensors (host or device); returns the same kind."""
