@@ -43,6 +43,93 @@ struct SlabKey {
   }
 };
 
+// What rv_set_option sets.  A child context takes its parent's as a whole (sync_child); slab_graph, async_depth, coalesce and gen are
+// read from the handle (root) only, so their copies on a child mean nothing.
+struct Options {
+  int split = 1;                            // concurrent decode sub-slabs (1..4); measured neutral at B=256
+  int att_nt = 0;
+  int side_ev = 1;                          // event chain on a side stream under the raw in-projection GEMM
+  int persist = 1;                          // whole beam-search loop in one launch, attention memory register-resident
+  int flash = 1;                            // single-pass Luong attend (two-pass when 0 / Bahdanau)
+  int split_proj = 2;                       // fused projection on split-bf16 MFMAs (six part products, f32-equivalent); 0 = f32 MFMAs
+  int mx_att = 1;                           // persistent decode (Luong, one cell): attention on the matrix pipe
+  int mx_cell = 1;                          // ... and its cell product [ctx' | h] . Wcat2 as well (needs mx_att)
+  int wide = 1;                             // matrix-pipe recurrence, 16 chunks per workgroup: 1 on (default: every call runs the same kernels whatever its slab
+                                            // size, so results do not depend on how a read is cut into slabs / shards), 0 packed-FMA kernels, -1 per-call choice
+  int lane_inproj = 1;                      // the event encoder's layer-0 input projection inside its matrix-pipe recurrence (0: k_inproj_small + pre-projected inputs)
+  int tail_wave = 1;                        // layer 0: cell update on a ninth wave, two row groups half a step apart
+  int fuse = 1;                             // layers >= 1: input projection inside the recurrence kernel (MFMA waves)
+  int fused_mem = 1;                        // option "fused_memory": the default decode form projects its own attention memory (no gemm_memory launch)
+  int taps = 0, graph = 1, profile = 0;
+  int ptaps = 0;                            // persist_taps: per-step logits of the persistent decode (debug)
+  int slab_graph = 0;                       // option "slab_graph": off by default -- measured (tools/graph_ab.py, C3, depth 10): a submit costs the host
+                                            // 22-27 us instead of 43-48, but the replayed slabs stream 1.5-3 % SLOWER (354-361 k against 361-370 k chunks/s
+                                            // settled; the runtime's per-node barrier packets), and the host is not what bounds the stream
+  int gen = 0;                              // (root) bumped by every rv_set_option / rv_load_weights: frozen arguments may have changed
+  int async_depth = 2;                      // contexts the asynchronous entry points rotate through (1..RV_MAX_ASYNC)
+  int coalesce = -1;                        // 0 / 1 off, n >= 2 slabs per group, -1 chosen from async_depth (coalesce_n)
+};
+
+// Device images derived from the weights by rv_load_weights.  The handle owns them; a child context takes the addresses as a whole (create_child)
+struct WeightImages {
+  float* WmemT = nullptr;                   // W_mem^T [128][256]
+  float* Up = nullptr;                      // recurrent kernels in the recurrence kernels' register order, [enc][layer][dir][65536]
+  float* Wp = nullptr;                      // input kernels of encoder layers >= 1 as MFMA B fragments, [enc][layer-1][dir][131072]
+  uint16_t* Wsb = nullptr;                  // the same kernels cut into three bf16 parts, [enc][layer-1][dir][32 tiles][3 parts][8 k-steps][64 lanes][8]
+  uint16_t* Wh = nullptr;                   // ... as two f16 parts of the column-scaled kernels + 512 column factors, [enc][layer-1][dir][RV_WH_SLOT]
+  uint16_t* Wl16 = nullptr;                 // (one decoder cell): [W_fc ; A_h W_fc] as MFMA B fragments (DecState::Wl16)
+  uint16_t* Wq16 = nullptr;                 // (Bahdanau, one decoder cell): W_q as MFMA B fragments (DecState::Wq16)
+  uint16_t* W1c16 = nullptr;                // (two decoder cells): [W_1 | U_1] as MFMA B fragments (DecState::W1c16)
+  uint16_t* Ua = nullptr;                   // recurrent kernels as MFMA A fragments (two f16 parts) + row factors, [enc][layer][dir][RV_UA_SLOT]
+  uint16_t* Wx16 = nullptr;                 // input kernels of encoder layers >= 1, both directions, as the split GEMM's B slabs, [enc][layer-1][RV_WX16_SLOT]
+  float* bx2 = nullptr;                     // [b_fwd | b_bwd] of those layers, [enc][layer-1][1024]
+  float* Wmp = nullptr;                     // [W_mem | A_c] [256][256] (A_c = W_att rows 128..383): projection of the attention memory for the persistent decode
+  float* Wcat2 = nullptr;                   // (one decoder cell): [W_a ; U + A_h W_a] [256][512]
+  float* Nh = nullptr;                      // (one decoder cell): A_h W_fc [128][V]
+  uint16_t* Wc16 = nullptr;                 // (one decoder cell): Wcat2 as two f16 parts in MFMA B-fragment order (DecState::Wc16)
+  uint16_t* Wmp16 = nullptr;                // Wmp as two f16 parts in MFMA fragment order + column factors (launch_gemm_mem_split)
+  uint16_t* Wkp16 = nullptr;                // the W_mem half of those parts, columns permuted into key-tile rows (DecState::Wkp16)
+  float* WcatT = nullptr;                   // ([W_dec[V:] ; U_dec])^T, [512][256]
+};
+
+// What a recording leaves behind for rv_get_tensor beside lB .. lptaps; a slab graph stores them at its capture and puts them back at every replay
+struct SlabFacts {
+  int lflash = 0, lkeys = 0, lpersist = 0, lsplit = 1, lW = 0;
+  int lmem2_stale = 0;                      // the last call's decode projected its own memory without persist_taps: mem2 is built when "projected_memory" is asked for
+};
+
+struct CallsOut { const uint8_t* lut; uint8_t* bases; int32_t* lengths; float* probs; };
+
+// The labels and score outputs of a forced decode (rv_teacher_forced*) or of rv_score_logits
+struct ForcedCall { const int32_t* targets; uint32_t omit_mask; const RvScore* out; };
+
+// One call as its entry point states it.  dev_out: tokens / out2 are device pointers written by the finalize kernel; else the results
+// wait in pinned memory for finish().  lut != nullptr: the fused post-processing (rv_beam_search_calls) instead of tokens / scores.
+struct Call {
+  const float *raw = nullptr, *ev = nullptr;
+  bool dev_in = false;
+  int B = 0, T_r = 0, T_e = 0, W = 1, L = 0;
+  bool greedy = false;
+  int32_t* tokens = nullptr;
+  float* out2 = nullptr;
+  bool dev_out = false;
+  const uint8_t* lut = nullptr;             // the letter table of the fused post-processing
+  const CallsOut* calls = nullptr;          // ... and its host outputs (synchronous calls; an asynchronous one names them at its collect)
+  bool whole_beam = false;                  // rv_beam_search_all* / rv_beam_search_submit_all*: every beam, through ...
+  const RvBeams* beams = nullptr;           // ... these outputs (null: an asynchronous call with host outputs, named at its collect)
+  const ForcedCall* forced = nullptr;       // rv_teacher_forced*
+};
+
+// What a recording needs beyond the call, resolved once before enqueue() (begin_all_beams, begin_forced, launch_group)
+struct CallParts {
+  bool whole_beam = false;                  // k_dec_finalize_beams in k_dec_finalize's place, writing to ...
+  BeamsOut beams{};                         // ... these device addresses (the caller's, or the context's d_beams)
+  const int* labels = nullptr;              // a forced decode feeds these label rows [B,L] (device: the caller's, or d_forced) instead of its argmax
+  ScoreArgs score{};                        // ... and scores them: omit_mask and the output addresses (device: the caller's, or the d_sc_* buffers; null = not asked for)
+  const DecMembers* members = nullptr;      // the member table of a group's internal call
+  int form_B = -1;                          // the B that picks the kernel forms (a group: its first member's), -1 = the call's own
+};
+
 }  // namespace
 
 struct RvContext {
@@ -57,54 +144,22 @@ struct RvContext {
   bool loaded = false;
   std::vector<std::vector<LstmW>> enc[2];   // [enc][layer][dir]
   std::vector<LstmW> dec;                   // stacked decoder cells
-  float* d_WmemT = nullptr;                 // derived: W_mem^T [128][256]
-  int opt_split = 1;                        // concurrent decode sub-slabs (1..4); measured neutral at B=256
-  hipStream_t side[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-  int opt_att_nt = 0;
-  int opt_side_ev = 1;                      // event chain on a side stream under the raw in-projection GEMM
-  int opt_persist = 1;                      // whole beam-search loop in one launch, attention memory register-resident
-  int* d_chunk_steps = nullptr;
-  int lpersist = 0;
-  int opt_flash = 1;                        // single-pass Luong attend (two-pass when 0 / Bahdanau)
-  int lflash = 0, lkeys = 0, lsplit = 1;
-  float* d_Up = nullptr;                    // derived: recurrent kernels in the recurrence kernels' register order, [enc][layer][dir][65536]
-  float* d_Wp = nullptr;                    // derived: input kernels of encoder layers >= 1 as MFMA B fragments, [enc][layer-1][dir][131072]
-  uint16_t* d_Wsb = nullptr;                // derived: the same kernels cut into three bf16 parts, [enc][layer-1][dir][32 tiles][3 parts][8 k-steps][64 lanes][8]
-  uint16_t* d_Wh = nullptr;                 // derived: ... as two f16 parts of the column-scaled kernels + 512 column factors, [enc][layer-1][dir][RV_WH_SLOT]
-  int opt_split_proj = 2;                   // fused projection on split-bf16 MFMAs (six part products, f32-equivalent); 0 = f32 MFMAs
-  int opt_mx_att = 1;                       // persistent decode (Luong, one cell): attention on the matrix pipe
-  int opt_mx_cell = 1;                      // ... and its cell product [ctx' | h] . Wcat2 as well (needs opt_mx_att)
+  WeightImages img;                         // derived from the weights; a child context holds its parent's addresses
+  const float *W_mem = nullptr, *W_q = nullptr, *v_att = nullptr, *W_att = nullptr, *W_fc = nullptr, *b_fc = nullptr;
   float mx_cdescale = 1.f;                  // 1 / the power-of-two scale of the Wc16 image (set by rv_load_weights)
   float mx_ldescale = 1.f;                  // ... of the Wl16 image
-  uint16_t* d_Wl16 = nullptr;               // derived (one decoder cell): [W_fc ; A_h W_fc] as MFMA B fragments (DecState::Wl16)
-  uint16_t* d_Wq16 = nullptr;               // derived (Bahdanau, one decoder cell): W_q as MFMA B fragments (DecState::Wq16)
   float mx_qdescale = 1.f;
-  uint16_t* d_W1c16 = nullptr;              // derived (two decoder cells): [W_1 | U_1] as MFMA B fragments (DecState::W1c16)
   float mx_c1descale = 1.f;
   float mx_kscale = 1.f, mx_uscale = 1.f;   // powers of two from the bounds of [keys | U'] = enc_out . Wmp (set by rv_load_weights)
-  uint16_t* d_Ua = nullptr;                 // derived: recurrent kernels as MFMA A fragments (two f16 parts) + row factors, [enc][layer][dir][RV_UA_SLOT]
-  uint16_t* d_Wx16 = nullptr;               // derived: input kernels of encoder layers >= 1, both directions, as the split GEMM's B slabs, [enc][layer-1][RV_WX16_SLOT]
-  float* d_bx2 = nullptr;                   // derived: [b_fwd | b_bwd] of those layers, [enc][layer-1][1024]
-  int opt_wide = 1;                         // matrix-pipe recurrence, 16 chunks per workgroup: 1 on (default: every call runs the same kernels whatever its slab
-                                            // size, so results do not depend on how a read is cut into slabs / shards), 0 packed-FMA kernels, -1 per-call choice
-  int lwide = 0;
-  int opt_lane_inproj = 1;                  // the event encoder's layer-0 input projection inside its matrix-pipe recurrence (0: k_inproj_small + pre-projected inputs)
-  int lrows8 = 0;                           // this call's matrix-pipe recurrences take eight chunks per workgroup (the latency form of lstm_mx.hip)
-  int opt_tail_wave = 1;                    // layer 0: cell update on a ninth wave, two row groups half a step apart
-  int opt_fuse = 1;                         // layers >= 1: input projection inside the recurrence kernel (MFMA waves)
+
+  Options opt;
   int dbg_role = 0;                         // timing probe (RV_DBG_ROLE): 1 = no projection math, 2 = no recurrence math
-  float* d_Wmp = nullptr;                   // derived: [W_mem | A_c] [256][256] (A_c = W_att rows 128..383): projection of the attention memory for the persistent decode
-  float* d_Wcat2 = nullptr;                 // derived (one decoder cell): [W_a ; U + A_h W_a] [256][512]
-  float* d_Nh = nullptr;                    // derived (one decoder cell): A_h W_fc [128][V]
-  uint16_t* d_Wc16 = nullptr;               // derived (one decoder cell): Wcat2 as two f16 parts in MFMA B-fragment order (DecState::Wc16)
-  uint16_t* d_Wmp16 = nullptr;              // derived: Wmp as two f16 parts in MFMA fragment order + column factors (launch_gemm_mem_split)
-  uint16_t* d_Wkp16 = nullptr;              // derived: the W_mem half of those parts, columns permuted into key-tile rows (DecState::Wkp16)
-  int opt_fused_mem = 1;                    // option "fused_memory": the default decode form projects its own attention memory (no gemm_memory launch)
-  int lmem2_stale = 0;                      // the last call did so without persist_taps: mem2 is built when "projected_memory" is asked for
+  hipStream_t side[3] = {nullptr, nullptr, nullptr};
+  hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
+  int* d_chunk_steps = nullptr;
+  int lwide = 0;
+  int lrows8 = 0;                           // this call's matrix-pipe recurrences take eight chunks per workgroup (the latency form of lstm_mx.hip)
   float* mem2 = nullptr;                    // [B,Tm,256] = enc_out . Wmp: keys | attention-layer image of the values
-  float* d_WcatT = nullptr;                 // derived: ([W_dec[V:] ; U_dec])^T, [512][256]
-  const float *W_mem = nullptr, *W_q = nullptr, *v_att = nullptr, *W_att = nullptr, *W_fc = nullptr, *b_fc = nullptr;
 
   // encoder buffers
   float *d_raw = nullptr, *d_ev = nullptr;
@@ -129,19 +184,13 @@ struct RvContext {
   // the whole beam (rv_beam_search_all*): device outputs and pinned staging of the host variants, [max_batch, max_output_len, max_beam]
   // and [max_batch, max_beam], allocated on this context's first such call (ensure_beam_buffers)
   BeamsOut d_beams{}, pin_beams{};
-  bool all_beams = false;                   // the call being recorded hands out the whole beam, through ...
-  BeamsOut lbeams{};                        // ... these device addresses (the caller's, or d_beams)
   // forced decode and scoring (rv_teacher_forced*, rv_score_logits)
-  const int* lforced = nullptr;             // the call being recorded feeds these label rows [B,L] (device: the caller's, or d_forced) instead of its argmax
-  ScoreArgs lscore{};                       // ... and scores them: omit_mask and the output addresses (device: the caller's, or the d_sc_* below; null = not asked for)
   int32_t* d_forced = nullptr;              // host variants: labels [max_batch, max_output_len] and the score outputs, allocated on this context's
   float *d_sc_nll = nullptr, *d_sc_sum = nullptr;   //   first such call (ensure_score_buffers): nll [max_batch, max_output_len], nll_sum [max_batch],
   int32_t* d_sc_cnt = nullptr;              //   n_labels | n_match | n_counted [3][max_batch]
 
-  int opt_taps = 0, opt_graph = 1, opt_profile = 0;
   long long* rec_ts = nullptr;              // diagnostic: per-wave cycle sums of the raw layer-0 recurrence (RV_REC_STAMPS=1) or of its fused layer 1 (=2)
   int rec_ts_layer = 0;
-  int opt_ptaps = 0, lptaps = 0;            // persist_taps: per-step logits of the persistent decode (debug)
   std::map<std::string, ProfEntry> prof;
   struct Pending { std::string name; hipEvent_t a, b; };
   std::vector<Pending> pending;
@@ -150,18 +199,15 @@ struct RvContext {
   // one hipGraph per slab context and call shape: the whole slab (ten launches on the default path) replays as ONE hipGraphLaunch.
   // Every kernel argument is frozen at capture; the addresses that change from call to call (caller inputs and outputs) reach the
   // kernels through a 4-entry table in mapped pinned memory (common.h: RV_PTAB_*), rewritten by the host before each replay
-  struct SlabGraph { hipGraphExec_t exec = nullptr; int lflash = 0, lkeys = 0, lpersist = 0, lsplit = 1, lW = 0, lmem2_stale = 0; };
+  struct SlabGraph { hipGraphExec_t exec = nullptr; SlabFacts fact; };
   std::map<SlabKey, SlabGraph> slab_graphs;
   const void** d_ptab = nullptr;
   const void** pin_ptab = nullptr;
-  int opt_slab_graph = 0;                   // option "slab_graph": off by default -- measured (tools/graph_ab.py, C3, depth 10): a submit costs the host
-                                            // 22-27 us instead of 43-48, but the replayed slabs stream 1.5-3 % SLOWER (354-361 k against 361-370 k chunks/s
-                                            // settled; the runtime's per-node barrier packets), and the host is not what bounds the stream
-  int opt_gen = 0;                          // (root) bumped by every rv_set_option / rv_load_weights: frozen arguments may have changed
-  int graph_gen = 0;                        // the opt_gen this context's slab graphs were captured under
+  int graph_gen = 0;                        // the opt.gen (of the root) this context's slab graphs were captured under
 
   // last call
-  int lB = 0, lW = 0, lTm = 0, lL = 0, lS = 0, lgreedy = 0, ltaps = 0;
+  int lB = 0, lTm = 0, lL = 0, lS = 0, lgreedy = 0, ltaps = 0, lptaps = 0;
+  SlabFacts fact;
   FormLog lforms;                           // the kernel instantiations it launched ("kernel_forms"); lforms_ok = 0: it ran as a slab graph
   int lforms_ok = 1;
   std::map<GraphKey, FormLog> graph_forms;  // ... those a captured decode graph of `graphs` launches (recorded at its capture)
@@ -170,15 +216,13 @@ struct RvContext {
   // own buffers, the PARENT's weights and derived images -- so that several slabs are in flight on the GPU at once
   RvContext* parent = nullptr;
   std::vector<RvContext*> kids;
-  int opt_async_depth = 2;                  // contexts the asynchronous entry points rotate through (1..RV_MAX_ASYNC)
-  int inflight_hint = 1;                    // slabs the caller keeps in flight (1 for the synchronous entry points): sizes the workgroups
+  int inflight_hint = 1;                   // slabs the caller keeps in flight (1 for the synchronous entry points): sizes the workgroups
   int next_slot = 0, generation = 0;
   struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false, all = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
 
   // coalesced asynchronous calls (option "coalesce"): up to n consecutively submitted slabs of the default streamed path are decoded as ONE
   // internal call of sum(B) chunks on a GROUP context -- a child context whose buffers hold n x max_batch chunks -- so that the narrow
   // recurrence launches are n times as wide and a handle fills the chip from few hardware queues.  Tickets stay per slab (`ticks`).
-  int opt_coalesce = -1;                    // 0 / 1 off, n >= 2 slabs per group, -1 chosen from async_depth (coalesce_n)
   std::vector<RvContext*> groups;           // (root) group contexts, created when a slab finds none idle
   RvContext* open_grp = nullptr;            // (root) the group that still takes members: filled, not launched
   struct Tick { bool busy = false, done = false, dev_out = false, calls = false; int ticket = -1, member = 0, B = 0, row0 = 0, steps = 0, S = 0; RvContext* grp = nullptr; };
@@ -186,11 +230,12 @@ struct RvContext {
   long long co_groups = 0, co_slabs = 0, co_largest = 0;     // (root) "coalesce_stats": groups launched, slabs in them, members of the largest
   // ... of a group context
   int g_cap = 0, g_n = 0, g_rows = 0, g_staged = 0, g_failed = RV_OK;     // members it takes / holds, chunks they add up to, members whose results wait in its staging
-  bool g_launched = false, g_synced = false, g_dev_in = false, g_dev_out = false, g_calls = false, group_call = false;
-  int g_Tr = 0, g_Te = 0, g_W = 0, g_L = 0, g_formB = 0;
+  bool g_launched = false, g_synced = false, g_dev_in = false, g_dev_out = false, g_calls = false;
+  int g_Tr = 0, g_Te = 0, g_W = 0, g_L = 0;
+  int g_B0 = 0;                             // its first member's B: the group takes the kernel forms that member would have got alone
   uint8_t g_lut[RV_MAX_VOCAB] = {};
   int g_tslot[RV_MAX_MEMBERS] = {};
-  DecMembers lmem{};                        // the member table of the call being recorded (n = 0: an ordinary call)
+  DecMembers g_members{};                   // its member table: output addresses as the members come (submit_group), rows at its launch (launch_group)
 };
 
 namespace {
@@ -208,6 +253,24 @@ int fail(RvContext* h, int code, const char* fmt, ...) {
     if (e_ != hipSuccess)                                                                 \
       return fail(h, RV_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
+
+#define TRY(x) do { int r_ = (x); if (r_ != RV_OK) return r_; } while (0)
+// rv_create and the context's buffers: the short form of HIPCHK's message
+#define HIPTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(h, RV_EHIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
+
+// The outcome of a call that ran on context `ctx` of handle h: rv_last_error answers from the handle
+int relay(RvContext* h, const RvContext* ctx, int rc) {
+  if (rc != RV_OK && ctx != h) h->err = ctx->err;
+  return rc;
+}
+
+int async_depth(const RvContext* h) { return std::min(std::max(h->opt.async_depth, 1), RV_MAX_ASYNC); }
+
+// The next ticket of handle h for `slot` (a slab context, or an entry of `ticks`)
+int issue_ticket(RvContext* h, int slot) {
+  h->generation = (h->generation + 1) & 0xFFFFF;
+  return (h->generation << 4) | slot;
+}
 
 template <class T>
 int dalloc(RvContext* h, T** p, size_t count) {
@@ -283,7 +346,7 @@ struct Scope {
   // profile 3: only the decode launches (the dominant kernel) are bracketed, so that the timed region of bench.py
   // carries two events per slab instead of two per launch (the per-launch events cost 2.6 % of a C3 slab)
   Scope(RvContext* h_, const char* n, hipStream_t st_ = nullptr, bool decode = false)
-      : h(h_), name(n), on(h_->opt_profile != 0 && (h_->opt_profile != 3 || decode)), st(st_ ? st_ : h_->stream) {
+      : h(h_), name(n), on(h_->opt.profile != 0 && (h_->opt.profile != 3 || decode)), st(st_ ? st_ : h_->stream) {
     if (!on) return;
     auto get = [&]() {
       hipEvent_t e;
@@ -335,9 +398,9 @@ int pick_rows_per_block(int B) {
 // Encoder.call for one encoder (basecaller.py:48-59) writing into enc_out at time offset t_off.
 // Does this slab run its encoder recurrences on the matrix pipe (lstm_mx.hip: 16 chunks of one direction per workgroup)?
 bool wide_recurrence(const RvContext* h, int B, int T_r) {
-  if (h->opt_wide == 0 || !h->opt_fuse) return false;
+  if (h->opt.wide == 0 || !h->opt.fuse) return false;
   if (h->cfg.mode != RV_MODE_EVENT && !lstm_rec_mx_window_fits(T_r)) return false;
-  if (h->opt_wide > 0) return true;
+  if (h->opt.wide > 0) return true;
   // Per-call choice (-1).  The packed-FMA kernels cost per chunk, the matrix forms per workgroup.  Synchronous calls at T = 300 + 30
   // (tools/rows8_ab.py, k chunks/s; FMA / matrix pipe with 8 / with 16 chunks per workgroup): 64 chunks 75 / 64 / 53; 128: 146 / 124 / 102;
   // 192: 159 / 181 / 150; 256: 203 / 224 / 189; 512: 208 / 298 / 266; 1,024: 212 / 342 / 341 -- FMA below 160 chunks in flight, the
@@ -348,9 +411,9 @@ bool wide_recurrence(const RvContext* h, int B, int T_r) {
 // ... and with eight chunks per workgroup (two MFMAs per tile and k-step, half the cell update per lane: a shorter step on twice the
 // workgroups)?  wide_recurrence = 2 always; = -1 (per-call choice) when the slabs in flight leave the chip room for it.
 bool rows8_wanted(const RvContext* h, int B) {
-  if (h->opt_wide == 2) return true;
+  if (h->opt.wide == 2) return true;
   const long long n = (long long)B * std::max(h->inflight_hint, 1);
-  return h->opt_wide < 0 && n >= 160 && n <= 512;
+  return h->opt.wide < 0 && n >= 160 && n <= 512;
 }
 
 void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int Tm, int t_off, hipStream_t s,
@@ -367,8 +430,8 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
     for (int dr = 0; dr < 2; ++dr) {
       const LstmW& w = h->enc[e][l][dr];
       a.U[dr] = w.U;
-      a.Up[dr] = h->d_Up + ((size_t)(e * depth + l) * 2 + dr) * RV_U * RV_G;
-      a.Ua[dr] = h->d_Ua + ((size_t)(e * depth + l) * 2 + dr) * RV_UA_SLOT;
+      a.Up[dr] = h->img.Up + ((size_t)(e * depth + l) * 2 + dr) * RV_U * RV_G;
+      a.Ua[dr] = h->img.Ua + ((size_t)(e * depth + l) * 2 + dr) * RV_UA_SLOT;
       a.h0[dr] = l > 0 ? h->st[e][rd][2 * dr] : nullptr;
       a.c0[dr] = l > 0 ? h->st[e][rd][2 * dr + 1] : nullptr;
       a.hT[dr] = h->st[e][wr][2 * dr];
@@ -378,7 +441,7 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
       // matrix-pipe recurrence.  Raw layer 0 folds its one-feature input projection in; every other layer reads pre-projected
       // inputs xw [B,T,2,512]: event layer 0 from a small elementwise kernel, layers >= 1 from the split-f16 GEMM (both directions
       // and their biases in one launch, A read once).
-      if (l == 0 && (F == 1 || (F == 5 && h->opt_lane_inproj && lstm_rec_mx_window_fits(T, 5)))) {
+      if (l == 0 && (F == 1 || (F == 5 && h->opt.lane_inproj && lstm_rec_mx_window_fits(T, 5)))) {
         // layer 0 takes x . W + b in the lane, from LDS windows of its chunks' inputs: no projection launch, no xw round trip (round 4: the
         // event encoder's five features too -- the same fused multiply-adds in the same order as k_inproj_small: identical bits)
         a.x = x;
@@ -397,8 +460,8 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
                             h->mask, T, Tm, t_off, h->cfg.padding_value, s, ptab, &h->lforms);
       } else {
         Scope sc(h, e == 0 ? "gemm_inproj_raw" : "gemm_inproj_event", s);
-        launch_gemm_split_blocks(h->act[e][(l - 1) & 1], B * T, h->d_Wx16 + (size_t)(e * (depth - 1) + (l - 1)) * RV_WX16_SLOT, 4,
-                                 h->d_bx2 + (size_t)(e * (depth - 1) + (l - 1)) * 2 * RV_G, h->xw[e], 2 * RV_G, s);
+        launch_gemm_split_blocks(h->act[e][(l - 1) & 1], B * T, h->img.Wx16 + (size_t)(e * (depth - 1) + (l - 1)) * RV_WX16_SLOT, 4,
+                                 h->img.bx2 + (size_t)(e * (depth - 1) + (l - 1)) * 2 * RV_G, h->xw[e], 2 * RV_G, s);
       }
       a.x = h->xw[e];
       a.dbg_ts = (e == 0 && l == 1 && h->rec_ts_layer == 1) ? h->rec_ts : nullptr;    // (RV_REC_STAMPS=2)
@@ -411,19 +474,19 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
       a.x = x;
       for (int dr = 0; dr < 2; ++dr) { a.W[dr] = h->enc[e][0][dr].W; a.bias[dr] = h->enc[e][0][dr].b; }
       Scope sc(h, e == 0 ? "lstm_rec_raw_l0" : "lstm_rec_event_l0", s);
-      a.tail_wave = h->opt_tail_wave;
+      a.tail_wave = h->opt.tail_wave;
       a.dbg_ts = (e == 0 && h->rec_ts_layer == 0) ? h->rec_ts : nullptr;
       launch_lstm_rec(a, F, bt, s, &h->lforms);
       a.dbg_ts = nullptr;
     } else {
       const float* in = h->act[e][(l - 1) & 1];
-      if (h->opt_fuse) {   // x . W + b on the matrix pipe inside the recurrence kernel: no K0 launch, no xw tensor
+      if (h->opt.fuse) {   // x . W + b on the matrix pipe inside the recurrence kernel: no K0 launch, no xw tensor
         a.x = in;
         a.dbg_role = h->dbg_role;
         for (int dr = 0; dr < 2; ++dr) {
-          a.Wp[dr] = h->d_Wp + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * RV_E * RV_G;
-          a.Wh[dr] = h->opt_split_proj == 2 ? h->d_Wh + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * RV_WH_SLOT : nullptr;
-          a.Wsb[dr] = h->opt_split_proj == 1 ? h->d_Wsb + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * 3 * RV_E * RV_G : nullptr;
+          a.Wp[dr] = h->img.Wp + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * RV_E * RV_G;
+          a.Wh[dr] = h->opt.split_proj == 2 ? h->img.Wh + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * RV_WH_SLOT : nullptr;
+          a.Wsb[dr] = h->opt.split_proj == 1 ? h->img.Wsb + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * 3 * RV_E * RV_G : nullptr;
           a.bias[dr] = h->enc[e][l][dr].b;
         }
         a.dbg_ts = (e == 0 && l == 1 && h->rec_ts_layer == 1) ? h->rec_ts : nullptr;
@@ -449,10 +512,10 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
 }
 
 void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool profiled, FormLog* log) {
-  const bool flash = h->lflash != 0;
+  const bool flash = h->fact.lflash != 0;
   auto cells = [&](int step, bool prof) {
     for (int k = 0; k < d.depth; ++k) {
-      const float* WcatT = h->d_WcatT + (size_t)k * RV_G * RV_E;
+      const float* WcatT = h->img.WcatT + (size_t)k * RV_G * RV_E;
       if (prof) { Scope sc(h, "dec_cell"); launch_dec_cell(d, k, WcatT, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s); }
       else launch_dec_cell(d, k, WcatT, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s);
     }
@@ -460,38 +523,35 @@ void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool pr
   for (int step = 0; step < d.L - 1; ++step) {
     if (profiled) {
       cells(step, true);
-      { Scope sc(h, "dec_attend"); launch_dec_attend(d, h->d_WmemT, flash, step, s, log); }
+      { Scope sc(h, "dec_attend"); launch_dec_attend(d, h->img.WmemT, flash, step, s, log); }
     } else {
       cells(step, false);
-      launch_dec_attend(d, h->d_WmemT, flash, step, s, log);
+      launch_dec_attend(d, h->img.WmemT, flash, step, s, log);
     }
   }
 }
 
-struct CallsOut { const uint8_t* lut; uint8_t* bases; int32_t* lengths; float* probs; };
-
 // The form of the one-launch persistent decode this call takes (dec_persist_form), or -1: the per-step kernels
-int persist_form(const RvContext* h, bool greedy, int W, int Tm) {
-  if (!h->opt_persist || !h->opt_flash || h->opt_taps) return -1;
+int persist_form(const RvContext* h, bool greedy, int W, int Tm, bool forced) {
+  if (!h->opt.persist || !h->opt.flash || h->opt.taps) return -1;
   const RvConfig& c = h->cfg;
-  if (h->lforced && c.vocab >= RV_MAX_VOCAB) return -1;      // (a forced decode keeps a bias-only row behind the vocabulary's in the resident token table)
-  return dec_persist_form(c.attention, c.dec_depth, greedy ? 1 : W, Tm, greedy, h->opt_mx_att, h->opt_mx_cell);
+  if (forced && c.vocab >= RV_MAX_VOCAB) return -1;      // (a forced decode keeps a bias-only row behind the vocabulary's in the resident token table)
+  return dec_persist_form(c.attention, c.dec_depth, greedy ? 1 : W, Tm, greedy, h->opt.mx_att, h->opt.mx_cell);
 }
 
-int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, int B, int T_r, int T_e, int W, int L, bool greedy,
-                int32_t* tk, float* o2, bool dev_out, const uint8_t* lut, const void* const* ptab);
+int record_slab(RvContext* h, const Call& call, const CallParts& res, const void* const* ptab);
 
-// Everything of a call up to (not including) the wait for the stream: launches and the D2H copies into pinned staging.
-// dev_out: tokens / out2 are device pointers written by the finalize kernel; else the results wait in pinned memory for finish().
-// lut != nullptr: the fused post-processing (rv_beam_search_calls) instead of tokens / scores.
-// The checks every call passes before anything is queued (T_r / T_e of an unused encoder become 0)
-int validate_call(RvContext* h, const float* raw, const float* ev, int B, int& T_r, int& T_e, int W, int L, const int32_t* tokens,
-                  const float* out2, bool dev_out) {
+// The checks every call passes before anything is queued.  `ok` becomes the call with its effective lengths: T_r / T_e of an encoder
+// the mode does not use are 0 there, and everything past this point works on `ok`
+int validate_call(RvContext* h, const Call& call, Call& ok) {
   const RvConfig& c = h->cfg;
   if (!h->loaded) return fail(h, RV_ESTATE, "no weights loaded (call rv_load_weights first)");
   const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
-  if (!use_raw) T_r = 0;
-  if (!use_ev) T_e = 0;
+  ok = call;
+  if (!use_raw) ok.T_r = 0;
+  if (!use_ev) ok.T_e = 0;
+  const int B = ok.B, T_r = ok.T_r, T_e = ok.T_e, W = ok.W, L = ok.L;
+  const float *raw = ok.raw, *ev = ok.ev;
   if (B < 0 || B > c.max_batch) return fail(h, RV_EINVAL, "B=%d outside [0,%d]", B, c.max_batch);
   if (use_raw && (T_r < 1 || T_r > c.max_raw_len)) return fail(h, RV_EINVAL, "T_r=%d outside [1,%d]", T_r, c.max_raw_len);
   if (use_ev && (T_e < 1 || T_e > c.max_event_len)) return fail(h, RV_EINVAL, "T_e=%d outside [1,%d]", T_e, c.max_event_len);
@@ -500,70 +560,72 @@ int validate_call(RvContext* h, const float* raw, const float* ev, int B, int& T
   if (B > 0 && ((use_raw && !raw) || (use_ev && !ev))) return fail(h, RV_EINVAL, "missing input pointer for this mode");   // (an empty device tensor has no address)
   if (T_r + T_e > 352) return fail(h, RV_EUNSUPPORTED, "attention memory of %d steps exceeds the 352 the decode kernel is built for", T_r + T_e);
   if (L > 64) return fail(h, RV_EUNSUPPORTED, "max_output_len %d exceeds 64", L);
-  if (dev_out && B > 0 && L > 1 && (!tokens || !out2)) return fail(h, RV_EINVAL, "null output pointer");
+  if (ok.dev_out && B > 0 && L > 1 && (!ok.tokens || !ok.out2)) return fail(h, RV_EINVAL, "null output pointer");
   return RV_OK;
 }
 
-int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W,
-            int L, bool greedy, int32_t* tokens, float* out2, bool dev_out, const uint8_t* lut) {
+// Everything of a call up to (not including) the wait for the stream: launches and the D2H copies into pinned staging.
+int enqueue(RvContext* h, const Call& stated, const CallParts& res) {
   if (!h) return RV_EINVAL;
   const RvConfig& c = h->cfg;
-  const bool calls = lut != nullptr;
   if (h->pend.busy) return fail(h, RV_ESTATE, "this context still holds an uncollected call");
   const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
-  { const int rc = validate_call(h, raw, ev, B, T_r, T_e, W, L, tokens, out2, dev_out); if (rc != RV_OK) return rc; }
-  if (!h->group_call) h->lmem.n = 0;
+  Call call;
+  TRY(validate_call(h, stated, call));
+  const int B = call.B, T_r = call.T_r, T_e = call.T_e, W = call.W, L = call.L;
+  const bool greedy = call.greedy, dev_out = call.dev_out, calls = call.lut != nullptr;
   HIPCHK(h, hipSetDevice(c.device));
-  h->lB = B; h->lW = W; h->lL = L; h->lS = 0; h->lgreedy = greedy; h->lTm = T_r + T_e; h->ltaps = h->opt_taps; h->lptaps = h->opt_ptaps;
+  h->lB = B; h->fact.lW = W; h->lL = L; h->lS = 0; h->lgreedy = greedy; h->lTm = T_r + T_e; h->ltaps = h->opt.taps; h->lptaps = h->opt.ptaps;
   h->lforms.n = 0; h->lforms.full = false; h->lforms_ok = 1;
   h->pend = RvContext::PendingCall{};
-  h->pend.busy = true; h->pend.greedy = greedy; h->pend.dev_out = dev_out; h->pend.calls = calls; h->pend.all = h->all_beams;
+  h->pend.busy = true; h->pend.greedy = greedy; h->pend.dev_out = dev_out; h->pend.calls = calls; h->pend.all = res.whole_beam;
   h->pend.B = B; h->pend.steps = std::max(L - 1, 0); h->pend.V = c.vocab; h->pend.Wd = greedy ? 1 : W;
   if (B == 0 || L <= 1) {
     h->pend.trivial = true;
-    if (h->all_beams && dev_out && B > 0) {      // nothing is launched: the initial state goes to the caller's device buffers by plain copies
+    if (res.whole_beam && dev_out && B > 0) {      // nothing is launched: the initial state goes to the caller's device buffers by plain copies
       std::vector<float> lp((size_t)B * W, -INFINITY);
       for (int b = 0; b < B; ++b) lp[(size_t)b * W] = 0.f;
-      if (h->lbeams.log_probs) HIPCHK(h, hipMemcpy(h->lbeams.log_probs, lp.data(), sizeof(float) * lp.size(), hipMemcpyHostToDevice));
-      if (h->lbeams.lengths) HIPCHK(h, hipMemset(h->lbeams.lengths, 0, sizeof(int32_t) * (size_t)B * W));
+      if (res.beams.log_probs) HIPCHK(h, hipMemcpy(res.beams.log_probs, lp.data(), sizeof(float) * lp.size(), hipMemcpyHostToDevice));
+      if (res.beams.lengths) HIPCHK(h, hipMemset(res.beams.lengths, 0, sizeof(int32_t) * (size_t)B * W));
     }
     return RV_OK;
   }
 
+  // From here on `call` names device memory throughout: the inputs the encoders read and the outputs the finalize kernel writes
+  // (dev_in / dev_out still say whose they are, so which copies the recording adds)
   hipStream_t s = h->stream;
-  const float *xr = raw, *xe = ev;
-  if (!dev_in) {   // host -> pinned staging (CPU memcpy); the H2D copies are part of the slab's stream work (record_slab)
-    if (use_raw) { memcpy(h->pin_raw, raw, sizeof(float) * B * T_r); xr = h->d_raw; }
-    if (use_ev) { memcpy(h->pin_ev, ev, sizeof(float) * B * T_e * 5); xe = h->d_ev; }
+  if (!call.dev_in) {   // host -> pinned staging (CPU memcpy); the H2D copies are part of the slab's stream work (record_slab)
+    if (use_raw) { memcpy(h->pin_raw, call.raw, sizeof(float) * B * T_r); call.raw = h->d_raw; }
+    if (use_ev) { memcpy(h->pin_ev, call.ev, sizeof(float) * B * T_e * 5); call.ev = h->d_ev; }
   }
+  if (!dev_out || !call.tokens) call.tokens = h->out_tokens;
+  if (!dev_out || !call.out2) call.out2 = h->out2;
 
-  const int form_B = h->group_call ? h->g_formB : B;      // a group takes the forms its first member would have got alone
+  const int form_B = res.form_B >= 0 ? res.form_B : B;      // a group takes the forms its first member would have got alone
   h->lwide = wide_recurrence(h, form_B, T_r) ? 1 : 0;
   h->lrows8 = h->lwide && rows8_wanted(h, form_B) ? 1 : 0;
-  if ((!h->opt_fuse && c.enc_depth > 1) || h->lwide) {   // pre-projected tensors [max_batch, T_max, 2, 512]: allocated with the context (alloc_slab_buffers); this is a safety net
-    if (use_raw && c.enc_depth > 1 && !h->xw[0]) { const int rc = dalloc(h, &h->xw[0], (size_t)c.max_batch * c.max_raw_len * 2 * RV_G); if (rc != RV_OK) return rc; }
-    if (use_ev && !h->xw[1]) { const int rc = dalloc(h, &h->xw[1], (size_t)c.max_batch * c.max_event_len * 2 * RV_G); if (rc != RV_OK) return rc; }
+  if ((!h->opt.fuse && c.enc_depth > 1) || h->lwide) {   // pre-projected tensors [max_batch, T_max, 2, 512]: allocated with the context (alloc_slab_buffers); this is a safety net
+    if (use_raw && c.enc_depth > 1 && !h->xw[0]) TRY(dalloc(h, &h->xw[0], (size_t)c.max_batch * c.max_raw_len * 2 * RV_G));
+    if (use_ev && !h->xw[1]) TRY(dalloc(h, &h->xw[1], (size_t)c.max_batch * c.max_event_len * 2 * RV_G));
   }
-  int32_t* tk = (dev_out && tokens) ? tokens : h->out_tokens;
-  float* o2 = (dev_out && out2) ? out2 : h->out2;
 
   // ---- one hipGraph per slab context and call shape (option "slab_graph"): the default path -- matrix-pipe recurrences + persistent
   // decode, no profiling, no taps -- replays as ONE hipGraphLaunch instead of ten launches (a submit's host time is what the GPU waits
   // for whenever the slabs in flight finish together).  All kernel arguments are frozen at capture; the caller's addresses of THIS
   // call go through the pointer table (mapped pinned memory, written here, read by the kernels).
   RvContext* root = h->parent ? h->parent : h;
-  if (h->graph_gen != root->opt_gen) {          // an option or the weights changed since the capture: frozen arguments may be stale
+  if (h->graph_gen != root->opt.gen) {          // an option or the weights changed since the capture: frozen arguments may be stale
     for (auto& kv : h->slab_graphs) hipGraphExecDestroy(kv.second.exec);
     h->slab_graphs.clear();
-    h->graph_gen = root->opt_gen;
+    h->graph_gen = root->opt.gen;
   }
-  const bool graphable = root->opt_slab_graph && h->lwide && !h->lrows8 && persist_form(h, greedy, W, T_r + T_e) >= 0 && h->opt_profile == 0 && !h->opt_taps &&
-                         !h->all_beams && !h->lforced && !h->opt_ptaps && !h->rec_ts && !h->dec_st.dbg_ts && h->d_ptab;
-  if (!graphable) return record_slab(h, xr, xe, !dev_in, B, T_r, T_e, W, L, greedy, tk, o2, dev_out, lut, nullptr);
+  const bool graphable = root->opt.slab_graph && h->lwide && !h->lrows8 && persist_form(h, greedy, W, T_r + T_e, res.labels != nullptr) >= 0 && h->opt.profile == 0 && !h->opt.taps &&
+                         !res.whole_beam && !res.labels && !h->opt.ptaps && !h->rec_ts && !h->dec_st.dbg_ts && h->d_ptab;
+  if (!graphable) return record_slab(h, call, res, nullptr);
   h->lforms_ok = 0;                             // (a slab graph replays without the host launchers: "kernel_forms" answers RV_ESTATE)
-  h->pin_ptab[RV_PTAB_RAW] = xr; h->pin_ptab[RV_PTAB_EVENT] = xe; h->pin_ptab[RV_PTAB_TOKENS] = tk; h->pin_ptab[RV_PTAB_OUT2] = o2;
-  SlabKey key{B, T_r, T_e, W, L, (greedy ? 1 : 0) | (calls ? 2 : 0) | (dev_in ? 0 : 4) | (dev_out ? 0 : 8), 0};
-  if (calls) memcpy(&key.lut, lut, std::min<size_t>(sizeof key.lut, (size_t)c.vocab));
+  h->pin_ptab[RV_PTAB_RAW] = call.raw; h->pin_ptab[RV_PTAB_EVENT] = call.ev; h->pin_ptab[RV_PTAB_TOKENS] = call.tokens; h->pin_ptab[RV_PTAB_OUT2] = call.out2;
+  SlabKey key{B, T_r, T_e, W, L, (greedy ? 1 : 0) | (calls ? 2 : 0) | (call.dev_in ? 0 : 4) | (dev_out ? 0 : 8), 0};
+  if (calls) memcpy(&key.lut, call.lut, std::min<size_t>(sizeof key.lut, (size_t)c.vocab));
   auto it = h->slab_graphs.find(key);
   if (it == h->slab_graphs.end()) {
     if (h->slab_graphs.size() >= 16) {          // bound the cache (callers with ever-changing slab shapes)
@@ -572,7 +634,7 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
     }
     hipGraph_t graph = nullptr;
     HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int rc = record_slab(h, xr, xe, !dev_in, B, T_r, T_e, W, L, greedy, tk, o2, dev_out, lut, h->d_ptab);
+    const int rc = record_slab(h, call, res, h->d_ptab);
     const hipError_t ce = hipStreamEndCapture(s, &graph);      // (always: the stream must leave capture mode whatever record_slab said)
     if (rc != RV_OK) { if (graph) hipGraphDestroy(graph); return rc; }
     HIPCHK(h, ce);
@@ -580,34 +642,55 @@ int enqueue(RvContext* h, const float* raw, const float* ev, bool dev_in, int B,
     const hipError_t ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
     HIPCHK(h, ie);
-    g.lflash = h->lflash; g.lkeys = h->lkeys; g.lpersist = h->lpersist; g.lsplit = h->lsplit; g.lW = h->lW; g.lmem2_stale = h->lmem2_stale;
+    g.fact = h->fact;
     it = h->slab_graphs.emplace(key, g).first;
   }
   const RvContext::SlabGraph& g = it->second;
-  h->lflash = g.lflash; h->lkeys = g.lkeys; h->lpersist = g.lpersist; h->lsplit = g.lsplit; h->lW = g.lW; h->lmem2_stale = g.lmem2_stale;
+  h->fact = g.fact;
   HIPCHK(h, hipGraphLaunch(g.exec, s));
   return RV_OK;
 }
 
-// The stream work of one slab, in order: input copies, encoders, memory set-up, decode, finalize, output copies.  `ptab` non-null =
-// the call is being captured into a slab graph: kernels that touch caller memory read its address from the table.
-int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, int B, int T_r, int T_e, int W, int L, bool greedy,
-                int32_t* tk, float* o2, bool dev_out, const uint8_t* lut, const void* const* ptab) {
+// One recording of a slab (record_slab): the call as enqueue() resolved it, and what the phases below hand on to each other
+struct Slab {
+  const Call& call;
+  const CallParts& res;
+  const void* const* ptab;      // non-null: the call is being captured into a slab graph
+  int Tm, steps;
+  int persist_att = -1;         // persist_form of the call
+  DecState d{};                 // the whole slab's decode ...
+  int nsplit = 1;
+  DecState part[4];             // ... and its sub-slabs (one part unless the per-step decode splits)
+  DecParts parts{};
+};
+
+// Phase 1 of a recording: the inputs of a host caller, pinned staging -> device
+int stage_inputs(RvContext* h, const Slab& sl) {
   const RvConfig& c = h->cfg;
-  const bool calls = lut != nullptr;
   const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
+  const int B = sl.call.B, T_r = sl.call.T_r, T_e = sl.call.T_e;
   hipStream_t s = h->stream;
-  const int Tm = T_r + T_e, V = c.vocab, steps = L - 1;
-  if (host_in) {   // pinned staging -> device
+  if (!sl.call.dev_in) {   // pinned staging -> device
     if (use_raw) HIPCHK(h, hipMemcpyAsync(h->d_raw, h->pin_raw, sizeof(float) * B * T_r, hipMemcpyHostToDevice, s));
     if (use_ev) HIPCHK(h, hipMemcpyAsync(h->d_ev, h->pin_ev, sizeof(float) * B * T_e * 5, hipMemcpyHostToDevice, s));
   }
+  return RV_OK;
+}
+
+// Phase 2: the input mask and the two encoders, on one of three stream arrangements
+int record_encoders(RvContext* h, const Slab& sl) {
+  const RvConfig& c = h->cfg;
+  const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
+  const int B = sl.call.B, T_r = sl.call.T_r, T_e = sl.call.T_e, Tm = sl.Tm;
+  const float *xr = sl.call.raw, *xe = sl.call.ev;
+  const void* const* ptab = sl.ptab;
+  hipStream_t s = h->stream;
   // ---- _encode_input (basecaller.py:395-416)
   // The mask is first read by the memory set-up / the decode: it runs on a side stream beside the encoders instead of in front
   // of them (profiling modes keep it on the main stream so that its events pair up).
   // (with several slabs in flight the other slabs fill the chip: one stream per context then, no fork / join)
   // The matrix-pipe layer-0 kernels write it themselves (they read every input sample anyway): no launch at all then.
-  const bool mask_aside = !h->lwide && (h->opt_profile == 0 || h->opt_profile == 3) && h->inflight_hint <= 1 && !h->parent;
+  const bool mask_aside = !h->lwide && (h->opt.profile == 0 || h->opt.profile == 3) && h->inflight_hint <= 1 && !h->parent;
   if (mask_aside) {
     hipStream_t sm = side_stream(h, 2);
     HIPCHK(h, hipEventRecord(h->ev_fork, s));
@@ -618,7 +701,7 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     Scope sc(h, "input_mask"); launch_input_mask(xr, xe, B, T_r, T_e, c.padding_value, h->mask, s);
   }
   // The two encoders are independent until the time-axis concat (basecaller.py:400-405).
-  const bool side_ev = use_raw && use_ev && h->opt_side_ev && c.enc_depth > 1 && !h->opt_fuse;   // (nothing MFMA-bound to hide under once the projection is fused)
+  const bool side_ev = use_raw && use_ev && h->opt.side_ev && c.enc_depth > 1 && !h->opt.fuse;   // (nothing MFMA-bound to hide under once the projection is fused)
   if (side_ev) {
     // raw layer 0 alone (every recurrence workgroup needs a whole CU); then the short event chain on a side stream
     // UNDER the raw encoder's input-projection GEMM: a recurrence workgroup (2 x 168 VGPRs per SIMD, VALU-bound) and a
@@ -631,7 +714,7 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     run_encoder(h, 0, xr, 1, B, T_r, Tm, 0, s, 1);
     HIPCHK(h, hipEventRecord(h->ev_join[0], sev));
     HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[0], 0));
-  } else if (h->lwide && use_raw && use_ev && h->inflight_hint <= 1 && !ptab && h->opt_profile == 0 && h->opt_side_ev) {
+  } else if (h->lwide && use_raw && use_ev && h->inflight_hint <= 1 && !ptab && h->opt.profile == 0 && h->opt.side_ev) {
     // One isolated slab on the matrix-pipe form: every encoder launch is 2 x ceil(B / 16) workgroups (32 of the chip's 256 CUs at B = 256), so
     // the event encoder's chain (four launches, ~0.15 ms at the C3 shape) runs on a side stream BESIDE the raw encoder's instead of in front of
     // it: the synchronous call's latency drops by that much.  (With several slabs in flight the other slabs fill the chip: one stream per
@@ -650,91 +733,117 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
   }
 
   if (mask_aside) HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[2], 0));
+  return RV_OK;
+}
+
+// Phase 3: which attend and which decode the call takes (lflash, persist_att), and the key GEMM where they need it
+int record_keys(RvContext* h, Slab& sl) {
+  const RvConfig& c = h->cfg;
+  const int B = sl.call.B, W = sl.call.W, Tm = sl.Tm;
+  const bool greedy = sl.call.greedy;
+  hipStream_t s = h->stream;
   // ---- setup_memory (basecaller.py:303): keys = (enc_output * mask) . W_mem.  The single-pass Luong
   //      attend never reads keys (score_t = values_t . (W_mem q)); they are built for the two-pass
   //      kernel and for the "keys" debug tap only.
   const int W_eff = greedy ? 1 : W;
-  h->lflash = (c.attention == RV_ATT_LUONG && h->opt_flash && W_eff <= 5) ? 1 : 0;   // wider beams: register budget -> two-pass
+  h->fact.lflash = (c.attention == RV_ATT_LUONG && h->opt.flash && W_eff <= 5) ? 1 : 0;   // wider beams: register budget -> two-pass
   // the persistent decode needs neither keys nor the per-step kernels
-  const int persist_att = persist_form(h, greedy, W, Tm);
-  h->lkeys = ((!h->lflash && persist_att < 0) || h->opt_taps) ? 1 : 0;
-  if (h->lkeys) {
+  const int persist_att = sl.persist_att = persist_form(h, greedy, W, Tm, sl.res.labels != nullptr);
+  h->fact.lkeys = ((!h->fact.lflash && persist_att < 0) || h->opt.taps) ? 1 : 0;
+  if (h->fact.lkeys) {
     GemmArgs g{};
     g.A = h->enc_out; g.lda = RV_E; g.Bm = h->W_mem; g.ldb = RV_U; g.C = h->keys; g.ldc = RV_U;
     g.M = B * Tm; g.N = RV_U; g.K = RV_E; g.row_mask = h->mask;
     Scope sc(h, "gemm_keys");
     launch_gemm_f32(g, false, s);
   }
+  return RV_OK;
+}
 
+// A debug-tap buffer of at least `need` floats
+int grow_tap_buffer(RvContext* h, float** buf, size_t* cap, size_t need) {
+  if (need <= *cap) return RV_OK;
+  if (*buf) hipFree(*buf);
+  *buf = nullptr; *cap = 0;
+  for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // captured args hold the old pointer
+  h->graphs.clear();
+  HIPCHK(h, hipMalloc((void**)buf, need * sizeof(float)));
+  *cap = need;
+  return RV_OK;
+}
+
+// Phase 4: the decode's arguments (sl.d) and the debug-tap buffers
+int fill_dec_state(RvContext* h, Slab& sl) {
+  const RvConfig& c = h->cfg;
+  const int B = sl.call.B, W = sl.call.W, L = sl.call.L, Tm = sl.Tm, V = c.vocab, steps = sl.steps;
+  const bool greedy = sl.call.greedy, calls = sl.call.lut != nullptr;
+  hipStream_t s = h->stream;
   // ---- decode loop
-  DecState d = h->dec_st;
+  DecState& d = sl.d;
+  d = h->dec_st;
   d.B = B; d.W = greedy ? 1 : W; d.Tm = Tm; d.V = V; d.L = L;
   d.greedy = greedy; d.attention = c.attention;
-  d.forced = h->lforced;
+  d.forced = sl.res.labels;
   d.start_token = c.start_token; d.end_token = c.end_token; d.pad_token = c.pad_token;
-  d.attend_threads = h->opt_att_nt;
+  d.attend_threads = h->opt.att_nt;
   d.keys = h->keys; d.values = h->enc_out; d.mask = h->mask;
   d.W_att = h->W_att; d.W_fc = h->W_fc; d.b_fc = h->b_fc; d.W_q = h->W_q; d.v_att = h->v_att;
   d.call_bases = nullptr; d.call_probs = nullptr; d.call_len = nullptr;
   if (calls) {
     d.call_bases = h->d_bases; d.call_probs = h->d_probs; d.call_len = h->d_clen;
-    for (int v = 0; v < RV_MAX_VOCAB; ++v) d.lut[v] = v < V ? lut[v] : 0;
+    for (int v = 0; v < RV_MAX_VOCAB; ++v) d.lut[v] = v < V ? sl.call.lut[v] : 0;
   }
-  const int N = B * d.W;
-  if (h->opt_taps) {
-    const size_t need = (size_t)steps * N * Tm;
-    if (need > h->step_align_cap) {
-      if (h->step_align) hipFree(h->step_align);
-      h->step_align = nullptr; h->step_align_cap = 0;
-      for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // captured args hold the old pointer
-      h->graphs.clear();
-      HIPCHK(h, hipMalloc((void**)&h->step_align, need * sizeof(float)));
-      h->step_align_cap = need;
-    }
+  const size_t need = (size_t)steps * B * d.W * Tm;      // alignments of every step
+  if (h->opt.taps) {
+    TRY(grow_tap_buffer(h, &h->step_align, &h->step_align_cap, need));
     d.step_align = h->step_align;
   } else {
     d.step_align = nullptr;
-    if (!greedy && !h->opt_ptaps) d.step_logits = nullptr;
+    if (!greedy && !h->opt.ptaps) d.step_logits = nullptr;
   }
   d.persist_align = nullptr;
-  if (h->opt_ptaps) {
-    const size_t need = (size_t)steps * N * Tm;
-    if (need > h->palign_cap) {
-      if (h->palign) hipFree(h->palign);
-      h->palign = nullptr; h->palign_cap = 0;
-      for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // captured args hold the old pointer
-      h->graphs.clear();
-      HIPCHK(h, hipMalloc((void**)&h->palign, need * sizeof(float)));
-      h->palign_cap = need;
-    }
+  if (h->opt.ptaps) {
+    TRY(grow_tap_buffer(h, &h->palign, &h->palign_cap, need));
     // NaN everywhere first: a step the kernel does not record is never read as a stale value of an earlier call
     if (need) HIPCHK(h, hipMemsetAsync(h->palign, 0xff, need * sizeof(float), s));
     d.persist_align = h->palign;
   }
+  return RV_OK;
+}
 
+// ... then which decode runs (lpersist), its sub-slabs (sl.part, sl.parts) and, for the per-step kernels, their initial state
+int split_decode(RvContext* h, Slab& sl) {
+  const RvConfig& c = h->cfg;
+  const int B = sl.call.B, Tm = sl.Tm, V = c.vocab, steps = sl.steps, persist_att = sl.persist_att;
+  const bool greedy = sl.call.greedy;
+  hipStream_t s = h->stream;
+  DecState& d = sl.d;
+  DecState* part = sl.part;
+  DecParts& parts = sl.parts;
+  int& nsplit = sl.nsplit;
+  const int N = B * d.W;
   // The slab decodes as `nsplit` independent sub-slabs on concurrent streams (inside one hipGraph):
   // while one sub-slab is in its HBM-bound attention sweep another runs its latency-bound cell /
   // output / beam phases.  Chunks never interact, and a sub-slab that finishes early is extended by
   // k_dec_finalize exactly as the reference's whole-slab loop would (beam search only; greedy rows
   // keep sampling after their end token, so greedy decodes as one piece).
-  int nsplit = (greedy || h->opt_taps || B < 64) ? 1 : std::min(std::max(h->opt_split, 1), 4);
+  nsplit = (greedy || h->opt.taps || B < 64) ? 1 : std::min(std::max(h->opt.split, 1), 4);
   d.chunk_steps = nullptr;
   d.persist_att = persist_att;
-  d.Wc16 = h->d_Wc16; d.mx_cdescale = h->mx_cdescale; d.Wl16 = h->d_Wl16; d.mx_ldescale = h->mx_ldescale;
-  d.Wq16 = h->d_Wq16; d.mx_qdescale = h->mx_qdescale; d.W1c16 = h->d_W1c16; d.mx_c1descale = h->mx_c1descale;
-  h->lpersist = persist_att >= 0 ? 1 : 0;
-  h->lmem2_stale = 0;
-  if (h->lpersist) { nsplit = 1; d.chunk_steps = h->d_chunk_steps; }
-  h->lsplit = nsplit;
-  if (!h->lpersist) {
+  d.Wc16 = h->img.Wc16; d.mx_cdescale = h->mx_cdescale; d.Wl16 = h->img.Wl16; d.mx_ldescale = h->mx_ldescale;
+  d.Wq16 = h->img.Wq16; d.mx_qdescale = h->mx_qdescale; d.W1c16 = h->img.W1c16; d.mx_c1descale = h->mx_c1descale;
+  h->fact.lpersist = persist_att >= 0 ? 1 : 0;
+  h->fact.lmem2_stale = 0;
+  if (h->fact.lpersist) { nsplit = 1; d.chunk_steps = h->d_chunk_steps; }
+  h->fact.lsplit = nsplit;
+  if (!h->fact.lpersist) {
     for (int k = 0; k < d.depth; ++k) {     // get_initial_state: all zeros (basecaller.py:305); the persistent kernel keeps state in LDS
       HIPCHK(h, hipMemsetAsync(d.xh + k * d.ls_xh, 0, sizeof(float) * N * RV_E, s));
       HIPCHK(h, hipMemsetAsync(d.c + k * d.ls_c, 0, sizeof(float) * N * RV_U, s));
     }
   }
   const int Wd = d.W;
-  DecState part[4];
-  DecParts parts{};
+  parts = DecParts{};
   parts.n = nsplit; parts.steps = steps; parts.S_dev = d.S_dev; parts.S_host = d.S_host;
   for (int g = 0; g < nsplit; ++g) {
     const size_t b0 = (size_t)B * g / nsplit, b1 = (size_t)B * (g + 1) / nsplit;
@@ -752,47 +861,77 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     if (p.persist_align) p.persist_align += (size_t)steps * Wd * Tm * b0;
     p.nfin = d.nfin + g * (c.max_output_len + 1);
     parts.nfin[g] = p.nfin; parts.B[g] = p.B;
-    if (!h->lpersist) launch_dec_init(p, s);
+    if (!h->fact.lpersist) launch_dec_init(p, s);
   }
-  auto enqueue_steps = [&](bool profiled, FormLog* log) -> int {
-    for (int g = 1; g < nsplit; ++g) {
-      HIPCHK(h, hipEventRecord(h->ev_fork, s));
-      HIPCHK(h, hipStreamWaitEvent(side_stream(h, g - 1), h->ev_fork, 0));
-    }
-    for (int g = 0; g < nsplit; ++g) launch_decode_steps(h, part[g], g == 0 ? s : side_stream(h, g - 1), profiled && nsplit == 1, log);
-    for (int g = 1; g < nsplit; ++g) {
-      HIPCHK(h, hipEventRecord(h->ev_join[g - 1], side_stream(h, g - 1)));
-      HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[g - 1], 0));
-    }
-    return RV_OK;
-  };
-  if (h->lpersist) {
-    part[0] = d; part[0].part = 0; parts.n = 1;
-    if (greedy) HIPCHK(h, hipMemsetAsync(d.nfin, 0, 2 * sizeof(int), s));   // chunks-finished count and latest first-finish step
-    // The default form (Luong, one cell, everything on the matrix pipe) takes enc_out and projects each chunk's rows in its own
-    // prologue, with the split GEMM's arithmetic (decode.hip, persist_project_memory); every other form reads the GEMM's mem2
-    const bool fused_mem = h->opt_fused_mem && h->opt_split_proj && persist_att == 3 && d.depth == 1;
-    h->lmem2_stale = fused_mem && !h->opt_ptaps;
-    d.enc_rows = nullptr; d.Wmp16 = h->d_Wmp16; d.Wkp16 = h->d_Wkp16; d.mem_tap = nullptr;
-    if (fused_mem) {
-      d.enc_rows = h->enc_out; d.mem_tap = h->opt_ptaps ? h->mem2 : nullptr;
-    } else {   // attention memory in the form the persistent decode keeps on chip: [keys | U'] = enc_out . [W_mem | A_c]
-      GemmArgs g{};
-      g.A = h->enc_out; g.lda = RV_E; g.Bm = h->d_Wmp; g.ldb = RV_E; g.C = h->mem2; g.ldc = RV_E;
-      g.M = B * Tm; g.N = RV_E; g.K = RV_E;
-      g.xcd_remap = 1;
-      Scope sc(h, "gemm_memory");
-      if (h->opt_split_proj) launch_gemm_mem_split(h->enc_out, B * Tm, h->d_Wmp16, h->mem2, s);
-      else launch_gemm_f32(g, false, s);
-    }
-    d.values = h->mem2; part[0].values = h->mem2;
-    d.mx_kscale = h->mx_kscale; d.mx_kdescale = std::ldexp(1.0f, -14) / h->mx_kscale;
-    d.mx_uscale = h->mx_uscale; d.mx_udescale = std::ldexp(1.0f, -14) / h->mx_uscale;
-    Scope sc(h, "dec_persist", nullptr, true);
-    launch_dec_persist(d, d.depth > 1 ? h->dec[0].W + (size_t)V * RV_G : h->d_Wcat2, h->dec[0].W, h->dec[0].b,
-                       d.depth > 1 ? h->dec[1].W : nullptr, d.depth > 1 ? h->dec[1].b : nullptr, h->d_Nh, s, &h->lforms);
-  } else if (h->opt_graph && h->opt_profile != 2 && !d.forced) {      // (a forced decode launches its steps without replay: the label pointer is no part of the key)
-    GraphKey key{B, d.W, Tm, L, greedy ? 1 : 0, h->opt_taps * 2 + h->lflash + 4 * h->opt_att_nt + 4096 * (d.step_logits ? 1 : 0) + 8192 * (d.persist_align ? 1 : 0), nsplit};   // every captured pointer that can change is in the key
+  return RV_OK;
+}
+
+// Phase 5: the persistent decode -- the whole loop in one launch, behind the projection of its attention memory where it does not project its own
+int decode_persist(RvContext* h, Slab& sl) {
+  const int B = sl.call.B, Tm = sl.Tm, V = h->cfg.vocab, persist_att = sl.persist_att;
+  const bool greedy = sl.call.greedy;
+  hipStream_t s = h->stream;
+  DecState& d = sl.d;
+  DecState* part = sl.part;
+  DecParts& parts = sl.parts;
+  part[0] = d; part[0].part = 0; parts.n = 1;
+  if (greedy) HIPCHK(h, hipMemsetAsync(d.nfin, 0, 2 * sizeof(int), s));   // chunks-finished count and latest first-finish step
+  // The default form (Luong, one cell, everything on the matrix pipe) takes enc_out and projects each chunk's rows in its own
+  // prologue, with the split GEMM's arithmetic (decode.hip, persist_project_memory); every other form reads the GEMM's mem2
+  const bool fused_mem = h->opt.fused_mem && h->opt.split_proj && persist_att == 3 && d.depth == 1;
+  h->fact.lmem2_stale = fused_mem && !h->opt.ptaps;
+  d.enc_rows = nullptr; d.Wmp16 = h->img.Wmp16; d.Wkp16 = h->img.Wkp16; d.mem_tap = nullptr;
+  if (fused_mem) {
+    d.enc_rows = h->enc_out; d.mem_tap = h->opt.ptaps ? h->mem2 : nullptr;
+  } else {   // attention memory in the form the persistent decode keeps on chip: [keys | U'] = enc_out . [W_mem | A_c]
+    GemmArgs g{};
+    g.A = h->enc_out; g.lda = RV_E; g.Bm = h->img.Wmp; g.ldb = RV_E; g.C = h->mem2; g.ldc = RV_E;
+    g.M = B * Tm; g.N = RV_E; g.K = RV_E;
+    g.xcd_remap = 1;
+    Scope sc(h, "gemm_memory");
+    if (h->opt.split_proj) launch_gemm_mem_split(h->enc_out, B * Tm, h->img.Wmp16, h->mem2, s);
+    else launch_gemm_f32(g, false, s);
+  }
+  d.values = h->mem2; part[0].values = h->mem2;
+  d.mx_kscale = h->mx_kscale; d.mx_kdescale = std::ldexp(1.0f, -14) / h->mx_kscale;
+  d.mx_uscale = h->mx_uscale; d.mx_udescale = std::ldexp(1.0f, -14) / h->mx_uscale;
+  Scope sc(h, "dec_persist", nullptr, true);
+  launch_dec_persist(d, d.depth > 1 ? h->dec[0].W + (size_t)V * RV_G : h->img.Wcat2, h->dec[0].W, h->dec[0].b,
+                     d.depth > 1 ? h->dec[1].W : nullptr, d.depth > 1 ? h->dec[1].b : nullptr, h->img.Nh, s, &h->lforms);
+  return RV_OK;
+}
+
+// The per-step launches of every sub-slab: part 0 on the context's stream, the others forked onto side streams and joined again
+int fork_decode_steps(RvContext* h, const Slab& sl, bool profiled, FormLog* log) {
+  const int nsplit = sl.nsplit;
+  hipStream_t s = h->stream;
+  for (int g = 1; g < nsplit; ++g) {
+    HIPCHK(h, hipEventRecord(h->ev_fork, s));
+    HIPCHK(h, hipStreamWaitEvent(side_stream(h, g - 1), h->ev_fork, 0));
+  }
+  for (int g = 0; g < nsplit; ++g) launch_decode_steps(h, sl.part[g], g == 0 ? s : side_stream(h, g - 1), profiled && nsplit == 1, log);
+  for (int g = 1; g < nsplit; ++g) {
+    HIPCHK(h, hipEventRecord(h->ev_join[g - 1], side_stream(h, g - 1)));
+    HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[g - 1], 0));
+  }
+  return RV_OK;
+}
+
+// FormLog::merge (inline, common.h) has always left this file out of line, and so among the library's dynamic symbols: the list stays
+// what it was whatever the inliner makes of the one call below
+[[gnu::used]] void (FormLog::*const formlog_merge_out_of_line)(const FormLog&) = &FormLog::merge;
+
+// Phase 6: the per-step decode -- a replay of the decode graph of this shape (captured on its first use), or direct launches
+int decode_steps(RvContext* h, Slab& sl) {
+  const int B = sl.call.B, L = sl.call.L, Tm = sl.Tm;
+  const bool greedy = sl.call.greedy;
+  hipStream_t s = h->stream;
+  DecState& d = sl.d;
+  DecState* part = sl.part;
+  DecParts& parts = sl.parts;
+  int& nsplit = sl.nsplit;
+  if (h->opt.graph && h->opt.profile != 2 && !d.forced) {      // (a forced decode launches its steps without replay: the label pointer is no part of the key)
+    GraphKey key{B, d.W, Tm, L, greedy ? 1 : 0, h->opt.taps * 2 + h->fact.lflash + 4 * h->opt.att_nt + 4096 * (d.step_logits ? 1 : 0) + 8192 * (d.persist_align ? 1 : 0), nsplit};   // every captured pointer that can change is in the key
     auto it = h->graphs.find(key);
     if (it == h->graphs.end()) {
       if (h->graphs.size() >= 32) {      // bound the cache (callers with ever-changing slab shapes)
@@ -804,7 +943,7 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
       gforms.n = 0; gforms.full = false;
       hipGraph_t graph = nullptr;
       HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      const int rc = enqueue_steps(false, &gforms);
+      const int rc = fork_decode_steps(h, sl, false, &gforms);
       hipError_t ce = hipStreamEndCapture(s, &graph);
       if (rc != RV_OK) return rc;
       HIPCHK(h, ce);
@@ -817,42 +956,59 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     Scope sc(h, "decode_graph", nullptr, true);
     HIPCHK(h, hipGraphLaunch(it->second, s));
   } else {
-    if (h->opt_profile == 2) nsplit = 1, parts.n = 1;     // per-kernel events need one stream
+    if (h->opt.profile == 2) nsplit = 1, parts.n = 1;     // per-kernel events need one stream
     if (nsplit == 1) { part[0] = d; part[0].part = 0; part[0].nfin = d.nfin; parts.nfin[0] = d.nfin; parts.B[0] = B; launch_dec_init(part[0], s); }
-    const int rc = enqueue_steps(h->opt_profile == 2, &h->lforms);
-    if (rc != RV_OK) return rc;
+    TRY(fork_decode_steps(h, sl, h->opt.profile == 2, &h->lforms));
   }
+  return RV_OK;
+}
 
-  if (h->all_beams) {      // the whole beam: k_dec_finalize_beams in k_dec_finalize's place (never a group, never captured)
-    Scope sc(h, "dec_finalize_beams");
-    if (!h->lpersist) launch_dec_reduce_steps(parts, s);
+// Phase 7: the outputs of every sub-slab from its beam records (k_dec_finalize, or k_dec_finalize_beams for the whole beam: never a
+// group, never captured), then the scores of a forced decode
+int finalize_and_score(RvContext* h, const Slab& sl) {
+  const RvConfig& c = h->cfg;
+  const int B = sl.call.B, L = sl.call.L, V = c.vocab, steps = sl.steps, Wd = sl.d.W;
+  const bool greedy = sl.call.greedy;
+  int32_t* tk = sl.call.tokens;
+  float* o2 = sl.call.out2;
+  hipStream_t s = h->stream;
+  const DecState& d = sl.d;
+  const DecParts& parts = sl.parts;
+  {
+    Scope sc(h, sl.res.whole_beam ? "dec_finalize_beams" : "dec_finalize");
+    if (!h->fact.lpersist) launch_dec_reduce_steps(parts, s);
     for (int g = 0; g < parts.n; ++g) {
-      const size_t b0 = parts.n == 1 ? 0 : (size_t)B * g / parts.n;
-      BeamsOut o = h->lbeams;
-      o.tokens += b0 * steps * Wd; o.scores += b0 * steps * Wd;
-      if (o.path_scores) o.path_scores += b0 * steps * Wd;
-      if (o.log_probs) o.log_probs += b0 * Wd;
-      if (o.lengths) o.lengths += b0 * Wd;
-      launch_dec_finalize_beams(part[g], o, s);
-    }
-  } else {
-    Scope sc(h, "dec_finalize");
-    if (!h->lpersist) launch_dec_reduce_steps(parts, s);
-    for (int g = 0; g < parts.n; ++g) {
-      const size_t b0 = parts.n == 1 ? 0 : (size_t)B * g / parts.n;
-      launch_dec_finalize(part[g], tk + b0 * steps, o2 + b0 * steps * (greedy ? V : 1), s, ptab,      // (ptab: persistent decode only, one part)
-                          h->lpersist && h->lmem.n ? &h->lmem : nullptr);
+      const size_t b0 = parts.n == 1 ? 0 : (size_t)B * g / parts.n;      // the sub-slab's first chunk
+      if (sl.res.whole_beam) {
+        BeamsOut o = sl.res.beams;
+        o.tokens += b0 * steps * Wd; o.scores += b0 * steps * Wd;
+        if (o.path_scores) o.path_scores += b0 * steps * Wd;
+        if (o.log_probs) o.log_probs += b0 * Wd;
+        if (o.lengths) o.lengths += b0 * Wd;
+        launch_dec_finalize_beams(sl.part[g], o, s);
+      } else {
+        launch_dec_finalize(sl.part[g], tk + b0 * steps, o2 + b0 * steps * (greedy ? V : 1), s, sl.ptab,      // (ptab: persistent decode only, one part)
+                            h->fact.lpersist ? sl.res.members : nullptr);
+      }
     }
   }
   if (d.forced) {      // the forced decode's labels target[:, 1:] against the logits the finalize kernel just wrote
-    ScoreArgs a = h->lscore;
+    ScoreArgs a = sl.res.score;
     a.logits = o2; a.labels = d.forced + 1; a.label_stride = L; a.B = B; a.S = steps; a.V = V; a.pad_token = c.pad_token; a.pred = nullptr;
     Scope sc(h, "score_tokens");
     launch_score_tokens(a, s);
   }
+  return RV_OK;
+}
+
+// Phase 8: the results of a host caller, device -> pinned staging
+int stage_outputs(RvContext* h, const Slab& sl) {
+  const int B = sl.call.B, V = h->cfg.vocab, steps = sl.steps, Wd = sl.d.W;
+  const bool greedy = sl.call.greedy, dev_out = sl.call.dev_out, calls = sl.call.lut != nullptr;
+  hipStream_t s = h->stream;
   // (S reaches the host through d.S_host: the finalize / reduce kernel stores it straight into the mapped pinned word)
-  if (h->all_beams && !dev_out) {
-    const BeamsOut &o = h->lbeams, &p = h->pin_beams;
+  if (sl.res.whole_beam && !dev_out) {
+    const BeamsOut &o = sl.res.beams, &p = h->pin_beams;
     const size_t n = (size_t)B * steps * Wd, nb = (size_t)B * Wd;
     HIPCHK(h, hipMemcpyAsync(p.tokens, o.tokens, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(p.scores, o.scores, sizeof(float) * n, hipMemcpyDeviceToHost, s));
@@ -860,15 +1016,30 @@ int record_slab(RvContext* h, const float* xr, const float* xe, bool host_in, in
     if (o.log_probs) HIPCHK(h, hipMemcpyAsync(p.log_probs, o.log_probs, sizeof(float) * nb, hipMemcpyDeviceToHost, s));
     if (o.lengths) HIPCHK(h, hipMemcpyAsync(p.lengths, o.lengths, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, s));
   } else if (!dev_out && !calls) {
-    HIPCHK(h, hipMemcpyAsync(h->pin_tok, tk, sizeof(int32_t) * B * steps, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(h->pin_out2, o2, sizeof(float) * B * steps * (greedy ? V : 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(h->pin_tok, sl.call.tokens, sizeof(int32_t) * B * steps, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(h->pin_out2, sl.call.out2, sizeof(float) * B * steps * (greedy ? V : 1), hipMemcpyDeviceToHost, s));
   }
   if (calls) {
     HIPCHK(h, hipMemcpyAsync(h->pin_bases, h->d_bases, (size_t)B * steps, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(h->pin_probs, h->d_probs, sizeof(float) * B * steps, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(h->pin_clen, h->d_clen, sizeof(int) * B, hipMemcpyDeviceToHost, s));
   }
-  h->lW = d.W;
+  return RV_OK;
+}
+
+// The stream work of one slab, in order: input copies, encoders, memory set-up, decode, finalize, output copies.  `ptab` non-null =
+// the call is being captured into a slab graph: kernels that touch caller memory read its address from the table.
+int record_slab(RvContext* h, const Call& call, const CallParts& res, const void* const* ptab) {
+  Slab sl{call, res, ptab, call.T_r + call.T_e, call.L - 1};
+  TRY(stage_inputs(h, sl));
+  TRY(record_encoders(h, sl));
+  TRY(record_keys(h, sl));
+  TRY(fill_dec_state(h, sl));
+  TRY(split_decode(h, sl));
+  TRY(h->fact.lpersist ? decode_persist(h, sl) : decode_steps(h, sl));
+  TRY(finalize_and_score(h, sl));
+  TRY(stage_outputs(h, sl));
+  h->fact.lW = sl.d.W;
   return RV_OK;
 }
 
@@ -934,10 +1105,8 @@ int ensure_beam_buffers(RvContext* h) {
   HIPCHK(h, hipSetDevice(c.device));
   BeamsOut& d = h->d_beams;
   BeamsOut& p = h->pin_beams;
-#define TRY(x) do { int r_ = (x); if (r_ != RV_OK) return r_; } while (0)
   TRY(dalloc(h, &d.tokens, n)); TRY(dalloc(h, &d.scores, n)); TRY(dalloc(h, &d.path_scores, n));
   TRY(dalloc(h, &d.log_probs, nb)); TRY(dalloc(h, &d.lengths, nb));
-#undef TRY
   HIPCHK(h, hipHostMalloc((void**)&p.scores, n * sizeof(float), hipHostMallocDefault));
   HIPCHK(h, hipHostMalloc((void**)&p.path_scores, n * sizeof(float), hipHostMallocDefault));
   HIPCHK(h, hipHostMalloc((void**)&p.log_probs, nb * sizeof(float), hipHostMallocDefault));
@@ -946,25 +1115,22 @@ int ensure_beam_buffers(RvContext* h) {
   return RV_OK;
 }
 
-// Before enqueue() of an all-beams call on `ctx`: where its finalize kernel writes.  `ab` null = every output, to the context's
+// Before enqueue() of an all-beams call on `ctx`: where its finalize kernel writes.  call.beams null = every output, to the context's
 // own buffers (an asynchronous call with host outputs: what is asked for is known at its collect); dev_out = the caller's addresses
-int begin_all_beams(RvContext* ctx, const RvBeams* ab, bool dev_out) {
-  if (dev_out) {
-    ctx->lbeams = BeamsOut{ab->tokens, ab->scores, ab->path_scores, ab->log_probs, ab->lengths};
+int begin_all_beams(RvContext* ctx, const Call& call, CallParts& res) {
+  const RvBeams* ab = call.beams;
+  if (call.dev_out) {
+    res.beams = BeamsOut{ab->tokens, ab->scores, ab->path_scores, ab->log_probs, ab->lengths};
   } else {
-    const int rc = ensure_beam_buffers(ctx);
-    if (rc != RV_OK) return rc;
-    ctx->lbeams = ctx->d_beams;
-    if (ab && !ab->path_scores) ctx->lbeams.path_scores = nullptr;
-    if (ab && !ab->log_probs) ctx->lbeams.log_probs = nullptr;
-    if (ab && !ab->lengths) ctx->lbeams.lengths = nullptr;
+    TRY(ensure_beam_buffers(ctx));
+    res.beams = ctx->d_beams;
+    if (ab && !ab->path_scores) res.beams.path_scores = nullptr;
+    if (ab && !ab->log_probs) res.beams.log_probs = nullptr;
+    if (ab && !ab->lengths) res.beams.lengths = nullptr;
   }
-  ctx->all_beams = true;
+  res.whole_beam = true;
   return RV_OK;
 }
-
-// The labels and score outputs of a forced decode (rv_teacher_forced*) or of rv_score_logits
-struct ForcedCall { const int32_t* targets; uint32_t omit_mask; const RvScore* out; };
 
 // Labels and score outputs of a context on the device, for the host variants of rv_teacher_forced and for rv_score_logits
 int ensure_score_buffers(RvContext* h) {
@@ -972,26 +1138,24 @@ int ensure_score_buffers(RvContext* h) {
   const RvConfig& c = h->cfg;
   const size_t n = (size_t)c.max_batch * c.max_output_len, nb = (size_t)c.max_batch;
   HIPCHK(h, hipSetDevice(c.device));
-#define TRY(x) do { int r_ = (x); if (r_ != RV_OK) return r_; } while (0)
   TRY(dalloc(h, &h->d_forced, n)); TRY(dalloc(h, &h->d_sc_nll, n)); TRY(dalloc(h, &h->d_sc_sum, nb));
   TRY(dalloc(h, &h->d_sc_cnt, 3 * nb));      // (last: its address says the set is complete)
-#undef TRY
   return RV_OK;
 }
 
 // Where a call's k_score_tokens writes: the caller's device addresses, or the context's buffers for the outputs a host caller asked for
-void set_score_outputs(RvContext* ctx, const ForcedCall* fc, bool dev_out) {
+ScoreArgs score_outputs(const RvContext* ctx, const ForcedCall* fc, bool dev_out) {
   const RvScore none{};
   const RvScore& o = fc->out ? *fc->out : none;
   const size_t nb = (size_t)ctx->cfg.max_batch;
-  ScoreArgs& a = ctx->lscore;
-  a = ScoreArgs{};
+  ScoreArgs a{};
   a.omit_mask = fc->omit_mask;
   a.nll = dev_out ? o.nll : (o.nll ? ctx->d_sc_nll : nullptr);
   a.nll_sum = dev_out ? o.nll_sum : (o.nll_sum ? ctx->d_sc_sum : nullptr);
   a.n_labels = dev_out ? o.n_labels : (o.n_labels ? ctx->d_sc_cnt : nullptr);
   a.n_match = dev_out ? o.n_match : (o.n_match ? ctx->d_sc_cnt + nb : nullptr);
   a.n_counted = dev_out ? o.n_counted : (o.n_counted ? ctx->d_sc_cnt + 2 * nb : nullptr);
+  return a;
 }
 
 // ids [n] all inside [0, vocab)?  (host labels: an id never reaches a kernel unchecked)
@@ -1004,26 +1168,30 @@ int check_token_ids(RvContext* h, const int32_t* ids, size_t n, int row_len, con
 }
 
 // Before enqueue() of a forced decode on the idle context `ctx`: the call's own checks, then its labels and score outputs
-int begin_forced(RvContext* ctx, const ForcedCall* fc, const float* raw, const float* ev, bool dev, int B, int T_r, int T_e, int L,
-                 const int32_t* tokens, const float* out2) {
-  { const int rc = validate_call(ctx, raw, ev, B, T_r, T_e, 1, L, tokens, out2, dev); if (rc != RV_OK) return rc; }
+int begin_forced(RvContext* ctx, const Call& call, CallParts& res) {
+  const ForcedCall* fc = call.forced;
+  const int B = call.B, L = call.L;
+  const bool dev = call.dev_in;      // (a forced decode's buffers are all the host's or all the device's)
+  Call one = call, ok;
+  one.W = 1;
+  TRY(validate_call(ctx, one, ok));
   if (B > 0 && !fc->targets) return fail(ctx, RV_EINVAL, "null target pointer");
   if (dev) {
-    ctx->lforced = fc->targets;
+    res.labels = fc->targets;
   } else {
-    { const int rc = check_token_ids(ctx, fc->targets, (size_t)B * L, L, "target"); if (rc != RV_OK) return rc; }
-    { const int rc = ensure_score_buffers(ctx); if (rc != RV_OK) return rc; }
+    TRY(check_token_ids(ctx, fc->targets, (size_t)B * L, L, "target"));
+    TRY(ensure_score_buffers(ctx));
     if (B > 0) HIPCHK(ctx, hipMemcpy(ctx->d_forced, fc->targets, sizeof(int32_t) * (size_t)B * L, hipMemcpyHostToDevice));
-    ctx->lforced = ctx->d_forced;
+    res.labels = ctx->d_forced;
   }
-  set_score_outputs(ctx, fc, dev);
+  res.score = score_outputs(ctx, fc, dev);
   return RV_OK;
 }
 
-// After the stream of `ctx` has drained: the scores of B chunks x S positions to a host caller's buffers (zeros when nothing was launched)
-int fetch_scores(RvContext* ctx, const RvScore* out, bool dev_out, int B, int S) {
+// After the stream of `ctx` has drained: the scores of B chunks x S positions (k_score_tokens wrote them through `a`) to a host
+// caller's buffers (zeros when nothing was launched)
+int fetch_scores(RvContext* ctx, const ScoreArgs& a, const RvScore* out, bool dev_out, int B, int S) {
   if (!out || B <= 0) return RV_OK;
-  const ScoreArgs& a = ctx->lscore;
   const size_t nb = (size_t)B, n = nb * (size_t)std::max(S, 0);
   if (S <= 0) {      // nothing ran: every per-chunk sum is zero
     if (dev_out) {
@@ -1050,7 +1218,7 @@ int sync_context(RvContext* h, RvContext** out) {
       // call is refused, touching nothing (the handle's own context is idle then, but the contract does not depend on the path)
     bool ticks_out = false;
     for (const auto& t : h->ticks) ticks_out = ticks_out || t.busy;
-    if (ticks_out && uncollected(h) >= std::min(std::max(h->opt_async_depth, 1), RV_MAX_ASYNC))
+    if (ticks_out && uncollected(h) >= async_depth(h))
       return fail(h, RV_ESTATE, "every slab context of this handle holds an uncollected asynchronous call: collect one before a synchronous call");
   }
   flush_open_group(h);      // (a group still filling goes first; a failure there is its tickets')
@@ -1059,7 +1227,7 @@ int sync_context(RvContext* h, RvContext** out) {
   // Debug taps and rv_get_tensor belong to the handle's own context, so with taps on that context must be the idle one.
   RvContext* ctx = h;
   if (h->pend.busy) {
-    if (h->opt_taps || h->opt_ptaps)
+    if (h->opt.taps || h->opt.ptaps)
       return fail(h, RV_ESTATE, "debug taps need the handle's own context, which holds an uncollected asynchronous call: collect ticket %d first", h->pend.ticket);
     ctx = nullptr;
     for (RvContext* k : h->kids) if (!k->pend.busy) { ctx = k; break; }
@@ -1071,28 +1239,24 @@ int sync_context(RvContext* h, RvContext** out) {
   return RV_OK;
 }
 
-int run(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W,
-        int L, bool greedy, int32_t* tokens, float* out2, bool dev_out, int32_t* S_out, const CallsOut* calls = nullptr,
-        const RvBeams* ab = nullptr, const ForcedCall* fc = nullptr) {
+// A synchronous call: what a kind of call adds to the plain one is resolved into `res`, which lives in this frame until the call is done
+int run(RvContext* h, const Call& call, int32_t* S_out) {
   if (!h) return RV_EINVAL;
-  if (!S_out || (B > 0 && L > 1 && !calls && (!tokens || !out2))) return fail(h, RV_EINVAL, "null output pointer");
+  const CallsOut* calls = call.calls;
+  if (!S_out || (call.B > 0 && call.L > 1 && !calls && (!call.tokens || !call.out2))) return fail(h, RV_EINVAL, "null output pointer");
   if (calls && (!calls->lut || !calls->bases || !calls->lengths || !calls->probs)) return fail(h, RV_EINVAL, "null calls output pointer");
   *S_out = 0;
   RvContext* ctx = nullptr;
-  { const int rc = sync_context(h, &ctx); if (rc != RV_OK) return rc; }
-  if (ab) { const int rb = begin_all_beams(ctx, ab, dev_out); if (rb != RV_OK) { if (ctx != h) h->err = ctx->err; return rb; } }
-  if (fc) {
-    const int rb = begin_forced(ctx, fc, raw, ev, dev_in, B, T_r, T_e, L, tokens, out2);
-    if (rb != RV_OK) { ctx->lforced = nullptr; if (ctx != h) h->err = ctx->err; return rb; }
-  }
-  const int rc = enqueue(ctx, raw, ev, dev_in, B, T_r, T_e, W, L, greedy, tokens, out2, dev_out, calls ? calls->lut : nullptr);
-  ctx->all_beams = false;
-  ctx->lforced = nullptr;
-  if (rc != RV_OK) { ctx->pend.busy = false; if (ctx != h) h->err = ctx->err; return rc; }   // (ctx was idle on entry: the flag is this call's)
-  int rf = finish(ctx, tokens, out2, calls, S_out, ab);
-  if (fc && rf == RV_OK) rf = fetch_scores(ctx, fc->out, dev_out, B, L - 1);
-  if (ctx != h) { if (rf != RV_OK) h->err = ctx->err; h->lS = ctx->lS; }
-  return rf;
+  TRY(sync_context(h, &ctx));
+  CallParts res;
+  if (call.whole_beam) { const int rb = begin_all_beams(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
+  if (call.forced) { const int rb = begin_forced(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
+  const int rc = enqueue(ctx, call, res);
+  if (rc != RV_OK) { ctx->pend.busy = false; return relay(h, ctx, rc); }   // (ctx was idle on entry: the flag is this call's)
+  int rf = finish(ctx, call.tokens, call.out2, calls, S_out, call.beams);
+  if (call.forced && rf == RV_OK) rf = fetch_scores(ctx, res.score, call.forced->out, call.dev_out, call.B, call.L - 1);
+  if (ctx != h) h->lS = ctx->lS;
+  return relay(h, ctx, rf);
 }
 
 
@@ -1100,8 +1264,6 @@ int run(RvContext* h, const float* raw, const float* ev, bool dev_in, int B, int
 // (child contexts of the asynchronous calls share their parent's).
 int alloc_slab_buffers(RvContext* h) {
   const RvConfig& c = h->cfg;
-#define TRY(x) do { int r_ = (x); if (r_ != RV_OK) return r_; } while (0)
-#define HIPTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(h, RV_EHIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
   const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
   const size_t B = c.max_batch, Tr = use_raw ? c.max_raw_len : 0, Te = use_ev ? c.max_event_len : 0;
   const size_t Tm = Tr + Te, L = c.max_output_len, N = B * c.max_beam, V = c.vocab;
@@ -1152,7 +1314,7 @@ int alloc_slab_buffers(RvContext* h) {
   //  stream of the process competes for the same few hardware queues)
   for (int g = 0; g < 3; ++g) HIPTRY(hipEventCreateWithFlags(&h->ev_join[g], hipEventDisableTiming));
   HIPTRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-  if (const char* e = getenv("RV_DECODE_SPLIT")) h->opt_split = atoi(e);
+  if (const char* e = getenv("RV_DECODE_SPLIT")) h->opt.split = atoi(e);
   TRY(dalloc(h, &h->out_tokens, B * L));
   TRY(dalloc(h, &h->out2, B * L * V));
   HIPTRY(hipHostMalloc((void**)&h->pin_raw, std::max<size_t>(B * Tr, 1) * sizeof(float), hipHostMallocDefault));
@@ -1171,8 +1333,6 @@ int alloc_slab_buffers(RvContext* h) {
   // (a device copy refreshed by a memcpy node in front of the graph measured the same, and is one node more)
   HIPTRY(hipHostMalloc((void**)&h->pin_ptab, sizeof(void*) * RV_PTAB_N, hipHostMallocMapped));
   HIPTRY(hipHostGetDevicePointer((void**)&h->d_ptab, h->pin_ptab, 0));
-#undef TRY
-#undef HIPTRY
   return RV_OK;
 }
 
@@ -1186,10 +1346,7 @@ int create_child(RvContext* p, RvContext** out, int slabs = 1) {
   //  no gain at the driver's 20 steps and 4 % less once the stream has settled: tools/stream_ab.py, round 4)
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return fail(p, RV_EHIP, "hipStreamCreate failed for an asynchronous context"); }
   h->d_w = p->d_w; h->n_w = p->n_w;
-  h->d_WmemT = p->d_WmemT; h->d_Up = p->d_Up; h->d_Wp = p->d_Wp; h->d_Wsb = p->d_Wsb; h->d_Wh = p->d_Wh; h->d_Ua = p->d_Ua;
-  h->d_Wx16 = p->d_Wx16; h->d_bx2 = p->d_bx2; h->d_Wmp = p->d_Wmp; h->d_Wcat2 = p->d_Wcat2; h->d_Nh = p->d_Nh; h->d_Wmp16 = p->d_Wmp16; h->d_Wkp16 = p->d_Wkp16; h->d_Wc16 = p->d_Wc16; h->d_Wl16 = p->d_Wl16;
-  h->d_Wq16 = p->d_Wq16; h->d_W1c16 = p->d_W1c16;
-  h->d_WcatT = p->d_WcatT;
+  h->img = p->img;
   bind_weights(h);
   const int rc = alloc_slab_buffers(h);
   if (rc != RV_OK) { p->err = h->err; rv_destroy(h); return rc; }
@@ -1200,17 +1357,16 @@ int create_child(RvContext* p, RvContext** out, int slabs = 1) {
 // options and weight-derived scalars of the parent, as of now
 void sync_child(RvContext* k, const RvContext* p) {
   k->loaded = p->loaded; k->mx_kscale = p->mx_kscale; k->mx_uscale = p->mx_uscale;
-  k->opt_split = p->opt_split; k->opt_att_nt = p->opt_att_nt; k->opt_side_ev = p->opt_side_ev; k->opt_lane_inproj = p->opt_lane_inproj; k->opt_persist = p->opt_persist;
-  k->opt_flash = p->opt_flash; k->opt_split_proj = p->opt_split_proj; k->opt_mx_att = p->opt_mx_att; k->opt_mx_cell = p->opt_mx_cell; k->mx_cdescale = p->mx_cdescale; k->mx_ldescale = p->mx_ldescale; k->opt_tail_wave = p->opt_tail_wave;
-  k->mx_qdescale = p->mx_qdescale; k->mx_c1descale = p->mx_c1descale;
-  k->opt_fuse = p->opt_fuse; k->opt_fused_mem = p->opt_fused_mem; k->opt_wide = p->opt_wide; k->opt_graph = p->opt_graph; k->opt_profile = p->opt_profile;
-  k->opt_taps = 0; k->opt_ptaps = 0;      // debug taps belong to the synchronous calls
+  k->mx_cdescale = p->mx_cdescale; k->mx_ldescale = p->mx_ldescale; k->mx_qdescale = p->mx_qdescale; k->mx_c1descale = p->mx_c1descale;
+  k->opt = p->opt;
+  k->opt.taps = 0; k->opt.ptaps = 0;      // debug taps belong to the synchronous calls
   k->inflight_hint = p->inflight_hint;
 }
 
 // ---- coalesced asynchronous calls
-int hw_queues() {       // what the runtime was (or will be) started with: rv_set_option("async_depth") warns from the same reading
+int hw_queues(const char** text = nullptr) {       // what the runtime was (or will be) started with (*text: as the environment words it, null = unset)
   const char* q = getenv("GPU_MAX_HW_QUEUES");
+  if (text) *text = q;
   const int nq = q ? atoi(q) : 4;
   return nq > 0 ? nq : 4;
 }
@@ -1220,7 +1376,7 @@ int hw_queues() {       // what the runtime was (or will be) started with: rv_se
 // coalesces only where the contexts outnumber the hardware queues -- with a queue per context the slabs overlap by themselves
 // (profiles/coalesce.md has the sweep behind the numbers).
 int coalesce_n(const RvContext* h, int depth) {
-  if (h->opt_coalesce >= 0) return std::max(1, std::min({h->opt_coalesce, depth, RV_MAX_MEMBERS}));
+  if (h->opt.coalesce >= 0) return std::max(1, std::min({h->opt.coalesce, depth, RV_MAX_MEMBERS}));
   if (depth <= 3 || hw_queues() >= depth) return 1;
   return depth < 8 ? 2 : std::min(depth / 2, 5);      // (C3 on 4 queues: depth 4 and 6 stream fastest with 2, depth 10 with 5)
 }
@@ -1233,9 +1389,9 @@ int uncollected(const RvContext* h) {
 }
 
 // Does this (validated) slab take the default streamed path, the only one that is coalesced?
-bool coalescible(const RvContext* h, int B, int T_r, int T_e, int W, int L) {
-  if (h->opt_profile != 0 || h->opt_taps || h->opt_ptaps || h->rec_ts || h->dec_st.dbg_ts || h->opt_slab_graph || L <= 1) return false;
-  return wide_recurrence(h, B, T_r) && persist_form(h, false, W, T_r + T_e) >= 0;
+bool coalescible(const RvContext* h, const Call& call) {
+  if (h->opt.profile != 0 || h->opt.taps || h->opt.ptaps || h->rec_ts || h->dec_st.dbg_ts || h->opt.slab_graph || call.L <= 1) return false;
+  return wide_recurrence(h, call.B, call.T_r) && persist_form(h, false, call.W, call.T_r + call.T_e, false) >= 0;
 }
 
 void reset_group(RvContext* g) {
@@ -1251,27 +1407,36 @@ int launch_group(RvContext* root, RvContext* g) {
   if (g->g_rows == 0) return RV_OK;          // empty slabs only: nothing to run, S = 0
   sync_child(g, root);
   const size_t steps = (size_t)g->g_L - 1;
-  DecMembers& m = g->lmem;
+  DecMembers& m = g->g_members;
   m.n = g->g_n;
   for (int i = 0; i < g->g_n; ++i) {
     const RvContext::Tick& t = root->ticks[g->g_tslot[i]];
     m.row0[i] = t.row0; m.rows[i] = t.B;
     if (!g->g_dev_out) { m.tokens[i] = g->out_tokens + (size_t)t.row0 * steps; m.out2[i] = g->out2 + (size_t)t.row0 * steps; }
   }
-  g->group_call = true;
-  int rc = enqueue(g, g->d_raw, g->d_ev, true, g->g_rows, g->g_Tr, g->g_Te, g->g_W, g->g_L, false, g->out_tokens, g->out2, g->g_dev_out,
-                   g->g_calls ? g->g_lut : nullptr);
-  g->group_call = false;
+  Call call;
+  call.raw = g->d_raw; call.ev = g->d_ev; call.dev_in = true;
+  call.B = g->g_rows; call.T_r = g->g_Tr; call.T_e = g->g_Te; call.W = g->g_W; call.L = g->g_L;
+  call.tokens = g->out_tokens; call.out2 = g->out2; call.dev_out = g->g_dev_out;
+  call.lut = g->g_calls ? g->g_lut : nullptr;
+  CallParts res;
+  res.members = &m;
+  res.form_B = g->g_B0;
+  const int rc = enqueue(g, call, res);
   g->pend.busy = false;                      // (the tickets live in the root's table)
-  if (rc != RV_OK) { root->err = g->err; g->g_failed = rc; }
-  return rc;
+  if (rc != RV_OK) g->g_failed = rc;
+  return relay(root, g, rc);
 }
 
 int flush_open_group(RvContext* h) { return h->open_grp ? launch_group(h, h->open_grp) : RV_OK; }
 
-int submit_group(RvContext* h, int n, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W, int L,
-                 int32_t* tokens, float* out2, bool dev_out, const uint8_t* lut, int32_t* ticket) {
+// A (validated, coalescible) slab joins the open group of n slabs, opening one if need be; the group is launched when it is full
+int submit_group(RvContext* h, int n, const Call& call, int32_t* ticket) {
   const RvConfig& c = h->cfg;
+  const float *raw = call.raw, *ev = call.ev;
+  const int B = call.B, T_r = call.T_r, T_e = call.T_e, W = call.W, L = call.L;
+  const bool dev_in = call.dev_in, dev_out = call.dev_out;
+  const uint8_t* lut = call.lut;
   const bool calls = lut != nullptr;
   HIPCHK(h, hipSetDevice(c.device));
   RvContext* g = h->open_grp;
@@ -1290,18 +1455,17 @@ int submit_group(RvContext* h, int n, const float* raw, const float* ev, bool de
     }
     // the group contexts an in-order stream needs, ceil(depth / n), exist from the first coalesced submit on, as the slab contexts do from the
     // first submit: none is allocated (gigabytes of hipMalloc at C3 sizes) in the middle of a stream.  One more only when none is idle
-    const int depth = std::min(std::max(h->opt_async_depth, 1), RV_MAX_ASYNC);
+    const int depth = async_depth(h);
     while (!g || (int)h->groups.size() < (depth + n - 1) / n) {
       RvContext* k = nullptr;
-      const int rc = create_child(h, &k, n);
-      if (rc != RV_OK) return rc;
+      TRY(create_child(h, &k, n));
       k->g_cap = n;
       reset_group(k);
       h->groups.push_back(k);
       if (!g) g = k;
     }
     reset_group(g);
-    g->g_Tr = T_r; g->g_Te = T_e; g->g_W = W; g->g_L = L; g->g_dev_in = dev_in; g->g_dev_out = dev_out; g->g_calls = calls; g->g_formB = B;
+    g->g_Tr = T_r; g->g_Te = T_e; g->g_W = W; g->g_L = L; g->g_dev_in = dev_in; g->g_dev_out = dev_out; g->g_calls = calls; g->g_B0 = B;
     memset(g->g_lut, 0, sizeof g->g_lut);
     if (calls) memcpy(g->g_lut, lut, (size_t)c.vocab);
     h->open_grp = g;
@@ -1323,12 +1487,11 @@ int submit_group(RvContext* h, int n, const float* raw, const float* ev, bool de
   const int i = g->g_n++;
   g->g_rows += B;
   g->g_tslot[i] = slot;
-  if (dev_out) { g->lmem.tokens[i] = tokens; g->lmem.out2[i] = out2; } else g->g_staged += 1;
+  if (dev_out) { g->g_members.tokens[i] = call.tokens; g->g_members.out2[i] = call.out2; } else g->g_staged += 1;
   RvContext::Tick& t = h->ticks[slot];
   t = RvContext::Tick{};
   t.busy = true; t.dev_out = dev_out; t.calls = calls; t.member = i; t.B = B; t.row0 = (int)row0; t.steps = L - 1; t.grp = g;
-  h->generation = (h->generation + 1) & 0xFFFFF;
-  t.ticket = (h->generation << 4) | slot;
+  t.ticket = issue_ticket(h, slot);
   *ticket = t.ticket;
   if (g->g_n == g->g_cap) launch_group(h, g);      // (a failed launch is reported when its tickets are collected)
   return RV_OK;
@@ -1382,6 +1545,15 @@ int collect_group(RvContext* h, int slot, int32_t* tokens, float* out2, const Ca
   return RV_OK;
 }
 
+// What every entry point states the same way.  An entry point's buffers are all the host's or all the device's (on_device); it adds
+// its outputs and what makes its kind of call
+Call slab_call(const float* raw, const float* event, bool on_device, int B, int T_r, int T_e, int W, int L) {
+  Call c;
+  c.raw = raw; c.ev = event; c.dev_in = on_device; c.dev_out = on_device;
+  c.B = B; c.T_r = T_r; c.T_e = T_e; c.W = W; c.L = L;
+  return c;
+}
+
 }  // namespace
 
 // Loading the library is the earliest point a C caller reaches: ask the HIP runtime for 16 hardware queues (the asynchronous calls keep up
@@ -1428,9 +1600,7 @@ int rv_create(const RvConfig* cfg, rv_handle* out) {
 
   RvContext* h = new RvContext();
   h->cfg = c;
-  auto bail = [&](int code) { g_create_error = h->err; rv_destroy(h); return code; };
-#define TRY(x) do { int r_ = (x); if (r_ != RV_OK) return bail(r_); } while (0)
-#define HIPTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fail(h, RV_EHIP, "%s: %s", #x, hipGetErrorString(e_)); return bail(RV_EHIP); } } while (0)
+  auto init = [&]() -> int {
   HIPTRY(hipSetDevice(c.device));
   HIPTRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   HIPTRY(configure_decode_kernels());    // a refused LDS opt-in would otherwise surface as an opaque launch error later
@@ -1439,31 +1609,33 @@ int rv_create(const RvConfig* cfg, rv_handle* out) {
   HIPTRY(configure_gemm_kernels());
   h->n_w = weight_count(c);
   TRY(dalloc(h, &h->d_w, h->n_w));
-  TRY(dalloc(h, &h->d_WcatT, (size_t)c.dec_depth * RV_G * RV_E));
-  TRY(dalloc(h, &h->d_Wmp, (size_t)RV_E * RV_E));
-  TRY(dalloc(h, &h->d_Wmp16, RV_WMP16_SLOT));
-  TRY(dalloc(h, &h->d_Wkp16, RV_WKP16_SLOT));
-  TRY(dalloc(h, &h->d_Wc16, (size_t)2 * 3 * RV_U * RV_G));      // (two cells: 384 rows)
-  if (c.dec_depth == 2) TRY(dalloc(h, &h->d_W1c16, (size_t)2 * RV_E * RV_G));
-  TRY(dalloc(h, &h->d_Wl16, (size_t)2 * RV_E * 16));
-  TRY(dalloc(h, &h->d_Wq16, (size_t)2 * RV_U * RV_U));
-  TRY(dalloc(h, &h->d_Wcat2, (size_t)RV_E * RV_G));
-  TRY(dalloc(h, &h->d_Nh, (size_t)RV_U * RV_MAX_VOCAB));
-  TRY(dalloc(h, &h->d_Up, (size_t)2 * c.enc_depth * 2 * RV_U * RV_G));
-  TRY(dalloc(h, &h->d_Ua, (size_t)2 * c.enc_depth * 2 * RV_UA_SLOT));
-  if (c.enc_depth > 1) TRY(dalloc(h, &h->d_Wx16, (size_t)2 * (c.enc_depth - 1) * RV_WX16_SLOT));
-  if (c.enc_depth > 1) TRY(dalloc(h, &h->d_bx2, (size_t)2 * (c.enc_depth - 1) * 2 * RV_G));
-  if (c.enc_depth > 1) TRY(dalloc(h, &h->d_Wp, (size_t)2 * (c.enc_depth - 1) * 2 * RV_E * RV_G));
-  if (c.enc_depth > 1) TRY(dalloc(h, &h->d_Wh, (size_t)2 * (c.enc_depth - 1) * 2 * RV_WH_SLOT));
-  if (c.enc_depth > 1) TRY(dalloc(h, &h->d_Wsb, (size_t)2 * (c.enc_depth - 1) * 2 * 3 * RV_E * RV_G));
+  TRY(dalloc(h, &h->img.WcatT, (size_t)c.dec_depth * RV_G * RV_E));
+  TRY(dalloc(h, &h->img.Wmp, (size_t)RV_E * RV_E));
+  TRY(dalloc(h, &h->img.Wmp16, RV_WMP16_SLOT));
+  TRY(dalloc(h, &h->img.Wkp16, RV_WKP16_SLOT));
+  TRY(dalloc(h, &h->img.Wc16, (size_t)2 * 3 * RV_U * RV_G));      // (two cells: 384 rows)
+  if (c.dec_depth == 2) TRY(dalloc(h, &h->img.W1c16, (size_t)2 * RV_E * RV_G));
+  TRY(dalloc(h, &h->img.Wl16, (size_t)2 * RV_E * 16));
+  TRY(dalloc(h, &h->img.Wq16, (size_t)2 * RV_U * RV_U));
+  TRY(dalloc(h, &h->img.Wcat2, (size_t)RV_E * RV_G));
+  TRY(dalloc(h, &h->img.Nh, (size_t)RV_U * RV_MAX_VOCAB));
+  TRY(dalloc(h, &h->img.Up, (size_t)2 * c.enc_depth * 2 * RV_U * RV_G));
+  TRY(dalloc(h, &h->img.Ua, (size_t)2 * c.enc_depth * 2 * RV_UA_SLOT));
+  if (c.enc_depth > 1) TRY(dalloc(h, &h->img.Wx16, (size_t)2 * (c.enc_depth - 1) * RV_WX16_SLOT));
+  if (c.enc_depth > 1) TRY(dalloc(h, &h->img.bx2, (size_t)2 * (c.enc_depth - 1) * 2 * RV_G));
+  if (c.enc_depth > 1) TRY(dalloc(h, &h->img.Wp, (size_t)2 * (c.enc_depth - 1) * 2 * RV_E * RV_G));
+  if (c.enc_depth > 1) TRY(dalloc(h, &h->img.Wh, (size_t)2 * (c.enc_depth - 1) * 2 * RV_WH_SLOT));
+  if (c.enc_depth > 1) TRY(dalloc(h, &h->img.Wsb, (size_t)2 * (c.enc_depth - 1) * 2 * 3 * RV_E * RV_G));
 #ifdef RV_DIAG
   if (const char* e = getenv("RV_DBG_ROLE")) h->dbg_role = atoi(e);
 #endif
-  TRY(dalloc(h, &h->d_WmemT, (size_t)RV_U * RV_E));
+  TRY(dalloc(h, &h->img.WmemT, (size_t)RV_U * RV_E));
   bind_weights(h);
   TRY(alloc_slab_buffers(h));
-#undef TRY
-#undef HIPTRY
+  return RV_OK;
+  };
+  const int rc = init();
+  if (rc != RV_OK) { g_create_error = h->err; rv_destroy(h); return rc; }
   *out = h;
   return RV_OK;
 }
@@ -1502,7 +1674,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
   if (uncollected(h)) return fail(h, RV_ESTATE, "collect the calls in flight before loading weights");
   for (RvContext* k : h->kids) if (k->pend.busy) return fail(h, RV_ESTATE, "collect the calls in flight before loading weights");
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  h->opt_gen++;                      // (weight-derived scalars travel by value in the decode's kernel arguments)
+  h->opt.gen++;                      // (weight-derived scalars travel by value in the decode's kernel arguments)
   HIPCHK(h, hipMemcpyAsync(h->d_w, blob, n_floats * sizeof(float), hipMemcpyHostToDevice, h->stream));
   {   // derived layout for the decoder cell kernel: the input-kernel rows that multiply a dense input
       // (rows V.. of W_0; all of W_k for k >= 1) followed by U_k form a contiguous [256][512] matrix in
@@ -1512,7 +1684,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
       const size_t off = (size_t)(h->dec[l].W - h->d_w) + (l == 0 ? (size_t)h->cfg.vocab * RV_G : 0);
       for (int k = 0; k < RV_E; ++k)
         for (int n = 0; n < RV_G; ++n) t[(size_t)n * RV_E + k] = blob[off + (size_t)k * RV_G + n];
-      HIPCHK(h, hipMemcpy(h->d_WcatT + (size_t)l * RV_G * RV_E, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(h->img.WcatT + (size_t)l * RV_G * RV_E, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     // every encoder layer: U [128][512] -> [32 i][512 threads][4 slots] (thread = 4 j + kq holds k = 32 kq + i, slot r = gate (kq + r) & 3)
     for (int e = 0; e < 2; ++e)
@@ -1526,7 +1698,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
               for (int r = 0; r < 4; ++r)
                 up[((size_t)i * 512 + tid) * 4 + r] = blob[off + (size_t)(32 * kq + i) * RV_G + ((kq + r) & 3) * RV_U + j];
             }
-          float* dst = h->d_Up + ((size_t)(e * h->cfg.enc_depth + l) * 2 + dr) * RV_U * RV_G;
+          float* dst = h->img.Up + ((size_t)(e * h->cfg.enc_depth + l) * 2 + dr) * RV_U * RV_G;
           HIPCHK(h, hipMemcpy(dst, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice));
         }
     // ... and as MFMA A fragments of U^T for the matrix-pipe recurrence: wave w, gate g, k-step ks, part p, lane (m = lane%16, kq = lane/16)
@@ -1559,7 +1731,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
                     ua[base + 64 * 8 + (size_t)ln * 8 + j] = lb;
                   }
           for (int r = 0; r < RV_G; ++r) { const float f = std::ldexp(1.0f, -14) / cs[r]; memcpy(&ua[(size_t)2 * RV_U * RV_G + 2 * r], &f, 4); }
-          HIPCHK(h, hipMemcpy(h->d_Ua + ((size_t)(e * h->cfg.enc_depth + l) * 2 + dr) * RV_UA_SLOT, ua.data(), ua.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+          HIPCHK(h, hipMemcpy(h->img.Ua + ((size_t)(e * h->cfg.enc_depth + l) * 2 + dr) * RV_UA_SLOT, ua.data(), ua.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
     // encoder layers >= 1, both directions' input kernels as the split GEMM's B slabs: column block cb = 2 dir + half holds columns
     // 256 half .. of direction dir; [cb][8 k-steps][16 tiles][2 parts][64 lanes][8 f16] of the column-scaled kernel, then 1024 factors
@@ -1575,8 +1747,8 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
         }
         rv_pack_split_image(blob, RV_G, 4, [&](int c) { return off[c / RV_G] + (size_t)(c % RV_G); }, img.data());
         const size_t slot = (size_t)(e * (h->cfg.enc_depth - 1) + (l - 1));
-        HIPCHK(h, hipMemcpy(h->d_Wx16 + slot * RV_WX16_SLOT, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(h->d_bx2 + slot * 2 * RV_G, b2.data(), b2.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->img.Wx16 + slot * RV_WX16_SLOT, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->img.bx2 + slot * 2 * RV_G, b2.data(), b2.size() * sizeof(float), hipMemcpyHostToDevice));
       }
     // encoder layers >= 1: W [256][512] -> [32 column tiles][16 k-groups][64 lanes][4]: lane (q = lane/16, col = lane%16)
     // of tile nt finds W[16 g + 4 i + q][16 nt + col] for its 4 MFMAs i of k-group g in one float4 (lstm_rec.hip)
@@ -1589,7 +1761,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
               for (int ln = 0; ln < 64; ++ln)
                 for (int i = 0; i < 4; ++i)
                   t[(((size_t)nt * 16 + g) * 64 + ln) * 4 + i] = blob[off + (size_t)(16 * g + 4 * i + (ln >> 4)) * RV_G + 16 * nt + (ln & 15)];
-          float* dst = h->d_Wp + ((size_t)(e * (h->cfg.enc_depth - 1) + (l - 1)) * 2 + dr) * RV_E * RV_G;
+          float* dst = h->img.Wp + ((size_t)(e * (h->cfg.enc_depth - 1) + (l - 1)) * 2 + dr) * RV_E * RV_G;
           HIPCHK(h, hipMemcpy(dst, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
           // ... and as bf16 parts: lane (kq = lane/16, col = lane%16) of tile nt, k-step ks holds W[32 ks + 8 kq + j][16 nt + col], j = 0..7
           std::vector<uint16_t> sb((size_t)3 * RV_E * RV_G);
@@ -1627,8 +1799,8 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
                   wh[((((size_t)nt * 2 + 1) * 8 + ks) * 64 + ln) * 8 + j] = lb;
                 }
           for (int n = 0; n < RV_G; ++n) { const float f = std::ldexp(1.0f, -14) / cs[n]; memcpy(&wh[(size_t)2 * RV_E * RV_G + 2 * n], &f, 4); }
-          HIPCHK(h, hipMemcpy(h->d_Wh + ((size_t)(e * (h->cfg.enc_depth - 1) + (l - 1)) * 2 + dr) * RV_WH_SLOT, wh.data(), wh.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-          uint16_t* dsb = h->d_Wsb + ((size_t)(e * (h->cfg.enc_depth - 1) + (l - 1)) * 2 + dr) * 3 * RV_E * RV_G;
+          HIPCHK(h, hipMemcpy(h->img.Wh + ((size_t)(e * (h->cfg.enc_depth - 1) + (l - 1)) * 2 + dr) * RV_WH_SLOT, wh.data(), wh.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+          uint16_t* dsb = h->img.Wsb + ((size_t)(e * (h->cfg.enc_depth - 1) + (l - 1)) * 2 + dr) * 3 * RV_E * RV_G;
           HIPCHK(h, hipMemcpy(dsb, sb.data(), sb.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
     {   // [W_mem | A_c] [256][256]: column block 0 = W_mem (keys), column block 1 = rows 128..383 of the attention layer
@@ -1640,7 +1812,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
           wmp[(size_t)kk * RV_E + n] = blob[mo + (size_t)kk * RV_U + n];
           wmp[(size_t)kk * RV_E + RV_U + n] = blob[ao + (size_t)kk * RV_U + n];
         }
-      HIPCHK(h, hipMemcpy(h->d_Wmp, wmp.data(), wmp.size() * sizeof(float), hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(h->img.Wmp, wmp.data(), wmp.size() * sizeof(float), hipMemcpyHostToDevice));
       {   // |enc_out| <= 1, so |key_tu| <= sum_k |W_mem[k][u]| and |U'_tn| <= sum_k |A_c[k][n]|: the largest column sums bound both
         double bk = 0.0, bu = 0.0;
         for (int n = 0; n < RV_E; ++n) {
@@ -1653,7 +1825,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
       }
       std::vector<uint16_t> img(RV_WMP16_SLOT);
       rv_pack_split_image(wmp.data(), RV_E, 1, [](int c) { return (size_t)c; }, img.data());
-      HIPCHK(h, hipMemcpy(h->d_Wmp16, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(h->img.Wmp16, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
       // the same f16 parts of the W_mem half, for the decode's own projection (DecState::Wkp16): lane (i, kq) of key tile 2 ks + y
       // takes what lane (c % 16, kq) of column tile c / 16 holds, c = 32 ks + 8 (i / 4) + 4 y + i % 4
       std::vector<uint16_t> kimg(RV_WKP16_SLOT);
@@ -1665,7 +1837,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
               memcpy(&kimg[((((size_t)st * 8 + t8) * 2 + part) * 64 + ln) * 8],
                      &img[((((size_t)st * 16 + c / 16) * 2 + part) * 64 + 16 * q + c % 16) * 8], 8 * sizeof(uint16_t));
             }
-      HIPCHK(h, hipMemcpy(h->d_Wkp16, kimg.data(), kimg.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(h->img.Wkp16, kimg.data(), kimg.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     }
     if (h->cfg.dec_depth <= 2) {
       // attention = h . A_h + ctx' (h = the top cell's output); its h part is folded into what consumes the attention vector (products in double):
@@ -1691,8 +1863,8 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
           for (int j = 0; j < RV_U; ++j) acc += (double)blob[ah + (size_t)i * RV_U + j] * (double)blob[fc + (size_t)j * V + v];
           nh[(size_t)i * V + v] = (float)acc;
         }
-      if (!two) HIPCHK(h, hipMemcpy(h->d_Wcat2, w2.data(), w2.size() * sizeof(float), hipMemcpyHostToDevice));     // (the packed-FMA form of one cell)
-      HIPCHK(h, hipMemcpy(h->d_Nh, nh.data(), nh.size() * sizeof(float), hipMemcpyHostToDevice));
+      if (!two) HIPCHK(h, hipMemcpy(h->img.Wcat2, w2.data(), w2.size() * sizeof(float), hipMemcpyHostToDevice));     // (the packed-FMA form of one cell)
+      HIPCHK(h, hipMemcpy(h->img.Nh, nh.data(), nh.size() * sizeof(float), hipMemcpyHostToDevice));
       {   // the same kernel for the matrix-pipe cell product (DecState::Wc16): rows divided by the factor their input's f16 image
           // carries (exact: powers of two), one power-of-two scale for the tensor, two f16 parts in B-fragment order per wave
         auto xs = [&](int k) { return k < RV_U ? h->mx_uscale : 16384.f; };
@@ -1717,7 +1889,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
                 img[(((((size_t)wv * NP + pr) * 2 + 0) * 64) + ln) * 8 + j] = hb;
                 img[(((((size_t)wv * NP + pr) * 2 + 1) * 64) + ln) * 8 + j] = lb;
               }
-        HIPCHK(h, hipMemcpy(h->d_Wc16, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->img.Wc16, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         if (two) {   // cell 1's kernels on h_0 (W_1) and on h_1 (U_1): DecState::W1c16, rows divided by the 2^14 their inputs' images carry
           const size_t w1 = (size_t)(h->dec[1].W - h->d_w), u1 = (size_t)(h->dec[1].U - h->d_w);
           float m1 = 0.f;
@@ -1739,7 +1911,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
                   i1[(((((size_t)wv * 32 + pr) * 2 + 0) * 64) + ln) * 8 + j] = hb;
                   i1[(((((size_t)wv * 32 + pr) * 2 + 1) * 64) + ln) * 8 + j] = lb;
                 }
-          HIPCHK(h, hipMemcpy(h->d_W1c16, i1.data(), i1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+          HIPCHK(h, hipMemcpy(h->img.W1c16, i1.data(), i1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
         // the output layer on the same [ctx' | h] image: logits = ctx' . W_fc + h . (A_h W_fc) + b_fc; columns >= V are zero
         auto wl = [&](int k, int v) -> float {
@@ -1764,7 +1936,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
               li[(((size_t)ks * 2 + 0) * 64 + ln) * 8 + j] = hb;
               li[(((size_t)ks * 2 + 1) * 64 + ln) * 8 + j] = lb;
             }
-        HIPCHK(h, hipMemcpy(h->d_Wl16, li.data(), li.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->img.Wl16, li.data(), li.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         if (!two) {   // Bahdanau's query layer W_q [128][128] for the matrix pipe (DecState::Wq16): one power-of-two scale, two f16 parts, per-wave B fragments
           const size_t qo = (size_t)(h->W_q - h->d_w);
           float mq = 0.f;
@@ -1785,7 +1957,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
                   qi[((((size_t)wv * 4 + ks) * 2 + 0) * 64 + ln) * 8 + j] = hb;
                   qi[((((size_t)wv * 4 + ks) * 2 + 1) * 64 + ln) * 8 + j] = lb;
                 }
-          HIPCHK(h, hipMemcpy(h->d_Wq16, qi.data(), qi.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+          HIPCHK(h, hipMemcpy(h->img.Wq16, qi.data(), qi.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
       }
     }
@@ -1793,7 +1965,7 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
     std::vector<float> m((size_t)RV_U * RV_E);
     for (int i = 0; i < RV_E; ++i)
       for (int j = 0; j < RV_U; ++j) m[(size_t)j * RV_E + i] = blob[moff + (size_t)i * RV_U + j];
-    HIPCHK(h, hipMemcpy(h->d_WmemT, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->img.WmemT, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice));
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->loaded = true;
@@ -1802,39 +1974,53 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
 
 int rv_beam_search(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e,
                    int32_t W, int32_t L, int32_t* tokens, float* scores, int32_t* S_out) {
-  return run(h, raw, event, false, B, T_r, T_e, W, L, false, tokens, scores, false, S_out);
+  Call c = slab_call(raw, event, false, B, T_r, T_e, W, L);
+  c.tokens = tokens; c.out2 = scores;
+  return run(h, c, S_out);
 }
 int rv_beam_search_dev(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e,
                        int32_t W, int32_t L, int32_t* tokens, float* scores, int32_t* S_out) {
-  return run(h, raw, event, true, B, T_r, T_e, W, L, false, tokens, scores, true, S_out);
+  Call c = slab_call(raw, event, true, B, T_r, T_e, W, L);
+  c.tokens = tokens; c.out2 = scores;
+  return run(h, c, S_out);
 }
 int rv_beam_search_calls(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e,
                          int32_t W, int32_t L, const uint8_t* lut, uint8_t* bases, int32_t* lengths, float* probs,
                          int32_t* S_out) {
-  const CallsOut c{lut, bases, lengths, probs};
-  return run(h, raw, event, false, B, T_r, T_e, W, L, false, nullptr, nullptr, false, S_out, &c);
+  const CallsOut co{lut, bases, lengths, probs};
+  Call c = slab_call(raw, event, false, B, T_r, T_e, W, L);
+  c.lut = lut; c.calls = &co;
+  return run(h, c, S_out);
 }
 int rv_greedy_search(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e,
                      int32_t L, int32_t* tokens, float* logits, int32_t* S_out) {
-  return run(h, raw, event, false, B, T_r, T_e, 1, L, true, tokens, logits, false, S_out);
+  Call c = slab_call(raw, event, false, B, T_r, T_e, 1, L);
+  c.greedy = true; c.tokens = tokens; c.out2 = logits;
+  return run(h, c, S_out);
 }
 int rv_greedy_search_dev(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e,
                          int32_t L, int32_t* tokens, float* logits, int32_t* S_out) {
-  return run(h, raw, event, true, B, T_r, T_e, 1, L, true, tokens, logits, true, S_out);
+  Call c = slab_call(raw, event, true, B, T_r, T_e, 1, L);
+  c.greedy = true; c.tokens = tokens; c.out2 = logits;
+  return run(h, c, S_out);
 }
 
 // Decoder.call under TrainingSampler, as _train_step drives it: greedy decode's launches with the labels fed in, then k_score_tokens
 int rv_teacher_forced(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t L,
                       const int32_t* targets, uint32_t omit_mask, int32_t* sample_id, float* logits, const RvScore* out) {
   const ForcedCall fc{targets, omit_mask, out};
+  Call c = slab_call(raw, event, false, B, T_r, T_e, 1, L);
+  c.greedy = true; c.tokens = sample_id; c.out2 = logits; c.forced = &fc;
   int32_t S = 0;
-  return run(h, raw, event, false, B, T_r, T_e, 1, L, true, sample_id, logits, false, &S, nullptr, nullptr, &fc);
+  return run(h, c, &S);
 }
 int rv_teacher_forced_dev(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t L,
                           const int32_t* targets, uint32_t omit_mask, int32_t* sample_id, float* logits, const RvScore* out) {
   const ForcedCall fc{targets, omit_mask, out};
+  Call c = slab_call(raw, event, true, B, T_r, T_e, 1, L);
+  c.greedy = true; c.tokens = sample_id; c.out2 = logits; c.forced = &fc;
   int32_t S = 0;
-  return run(h, raw, event, true, B, T_r, T_e, 1, L, true, sample_id, logits, true, &S, nullptr, nullptr, &fc);
+  return run(h, c, &S);
 }
 
 // loss_function / masked_accuracy on logits the caller holds (test_step: the zero-padded greedy logits); host buffers
@@ -1846,55 +2032,49 @@ int rv_score_logits(rv_handle h, const float* logits, const int32_t* labels, int
   if (S < 0 || S > c.max_output_len || S > 64) return fail(h, RV_EINVAL, "S=%d outside [0,%d]", S, std::min(c.max_output_len, 64));
   if (B > 0 && S > 0 && (!logits || !labels)) return fail(h, RV_EINVAL, "null input pointer");
   const size_t n = (size_t)B * S;
-  { const int rc = check_token_ids(h, labels, n, std::max(S, 1), "label"); if (rc != RV_OK) return rc; }
+  TRY(check_token_ids(h, labels, n, std::max(S, 1), "label"));
   RvContext* ctx = nullptr;
-  { const int rc = sync_context(h, &ctx); if (rc != RV_OK) return rc; }
+  TRY(sync_context(h, &ctx));
   auto body = [&]() -> int {
-    if (n == 0) return fetch_scores(ctx, out, false, B, 0);
+    if (n == 0) return fetch_scores(ctx, ScoreArgs{}, out, false, B, 0);
     HIPCHK(ctx, hipSetDevice(c.device));
-    { const int rc = ensure_score_buffers(ctx); if (rc != RV_OK) return rc; }
+    TRY(ensure_score_buffers(ctx));
     const ForcedCall fc{labels, omit_mask, out};
-    set_score_outputs(ctx, &fc, false);
     HIPCHK(ctx, hipMemcpy(ctx->out2, logits, sizeof(float) * n * c.vocab, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(ctx->d_forced, labels, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    ScoreArgs a = ctx->lscore;
+    ScoreArgs a = score_outputs(ctx, &fc, false);
     a.logits = ctx->out2; a.labels = ctx->d_forced; a.label_stride = S; a.B = B; a.S = S; a.V = c.vocab; a.pad_token = c.pad_token;
     a.pred = pred ? ctx->out_tokens : nullptr;
     launch_score_tokens(a, ctx->stream);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     if (pred) HIPCHK(ctx, hipMemcpy(pred, ctx->out_tokens, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    return fetch_scores(ctx, out, false, B, S);
+    return fetch_scores(ctx, a, out, false, B, S);
   };
-  const int rc = body();
-  if (rc != RV_OK && ctx != h) h->err = ctx->err;
-  return rc;
+  return relay(h, ctx, body());
 }
 
 // ---- asynchronous calls: submit returns once the slab's work is queued on one of the handle's contexts; collect waits for it.
-static int submit(rv_handle h, const float* raw, const float* ev, bool dev_in, int B, int T_r, int T_e, int W, int L,
-                  int32_t* tokens, float* out2, bool dev_out, const uint8_t* lut, int32_t* ticket, bool all = false, const RvBeams* ab = nullptr) {
+static int submit(rv_handle h, const Call& call, int32_t* ticket) {
   if (!h || !ticket) return RV_EINVAL;
   *ticket = -1;
-  const int depth = std::min(std::max(h->opt_async_depth, 1), RV_MAX_ASYNC);
+  const int depth = async_depth(h);
   const int n_co = coalesce_n(h, depth);
   bool ticks_out = false;
   for (const auto& t : h->ticks) ticks_out = ticks_out || t.busy;
   if (n_co >= 2 || ticks_out) {            // (neither: the path below, one context per slab, as it always was)
-    int tr = T_r, te = T_e;
-    const int rv = validate_call(h, raw, ev, B, tr, te, W, L, tokens, out2, dev_out);
-    if (rv != RV_OK) return rv;
+    Call ok;
+    TRY(validate_call(h, call, ok));
     if (uncollected(h) >= depth)
       return fail(h, RV_ESTATE, "all %d asynchronous slots hold uncollected calls (option async_depth): collect one first", depth);
     h->inflight_hint = depth;
-    if (n_co >= 2 && !all && coalescible(h, B, tr, te, W, L))
-      return submit_group(h, n_co, raw, ev, dev_in, B, tr, te, W, L, tokens, out2, dev_out, lut, ticket);
+    if (n_co >= 2 && !call.whole_beam && coalescible(h, ok))
+      return submit_group(h, n_co, ok, ticket);
     flush_open_group(h);      // a slab of another path: the group goes as it is, this slab on a context of its own
   }
   while ((int)h->kids.size() < depth - 1) {
     RvContext* k = nullptr;
-    const int rc = create_child(h, &k);
-    if (rc != RV_OK) return rc;
+    TRY(create_child(h, &k));
     h->kids.push_back(k);
   }
   RvContext* ctx = nullptr; int slot = -1;
@@ -1906,13 +2086,12 @@ static int submit(rv_handle h, const float* raw, const float* ev, bool dev_in, i
   if (!ctx) return fail(h, RV_ESTATE, "all %d asynchronous contexts hold uncollected calls (option async_depth): collect one first", depth);
   h->inflight_hint = depth;
   if (ctx != h) sync_child(ctx, h);
-  if (all) { const int rb = begin_all_beams(ctx, ab, dev_out); if (rb != RV_OK) { if (ctx != h) h->err = ctx->err; return rb; } }
-  const int rc = enqueue(ctx, raw, ev, dev_in, B, T_r, T_e, W, L, false, tokens, out2, dev_out, lut);
-  ctx->all_beams = false;
-  if (rc != RV_OK) { ctx->pend.busy = false; if (ctx != h) h->err = ctx->err; return rc; }
+  CallParts res;
+  if (call.whole_beam) { const int rb = begin_all_beams(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
+  const int rc = enqueue(ctx, call, res);
+  if (rc != RV_OK) { ctx->pend.busy = false; return relay(h, ctx, rc); }
   h->next_slot = (slot + 1) % depth;
-  h->generation = (h->generation + 1) & 0xFFFFF;
-  ctx->pend.ticket = (h->generation << 4) | slot;
+  ctx->pend.ticket = issue_ticket(h, slot);
   *ticket = ctx->pend.ticket;
   return RV_OK;
 }
@@ -1926,20 +2105,20 @@ static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, co
   if (ticket < 0 || slot > (int)h->kids.size()) return fail(h, RV_EINVAL, "unknown ticket %d", ticket);
   RvContext* ctx = slot == 0 ? h : h->kids[slot - 1];
   if (!ctx->pend.busy || ctx->pend.ticket != ticket) return fail(h, RV_ESTATE, "ticket %d is not in flight (collected already?)", ticket);
-  const int rc = finish(ctx, tokens, out2, calls, S_out, beams);
-  if (rc != RV_OK && ctx != h) h->err = ctx->err;
-  return rc;
+  return relay(h, ctx, finish(ctx, tokens, out2, calls, S_out, beams));
 }
 int rv_beam_search_submit(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
                           int32_t* ticket) {
-  return submit(h, raw, event, false, B, T_r, T_e, W, L, nullptr, nullptr, false, nullptr, ticket);
+  return submit(h, slab_call(raw, event, false, B, T_r, T_e, W, L), ticket);
 }
 int rv_beam_search_collect(rv_handle h, int32_t ticket, int32_t* tokens, float* scores, int32_t* S_out) {
   return collect(h, ticket, tokens, scores, nullptr, S_out);
 }
 int rv_beam_search_submit_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
                               int32_t L, int32_t* d_tokens, float* d_scores, int32_t* ticket) {
-  return submit(h, d_raw, d_event, true, B, T_r, T_e, W, L, d_tokens, d_scores, true, nullptr, ticket);
+  Call c = slab_call(d_raw, d_event, true, B, T_r, T_e, W, L);
+  c.tokens = d_tokens; c.out2 = d_scores;
+  return submit(h, c, ticket);
 }
 int rv_beam_search_collect_dev(rv_handle h, int32_t ticket, int32_t* S_out) {
   return collect(h, ticket, nullptr, nullptr, nullptr, S_out);
@@ -1947,7 +2126,9 @@ int rv_beam_search_collect_dev(rv_handle h, int32_t ticket, int32_t* S_out) {
 int rv_beam_search_submit_calls(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
                                 int32_t L, const uint8_t* lut, int32_t* ticket) {
   if (!lut) return h ? fail(h, RV_EINVAL, "null lut") : RV_EINVAL;
-  return submit(h, raw, event, false, B, T_r, T_e, W, L, nullptr, nullptr, false, lut, ticket);
+  Call c = slab_call(raw, event, false, B, T_r, T_e, W, L);
+  c.lut = lut;
+  return submit(h, c, ticket);
 }
 int rv_beam_search_collect_calls(rv_handle h, int32_t ticket, uint8_t* bases, int32_t* lengths, float* probs, int32_t* S_out) {
   const CallsOut c{nullptr, bases, lengths, probs};
@@ -1960,17 +2141,23 @@ int rv_beam_search_all(rv_handle h, const float* raw, const float* event, int32_
                        const RvBeams* out, int32_t* S_out) {
   if (!h) return RV_EINVAL;
   if (beams_missing(out, B, L)) return fail(h, RV_EINVAL, "null output pointer");
-  return run(h, raw, event, false, B, T_r, T_e, W, L, false, out->tokens, out->scores, false, S_out, nullptr, out);
+  Call c = slab_call(raw, event, false, B, T_r, T_e, W, L);
+  c.tokens = out->tokens; c.out2 = out->scores; c.whole_beam = true; c.beams = out;
+  return run(h, c, S_out);
 }
 int rv_beam_search_all_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
                            int32_t L, const RvBeams* d_out, int32_t* S_out) {
   if (!h) return RV_EINVAL;
   if (beams_missing(d_out, B, L)) return fail(h, RV_EINVAL, "null output pointer");
-  return run(h, d_raw, d_event, true, B, T_r, T_e, W, L, false, d_out->tokens, d_out->scores, true, S_out, nullptr, d_out);
+  Call c = slab_call(d_raw, d_event, true, B, T_r, T_e, W, L);
+  c.tokens = d_out->tokens; c.out2 = d_out->scores; c.whole_beam = true; c.beams = d_out;
+  return run(h, c, S_out);
 }
 int rv_beam_search_submit_all(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
                               int32_t L, int32_t* ticket) {
-  return submit(h, raw, event, false, B, T_r, T_e, W, L, nullptr, nullptr, false, nullptr, ticket, true, nullptr);
+  Call c = slab_call(raw, event, false, B, T_r, T_e, W, L);
+  c.whole_beam = true;
+  return submit(h, c, ticket);
 }
 int rv_beam_search_collect_all(rv_handle h, int32_t ticket, const RvBeams* out, int32_t* S_out) {
   if (!h) return RV_EINVAL;
@@ -1981,7 +2168,9 @@ int rv_beam_search_submit_all_dev(rv_handle h, const float* d_raw, const float* 
                                   int32_t W, int32_t L, const RvBeams* d_out, int32_t* ticket) {
   if (!h) return RV_EINVAL;
   if (beams_missing(d_out, B, L)) return fail(h, RV_EINVAL, "null output pointer");
-  return submit(h, d_raw, d_event, true, B, T_r, T_e, W, L, d_out->tokens, d_out->scores, true, nullptr, ticket, true, d_out);
+  Call c = slab_call(d_raw, d_event, true, B, T_r, T_e, W, L);
+  c.tokens = d_out->tokens; c.out2 = d_out->scores; c.whole_beam = true; c.beams = d_out;
+  return submit(h, c, ticket);
 }
 
 int rv_beam_search_flush(rv_handle h) {
@@ -1992,66 +2181,65 @@ int rv_beam_search_flush(rv_handle h) {
 int rv_set_option(rv_handle h, const char* key, int32_t value) {
   if (!h || !key) return RV_EINVAL;
   flush_open_group(h);               // a group still filling was submitted under the options as they were
-  h->opt_gen++;                      // slab graphs captured under the old options are rebuilt on their next use
-  if (!strcmp(key, "debug_taps")) h->opt_taps = value != 0;
-  else if (!strcmp(key, "slab_graph")) h->opt_slab_graph = value != 0;
+  h->opt.gen++;                      // slab graphs captured under the old options are rebuilt on their next use
+  if (!strcmp(key, "debug_taps")) h->opt.taps = value != 0;
+  else if (!strcmp(key, "slab_graph")) h->opt.slab_graph = value != 0;
   else if (!strcmp(key, "coalesce")) {
     if (value < -1 || value > RV_MAX_MEMBERS) return fail(h, RV_EINVAL, "coalesce must be -1 (chosen from async_depth), 0, 1 or 2..%d", RV_MAX_MEMBERS);
-    h->opt_coalesce = value;
+    h->opt.coalesce = value;
   }
-  else if (!strcmp(key, "persist_taps")) h->opt_ptaps = value != 0;
-  else if (!strcmp(key, "fused_memory")) h->opt_fused_mem = value != 0;
-  else if (!strcmp(key, "use_graph")) h->opt_graph = value != 0;
-  else if (!strcmp(key, "flash_attend")) h->opt_flash = value != 0;
-  else if (!strcmp(key, "persistent_decode")) h->opt_persist = value != 0;
-  else if (!strcmp(key, "concurrent_encoders")) h->opt_side_ev = value != 0;
-  else if (!strcmp(key, "lane_projection")) h->opt_lane_inproj = value != 0;
-  else if (!strcmp(key, "fused_projection")) h->opt_fuse = value != 0;
-  else if (!strcmp(key, "tail_wave")) h->opt_tail_wave = value != 0;
-  else if (!strcmp(key, "wide_recurrence")) h->opt_wide = value < 0 ? -1 : (value == 2 ? 2 : (value != 0));
+  else if (!strcmp(key, "persist_taps")) h->opt.ptaps = value != 0;
+  else if (!strcmp(key, "fused_memory")) h->opt.fused_mem = value != 0;
+  else if (!strcmp(key, "use_graph")) h->opt.graph = value != 0;
+  else if (!strcmp(key, "flash_attend")) h->opt.flash = value != 0;
+  else if (!strcmp(key, "persistent_decode")) h->opt.persist = value != 0;
+  else if (!strcmp(key, "concurrent_encoders")) h->opt.side_ev = value != 0;
+  else if (!strcmp(key, "lane_projection")) h->opt.lane_inproj = value != 0;
+  else if (!strcmp(key, "fused_projection")) h->opt.fuse = value != 0;
+  else if (!strcmp(key, "tail_wave")) h->opt.tail_wave = value != 0;
+  else if (!strcmp(key, "wide_recurrence")) h->opt.wide = value < 0 ? -1 : (value == 2 ? 2 : (value != 0));
   else if (!strcmp(key, "async_depth")) {
     if (value < 1 || value > RV_MAX_ASYNC) return fail(h, RV_EINVAL, "async_depth must be 1..%d", RV_MAX_ASYNC);
-    h->opt_async_depth = value;
+    h->opt.async_depth = value;
     // every context is one HIP stream; the runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless the
     // environment says otherwise when the runtime starts).  More contexts than queues: some share a queue and their slabs serialise.
-    const char* q = getenv("GPU_MAX_HW_QUEUES");
-    const int nq = q ? atoi(q) : 4;
-    if (value > nq)
+    const char* q = nullptr;
+    if (value > hw_queues(&q))
       return fail(h, RV_WQUEUES, "async_depth %d set, but GPU_MAX_HW_QUEUES is %s: contexts beyond the hardware queues share one and serialise "
                   "(C3: depth 10 -> 278 k chunks/s on 8 queues, 317 k on 16); set GPU_MAX_HW_QUEUES >= %d in the environment before the "
                   "process's first HIP call", value, q ? q : "unset (4 queues)", value);
   }
-  else if (!strcmp(key, "matrix_attention")) h->opt_mx_att = value != 0;
-  else if (!strcmp(key, "matrix_cell")) h->opt_mx_cell = value != 0;
-  else if (!strcmp(key, "split_projection")) h->opt_split_proj = value < 0 ? 0 : (value > 2 ? 2 : value);
+  else if (!strcmp(key, "matrix_attention")) h->opt.mx_att = value != 0;
+  else if (!strcmp(key, "matrix_cell")) h->opt.mx_cell = value != 0;
+  else if (!strcmp(key, "split_projection")) h->opt.split_proj = value < 0 ? 0 : (value > 2 ? 2 : value);
   else if (!strcmp(key, "attend_threads")) {
     if (value != 0 && value != 256 && value != 512) return fail(h, RV_EINVAL, "attend_threads must be 0, 256 or 512");
-    h->opt_att_nt = value;
+    h->opt.att_nt = value;
   }
-  else if (!strcmp(key, "decode_split")) h->opt_split = value < 1 ? 1 : (value > 4 ? 4 : value);
-  else if (!strcmp(key, "profile")) h->opt_profile = value < 0 ? 0 : (value > 3 ? 3 : value);
+  else if (!strcmp(key, "decode_split")) h->opt.split = value < 1 ? 1 : (value > 4 ? 4 : value);
+  else if (!strcmp(key, "profile")) h->opt.profile = value < 0 ? 0 : (value > 3 ? 3 : value);
   else return fail(h, RV_EINVAL, "unknown option '%s'", key);
   return RV_OK;
 }
 
 int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, size_t* n_written) {
   if (!h || !name || !n_written) return RV_EINVAL;
-  const size_t B = h->lB, W = h->lW, Tm = h->lTm, S = h->lS, V = h->cfg.vocab;
+  const size_t B = h->lB, W = h->fact.lW, Tm = h->lTm, S = h->lS, V = h->cfg.vocab;
   const void* src = nullptr; size_t n = 0; int kind = 0;   // 0 f32, 1 i32, 2 u8
   const DecState& d = h->dec_st;
   if (!strcmp(name, "enc_output")) { src = h->enc_out; n = B * Tm * RV_E; }
   else if (!strcmp(name, "mask")) { src = h->mask; n = B * Tm; kind = 2; }
   else if (!strcmp(name, "keys")) {
-    if (!h->lkeys) return fail(h, RV_ESTATE, "keys were not built by the last call (single-pass attend); set debug_taps=1");
+    if (!h->fact.lkeys) return fail(h, RV_ESTATE, "keys were not built by the last call (single-pass attend); set debug_taps=1");
     src = h->keys; n = B * Tm * RV_U;
   }
   else if (!strcmp(name, "projected_memory")) {
-    if (!h->lpersist) return fail(h, RV_ESTATE, "the projected memory is built for the persistent decode only (the last call ran the per-step kernels)");
-    if (h->lmem2_stale) {   // the decode projected its chunks itself and stored nothing: the same product of that call's enc_out, now
+    if (!h->fact.lpersist) return fail(h, RV_ESTATE, "the projected memory is built for the persistent decode only (the last call ran the per-step kernels)");
+    if (h->fact.lmem2_stale) {   // the decode projected its chunks itself and stored nothing: the same product of that call's enc_out, now
       HIPCHK(h, hipSetDevice(h->cfg.device));
-      launch_gemm_mem_split(h->enc_out, (int)(B * Tm), h->d_Wmp16, h->mem2, h->stream);
+      launch_gemm_mem_split(h->enc_out, (int)(B * Tm), h->img.Wmp16, h->mem2, h->stream);
       HIPCHK(h, hipStreamSynchronize(h->stream));
-      h->lmem2_stale = 0;
+      h->fact.lmem2_stale = 0;
     }
     src = h->mem2; n = B * Tm * RV_E;
   }
@@ -2059,7 +2247,7 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     *n_written = 4;
     if (!dst || dst_floats < 4) return fail(h, RV_EINVAL, "coalesce_stats needs 4 floats");
     dst[0] = (float)h->co_groups; dst[1] = (float)h->co_slabs; dst[2] = (float)h->co_largest;
-    dst[3] = (float)coalesce_n(h, std::min(std::max(h->opt_async_depth, 1), RV_MAX_ASYNC));
+    dst[3] = (float)coalesce_n(h, async_depth(h));
     return RV_OK;
   }
   else if (!strcmp(name, "rec_stamps")) {
@@ -2096,10 +2284,10 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     for (int i = 0; i < 16; ++i) dst[i] = (float)(ts[i] - ts[0]);
     return RV_OK;
   }
-  else if ((!strncmp(name, "step_", 5) || !strcmp(name, "parent_ids")) && h->lsplit > 1)
+  else if ((!strncmp(name, "step_", 5) || !strcmp(name, "parent_ids")) && h->fact.lsplit > 1)
     return fail(h, RV_ESTATE, "per-step records are laid out per sub-slab when decode_split > 1; read them with decode_split=1 or debug_taps=1");
   else if (!strcmp(name, "chunk_steps")) {
-    if (!h->lpersist) return fail(h, RV_ESTATE, "chunk_steps exist only after a persistent decode");
+    if (!h->fact.lpersist) return fail(h, RV_ESTATE, "chunk_steps exist only after a persistent decode");
     src = h->d_chunk_steps; n = B; kind = 1;
   }
   else if (!strcmp(name, "step_ids")) { src = d.step_ids; n = S * B * W; kind = 1; }
@@ -2110,7 +2298,7 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     src = d.step_logits; n = S * B * W * V;
   } else if (!strcmp(name, "step_alignments")) {
     if (h->ltaps) src = h->step_align;
-    else if (h->lptaps && h->lpersist) src = h->palign;   // [S][B][W][T_m] as the per-step tap
+    else if (h->lptaps && h->fact.lpersist) src = h->palign;   // [S][B][W][T_m] as the per-step tap
     else return fail(h, RV_ESTATE, "step_alignments needs option debug_taps=1, or persist_taps=1 on the persistent decode");
     n = S * B * W * Tm;
   } else return fail(h, RV_EINVAL, "unknown tensor '%s'", name);
@@ -2120,7 +2308,7 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (kind == 0) {
     HIPCHK(h, hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (src == h->step_align && h->lflash) {
+    if (src == h->step_align && h->fact.lflash) {
       // the single-pass kernel taps raw log2-domain masked scores; normalise here (debug path only)
       for (size_t r = 0; r < n / Tm; ++r) {
         float* a = dst + r * Tm;

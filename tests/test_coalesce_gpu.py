@@ -231,3 +231,49 @@ def test_what_is_never_coalesced(world, rv):
     assert all(_same(o, r) for o, r in zip(outs, ref)) and _stats(bc)[:2] == g0
     outs = list(bc.beam_search_stream(dev[:4], W, L))
     assert all(_same(o, r) for o, r in zip(outs, ref)) and _stats(bc)[1] == g0[1] + 4
+
+
+def test_call_kinds_do_not_leak_into_the_next_call(world, rv):
+    """Every kind of call through the same contexts, one after the other: what one kind adds to a call (the whole beam, forced
+    labels, a letter table, a member table) must be gone when the next call is recorded, so every plain beam search between them
+    gives the bytes of the fixture's synchronous reference."""
+    bc, dev, ref = (world[k] for k in ("bc", "dev", "ref"))
+    big, small = SIZES.index(7), SIZES.index(1)
+    x, want = dev[big], ref[big]
+    cfg = bc.cfg
+    plain = lambda: _same(bc.beam_search_prediction(x, W, L), want)
+    slot0 = lambda hyp: _same((hyp.tokens[:, :, 0], hyp.scores[:, :, 0]), want)
+    fresh, _ = _handle(rv)
+    greedy_want = [a.cpu().numpy().copy() for a in fresh.greedy_search_prediction(x, L)]
+    fresh.close()
+    bc.set_coalesce(-1)
+    bc.set_async_depth(4)
+    try:
+        assert plain()                                                       # 1
+        assert slot0(bc.beam_search_hypotheses(x, W, L))                     # 2
+        assert plain()                                                       # 3
+        labels = np.full((7, L), cfg.pad_token, np.int32)                    # 4: the plain call's own best tokens as labels
+        labels[:, 0] = cfg.start_token
+        labels[:, 1:1 + want[2]] = want[0][:, :want[2]]
+        sid, logits = bc.teacher_forced_prediction(x, labels)
+        assert tuple(sid.shape) == (7, STEPS) and tuple(logits.shape) == (7, STEPS, cfg.vocab)
+        greedy = [a.cpu().numpy() for a in bc.greedy_search_prediction(x, L)]                     # 5
+        assert greedy[0].shape == greedy_want[0].shape and np.array_equal(greedy[0], greedy_want[0])
+        assert np.array_equal(greedy[1].view(np.int32), greedy_want[1].view(np.int32))
+        got = bc.beam_search_call_arrays(world["slabs"][big], W, L)          # 6
+        assert all(np.array_equal(g, w) for g, w in zip(got, world["ref_calls"][big]))
+        assert plain()                                                       # 7
+        with pytest.raises(rv._capi.RavventHipError, match="beam width %d outside" % (cfg.max_beam + 1)):       # 8
+            bc.beam_search_hypotheses(x, cfg.max_beam + 1, L)
+        assert plain()                                                       # 9: the refused call left the handle usable
+        bc.set_coalesce(2)                                                   # 10
+        g0 = _stats(bc)[0]
+        t = [bc.submit_beam_search(dev[big], W, L), bc.submit_beam_search(dev[small], W, L)]
+        assert _stats(bc)[0] == g0 + 1
+        assert _same(bc.collect(t[0]), ref[big]) and _same(bc.collect(t[1]), ref[small])
+        assert slot0(bc.collect(bc.submit_beam_search(x, W, L, all_beams=True)))                  # 11
+        assert _same(bc.collect(bc.submit_beam_search(x, W, L)), want)       # 12
+        assert plain()                                                       # 13
+    finally:
+        bc.set_coalesce(-1)
+        bc.set_async_depth(2)
