@@ -1162,39 +1162,202 @@ __device__ __forceinline__ int persist_forced_tok(const DecState& d, int b, int 
   return (unsigned)t < (unsigned)d.V ? t : d.V;
 }
 
+// The compile-time facts of one form k_dec_persist<W, NIT, D, ATT>
+template <int W_, int NIT_, int D_, int ATT_>
+struct PersistTraits {
+  static constexpr int W = W_, NIT = NIT_, D = D_, ATT = ATT_;
+  static constexpr bool BAH = ATT == 1 || ATT == 4;   // Bahdanau scores on the VALU (fp32 key rows)
+  static constexpr bool MX = ATT >= 2;            // the context on the matrix pipe (U' resident as f16 B fragments, alignments through an LDS image)
+  static constexpr bool MXS = ATT == 2 || ATT == 3;   // ... and the Luong scores (keys resident as f16 B fragments, query through an LDS image)
+  static constexpr bool MXC = ATT == 3 || ATT == 4;   // ... and the cell product [ctx' | h] . Wcat2 and the output layer (weights as B fragments: Wc16, Wl16)
+  static constexpr bool MXC2 = MXC && D == 2;     // two decoder cells, every product on the matrix pipe
+  static constexpr int ZS = MXC ? MXC_ZS : RV_G;  // row stride of the gate pre-activations in `part`
+  static constexpr int NC = MXC2 ? 0 : mxc_nc(W);
+  static constexpr int NR = (ATT == 3 && D == 1 && NIT <= 8) ? 5 : 0;   // T_m <= 256 leaves ~50 registers: waves 1-7 keep NR more (k-step, gate) pairs of their share there
+  static constexpr int NP = (NIT + 1) / 2;        // fp32 key rows: pairs of rows per stream
+  static constexpr int NTT = (2 * NIT + 7) / 8;   // matrix pipe: a wave's 16-step key tiles
+  static constexpr int NI = W > 4 ? 2 : 1;        // C/D registers of a tile: pairs of part rows per lane (beams kq, kq + 4)
+  static constexpr bool CACHE = MXC || persist_weight_cache(W, D);
+  static constexpr bool FUSE = ATT == 3 && D == 1;   // the default form projects its chunk's memory itself when the call hands it enc_out (persist_project_memory)
+  // output layer weights, transposed to [v][k] (rows padded to 132 floats: the 8-lane groups of two outputs then read different banks)
+  static constexpr int FCW = RV_U + 4;
+  static constexpr int BFC = MXC ? 0 : RV_MAX_VOCAB * FCW;      // offset of b_fc in s_wfc
+  static_assert(!MX || D == 1 || ATT == 3, "two decoder cells run either on packed FMAs (ATT 0) or with everything on the matrix pipe (ATT 3)");
+  static_assert(NIT <= PERSIST_MAX_NIT && NIT * 256 <= (MXC ? part_floats_mxc(W) : part_floats(W)), "the alignment image (2 f16 parts x 32 NIT steps x 8 slots) must fit `part`");
+  static_assert(2 * 1024 * sizeof(_Float16) /* query image: 2 parts x [16 k-blocks][8 slots][8] f16 */ <= (8 * 4 * 2 * 16 * 4) * sizeof(float), "the query image must fit `fold`");
+};
+
+// ---- bodies the phases of the persistent decode share
+// C/D registers of a 16-column tile: lane (column l16, kq) holds rows 4 kq + i: registers 0 + 1 = beam kq (its high- and low-part rows),
+// 2 + 3 = beam kq + 4.  Beam kq + 4 i of a product taken against the high (a0) and the low part (a1) of its B operand
+__device__ __forceinline__ float tile_pair_sum(const f4v& a0, const f4v& a1, int i) { return (a0[2 * i] + a0[2 * i + 1]) + (a1[2 * i] + a1[2 * i + 1]); }
+// packed FMAs: one float4 weight row times the W beams' values xrow[0..W-1], into 4 columns per beam
+template <int W>
+__device__ __forceinline__ void beams_fma_row(f2 (&acc)[W][2], const float4& wr, const float* xrow) {
+  float xv[WB];
+  *reinterpret_cast<float4*>(xv) = *reinterpret_cast<const float4*>(xrow);
+  if (W > 4) *reinterpret_cast<float4*>(xv + 4) = *reinterpret_cast<const float4*>(xrow + 4);
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    acc[w][0] = __builtin_elementwise_fma(f2{xv[w], xv[w]}, f2{wr.x, wr.y}, acc[w][0]);
+    acc[w][1] = __builtin_elementwise_fma(f2{xv[w], xv[w]}, f2{wr.z, wr.w}, acc[w][1]);
+  }
+}
+// h . M for a [128,128] matrix M -- W_q (Bahdanau's processed query) or A_h (two cells: the attention layer's h part) -- of which this
+// thread holds 8 rows x 4 columns in pw: thread = (4 columns, 1 of 16 K groups of 8 rows), one batch; partial sums [16][W][128] -> `part`
+template <int W>
+__device__ __forceinline__ void persist_h_times_rows(float* part, const float* hcT, const float4 (&pw)[8], int tid) {
+  const int d4 = tid & 31, kg = tid >> 5;
+  f2 acc[W][2];
+#pragma unroll
+  for (int w = 0; w < W; ++w) { acc[w][0] = f2{0.f, 0.f}; acc[w][1] = f2{0.f, 0.f}; }
+#pragma unroll
+  for (int u = 0; u < 8; ++u) beams_fma_row<W>(acc, pw[u], &hcT[(8 * kg + u) * WB]);
+#pragma unroll
+  for (int w = 0; w < W; ++w)
+    *reinterpret_cast<float4*>(&part[(kg * W + w) * RV_U + 4 * d4]) = make_float4(acc[w][0].x, acc[w][0].y, acc[w][1].x, acc[w][1].y);
+}
+
+// ================= the phases of the prologue that stand as functions, in the order the kernel calls them (the other phases stay
+//   inline in the kernel).  Each takes the thread id and derives the coordinates it needs.
+
+// ---- the keys of d.values = [keys | U'] as MFMA B fragments (v_mfma_f32_16x16x32_f16), two f16 parts of the scaled values each.  Scores (MXS): wave
+//   wv owns the 16-step tiles wv + 8 c; lane (n = step l % 16 of the tile, kq = l / 16) holds key[t][32 ks + 8 kq + 0..7].
+//   Context (MX, inline in the kernel): wave wv owns units 16 wv .. 16 wv + 15; lane (n = unit, kq) holds U'[32 ks + 8 kq + 0..7][unit].  The scales are
+//   powers of two from the weights (|key| <= sum_k |W_mem[k][u]| because |enc_out| <= 1): nothing can overflow f16, and what
+//   falls into its subnormals is below 2^-28 of the largest value the column can take.
+template <typename T>
+__device__ __forceinline__ void persist_load_keys_mx(const DecState& d, int b, int tid, float4 (&kb)[T::MXS ? T::NTT : 1][4][2], unsigned& livebits) {
+  const int lane = tid & 63, l16 = lane & 15, kq = lane >> 4, wv0 = tid >> 6, Tm = d.Tm;
+  const float* cbase = d.values + (size_t)b * Tm * RV_E;
+  const uint8_t* mrow = d.mask + (size_t)b * Tm;
+#pragma unroll
+  for (int c = 0; c < T::NTT; ++c) {
+    const int t = 16 * (wv0 + 8 * c) + l16, tc = min(t, Tm - 1);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      float v[8];
+      *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(cbase + (size_t)tc * RV_E + 32 * ks + 8 * kq);
+      *reinterpret_cast<float4*>(v + 4) = *reinterpret_cast<const float4*>(cbase + (size_t)tc * RV_E + 32 * ks + 8 * kq + 4);
+      split_f16x8(v, d.mx_kscale, kb[c][ks][0], kb[c][ks][1]);
+    }
+    if (t < Tm && mrow[tc]) livebits |= 1u << c;          // _maybe_mask_score: padded steps never score
+  }
+}
+
+// ---- Bahdanau beside the matrix pipe: tanh(k + q) = 1 - 2 / (1 + 2^(k' + q')) with k' = 2 log2(e) k, and 2^(k' + q') = 2^k' . 2^q': the resident
+//   rows hold E_k = 2^k' (ONE exponential per key element for the whole decode), a step's queries come as E_q = 2^q', and a score element
+//   costs a multiply-add and ONE reciprocal instead of an exponential and a reciprocal -- the loop is bound by the transcendental rate
+//   (16 lanes per clock and CU).  Exact for |k'| <= 64 and |q'| <= 60 (the product stays a normal f32: |k| <= 22, |h . W_q| <= 20);
+//   a chunk with a larger key keeps k' and takes the two-transcendental form for all its steps, a step with a larger query takes
+//   2^(log2(E_k) + q') -- both block-uniform choices, neither ever seen with weights of any plausible scale.
+//   Two phases around the kernel's block-wide OR: does this thread hold a key out of range; k' -> E_k
+template <typename T>
+__device__ __forceinline__ bool persist_keys_out_of_range(const float4 (&kr)[T::MXS ? 1 : T::NP][4]) {
+  bool big = false;
+#pragma unroll
+  for (int p = 0; p < T::NP; ++p)
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+      big = big || !(fabsf(kr[p][m].x) <= 64.f && fabsf(kr[p][m].y) <= 64.f && fabsf(kr[p][m].z) <= 64.f && fabsf(kr[p][m].w) <= 64.f);
+  return big;
+}
+template <typename T>
+__device__ __forceinline__ void persist_keys_to_exp2(float4 (&kr)[T::MXS ? 1 : T::NP][4]) {
+#pragma unroll
+  for (int p = 0; p < T::NP; ++p)
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      kr[p][m].x = __builtin_amdgcn_exp2f(kr[p][m].x); kr[p][m].y = __builtin_amdgcn_exp2f(kr[p][m].y);
+      kr[p][m].z = __builtin_amdgcn_exp2f(kr[p][m].z); kr[p][m].w = __builtin_amdgcn_exp2f(kr[p][m].w);
+    }
+}
+
+// ---- (T_m <= 256, default form) pairs 32 - NC - NR .. 32 - NC - 1 of this wave's share of the cell product, in registers for the whole decode
+template <typename T>
+__device__ __forceinline__ void persist_load_resident_pairs(const DecState& d, int tid, uint4 (&rbh)[T::NR > 0 ? T::NR : 1], uint4 (&rbl)[T::NR > 0 ? T::NR : 1]) {
+  const uint4* wimg = reinterpret_cast<const uint4*>(d.Wc16) + (size_t)(tid >> 6) * (32 * 128) + (tid & 63);
+#pragma unroll
+  for (int r = 0; r < T::NR; ++r) { rbh[r] = wimg[(2 * (32 - T::NC - T::NR + r)) * 64]; rbl[r] = wimg[(2 * (32 - T::NC - T::NR + r) + 1) * 64]; }
+}
+
+// ================= the phases of a step that stand as functions, in the order the kernel calls them.  None holds a barrier: every
+//   __syncthreads of a step stands in the kernel body.  Each takes the thread id of this step (the opaque copy) and the pointers it uses.
+
+// ---- Luong scores on the matrix pipe: rows = beams, columns = the 16 steps of a tile, K = 128 units, query image in `fold` -> sc
+template <typename T>
+__device__ __forceinline__ void persist_scores_mx(const DecState& d, int tid, unsigned livebits, const float4 (&kb)[T::MXS ? T::NTT : 1][4][2], float (&sc)[T::NTT][T::NI], const float* fold) {
+
+  constexpr int W = T::W;
+  const int lane = tid & 63, wv = tid >> 6, l16 = lane & 15, kq = lane >> 4;
+
+  {
+    const _Float16* qa = reinterpret_cast<const _Float16*>(fold) + (kq * 16 + l16) * 8;    // row l16 of k-block 4 ks + kq
+    // the tiles in turns (against the low, then against the high part of the keys): an MFMA accumulates onto a result that is NTT
+    // instructions old, not onto the one issued just before it
+    f4v acc[T::NTT];
+#pragma unroll
+    for (int c = 0; c < T::NTT; ++c) acc[c] = f4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {                    // one k-step of the query at a time: 4 registers of A fragments live
+      const h8 a = *reinterpret_cast<const h8*>(qa + ks * 512);
+#pragma unroll
+      for (int c = 0; c < T::NTT; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, __builtin_bit_cast(h8, kb[c][ks][1]), acc[c], 0, 0, 0);
+#pragma unroll
+      for (int c = 0; c < T::NTT; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, __builtin_bit_cast(h8, kb[c][ks][0]), acc[c], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int c = 0; c < T::NTT; ++c) {
+      const bool live = (livebits >> c) & 1u;
+#pragma unroll
+      for (int i = 0; i < T::NI; ++i)
+        sc[c][i] = (live && kq + 4 * i < W) ? (acc[c][2 * i] + acc[c][2 * i + 1]) * d.mx_kdescale : -INFINITY;
+    }
+  }
+}
+
+// ---- softmax on the matrix-pipe scores, first half: this wave's maximum (-> mrow_) and sum of every beam -> `ml`; sc <- exp2(sc - max)
+template <typename T>
+__device__ __forceinline__ void persist_softmax_wave_mx(int tid, float (&sc)[T::NTT][T::NI], float (&mrow_)[T::NI], float* ml) {
+
+  const int lane = tid & 63, wv = tid >> 6, l16 = lane & 15, kq = lane >> 4;
+
+#pragma unroll
+  for (int i = 0; i < T::NI; ++i) {
+    float m = sc[0][i];
+#pragma unroll
+    for (int c = 1; c < T::NTT; ++c) m = fmaxf(m, sc[c][i]);
+    m = fmaxf(m, dpp<0xB1>(m)); m = fmaxf(m, dpp<0x4E>(m)); m = fmaxf(m, dpp<0x141>(m)); m = fmaxf(m, dpp<0x140>(m));
+    const float ms = m == -INFINITY ? 0.f : m;           // a wave without live steps for this beam: every term exp2(-inf) = 0
+    float lsum = 0.f;
+#pragma unroll
+    for (int c = 0; c < T::NTT; ++c) { sc[c][i] = __builtin_amdgcn_exp2f(sc[c][i] - ms); lsum += sc[c][i]; }
+    lsum = row16_sum(lsum);
+    mrow_[i] = m;
+    if (l16 == 0) { ml[wv * WB + kq + 4 * i] = m; ml[(8 + wv) * WB + kq + 4 * i] = lsum; }
+  }
+}
+
 template <int W, int NIT, int D, int ATT = 0>
 __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __restrict__ Wcat /*[256,512] = [W_in rows of the attention input ; U]*/,
                                                       const float* __restrict__ Wtok /*[V,512]*/, const float* __restrict__ bdec /*[512]*/,
                                                       const float* __restrict__ Wcat1 /*D == 2: [256,512] = [W_1 ; U_1]*/, const float* __restrict__ bdec1,
                                                       const float* __restrict__ Nh /*D == 1: A_h . W_fc [128,V]*/) {
   constexpr int NT = 512;
-  constexpr bool BAH = ATT == 1 || ATT == 4;   // Bahdanau scores on the VALU (fp32 key rows)
-  constexpr bool MX = ATT >= 2;            // the context on the matrix pipe (U' resident as f16 B fragments, alignments through an LDS image)
-  constexpr bool MXS = ATT == 2 || ATT == 3;   // ... and the Luong scores (keys resident as f16 B fragments, query through an LDS image)
-  constexpr bool MXC = ATT == 3 || ATT == 4;   // ... and the cell product [ctx' | h] . Wcat2 and the output layer (weights as B fragments: Wc16, Wl16)
-  constexpr bool MXC2 = MXC && D == 2;     // two decoder cells, every product on the matrix pipe
-  constexpr int ZS = MXC ? MXC_ZS : RV_G;  // row stride of the gate pre-activations in `part`
-  constexpr int NC = MXC2 ? 0 : mxc_nc(W);
-  constexpr int NR = (ATT == 3 && D == 1 && NIT <= 8) ? 5 : 0;   // T_m <= 256 leaves ~50 registers: waves 1-7 keep NR more (k-step, gate) pairs of their share there
-  static_assert(!MX || D == 1 || ATT == 3, "two decoder cells run either on packed FMAs (ATT 0) or with everything on the matrix pipe (ATT 3)");
-  static_assert(NIT <= PERSIST_MAX_NIT && NIT * 256 <= (MXC ? part_floats_mxc(W) : part_floats(W)), "the alignment image (2 f16 parts x 32 NIT steps x 8 slots) must fit `part`");
-  static_assert(2 * 1024 * sizeof(_Float16) /* query image: 2 parts x [16 k-blocks][8 slots][8] f16 */ <= (8 * 4 * 2 * 16 * 4) * sizeof(float), "the query image must fit `fold`");
+  using T = PersistTraits<W, NIT, D, ATT>;
   extern __shared__ __align__(16) float dsm[];
   const PersistLds L(W, D, ATT);
   _Float16* xim = reinterpret_cast<_Float16*>(dsm + L.xim);   // MXC only
   float* pqs = dsm + L.pq;  float* vat = dsm + L.vat;   // ATT == 1 only
-  constexpr bool CACHE = MXC || persist_weight_cache(W, D);
   float* wcache = dsm + L.wcache;                        // CACHE only: rows 72 g + 104 + i of Wcat at [(8 g + i) * 512], g = 0..2
   float* attT = dsm + L.attT;  float* zb = dsm + L.zb;  float* cS = dsm + L.cS;
   float* qp = dsm + L.qp;  float* part = dsm + L.part;  float* ctxp = dsm + L.ctxp;  float* hcT = dsm + L.hcT;  float* att = dsm + L.att;
   float* ml = dsm + L.ml;  float* mg = dsm + L.mg;  float* lg = dsm + L.lg;  float* fold = dsm + L.fold;
   float* h0T = dsm + L.h0T;  float* cS1 = dsm + L.cS1;  float* b1s = dsm + L.b1s;  float* partU = ctxp;   // D == 2 only (FMA form: spans ctxp + fold)
-  // output layer weights, transposed to [v][k] (rows padded to 132 floats: the 8-lane groups of two outputs then read different banks)
-  constexpr int FCW = RV_U + 4;
   // (the matrix-pipe form takes the output layer from the Wl16 fragments: it only needs the bias here, and neither `qp` nor `att`)
-  __shared__ __align__(16) float s_wfc[(MXC ? 0 : RV_MAX_VOCAB * FCW) + RV_MAX_VOCAB];
-  __shared__ __align__(16) float s_nh[(D == 1 && !MXC) ? RV_MAX_VOCAB * FCW : 4];
-  constexpr int BFC = MXC ? 0 : RV_MAX_VOCAB * FCW;      // offset of b_fc in s_wfc
+  __shared__ __align__(16) float s_wfc[(T::MXC ? 0 : RV_MAX_VOCAB * T::FCW) + RV_MAX_VOCAB];
+  __shared__ __align__(16) float s_nh[(D == 1 && !T::MXC) ? RV_MAX_VOCAB * T::FCW : 4];
   __shared__ float s_lprob[WB];
   __shared__ int s_fin[WB], s_len[WB], s_parent[WB], s_tok[WB], s_allfin;
   __shared__ int s_qbig;                   // Bahdanau on the matrix pipe: some processed query of this step lies outside the fast form's range
@@ -1204,68 +1367,45 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
   const size_t row0 = (size_t)b * W;
   const int steps = d.L - 1;
 
-  // ---- the chunk's attention memory -> registers (once).  Keys: the 16 lanes of a stream hold TWO rows at a time, lanes 0-7
-  //      row sid + 32 (2p), lanes 8-15 row sid + 32 (2p + 1), 16 columns each, so that a score is an 8-lane reduction and one
-  //      pass over the registers scores two rows.  U' (the context side): every lane 8 columns of each of the stream's rows.
-  constexpr int NP = (NIT + 1) / 2;
   const int half = sub >> 3, s8 = sub & 7;
-  float4 kr[MXS ? 1 : NP][4], ur[MX ? 1 : NIT][2];
-  // MX: the same memory as MFMA B fragments (v_mfma_f32_16x16x32_f16), two f16 parts of the scaled values each.  Scores: wave
-  // wv owns the 16-step tiles wv + 8 c; lane (n = step l % 16 of the tile, kq = l / 16) holds key[t][32 ks + 8 kq + 0..7].
-  // Context: wave wv owns units 16 wv .. 16 wv + 15; lane (n = unit, kq) holds U'[32 ks + 8 kq + 0..7][unit].  The scales are
-  // powers of two from the weights (|key| <= sum_k |W_mem[k][u]| because |enc_out| <= 1): nothing can overflow f16, and what
-  // falls into its subnormals is below 2^-28 of the largest value the column can take.
-  constexpr int NTT = (2 * NIT + 7) / 8;
-  float4 kb[MXS ? NTT : 1][4][2], ub[MX ? NIT : 1][2];
+  float4 kr[T::MXS ? 1 : T::NP][4], ur[T::MX ? 1 : NIT][2];
+  float4 kb[T::MXS ? T::NTT : 1][4][2], ub[T::MX ? NIT : 1][2];
   unsigned livebits = 0;
   // the default form projects its chunk's memory itself when the call hands it enc_out (persist_project_memory); d.values is unused then
-  constexpr bool FUSE = ATT == 3 && D == 1;
   bool fused = false;
-  if constexpr (FUSE) {
+  if constexpr (T::FUSE) {
     fused = d.enc_rows != nullptr;
     if (fused) persist_project_memory<NIT>(d, b, dsm, kb, ub, livebits);
   }
   if (!fused) {
-  if constexpr (MXS) {
-    const float* cbase = d.values + (size_t)b * Tm * RV_E;
-    const uint8_t* mrow = d.mask + (size_t)b * Tm;
-    const int l16 = lane & 15, kq = lane >> 4, wv0 = tid >> 6;
+    if constexpr (T::MXS) persist_load_keys_mx<T>(d, b, tid, kb, livebits);
+    if constexpr (T::MX) {     // (inline) U' as B fragments: wave wv0 owns units 16 wv0 .. + 15
+      const float* cbase = d.values + (size_t)b * Tm * RV_E;
+      const int l16 = lane & 15, kq = lane >> 4, wv0 = tid >> 6;
 #pragma unroll
-    for (int c = 0; c < NTT; ++c) {
-      const int t = 16 * (wv0 + 8 * c) + l16, tc = min(t, Tm - 1);
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
+      for (int ks = 0; ks < NIT; ++ks) {
         float v[8];
-        *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(cbase + (size_t)tc * RV_E + 32 * ks + 8 * kq);
-        *reinterpret_cast<float4*>(v + 4) = *reinterpret_cast<const float4*>(cbase + (size_t)tc * RV_E + 32 * ks + 8 * kq + 4);
-        split_f16x8(v, d.mx_kscale, kb[c][ks][0], kb[c][ks][1]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = cbase[(size_t)min(32 * ks + 8 * kq + j, Tm - 1) * RV_E + RV_U + 16 * wv0 + l16];
+        split_f16x8(v, d.mx_uscale, ub[ks][0], ub[ks][1]);
       }
-      if (t < Tm && mrow[tc]) livebits |= 1u << c;          // _maybe_mask_score: padded steps never score
     }
   }
-  if constexpr (MX) {
-    const float* cbase = d.values + (size_t)b * Tm * RV_E;
-    const int l16 = lane & 15, kq = lane >> 4, wv0 = tid >> 6;
-#pragma unroll
-    for (int ks = 0; ks < NIT; ++ks) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = cbase[(size_t)min(32 * ks + 8 * kq + j, Tm - 1) * RV_E + RV_U + 16 * wv0 + l16];
-      split_f16x8(v, d.mx_uscale, ub[ks][0], ub[ks][1]);
-    }
-  }
-  }   // !fused
-  if constexpr (!MXS) {
+  // ---- (inline) forms that score on fp32 key rows.  Keys: the 16
+  //      lanes of a stream hold TWO rows at a time, lanes 0-7 row sid + 32 (2p), lanes 8-15 row sid + 32 (2p + 1), 16 columns each, so
+  //      that a score is an 8-lane reduction and one pass over the registers scores two rows.  U' (the context side, unless it sits
+  //      on the matrix pipe): every lane 8 columns of each of the stream's rows.
+  if constexpr (!T::MXS) {
     const float* cbase = d.values + (size_t)b * Tm * RV_E;
     const uint8_t* mrow = d.mask + (size_t)b * Tm;
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
+    for (int p = 0; p < T::NP; ++p) {
       const int tc = min(sid + 32 * (2 * p + half), Tm - 1);
       const float* q = cbase + (size_t)tc * RV_E + 16 * s8;
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         kr[p][m] = *reinterpret_cast<const float4*>(q + 4 * m);
-        if (BAH) {   // Bahdanau: tanh(k + pq) = 1 - 2 / (1 + exp2((k + pq) * 2 log2 e)): the keys carry the factor from here on
+        if (T::BAH) {   // Bahdanau: tanh(k + pq) = 1 - 2 / (1 + exp2((k + pq) * 2 log2 e)): the keys carry the factor from here on
           kr[p][m].x *= 2.0f * LOG2E; kr[p][m].y *= 2.0f * LOG2E; kr[p][m].z *= 2.0f * LOG2E; kr[p][m].w *= 2.0f * LOG2E;
         }
       }
@@ -1273,7 +1413,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int t = sid + 32 * it, tc = min(t, Tm - 1);
-      if constexpr (!MX) {
+      if constexpr (!T::MX) {
         const float* q = cbase + (size_t)tc * RV_E + RV_U + 4 * sub;
 #pragma unroll
         for (int m = 0; m < 2; ++m) ur[it][m] = *reinterpret_cast<const float4*>(q + 64 * m);
@@ -1281,76 +1421,56 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
       if (t < Tm && mrow[tc]) livebits |= 1u << it;       // _maybe_mask_score: padded steps never score
     }
   }
-  // Bahdanau on the matrix pipe: tanh(k + q) = 1 - 2 / (1 + 2^(k' + q')) with k' = 2 log2(e) k, and 2^(k' + q') = 2^k' . 2^q': the resident
-  // rows hold E_k = 2^k' (ONE exponential per key element for the whole decode), a step's queries come as E_q = 2^q', and a score element
-  // costs a multiply-add and ONE reciprocal instead of an exponential and a reciprocal -- the loop is bound by the transcendental rate
-  // (16 lanes per clock and CU).  Exact for |k'| <= 64 and |q'| <= 60 (the product stays a normal f32: |k| <= 22, |h . W_q| <= 20);
-  // a chunk with a larger key keeps k' and takes the two-transcendental form for all its steps, a step with a larger query takes
-  // 2^(log2(E_k) + q') -- both block-uniform choices, neither ever seen with weights of any plausible scale.
   bool kbig = false;
-  if constexpr (BAH && MXC) {
-    bool big = false;
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-        big = big || !(fabsf(kr[p][m].x) <= 64.f && fabsf(kr[p][m].y) <= 64.f && fabsf(kr[p][m].z) <= 64.f && fabsf(kr[p][m].w) <= 64.f);
-    kbig = __syncthreads_or(big ? 1 : 0) != 0;
-    if (!kbig) {
-#pragma unroll
-      for (int p = 0; p < NP; ++p)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          kr[p][m].x = __builtin_amdgcn_exp2f(kr[p][m].x); kr[p][m].y = __builtin_amdgcn_exp2f(kr[p][m].y);
-          kr[p][m].z = __builtin_amdgcn_exp2f(kr[p][m].z); kr[p][m].w = __builtin_amdgcn_exp2f(kr[p][m].w);
-        }
-    }
+  if constexpr (T::BAH && T::MXC) {          // Bahdanau beside the matrix pipe: the resident keys k' become E_k = 2^k' unless one of the chunk is out of range
+    kbig = __syncthreads_or(persist_keys_out_of_range<T>(kr) ? 1 : 0) != 0;
+    if (!kbig) persist_keys_to_exp2<T>(kr);
   }
   // ---- decoder initial state: zeros; start tokens; log_probs = [0, -inf, ...]
   // The cell's matrix-vector product of a step is taken on the PREVIOUS step's beams, before they are re-ordered (it only
   // needs their attention vector and h); the gate math then picks up the partial sums and the cell state of its parent
   // beam.  Zero initial state: partial sums 0, parents = identity.
-  if (!MXC) {
+  if (!T::MXC) {
     for (int i = tid; i < RV_U * WB; i += NT) attT[i] = 0.f;
     for (int i = tid; i < RV_U * WB; i += NT) hcT[i] = 0.f;
   }
   for (int i = tid; i < 2 * W * RV_U; i += NT) cS[i] = 0.f;
-  for (int i = tid; i < (MXC ? W * ZS : 4 * W * RV_G); i += NT) part[i] = 0.f;
-  if (MXC) for (int i = tid; i < (MXC2 ? 3072 : 2048); i += NT) dsm[L.xim + i] = 0.f;
+  for (int i = tid; i < (T::MXC ? W * T::ZS : 4 * W * RV_G); i += NT) part[i] = 0.f;
+  if (T::MXC) for (int i = tid; i < (T::MXC2 ? 3072 : 2048); i += NT) dsm[L.xim + i] = 0.f;
   if (D > 1) {
-    if (!MXC) for (int i = tid; i < RV_U * WB; i += NT) h0T[i] = 0.f;
+    if (!T::MXC) for (int i = tid; i < RV_U * WB; i += NT) h0T[i] = 0.f;
     for (int i = tid; i < 2 * W * RV_U; i += NT) cS1[i] = 0.f;
-    for (int i = tid; i < (MXC ? W * ZS : 3 * W * RV_G); i += NT) partU[i] = 0.f;
+    for (int i = tid; i < (T::MXC ? W * T::ZS : 3 * W * RV_G); i += NT) partU[i] = 0.f;
     b1s[tid] = bdec1[tid];
   }
-  if (!MXC) {
-    for (int i = tid; i < RV_U * V; i += NT) s_wfc[(i % V) * FCW + i / V] = d.W_fc[i];
-    if (D == 1) for (int i = tid; i < RV_U * V; i += NT) s_nh[(i % V) * FCW + i / V] = Nh[i] * (1.0f / LOG2E);   // applied to qp = h * log2(e), the row-major copy of h
+  if (!T::MXC) {
+    for (int i = tid; i < RV_U * V; i += NT) s_wfc[(i % V) * T::FCW + i / V] = d.W_fc[i];
+    if (D == 1) for (int i = tid; i < RV_U * V; i += NT) s_nh[(i % V) * T::FCW + i / V] = Nh[i] * (1.0f / LOG2E);   // applied to qp = h * log2(e), the row-major copy of h
   }
-  if (tid < V) s_wfc[BFC + tid] = d.b_fc[tid];
-  if (MXC) {   // the output layer's fragments
+  if (tid < V) s_wfc[T::BFC + tid] = d.b_fc[tid];
+  if (T::MXC) {   // the output layer's fragments
     const uint4* src = reinterpret_cast<const uint4*>(d.Wl16);
     uint4* dst = reinterpret_cast<uint4*>(dsm + L.wl16);
     for (int i = tid; i < 1024; i += NT) dst[i] = src[i];
   }
-  if (MXC2) {  // the first MXC2_CACHE of wave 0's end-of-step pairs (cell 0's product, image order)
+  if (T::MXC2) {  // the first MXC2_CACHE of wave 0's end-of-step pairs (cell 0's product, image order)
     const uint4* src = reinterpret_cast<const uint4*>(d.Wc16);
     uint4* dst = reinterpret_cast<uint4*>(wcache);
     for (int i = tid; i < MXC2_CACHE * 128; i += NT) dst[i] = src[i];
-  } else if (MXC) {   // wave 0's 32 pairs, then the last NC pairs of waves 1-7: 2 KB each, in image order
+  } else if (T::MXC) {   // wave 0's 32 pairs, then the last NC pairs of waves 1-7: 2 KB each, in image order
     const uint4* src = reinterpret_cast<const uint4*>(d.Wc16);
     uint4* dst = reinterpret_cast<uint4*>(wcache);
     for (int i = tid; i < 32 * 128; i += NT) dst[i] = src[i];
-    if constexpr (NC > 0)
-      for (int i = tid; i < 7 * NC * 128; i += NT) dst[32 * 128 + i] = src[(size_t)((1 + i / (NC * 128)) * 32 + 32 - NC) * 128 + i % (NC * 128)];
-  } else if (CACHE) {
+    if constexpr (T::NC > 0)
+      for (int i = tid; i < 7 * T::NC * 128; i += NT) dst[32 * 128 + i] = src[(size_t)((1 + i / (T::NC * 128)) * 32 + 32 - T::NC) * 128 + i % (T::NC * 128)];
+  } else if (T::CACHE) {
     for (int i = tid; i < 24 * (RV_G / 4); i += NT) {
       const int r = i >> 7, c = i & 127;
       *reinterpret_cast<float4*>(&wcache[r * RV_G + 4 * c]) =
           *reinterpret_cast<const float4*>(Wcat + (size_t)(72 * (r >> 3) + 104 + (r & 7)) * RV_G + 4 * c);
     }
   }
-  if (BAH && tid < RV_U) vat[tid] = d.v_att[tid] * (-2.0f * LOG2E);   // score = sum_j v_j tanh(.) = const - 2 sum_j v_j / (1 + exp(.)): softmax drops the constant
+  if (T::BAH && tid < RV_U) vat[tid] = d.v_att[tid] * (-2.0f * LOG2E);   // score = sum_j v_j tanh(.) = const - 2 sum_j v_j / (1 + exp(.)): softmax drops the constant
   if (tid < WB) {
     s_tok[tid] = (W == 1 && d.forced) ? persist_forced_tok(d, b, 0) : d.start_token; s_lprob[tid] = tid == 0 ? 0.f : -INFINITY;
     s_fin[tid] = 0; s_len[tid] = 0; s_parent[tid] = tid;
@@ -1360,12 +1480,8 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
   if (W == 1 && d.forced) for (int i = tid; i < RV_G; i += NT) zb[V * RV_G + i] = bdec[i];      // row V (V < RV_MAX_VOCAB: ravvent_hip.cpp, persist_form): no input row, persist_forced_tok
   __syncthreads();
 
-  uint4 rbh[NR > 0 ? NR : 1], rbl[NR > 0 ? NR : 1];       // pairs 32 - NC - NR .. 32 - NC - 1 of this wave, resident for the whole decode
-  if constexpr (NR > 0) {
-    const uint4* wimg = reinterpret_cast<const uint4*>(d.Wc16) + (size_t)(tid >> 6) * (32 * 128) + (tid & 63);
-#pragma unroll
-    for (int r = 0; r < NR; ++r) { rbh[r] = wimg[(2 * (32 - NC - NR + r)) * 64]; rbl[r] = wimg[(2 * (32 - NC - NR + r) + 1) * 64]; }
-  }
+  uint4 rbh[T::NR > 0 ? T::NR : 1], rbl[T::NR > 0 ? T::NR : 1];       // pairs 32 - NC - NR .. 32 - NC - 1 of this wave, resident for the whole decode
+  if constexpr (T::NR > 0) persist_load_resident_pairs<T>(d, tid, rbh, rbl);
   int done_steps = steps;
   const int tid0 = tid;
   for (int step = 0; step < steps; ++step) {
@@ -1375,7 +1491,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
     asm volatile("" : "+v"(tid));
     const int lane = tid & 63, wv = tid >> 6, sub = lane & 15, sid = tid >> 4, row = lane >> 4;
     RV_STAMP(d, step, 0);
-    if (BAH && MXC && tid == 0) s_qbig = 0;              // (set again, if at all, after the gates' barrier; last read before this step's last barrier)
+    if (T::BAH && T::MXC && tid == 0) s_qbig = 0;              // (set again, if at all, after the gates' barrier; last read before this step's last barrier)
     // ================= gates of this step: the cell product was taken at the end of the previous step on the parent beams
     const int cb = step & 1;                             // cell-state buffer holding the previous step's states
     // The chunk's resident rows are [keys | U'] = values . [W_mem | A_c] (A_c = the attention layer's context rows), built once
@@ -1396,13 +1512,13 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
       for (int u = 0; u < 8; ++u) pw[u] = *reinterpret_cast<const float4*>(wq + (size_t)u * RV_U);
     };
     // Bahdanau + matrix pipe: this wave's B fragments of W_q (its 16 columns, K = 128: 4 k-steps x 2 parts), requested before the gate math
-    uint4 wqf[(BAH && MXC) ? 8 : 1];
-    if constexpr (BAH && MXC) {
+    uint4 wqf[(T::BAH && T::MXC) ? 8 : 1];
+    if constexpr (T::BAH && T::MXC) {
       const uint4* wq = reinterpret_cast<const uint4*>(d.Wq16) + (size_t)wv * (8 * 64) + lane;
 #pragma unroll
       for (int j = 0; j < 8; ++j) wqf[j] = wq[j * 64];
-    } else if (BAH) wq_prefetch();
-    if constexpr (MXC) {
+    } else if (T::BAH) wq_prefetch();
+    if constexpr (T::MXC) {
       // W * 128 (beam, unit) items on 512 threads: waves 0-1 take two (W = 5).  Both items' operands are read first, then both are
       // computed, then stored: the second item rides in the first one's LDS and transcendental latencies instead of doubling the phase.
       // CELL 0: z = the end-of-step product of the PARENT beam + the token's row; CELL 1 (two cells): z = h_0 . W_1 of this beam (taken
@@ -1422,8 +1538,8 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
           const int w = ok[it] ? idx >> 7 : 0, u = idx & 127, pb = s_parent[w], tk = s_tok[w];
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            if constexpr (CELL == 0) z4[it][g] = part[pb * ZS + g * RV_U + u] + zb[tk * RV_G + g * RV_U + u];
-            else z4[it][g] = (part[w * ZS + g * RV_U + u] + partU[pb * ZS + g * RV_U + u]) + b1s[g * RV_U + u];
+            if constexpr (CELL == 0) z4[it][g] = part[pb * T::ZS + g * RV_U + u] + zb[tk * RV_G + g * RV_U + u];
+            else z4[it][g] = (part[w * T::ZS + g * RV_U + u] + partU[pb * T::ZS + g * RV_U + u]) + b1s[g * RV_U + u];
           }
           cp[it] = cst[cb * W * RV_U + pb * RV_U + u];
         }
@@ -1440,7 +1556,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
             _Float16* xq = xim + ((((TOP ? 1 : 2) * RV_U + u) >> 3) * 16 + mx_row(w)) * 8 + (u & 7);
             xq[0] = hi; xq[8] = lo;
           }
-          if constexpr (MXS && TOP) {   // the score query as MFMA A fragments: [k-block u / 8][row mx_row(w) (+ 1: low part)][u % 8] f16 of h log2(e) 2^14
+          if constexpr (T::MXS && TOP) {   // the score query as MFMA A fragments: [k-block u / 8][row mx_row(w) (+ 1: low part)][u % 8] f16 of h log2(e) 2^14
             const float sv = (hh * LOG2E) * 16384.f;
             const _Float16 hi = (_Float16)sv, lo = (_Float16)(sv - (float)hi);
             _Float16* qa = reinterpret_cast<_Float16*>(fold) + ((u >> 3) * 16 + mx_row(w)) * 8 + (u & 7);
@@ -1449,7 +1565,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         }
       };
       mxc_gates(std::integral_constant<int, 0>{});
-      if constexpr (MXC2) {
+      if constexpr (T::MXC2) {
         __syncthreads();
         // ---- cell 1's input product z_1a = h_0(new) . W_1 on the matrix pipe: every wave its 16 units x 4 gates, K = 128 (the h_0 segment
         //      of the image: k-steps 8..11), 16 pairs streamed from the W1c16 image through a window of 4; `part` (cell 0's z~, consumed by
@@ -1473,39 +1589,39 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
             if (p + 4 < 16) { bh[p & 3] = wimg[(2 * (p + 4)) * 64]; bl[p & 3] = wimg[(2 * (p + 4) + 1) * 64]; }
             __builtin_amdgcn_sched_barrier(0);
           }
-          constexpr int NI = W > 4 ? 2 : 1;
 #pragma unroll
           for (int g = 0; g < 4; ++g)
 #pragma unroll
-            for (int i = 0; i < NI; ++i)
-              if (kq + 4 * i < W) part[(kq + 4 * i) * ZS + RV_U * g + 16 * wv + l16] = (acc[g][2 * i] + acc[g][2 * i + 1]) * d.mx_c1descale;
+            for (int i = 0; i < T::NI; ++i)
+              if (kq + 4 * i < W) part[(kq + 4 * i) * T::ZS + RV_U * g + 16 * wv + l16] = (acc[g][2 * i] + acc[g][2 * i + 1]) * d.mx_c1descale;
         }
         __syncthreads();
         mxc_gates(std::integral_constant<int, 1>{});
       }
-    } else
-    for (int idx = tid; idx < W * RV_U; idx += NT) {       // K-group sums in fixed order, gate math, cell update
-      const int w = idx >> 7, u = idx & 127, pb = s_parent[w];
-      float z4[4];
+    } else {
+      for (int idx = tid; idx < W * RV_U; idx += NT) {       // K-group sums in fixed order, gate math, cell update
+        const int w = idx >> 7, u = idx & 127, pb = s_parent[w];
+        float z4[4];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int col = g * RV_U + u;
-        z4[g] = (((part[(0 * W + pb) * RV_G + col] + part[(1 * W + pb) * RV_G + col]) + part[(2 * W + pb) * RV_G + col]) +
-                   part[(3 * W + pb) * RV_G + col]) + zb[s_tok[w] * RV_G + col];
-      }
-      const float c2 = fmaf(rv_sigmoid(z4[1]), cS[cb * W * RV_U + pb * RV_U + u], rv_sigmoid(z4[0]) * dec_gate_tanh<ATT>(z4[2]));
-      const float hh = rv_sigmoid(z4[3]) * rv_tanh(c2);
-      cS[(cb ^ 1) * W * RV_U + idx] = c2;
-      if (D > 1) h0T[u * WB + w] = hh; else { hcT[u * WB + w] = hh; qp[idx] = hh * LOG2E; }
-      if constexpr (MXS) {     // the score query as MFMA A fragments: [k-block u / 8][row mx_row(w) (+ 1: low part)][u % 8] f16 of h log2(e) 2^14
-        const float sv = (hh * LOG2E) * 16384.f;
-        const _Float16 hi = (_Float16)sv, lo = (_Float16)(sv - (float)hi);
-        _Float16* qa = reinterpret_cast<_Float16*>(fold) + ((u >> 3) * 16 + mx_row(w)) * 8 + (u & 7);
-        qa[0] = hi; qa[8] = lo;
+        for (int g = 0; g < 4; ++g) {
+          const int col = g * RV_U + u;
+          z4[g] = (((part[(0 * W + pb) * RV_G + col] + part[(1 * W + pb) * RV_G + col]) + part[(2 * W + pb) * RV_G + col]) +
+                     part[(3 * W + pb) * RV_G + col]) + zb[s_tok[w] * RV_G + col];
+        }
+        const float c2 = fmaf(rv_sigmoid(z4[1]), cS[cb * W * RV_U + pb * RV_U + u], rv_sigmoid(z4[0]) * dec_gate_tanh<ATT>(z4[2]));
+        const float hh = rv_sigmoid(z4[3]) * rv_tanh(c2);
+        cS[(cb ^ 1) * W * RV_U + idx] = c2;
+        if (D > 1) h0T[u * WB + w] = hh; else { hcT[u * WB + w] = hh; qp[idx] = hh * LOG2E; }
+        if constexpr (T::MXS) {     // the score query as MFMA A fragments: [k-block u / 8][row mx_row(w) (+ 1: low part)][u % 8] f16 of h log2(e) 2^14
+          const float sv = (hh * LOG2E) * 16384.f;
+          const _Float16 hi = (_Float16)sv, lo = (_Float16)(sv - (float)hi);
+          _Float16* qa = reinterpret_cast<_Float16*>(fold) + ((u >> 3) * 16 + mx_row(w)) * 8 + (u & 7);
+          qa[0] = hi; qa[8] = lo;
+        }
       }
     }
     __syncthreads();
-    if (D > 1 && !MXC) {
+    if (D > 1 && !T::MXC) {
       // ---- second cell: z_1 = h_0(new) . W_1 + [h_1(prev) . U_1 of the parent beam, taken at the end of the previous step] + b_1
       {
         const int c4 = tid & 127, kg = tid >> 7;           // 32 rows of W_1 per K group
@@ -1521,16 +1637,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
           for (int i = 0; i < 8; ++i) wr[i] = *reinterpret_cast<const float4*>(wc + (size_t)(k0 + i) * RV_G);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            float xv[WB];
-            *reinterpret_cast<float4*>(xv) = *reinterpret_cast<const float4*>(&xk[(k0 + i) * WB]);
-            if (W > 4) *reinterpret_cast<float4*>(xv + 4) = *reinterpret_cast<const float4*>(&xk[(k0 + i) * WB + 4]);
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-              acc[w][0] = __builtin_elementwise_fma(f2{xv[w], xv[w]}, f2{wr[i].x, wr[i].y}, acc[w][0]);
-              acc[w][1] = __builtin_elementwise_fma(f2{xv[w], xv[w]}, f2{wr[i].z, wr[i].w}, acc[w][1]);
-            }
-          }
+          for (int i = 0; i < 8; ++i) beams_fma_row<W>(acc, wr[i], &xk[(k0 + i) * WB]);
         }
 #pragma unroll
         for (int w = 0; w < W; ++w)
@@ -1555,7 +1662,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
       }
       __syncthreads();
     }
-    if constexpr (BAH && MXC) {
+    if constexpr (T::BAH && T::MXC) {
       // ================= Bahdanau: processed query pq = h . W_q (BahdanauAttention.query_layer, no bias) on the matrix pipe: A = the h rows
       //   of the [ctx' | h] image (k-steps 4..7), B = this wave's 16 columns of W_q (Wq16, requested before the gate math): complete in the wave
       const int l16 = lane & 15, kq = lane >> 4;
@@ -1568,36 +1675,18 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         a1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, __builtin_bit_cast(h8, wqf[2 * ks + 1]), a1, 0, 0, 0);
       }
 #pragma unroll
-      for (int i = 0; i < (W > 4 ? 2 : 1); ++i)
+      for (int i = 0; i < T::NI; ++i)
         if (kq + 4 * i < W) {
-          const float qv = ((a0[2 * i] + a0[2 * i + 1]) + (a1[2 * i] + a1[2 * i + 1])) * (d.mx_qdescale * 2.0f * LOG2E);
+          const float qv = tile_pair_sum(a0, a1, i) * (d.mx_qdescale * 2.0f * LOG2E);
           pqs[(kq + 4 * i) * RV_U + 16 * wv + l16] = qv;                       // q' ...
           fold[(kq + 4 * i) * RV_U + 16 * wv + l16] = __builtin_amdgcn_exp2f(fminf(fmaxf(qv, -126.f), 126.f));   // ... and E_q = 2^q' (`fold` holds no query image here)
           if (!(fabsf(qv) <= 60.f)) s_qbig = 1;
         }
       __syncthreads();
-    } else if (BAH) {
+    } else if (T::BAH) {
       // ================= Bahdanau: processed query pq = h . W_q (BahdanauAttention.query_layer, no bias); thread = (4 columns,
       //   1 of 16 K groups of 8 rows), partial sums through `part` (free between the gates and the context phase)
-      const int d4 = tid & 31, kg = tid >> 5;
-      f2 acc[W][2];
-#pragma unroll
-      for (int w = 0; w < W; ++w) { acc[w][0] = f2{0.f, 0.f}; acc[w][1] = f2{0.f, 0.f}; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        float hv[WB];
-        *reinterpret_cast<float4*>(hv) = *reinterpret_cast<const float4*>(&hcT[(8 * kg + u) * WB]);
-        if (W > 4) *reinterpret_cast<float4*>(hv + 4) = *reinterpret_cast<const float4*>(&hcT[(8 * kg + u) * WB + 4]);
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          acc[w][0] = __builtin_elementwise_fma(f2{hv[w], hv[w]}, f2{pw[u].x, pw[u].y}, acc[w][0]);
-          acc[w][1] = __builtin_elementwise_fma(f2{hv[w], hv[w]}, f2{pw[u].z, pw[u].w}, acc[w][1]);
-        }
-      }
-#pragma unroll
-      for (int w = 0; w < W; ++w)
-        *reinterpret_cast<float4*>(&part[(kg * W + w) * RV_U + 4 * d4]) =
-            make_float4(acc[w][0].x, acc[w][0].y, acc[w][1].x, acc[w][1].y);
+      persist_h_times_rows<W>(part, hcT, pw, tid);
       __syncthreads();
       for (int i = tid; i < W * RV_U; i += NT) {
         const int w = i >> 7, col = i & 127;
@@ -1610,80 +1699,25 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
     }
     RV_STAMP(d, step, 2);
     // ================= (two cells) attention layer, h part: h . A_h ; thread = (4 columns, 1 of 16 K groups of 8 rows), one batch
-    if (D > 1 && !MXC) {
-      const int d4 = tid & 31, kg = tid >> 5;
-      f2 acc[W][2];
-#pragma unroll
-      for (int w = 0; w < W; ++w) { acc[w][0] = f2{0.f, 0.f}; acc[w][1] = f2{0.f, 0.f}; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        float hv[WB];
-        *reinterpret_cast<float4*>(hv) = *reinterpret_cast<const float4*>(&hcT[(8 * kg + u) * WB]);
-        if (W > 4) *reinterpret_cast<float4*>(hv + 4) = *reinterpret_cast<const float4*>(&hcT[(8 * kg + u) * WB + 4]);
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          acc[w][0] = __builtin_elementwise_fma(f2{hv[w], hv[w]}, f2{pw[u].x, pw[u].y}, acc[w][0]);
-          acc[w][1] = __builtin_elementwise_fma(f2{hv[w], hv[w]}, f2{pw[u].z, pw[u].w}, acc[w][1]);
-        }
-      }
-#pragma unroll
-      for (int w = 0; w < W; ++w)    // (the cell-product partial sums in `part` were consumed by the gates above)
-        *reinterpret_cast<float4*>(&part[(kg * W + w) * RV_U + 4 * d4]) =
-            make_float4(acc[w][0].x, acc[w][0].y, acc[w][1].x, acc[w][1].y);
-    }
+    if (D > 1 && !T::MXC) persist_h_times_rows<W>(part, hcT, pw, tid);   // (the cell-product partial sums in `part` were consumed by the gates above)
     RV_STAMP(d, step, 3);
 
-    if constexpr (MXS) {
+    if constexpr (T::MXS) {
       // ================= scores on the matrix pipe: rows = beams, columns = the 16 steps of a tile, K = 128 units.
       //   C/D map: lane l holds column l % 16 and rows 4 g + i (g = l / 16).  Beam w sits in rows mx_row(w), + 1 (its high and its low
       //   part: see mx_row), so that registers 0 + 1 hold beams 0-3 (one per 16-lane group, all 64 lanes busy) and 2 + 3 beams 4-7: the
       //   softmax below touches W <= 4 ? 1 : 2 values per tile.  A row of A only feeds its own row of C, so the rows of absent beams
       //   hold whatever the LDS image holds there, harmlessly.
-      constexpr int NI = W > 4 ? 2 : 1;
       const int l16 = lane & 15, kq = lane >> 4;
-      float sc[NTT][NI];
-      {
-        const _Float16* qa = reinterpret_cast<const _Float16*>(fold) + (kq * 16 + l16) * 8;    // row l16 of k-block 4 ks + kq
-        // the tiles in turns (against the low, then against the high part of the keys): an MFMA accumulates onto a result that is NTT
-        // instructions old, not onto the one issued just before it
-        f4v acc[NTT];
-#pragma unroll
-        for (int c = 0; c < NTT; ++c) acc[c] = f4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {                    // one k-step of the query at a time: 4 registers of A fragments live
-          const h8 a = *reinterpret_cast<const h8*>(qa + ks * 512);
-#pragma unroll
-          for (int c = 0; c < NTT; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, __builtin_bit_cast(h8, kb[c][ks][1]), acc[c], 0, 0, 0);
-#pragma unroll
-          for (int c = 0; c < NTT; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, __builtin_bit_cast(h8, kb[c][ks][0]), acc[c], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int c = 0; c < NTT; ++c) {
-          const bool live = (livebits >> c) & 1u;
-#pragma unroll
-          for (int i = 0; i < NI; ++i)
-            sc[c][i] = (live && kq + 4 * i < W) ? (acc[c][2 * i] + acc[c][2 * i + 1]) * d.mx_kdescale : -INFINITY;
-        }
-      }
+      float sc[T::NTT][T::NI];
+      persist_scores_mx<T>(d, tid, livebits, kb, sc, fold);
+
       RV_STAMP(d, step, 4);
       // ================= softmax over the chunk's T_m steps: per-wave (max, sum) of every beam, one fixed-order merge
       //   (raw v_exp_f32: arguments <= 0, a result below 2^-126 is an alignment of 0 either way)
-      float mrow_[NI];
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        float m = sc[0][i];
-#pragma unroll
-        for (int c = 1; c < NTT; ++c) m = fmaxf(m, sc[c][i]);
-        m = fmaxf(m, dpp<0xB1>(m)); m = fmaxf(m, dpp<0x4E>(m)); m = fmaxf(m, dpp<0x141>(m)); m = fmaxf(m, dpp<0x140>(m));
-        const float ms = m == -INFINITY ? 0.f : m;           // a wave without live steps for this beam: every term exp2(-inf) = 0
-        float lsum = 0.f;
-#pragma unroll
-        for (int c = 0; c < NTT; ++c) { sc[c][i] = __builtin_amdgcn_exp2f(sc[c][i] - ms); lsum += sc[c][i]; }
-        lsum = row16_sum(lsum);
-        mrow_[i] = m;
-        if (l16 == 0) { ml[wv * WB + kq + 4 * i] = m; ml[(8 + wv) * WB + kq + 4 * i] = lsum; }
-      }
+      float mrow_[T::NI];
+      persist_softmax_wave_mx<T>(tid, sc, mrow_, ml);
+
       RV_STAMP(d, step, 14);
       __syncthreads();
       RV_STAMP(d, step, 15);
@@ -1700,20 +1734,20 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         // alignments -> A fragments of the context product: [k-block t / 8][row mx_row(beam) (+ 1: low part)][t % 8] f16 of alpha 2^14 (in `part`,
         // idle between the gates and the cell product at the end of the step)
         _Float16* aa = reinterpret_cast<_Float16*>(part);
-        float Mg_[NI], rr_[NI];                                // (both beams' pairs fetched before either is used: one LDS round trip, not two)
+        float Mg_[T::NI], rr_[T::NI];                                // (both beams' pairs fetched before either is used: one LDS round trip, not two)
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
+        for (int i = 0; i < T::NI; ++i) {
           Mg_[i] = __int_as_float(__builtin_amdgcn_ds_bpermute(32 * (kq + 4 * i), __float_as_int(Mgl)));
           rr_[i] = __int_as_float(__builtin_amdgcn_ds_bpermute(32 * (kq + 4 * i), __float_as_int(rt)));
         }
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
+        for (int i = 0; i < T::NI; ++i) {
           const int beam = kq + 4 * i;                         // its merged pair sits in lanes 8 beam .. 8 beam + 7
           const float Mg = Mg_[i], rr = rr_[i];
           const bool nanrow = rr != rr && beam < W;
           const float f = (beam >= W || mrow_[i] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mrow_[i] - Mg) * rr * 16384.f;
 #pragma unroll
-          for (int c = 0; c < NTT; ++c) {
+          for (int c = 0; c < T::NTT; ++c) {
             const int t = 16 * (wv + 8 * c) + l16;
             if (t < 32 * NIT) {
               const float av = nanrow ? rr : sc[c][i] * f;
@@ -1728,198 +1762,197 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
       if (d.persist_align) tap_align_image<W, false>(d, part, b, step, tid);
       RV_STAMP(d, step, 5);
     } else {
-    // ================= scores from the resident key rows: lane w keeps beam w's score of the even row of a pair, lane 8 + w
-    //   that of the odd row
-    float sc[NP];
+      // ================= scores from the resident key rows: lane w keeps beam w's score of the even row of a pair, lane 8 + w
+      //   that of the odd row
+      float sc[T::NP];
 #pragma unroll
-    for (int p = 0; p < NP; ++p) sc[p] = -INFINITY;
-    if constexpr (BAH && MXC) {
-      // score_t log2(e) = const + sum_j v'_j / (1 + 2^(k'_tj + q'_j)) (see the resident rows above): MODE 1 = E_k . E_q + 1, one reciprocal;
-      // MODE 0 = the chunk kept k' (a key out of range); MODE 2 = this step has a query out of range
-      auto bah_scores = [&](auto mode_tag) {
-        constexpr int MODE = decltype(mode_tag)::value;
-        const float* qsrc = MODE == 1 ? fold : pqs;
+      for (int p = 0; p < T::NP; ++p) sc[p] = -INFINITY;
+      if constexpr (T::BAH && T::MXC) {
+        // score_t log2(e) = const + sum_j v'_j / (1 + 2^(k'_tj + q'_j)) (see the resident rows above): MODE 1 = E_k . E_q + 1, one reciprocal;
+        // MODE 0 = the chunk kept k' (a key out of range); MODE 2 = this step has a query out of range
+        auto bah_scores = [&](auto mode_tag) {
+          constexpr int MODE = decltype(mode_tag)::value;
+          const float* qsrc = MODE == 1 ? fold : pqs;
+#pragma unroll
+          for (int w = 0; w < W; ++w) {
+            float4 qv[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) qv[m] = *reinterpret_cast<const float4*>(&qsrc[w * RV_U + 16 * s8 + 4 * m]);
+#pragma unroll
+            for (int p = 0; p < T::NP; ++p) {
+              f2 pp = f2{0.f, 0.f};
+#pragma unroll
+              for (int m = 0; m < 4; ++m) {
+                const float4 vv = *reinterpret_cast<const float4*>(&vat[16 * s8 + 4 * m]);
+                auto el = [&](float k, float q) -> float {
+                  if constexpr (MODE == 1) return __builtin_amdgcn_rcpf(fmaf(k, q, 1.0f));
+                  else if constexpr (MODE == 0) return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(k + q));
+                  else return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(k) + q));
+                };
+                const float r0 = el(kr[p][m].x, qv[m].x), r1 = el(kr[p][m].y, qv[m].y), r2 = el(kr[p][m].z, qv[m].z), r3 = el(kr[p][m].w, qv[m].w);
+                pp = __builtin_elementwise_fma(f2{vv.x, vv.y}, f2{r0, r1}, pp);
+                pp = __builtin_elementwise_fma(f2{vv.z, vv.w}, f2{r2, r3}, pp);
+              }
+              float sw = pp.x + pp.y;
+              sw += dpp<0xB1>(sw); sw += dpp<0x4E>(sw); sw += dpp<0x141>(sw);      // the 8 lanes of this half row
+              const int it = 2 * p + half;
+              sc[p] = (s8 == w && it < NIT && ((livebits >> it) & 1u)) ? sw : sc[p];
+            }
+          }
+        };
+        if (kbig) bah_scores(std::integral_constant<int, 0>{});
+        else if (s_qbig) bah_scores(std::integral_constant<int, 2>{});
+        else bah_scores(std::integral_constant<int, 1>{});
+      } else {
 #pragma unroll
         for (int w = 0; w < W; ++w) {
           float4 qv[4];
 #pragma unroll
-          for (int m = 0; m < 4; ++m) qv[m] = *reinterpret_cast<const float4*>(&qsrc[w * RV_U + 16 * s8 + 4 * m]);
+          for (int m = 0; m < 4; ++m) qv[m] = *reinterpret_cast<const float4*>(&(T::BAH ? pqs : qp)[w * RV_U + 16 * s8 + 4 * m]);
 #pragma unroll
-          for (int p = 0; p < NP; ++p) {
+          for (int p = 0; p < T::NP; ++p) {
             f2 pp = f2{0.f, 0.f};
+            if (T::BAH) {
+              // Bahdanau, normalize = False: score_t = sum_j v_j tanh(keys_tj + pq_j); keys and pq carry 2 log2(e),
+              // v carries -2 log2(e): score * log2(e) = const + sum_j v'_j / (1 + exp2(k'_tj + pq'_j)), the constant cancels in the softmax.
+              // Raw v_exp_f32 (no denormal-range rescue: 1 + e does not see it; +inf gives rcp = 0 = tanh's limit)
 #pragma unroll
-            for (int m = 0; m < 4; ++m) {
-              const float4 vv = *reinterpret_cast<const float4*>(&vat[16 * s8 + 4 * m]);
-              auto el = [&](float k, float q) -> float {
-                if constexpr (MODE == 1) return __builtin_amdgcn_rcpf(fmaf(k, q, 1.0f));
-                else if constexpr (MODE == 0) return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(k + q));
-                else return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(k) + q));
-              };
-              const float r0 = el(kr[p][m].x, qv[m].x), r1 = el(kr[p][m].y, qv[m].y), r2 = el(kr[p][m].z, qv[m].z), r3 = el(kr[p][m].w, qv[m].w);
-              pp = __builtin_elementwise_fma(f2{vv.x, vv.y}, f2{r0, r1}, pp);
-              pp = __builtin_elementwise_fma(f2{vv.z, vv.w}, f2{r2, r3}, pp);
+              for (int m = 0; m < 4; ++m) {
+                const float4 vv = *reinterpret_cast<const float4*>(&vat[16 * s8 + 4 * m]);
+                const float r0 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(kr[p][m].x + qv[m].x));
+                const float r1 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(kr[p][m].y + qv[m].y));
+                const float r2 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(kr[p][m].z + qv[m].z));
+                const float r3 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(kr[p][m].w + qv[m].w));
+                pp = __builtin_elementwise_fma(f2{vv.x, vv.y}, f2{r0, r1}, pp);
+                pp = __builtin_elementwise_fma(f2{vv.z, vv.w}, f2{r2, r3}, pp);
+              }
+            } else {
+#pragma unroll
+              for (int m = 0; m < 4; ++m) {
+                pp = __builtin_elementwise_fma(f2{kr[p][m].x, kr[p][m].y}, f2{qv[m].x, qv[m].y}, pp);
+                pp = __builtin_elementwise_fma(f2{kr[p][m].z, kr[p][m].w}, f2{qv[m].z, qv[m].w}, pp);
+              }
             }
             float sw = pp.x + pp.y;
-            sw += dpp<0xB1>(sw); sw += dpp<0x4E>(sw); sw += dpp<0x141>(sw);      // the 8 lanes of this half row
+            sw += dpp<0xB1>(sw);    // quad_perm [1,0,3,2]
+            sw += dpp<0x4E>(sw);    // quad_perm [2,3,0,1]
+            sw += dpp<0x141>(sw);   // row_half_mirror: the other quad of this 8-lane half
             const int it = 2 * p + half;
             sc[p] = (s8 == w && it < NIT && ((livebits >> it) & 1u)) ? sw : sc[p];
           }
         }
-      };
-      if (kbig) bah_scores(std::integral_constant<int, 0>{});
-      else if (s_qbig) bah_scores(std::integral_constant<int, 2>{});
-      else bah_scores(std::integral_constant<int, 1>{});
-    } else
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-      float4 qv[4];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) qv[m] = *reinterpret_cast<const float4*>(&(BAH ? pqs : qp)[w * RV_U + 16 * s8 + 4 * m]);
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        f2 pp = f2{0.f, 0.f};
-        if (BAH) {
-          // Bahdanau, normalize = False: score_t = sum_j v_j tanh(keys_tj + pq_j); keys and pq carry 2 log2(e),
-          // v carries -2 log2(e): score * log2(e) = const + sum_j v'_j / (1 + exp2(k'_tj + pq'_j)), the constant cancels in the softmax.
-          // Raw v_exp_f32 (no denormal-range rescue: 1 + e does not see it; +inf gives rcp = 0 = tanh's limit)
-#pragma unroll
-          for (int m = 0; m < 4; ++m) {
-            const float4 vv = *reinterpret_cast<const float4*>(&vat[16 * s8 + 4 * m]);
-            const float r0 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(kr[p][m].x + qv[m].x));
-            const float r1 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(kr[p][m].y + qv[m].y));
-            const float r2 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(kr[p][m].z + qv[m].z));
-            const float r3 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(kr[p][m].w + qv[m].w));
-            pp = __builtin_elementwise_fma(f2{vv.x, vv.y}, f2{r0, r1}, pp);
-            pp = __builtin_elementwise_fma(f2{vv.z, vv.w}, f2{r2, r3}, pp);
-          }
-        } else {
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          pp = __builtin_elementwise_fma(f2{kr[p][m].x, kr[p][m].y}, f2{qv[m].x, qv[m].y}, pp);
-          pp = __builtin_elementwise_fma(f2{kr[p][m].z, kr[p][m].w}, f2{qv[m].z, qv[m].w}, pp);
-        }
-        }
-        float sw = pp.x + pp.y;
-        sw += dpp<0xB1>(sw);    // quad_perm [1,0,3,2]
-        sw += dpp<0x4E>(sw);    // quad_perm [2,3,0,1]
-        sw += dpp<0x141>(sw);   // row_half_mirror: the other quad of this 8-lane half
-        const int it = 2 * p + half;
-        sc[p] = (s8 == w && it < NIT && ((livebits >> it) & 1u)) ? sw : sc[p];
       }
-    }
-    RV_STAMP(d, step, 4);
-    // ================= softmax over the chunk's T_m steps: per-stream (max, sum), one fixed-order merge per beam
-    {
-      float m = -INFINITY;
+      RV_STAMP(d, step, 4);
+      // ================= softmax over the chunk's T_m steps: per-stream (max, sum), one fixed-order merge per beam
+      {
+        float m = -INFINITY;
 #pragma unroll
-      for (int p = 0; p < NP; ++p) m = fmaxf(m, sc[p]);
-      m = fmaxf(m, dpp<0x128>(m));                          // row_ror:8 -- the stream's other half
-      float lsum = 0.f;
+        for (int p = 0; p < T::NP; ++p) m = fmaxf(m, sc[p]);
+        m = fmaxf(m, dpp<0x128>(m));                          // row_ror:8 -- the stream's other half
+        float lsum = 0.f;
 #pragma unroll
-      for (int p = 0; p < NP; ++p) { sc[p] = exp2f(sc[p] - m); lsum += sc[p]; }   // stream without live rows: NaN, dropped below
-      lsum += dpp<0x128>(lsum);
-      if (sub < W) { ml[sid * WB + sub] = m; ml[(32 + sid) * WB + sub] = m == -INFINITY ? 0.f : lsum; }
-      __syncthreads();
-      if (wv < W) {
-        const float ms = lane < 32 ? ml[lane * WB + wv] : -INFINITY;
-        const float ls = lane < 32 ? ml[(32 + lane) * WB + wv] : 0.f;
-        const float Mg = wave_max_fast(ms);
-        const float tot = wave_sum_fast(ms == -INFINITY ? 0.f : ls * exp2f(ms - Mg));   // all-masked chunk: 0 -> NaN like the reference
-        if (lane == 0) { mg[wv] = Mg; mg[WB + wv] = Mg == -INFINITY ? __int_as_float(0x7fc00000) : 1.0f / tot; }
-      }
-      __syncthreads();
-      const float f = (s8 < W && m != -INFINITY) ? exp2f(m - mg[s8]) * mg[WB + s8] : 0.f;
-      const float nanv = (s8 < W && mg[WB + s8] != mg[WB + s8]) ? mg[WB + s8] : 0.f;
+        for (int p = 0; p < T::NP; ++p) { sc[p] = exp2f(sc[p] - m); lsum += sc[p]; }   // stream without live rows: NaN, dropped below
+        lsum += dpp<0x128>(lsum);
+        if (sub < W) { ml[sid * WB + sub] = m; ml[(32 + sid) * WB + sub] = m == -INFINITY ? 0.f : lsum; }
+        __syncthreads();
+        if (wv < W) {
+          const float ms = lane < 32 ? ml[lane * WB + wv] : -INFINITY;
+          const float ls = lane < 32 ? ml[(32 + lane) * WB + wv] : 0.f;
+          const float Mg = wave_max_fast(ms);
+          const float tot = wave_sum_fast(ms == -INFINITY ? 0.f : ls * exp2f(ms - Mg));   // all-masked chunk: 0 -> NaN like the reference
+          if (lane == 0) { mg[wv] = Mg; mg[WB + wv] = Mg == -INFINITY ? __int_as_float(0x7fc00000) : 1.0f / tot; }
+        }
+        __syncthreads();
+        const float f = (s8 < W && m != -INFINITY) ? exp2f(m - mg[s8]) * mg[WB + s8] : 0.f;
+        const float nanv = (s8 < W && mg[WB + s8] != mg[WB + s8]) ? mg[WB + s8] : 0.f;
 #pragma unroll
-      for (int p = 0; p < NP; ++p) sc[p] = m == -INFINITY ? nanv : sc[p] * f;   // alignments of beam s8 on this half's rows
-      if constexpr (!MX) {
-        if (d.persist_align && s8 < W) {     // tap (option persist_taps): the fp32 alignments the context sum below consumes
-          int t0 = sid, w0 = s8;
-          asm volatile("" : "+v"(t0), "+v"(w0));   // nothing of the tap is hoisted out of the step loop (no registers held while taps are off)
-          float* out = d.persist_align + ((size_t)step * d.B + b) * W * Tm;   // (uniform base, 32-bit lane offset)
+        for (int p = 0; p < T::NP; ++p) sc[p] = m == -INFINITY ? nanv : sc[p] * f;   // alignments of beam s8 on this half's rows
+        if constexpr (!T::MX) {
+          if (d.persist_align && s8 < W) {     // tap (option persist_taps): the fp32 alignments the context sum below consumes
+            int t0 = sid, w0 = s8;
+            asm volatile("" : "+v"(t0), "+v"(w0));   // nothing of the tap is hoisted out of the step loop (no registers held while taps are off)
+            float* out = d.persist_align + ((size_t)step * d.B + b) * W * Tm;   // (uniform base, 32-bit lane offset)
 #pragma unroll
-          for (int p = 0; p < NP; ++p) {
-            const int it = 2 * p + half, t = t0 + 32 * it;
-            if (it < NIT && t < Tm) out[(unsigned)(w0 * Tm + t)] = sc[p];
+            for (int p = 0; p < T::NP; ++p) {
+              const int it = 2 * p + half, t = t0 + 32 * it;
+              if (it < NIT && t < Tm) out[(unsigned)(w0 * Tm + t)] = sc[p];
+            }
           }
         }
       }
-    }
-    RV_STAMP(d, step, 5);
-    if constexpr (MX) {
-      // ================= (Bahdanau on the matrix pipe) the alignments this lane holds -- beam s8 on rows t = sid + 32 (2 p + half) -- as the
-      //   context product's A fragments: [k-block t / 8][row mx_row(beam) (+ 1: low part)][t % 8] f16 of alpha 2^14, in `part` (idle
-      //   between the gates and the cell product at the end of the step); padded steps carry an alignment of exactly 0
-      if (s8 < W) {
-        _Float16* aa = reinterpret_cast<_Float16*>(part);
+      RV_STAMP(d, step, 5);
+      if constexpr (T::MX) {
+        // ================= (Bahdanau on the matrix pipe) the alignments this lane holds -- beam s8 on rows t = sid + 32 (2 p + half) -- as the
+        //   context product's A fragments: [k-block t / 8][row mx_row(beam) (+ 1: low part)][t % 8] f16 of alpha 2^14, in `part` (idle
+        //   between the gates and the cell product at the end of the step); padded steps carry an alignment of exactly 0
+        if (s8 < W) {
+          _Float16* aa = reinterpret_cast<_Float16*>(part);
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          const int it = 2 * p + half, t = sid + 32 * it;
-          if (it < NIT) {
-            const float av = sc[p] * 16384.f;
-            const _Float16 hi = (_Float16)av, lo = (_Float16)(av - (float)hi);
-            _Float16* q = aa + ((t >> 3) * 16 + mx_row(s8)) * 8 + (t & 7);
-            q[0] = hi; q[8] = lo;
+          for (int p = 0; p < T::NP; ++p) {
+            const int it = 2 * p + half, t = sid + 32 * it;
+            if (it < NIT) {
+              const float av = sc[p] * 16384.f;
+              const _Float16 hi = (_Float16)av, lo = (_Float16)(av - (float)hi);
+              _Float16* q = aa + ((t >> 3) * 16 + mx_row(s8)) * 8 + (t & 7);
+              q[0] = hi; q[8] = lo;
+            }
           }
         }
-      }
-      __syncthreads();
-      if (d.persist_align) tap_align_image<W, true>(d, part, b, step, tid);
-    } else {
-    // ================= attention-layer context part = sum_t alpha_t * U'_t, one beam at a time (8-register accumulator)
-    {
-      float4* slab = reinterpret_cast<float4*>(fold + (size_t)wv * (4 * 2 * 16 * 4));
+        __syncthreads();
+        if (d.persist_align) tap_align_image<W, true>(d, part, b, step, tid);
+      } else {
+        // ================= attention-layer context part = sum_t alpha_t * U'_t, one beam at a time (8-register accumulator)
+        {
+          float4* slab = reinterpret_cast<float4*>(fold + (size_t)wv * (4 * 2 * 16 * 4));
 #pragma unroll
-      for (int w = 0; w < W; ++w) {
-        f2 a[4];
+          for (int w = 0; w < W; ++w) {
+            f2 a[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = f2{0.f, 0.f};
+            for (int i = 0; i < 4; ++i) a[i] = f2{0.f, 0.f};
 #pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-          const float al = row_bcast16(sc[it >> 1], 8 * (it & 1) + w);
+            for (int it = 0; it < NIT; ++it) {
+              const float al = row_bcast16(sc[it >> 1], 8 * (it & 1) + w);
 #pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            a[2 * m] = __builtin_elementwise_fma(f2{al, al}, f2{ur[it][m].x, ur[it][m].y}, a[2 * m]);
-            a[2 * m + 1] = __builtin_elementwise_fma(f2{al, al}, f2{ur[it][m].z, ur[it][m].w}, a[2 * m + 1]);
+              for (int m = 0; m < 2; ++m) {
+                a[2 * m] = __builtin_elementwise_fma(f2{al, al}, f2{ur[it][m].x, ur[it][m].y}, a[2 * m]);
+                a[2 * m + 1] = __builtin_elementwise_fma(f2{al, al}, f2{ur[it][m].z, ur[it][m].w}, a[2 * m + 1]);
+              }
+            }
+            // fold the wave's 4 streams (same columns) in ONE LDS round trip: every row parks its 2 column blocks, rows 0 and 1
+            // then sum one block each over the 4 streams in fixed order.  DS operations of one wave execute in issue order, so
+            // the reads see the writes without a wait in between.
+#pragma unroll
+            for (int m = 0; m < 2; ++m) slab[(row * 2 + m) * 16 + sub] = make_float4(a[2 * m].x, a[2 * m].y, a[2 * m + 1].x, a[2 * m + 1].y);
+            asm volatile("" ::: "memory");
+            if (row < 2) {
+              const float4 p0 = slab[(0 * 2 + row) * 16 + sub], p1 = slab[(1 * 2 + row) * 16 + sub];
+              const float4 p2 = slab[(2 * 2 + row) * 16 + sub], p3 = slab[(3 * 2 + row) * 16 + sub];
+              *reinterpret_cast<float4*>(&ctxp[(wv * W + w) * RV_U + 4 * sub + 64 * row]) =
+                  make_float4(((p0.x + p1.x) + p2.x) + p3.x, ((p0.y + p1.y) + p2.y) + p3.y, ((p0.z + p1.z) + p2.z) + p3.z, ((p0.w + p1.w) + p2.w) + p3.w);
+            }
+            asm volatile("" ::: "memory");
           }
         }
-        // fold the wave's 4 streams (same columns) in ONE LDS round trip: every row parks its 2 column blocks, rows 0 and 1
-        // then sum one block each over the 4 streams in fixed order.  DS operations of one wave execute in issue order, so
-        // the reads see the writes without a wait in between.
+        __syncthreads();
+        RV_STAMP(d, step, 6);
+        for (int i = tid; i < W * RV_U; i += NT) {              // ctx' (8 waves, fixed order) [+ h . A_h (16 K groups) = attention vector when D == 2]
+          const int w = i >> 7, col = i & 127;
+          float s0 = 0.f;
+          if (D > 1) {
 #pragma unroll
-        for (int m = 0; m < 2; ++m) slab[(row * 2 + m) * 16 + sub] = make_float4(a[2 * m].x, a[2 * m].y, a[2 * m + 1].x, a[2 * m + 1].y);
-        asm volatile("" ::: "memory");
-        if (row < 2) {
-          const float4 p0 = slab[(0 * 2 + row) * 16 + sub], p1 = slab[(1 * 2 + row) * 16 + sub];
-          const float4 p2 = slab[(2 * 2 + row) * 16 + sub], p3 = slab[(3 * 2 + row) * 16 + sub];
-          *reinterpret_cast<float4*>(&ctxp[(wv * W + w) * RV_U + 4 * sub + 64 * row]) =
-              make_float4(((p0.x + p1.x) + p2.x) + p3.x, ((p0.y + p1.y) + p2.y) + p3.y, ((p0.z + p1.z) + p2.z) + p3.z, ((p0.w + p1.w) + p2.w) + p3.w);
+            for (int g = 0; g < 16; ++g) s0 += part[(g * W + w) * RV_U + col];
+          }
+          float s1 = 0.f;
+#pragma unroll
+          for (int g = 0; g < 8; ++g) s1 += ctxp[(g * W + w) * RV_U + col];
+          const float av = s0 + s1;
+          att[i] = av; attT[col * WB + w] = av;
         }
-        asm volatile("" ::: "memory");
+        __syncthreads();
       }
     }
-    __syncthreads();
-    RV_STAMP(d, step, 6);
-    for (int i = tid; i < W * RV_U; i += NT) {              // ctx' (8 waves, fixed order) [+ h . A_h (16 K groups) = attention vector when D == 2]
-      const int w = i >> 7, col = i & 127;
-      float s0 = 0.f;
-      if (D > 1) {
-#pragma unroll
-        for (int g = 0; g < 16; ++g) s0 += part[(g * W + w) * RV_U + col];
-      }
-      float s1 = 0.f;
-#pragma unroll
-      for (int g = 0; g < 8; ++g) s1 += ctxp[(g * W + w) * RV_U + col];
-      const float av = s0 + s1;
-      att[i] = av; attT[col * WB + w] = av;
-    }
-    __syncthreads();
-    
-    }
-    }
-    if constexpr (MX) {
+    if constexpr (T::MX) {
       const int l16 = lane & 15, kq = lane >> 4;
-      constexpr int NI = W > 4 ? 2 : 1;
       // ================= attention-layer context part = sum_t alpha_t U'_t on the matrix pipe: rows = beams, this wave's 16 units,
       //   K = the chunk's steps; the product is complete in one wave (no partial sums to merge)
       {
@@ -1933,15 +1966,15 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         }
         float acc[2];                                      // beams kq, kq + 4
 #pragma unroll
-        for (int i = 0; i < 2; ++i) acc[i] = (a0[2 * i] + a0[2 * i + 1]) + (a1[2 * i] + a1[2 * i + 1]);
+        for (int i = 0; i < 2; ++i) acc[i] = tile_pair_sum(a0, a1, i);
         RV_STAMP(d, step, 6);
         const int col = 16 * wv + l16;
 #pragma unroll
-        for (int i = 0; i < NI; ++i)
+        for (int i = 0; i < T::NI; ++i)
           if (kq + 4 * i < W) {
             const float av = acc[i] * d.mx_udescale;
-            if constexpr (!MXC) att[(kq + 4 * i) * RV_U + col] = av;
-            if constexpr (MXC) {   // ctx' as A fragments of the cell product: k = col, ctx' . mx_uscale (= acc 2^-14, below 2^14) in two f16 parts
+            if constexpr (!T::MXC) att[(kq + 4 * i) * RV_U + col] = av;
+            if constexpr (T::MXC) {   // ctx' as A fragments of the cell product: k = col, ctx' . mx_uscale (= acc 2^-14, below 2^14) in two f16 parts
               const float sv = acc[i] * (1.0f / 16384.f);
               const _Float16 hi = (_Float16)sv, lo = (_Float16)(sv - (float)hi);
               _Float16* xq = xim + ((col >> 3) * 16 + mx_row(kq + 4 * i)) * 8 + (col & 7);
@@ -1953,7 +1986,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
     }
     RV_STAMP(d, step, 8);
     // ================= logits = attention . W_fc + b_fc
-    if constexpr (MXC) {
+    if constexpr (T::MXC) {
       // Matrix-pipe cell product: the logits are ONE 16-column tile over the beams' [ctx' | h] image (the cell product's A operand),
       // 24 MFMAs that wave 0 takes alone, B fragments from the LDS copy of the 16 KB Wl16 image (from L2 the same reads queue behind
       // the other waves' weight stream: 4.4 k cycles) -- the other waves go straight on to the cell product (they only need ctx' and
@@ -1977,14 +2010,12 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         }
         float acc[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) acc[i] = (a0[2 * i] + a0[2 * i + 1]) + (a1[2 * i] + a1[2 * i + 1]);
-        constexpr int NI = W > 4 ? 2 : 1;               // C/D: lane (column v = l16, kq) holds beams kq + 4 i
+        for (int i = 0; i < 2; ++i) acc[i] = tile_pair_sum(a0, a1, i);
 #pragma unroll
-        for (int i = 0; i < NI; ++i)
-          if (kq + 4 * i < W && l16 < V) lg[(kq + 4 * i) * RV_MAX_VOCAB + l16] = acc[i] * d.mx_ldescale + s_wfc[BFC + l16];
+        for (int i = 0; i < T::NI; ++i)
+          if (kq + 4 * i < W && l16 < V) lg[(kq + 4 * i) * RV_MAX_VOCAB + l16] = acc[i] * d.mx_ldescale + s_wfc[T::BFC + l16];
       }
     } else {
-    {
       const int o8 = tid >> 3, s8 = tid & 7;
       if (o8 < W * V) {                                     // whole 8-lane groups take the branch together
         const int w = o8 / V, v = o8 % V;
@@ -1993,7 +2024,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           const float4 a4 = *reinterpret_cast<const float4*>(&att[w * RV_U + 16 * s8 + 4 * m]);
-          const float4 w4 = *reinterpret_cast<const float4*>(&s_wfc[v * FCW + 16 * s8 + 4 * m]);
+          const float4 w4 = *reinterpret_cast<const float4*>(&s_wfc[v * T::FCW + 16 * s8 + 4 * m]);
           pp = __builtin_elementwise_fma(f2{a4.x, a4.y}, f2{w4.x, w4.y}, pp);
           pp = __builtin_elementwise_fma(f2{a4.z, a4.w}, f2{w4.z, w4.w}, pp);
         }
@@ -2001,7 +2032,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
 #pragma unroll
           for (int m = 0; m < 4; ++m) {
             const float4 a4 = *reinterpret_cast<const float4*>(&qp[w * RV_U + 16 * s8 + 4 * m]);
-            const float4 w4 = *reinterpret_cast<const float4*>(&s_nh[v * FCW + 16 * s8 + 4 * m]);
+            const float4 w4 = *reinterpret_cast<const float4*>(&s_nh[v * T::FCW + 16 * s8 + 4 * m]);
             pp = __builtin_elementwise_fma(f2{a4.x, a4.y}, f2{w4.x, w4.y}, pp);
             pp = __builtin_elementwise_fma(f2{a4.z, a4.w}, f2{w4.z, w4.w}, pp);
           }
@@ -2010,10 +2041,9 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         p += dpp<0xB1>(p);    // quad_perm [1,0,3,2]
         p += dpp<0x4E>(p);    // quad_perm [2,3,0,1]
         p += dpp<0x141>(p);   // row_half_mirror: the other quad of this 8-lane group
-        if (s8 == 0) lg[w * RV_MAX_VOCAB + v] = p + s_wfc[BFC + v];
+        if (s8 == 0) lg[w * RV_MAX_VOCAB + v] = p + s_wfc[T::BFC + v];
       }
-    }
-    __syncthreads();
+      __syncthreads();
     }
     RV_STAMP(d, step, 9);
     // ================= beam step (wave 0): log-softmax, finished masking, top-W, bookkeeping
@@ -2097,7 +2127,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
     // ================= next step's cell product on THIS step's beams: z~[w] = [attention_w | h_w] . Wcat (the beam step above
     //   only decides which z~ each new beam inherits).  thread = (4 gate columns c4, K group kg); waves 1-7 start at once,
     //   wave 0 joins after the beam step, so K group 0 (waves 0-1) is the short one: rows 0-39 | 40-111 | 112-183 | 184-255.
-    if constexpr (MXC2) {
+    if constexpr (T::MXC2) {
       // Two cells on the matrix pipe.  End of the step, on THIS step's beams (the beam step only decides which rows each new beam inherits):
       //   cell 0's next product  z~_0 = [ctx' | h_1 | h_0] . [W_a ; A_h W_a ; U_0]   (K = 384: jobs 0..47, pair j = 4 ks + g of the Wc16 image)
       //   cell 1's recurrent one z~_1 = h_1 . U_1                                     (K = 128: jobs 48..63, pairs 16..31 of the W1c16 image)
@@ -2110,7 +2140,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         const uint4* w0img = reinterpret_cast<const uint4*>(d.Wc16) + (size_t)wv * (48 * 128) + lane;
         const uint4* w1img = reinterpret_cast<const uint4*>(d.W1c16) + (size_t)wv * (32 * 128) + 16 * 128 + lane;
         const _Float16* xa = xim + (kq * 16 + l16) * 8;
-        constexpr int NI = W > 4 ? 2 : 1, NB = 4;
+        constexpr int NB = 4;
         f4v acc[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) acc[g] = f4v{0.f, 0.f, 0.f, 0.f};
@@ -2125,8 +2155,8 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
 #pragma unroll
-            for (int i = 0; i < NI; ++i)
-              if (kq + 4 * i < W) dst[(kq + 4 * i) * ZS + RV_U * g + 16 * wv + l16] = (acc[g][2 * i] + acc[g][2 * i + 1]) * scale;
+            for (int i = 0; i < T::NI; ++i)
+              if (kq + 4 * i < W) dst[(kq + 4 * i) * T::ZS + RV_U * g + 16 * wv + l16] = (acc[g][2 * i] + acc[g][2 * i + 1]) * scale;
             acc[g] = f4v{0.f, 0.f, 0.f, 0.f};
           }
         };
@@ -2161,7 +2191,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         else stream(std::integral_constant<int, 0>{});
         RV_STAMP_W1(d, step, 13);
       }
-    } else if constexpr (MXC) {
+    } else if constexpr (T::MXC) {
       // Matrix pipe: z~ [beams x 512] = x [beams x 256] . Wcat2 as split-f16 MFMAs.  Wave wv owns units 16 wv .. 16 wv + 15 of all
       // four gates over the whole K (no partial sums to merge): 32 (k-step, gate) pairs, each one B fragment pair (high, low
       // part; 2 KB per wave) streamed from the Wc16 image through a rolling window of NB pairs, the last NC pairs from LDS.  A = the
@@ -2171,7 +2201,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         const int l16 = lane & 15, kq = lane >> 4;
         const uint4* wimg = reinterpret_cast<const uint4*>(d.Wc16) + (size_t)wv * (32 * 128) + lane;   // pair p, part q: [(2 p + q) * 64]
         const _Float16* xa = xim + (kq * 16 + l16) * 8;      // k-step ks: + 512 ks (both parts of a beam in rows mx_row, + 1)
-        constexpr int NS = 32 - NC - NR, NB = 4;             // streamed pairs
+        constexpr int NS = 32 - T::NC - T::NR, NB = 4;             // streamed pairs
         f4v acc[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) acc[g] = f4v{0.f, 0.f, 0.f, 0.f};
@@ -2211,9 +2241,9 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
 #pragma unroll
           for (int i = 0; i < NB; ++i) { bh[i] = wimg[(2 * i) * 64]; bl[i] = wimg[(2 * i + 1) * 64]; }
           {                                                  // the on-chip pairs first: the first requests are in flight meanwhile
-            const uint4* wc = reinterpret_cast<const uint4*>(wcache) + 32 * 128 + (size_t)(wv - 1) * (NC * 128) + lane;
+            const uint4* wc = reinterpret_cast<const uint4*>(wcache) + 32 * 128 + (size_t)(wv - 1) * (T::NC * 128) + lane;
 #pragma unroll
-            for (int c = 0; c < NC; ++c) mm(32 - NC + c, wc[(2 * c) * 64], wc[(2 * c + 1) * 64]);
+            for (int c = 0; c < T::NC; ++c) mm(32 - T::NC + c, wc[(2 * c) * 64], wc[(2 * c + 1) * 64]);
           }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -2223,22 +2253,20 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
             if (p + NB < NS) { bh[p % NB] = wimg[(2 * (p + NB)) * 64]; bl[p % NB] = wimg[(2 * (p + NB) + 1) * 64]; }
             __builtin_amdgcn_sched_barrier(0);
           }
-          if constexpr (NR > 0) {                            // the pairs that live in registers
+          if constexpr (T::NR > 0) {                            // the pairs that live in registers
 #pragma unroll
-            for (int r = 0; r < NR; ++r) mm(NS + r, rbh[r], rbl[r]);
+            for (int r = 0; r < T::NR; ++r) mm(NS + r, rbh[r], rbl[r]);
           }
         }
         // C/D: lane (column l16, kq) holds rows 4 kq + i: registers 0 + 1 = beam kq (high- and low-part rows), 2 + 3 = beam kq + 4
-        constexpr int NI = W > 4 ? 2 : 1;
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
-          for (int i = 0; i < NI; ++i)
-            if (kq + 4 * i < W) part[(kq + 4 * i) * ZS + RV_U * g + 16 * wv + l16] = (acc[g][2 * i] + acc[g][2 * i + 1]) * d.mx_cdescale;
+          for (int i = 0; i < T::NI; ++i)
+            if (kq + 4 * i < W) part[(kq + 4 * i) * T::ZS + RV_U * g + 16 * wv + l16] = (acc[g][2 * i] + acc[g][2 * i + 1]) * d.mx_cdescale;
         RV_STAMP_W1(d, step, 13);
       }
-    } else
-    if (step + 1 < steps) {
+    } else if (step + 1 < steps) {
       const int c4 = tid & 127, kg = tid >> 7;
       // one cell: rows 0-39 | 40-111 | 112-183 | 184-255;  two cells: 64 rows each here, and K groups 1-3 also take the
       // second cell's recurrent product below (48 / 40 / 40 rows)
@@ -2247,17 +2275,8 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
 #pragma unroll
       for (int w = 0; w < W; ++w) { acc[w][0] = f2{0.f, 0.f}; acc[w][1] = f2{0.f, 0.f}; }
       const float* wc = Wcat + 4 * c4;
-      auto fma_row = [&](const float4& wv, const float* xrow) {
-        float xv[WB];
-        *reinterpret_cast<float4*>(xv) = *reinterpret_cast<const float4*>(xrow);
-        if (W > 4) *reinterpret_cast<float4*>(xv + 4) = *reinterpret_cast<const float4*>(xrow + 4);
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          acc[w][0] = __builtin_elementwise_fma(f2{xv[w], xv[w]}, f2{wv.x, wv.y}, acc[w][0]);
-          acc[w][1] = __builtin_elementwise_fma(f2{xv[w], xv[w]}, f2{wv.z, wv.w}, acc[w][1]);
-        }
-      };
-      const bool cached = CACHE && kg > 0;                  // wave-uniform: K groups 1-3 find their last 8 rows in LDS
+      auto fma_row = [&](const float4& wr, const float* xrow) { beams_fma_row<W>(acc, wr, xrow); };
+      const bool cached = T::CACHE && kg > 0;                  // wave-uniform: K groups 1-3 find their last 8 rows in LDS
       const int ke_g = cached ? ke - 8 : ke;                // rows streamed from L2
       if (cached) {                                         // the rows that are already on chip
         const int kc = ke - 8;
@@ -2291,16 +2310,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
           for (int i = 0; i < 8; ++i) wr[i] = *reinterpret_cast<const float4*>(wu + (size_t)(k0 + i) * RV_G);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            float xv[WB];
-            *reinterpret_cast<float4*>(xv) = *reinterpret_cast<const float4*>(&hcT[(k0 + i) * WB]);
-            if (W > 4) *reinterpret_cast<float4*>(xv + 4) = *reinterpret_cast<const float4*>(&hcT[(k0 + i) * WB + 4]);
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-              acc[w][0] = __builtin_elementwise_fma(f2{xv[w], xv[w]}, f2{wr[i].x, wr[i].y}, acc[w][0]);
-              acc[w][1] = __builtin_elementwise_fma(f2{xv[w], xv[w]}, f2{wr[i].z, wr[i].w}, acc[w][1]);
-            }
-          }
+          for (int i = 0; i < 8; ++i) beams_fma_row<W>(acc, wr[i], &hcT[(k0 + i) * WB]);
         }
 #pragma unroll
         for (int w = 0; w < W; ++w)

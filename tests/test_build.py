@@ -15,17 +15,17 @@ CSRC = os.path.join(ROOT, "ravvent-basecaller_amd", "csrc")
 
 # kernel-name regex -> max bytes of scratch per lane
 LIMITS = {
-    r"k_dec_persistILi5ELi11ELi1ELi0E": 64,      # C3: Luong, beam 5, T_m <= 352 (36 B today)
+    r"k_dec_persistILi5ELi11ELi1ELi0E": 64,      # C3: Luong, beam 5, T_m <= 352 (40 B today)
     r"k_dec_persistILi5ELi8ELi1ELi0E": 0,        # R: T_m <= 256
-    r"k_dec_persistILi5ELi11ELi1ELi1E": 64,      # C3 with Bahdanau (28 B today)
+    r"k_dec_persistILi5ELi11ELi1ELi1E": 64,      # C3 with Bahdanau (44 B today)
     r"k_dec_persistILi5ELi11ELi1ELi2E": 24,      # C3 with the attention on the matrix pipe (20 B today; 100 B in round 2)
     r"k_dec_persistILi5ELi8ELi1ELi2E": 0,        # R
     r"k_dec_persistILi5ELi11ELi1ELi3E": 8,       # C3, attention, cell product and output layer on the matrix pipe: the default since round 3 (0 B today)
     r"k_dec_persistILi5ELi8ELi1ELi3E": 0,        # R, the same
-    r"k_dec_persistILi5ELi11ELi1ELi4E": 192,     # C3 with Bahdanau scores on the VALU and everything else on the matrix pipe, the Bahdanau default since round 4: 176 B today,
+    r"k_dec_persistILi5ELi11ELi1ELi4E": 192,     # C3 with Bahdanau scores on the VALU and everything else on the matrix pipe, the Bahdanau default since round 4: 180 B today,
                                                  # of which the step loop touches 56 (three U' fragments reloaded in the context phase); the rest is the prologue's (keys -> 2^k')
-    r"k_dec_persistILi5ELi8ELi1ELi4E": 96,       # R, the same (60-76 B: single registers of the unrolled score loop)
-    r"k_dec_persistILi5ELi11ELi2ELi3E": 96,      # C3 with two decoder cells on the matrix pipe, the enc3/dec2 default since round 4 (80 B today: five U' fragments reloaded in the context phase)
+    r"k_dec_persistILi5ELi8ELi1ELi4E": 96,       # R, the same (92 B today: single registers of the unrolled score loop)
+    r"k_dec_persistILi5ELi11ELi2ELi3E": 96,      # C3 with two decoder cells on the matrix pipe, the enc3/dec2 default since round 4 (84 B today: five U' fragments reloaded in the context phase)
     r"k_dec_persistILi5ELi8ELi2ELi3E": 0,        # R, the same
     r"k_lstm_rec_projILi2ELi[012]EE": 0,         # C3 fused recurrence + projection (f32, split-bf16 and split-f16 MFMA forms)
     r"k_gemm_mem_split3": 0,                     # attention-memory projection on split-f16 MFMAs (compute waves + loader waves)
