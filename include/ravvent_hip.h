@@ -172,6 +172,40 @@ int rv_beam_search_collect_all(rv_handle h, int32_t ticket, const RvBeams* out, 
 int rv_beam_search_submit_all_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e,
                                   int32_t W, int32_t L, const RvBeams* d_out, int32_t* ticket);
 
+/* Moves: where in the signal each called base lies.  Every decode step computes attention weights a_t over the chunk's
+ * T_m = T_r + T_e memory positions (the raw samples' encoder rows first, then the events'); a moves call reduces them on chip to a few
+ * numbers per step and beam row and back-traces those through the beam like the tokens -- no [.., T_m] tensor leaves the chip.
+ * `out` is rv_beam_search_all's, with its rules (tokens and scores required) and its bytes; `moves` holds six outputs [B, L-1, W], beam
+ * innermost, each of which may be NULL, but not all of them.  For column t < lengths[b, w] of hypothesis w, with the weights of the
+ * step that produced tokens[b, t, w]:
+ *   raw_pos     f32  sum a_t t / sum a_t over the raw segment t < T_r, in samples of the chunk (correctly rounded fp32 division);
+ *                    -1 when raw_mass is 0 (event mode, or every raw position padding)
+ *   raw_mass    f32  sum a_t over the raw segment (T_r = T_m in raw mode, 0 in event mode)
+ *   event_pos   f32  the same over the event segment T_r <= t < T_m, in event-index units (t - T_r); -1 when event_mass is 0
+ *   event_mass  f32
+ *   peak        i32  the first memory index t in [0, T_m) holding the largest weight
+ *   peak_weight f32  that weight
+ * A chunk that is padding from end to end has NaN weights: NaN in the five float outputs, -1 in peak.  Columns t >= lengths[b, w],
+ * those >= S included: masses and peak_weight 0, positions -1, peak -1.  B == 0 or L == 1 launches nothing.  Limits, RV_ESTATE rules
+ * and messages are those of rv_beam_search_all*; like an all-beams slab a moves slab is never coalesced, never replayed as a
+ * "slab_graph" and runs on a slab context of its own.  The per-step decode launches its steps directly for such a call (no decode
+ * graph); where its single-pass attend runs the steps (Luong, beam <= 5) that kernel still does, so that the beam keeps its bytes, and
+ * the weights of the records are those of a second, two-pass attend launch on the same rows: they differ from what the step's context
+ * consumed by fp32 re-association (~1e-7), and the call costs 1.6 x an all-beams call there (1.1 x on the persistent decode).  Profile scope "dec_finalize_moves" (behind "dec_finalize_beams").  rv_get_tensor "step_moves": the records [S, B, W, 6]
+ * (raw_mass, raw_m1, event_mass, event_m1, peak_weight, peak_t) of the last moves call on the handle's own context, indexed by the beam
+ * row the step's attention ran on; rows of a chunk beyond its chunk_steps are not written.
+ *   rv_beam_search_moves           host inputs and outputs (records and staging are allocated on a slab context's first such call)
+ *   rv_beam_search_moves_dev       device inputs and outputs (`d_out`, `d_moves`: host structs of device addresses)
+ *   rv_beam_search_submit_moves / rv_beam_search_collect_moves      asynchronous, host buffers (collect takes both structs) */
+typedef struct RvMoves { float* raw_pos; float* raw_mass; float* event_pos; float* event_mass; int32_t* peak; float* peak_weight; } RvMoves;
+int rv_beam_search_moves(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                         const RvBeams* out, const RvMoves* moves, int32_t* S_out);
+int rv_beam_search_moves_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
+                             int32_t L, const RvBeams* d_out, const RvMoves* d_moves, int32_t* S_out);
+int rv_beam_search_submit_moves(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
+                                int32_t L, int32_t* ticket);
+int rv_beam_search_collect_moves(rv_handle h, int32_t ticket, const RvBeams* out, const RvMoves* moves, int32_t* S_out);
+
 /* Coalesced slabs (option "coalesce" = n >= 2, or its default when it chooses so): up to n consecutively submitted slabs of the default
  * streamed path -- beam search, persistent decode, matrix-pipe recurrences, "profile" 0, no taps, "slab_graph" 0 -- are decoded as ONE
  * internal call of sum(B) chunks on a group context (buffers for n x max_batch chunks; ceil(async_depth / n) of them in ordinary use, one

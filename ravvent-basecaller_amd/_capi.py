@@ -21,6 +21,12 @@ class CRvBeams(ctypes.Structure):
     _fields_ = [("tokens", c_void_p), ("scores", c_void_p), ("path_scores", c_void_p), ("log_probs", c_void_p), ("lengths", c_void_p)]
 
 
+class CRvMoves(ctypes.Structure):
+    """RvMoves (include/ravvent_hip.h): the six outputs [B, L-1, W] of the rv_beam_search_moves* calls; each may be None, not all."""
+    _fields_ = [("raw_pos", c_void_p), ("raw_mass", c_void_p), ("event_pos", c_void_p), ("event_mass", c_void_p), ("peak", c_void_p),
+                ("peak_weight", c_void_p)]
+
+
 class CRvScore(ctypes.Structure):
     """RvScore (include/ravvent_hip.h): the outputs of rv_teacher_forced* / rv_score_logits; each may be None."""
     _fields_ = [("nll", c_void_p), ("nll_sum", c_void_p), ("n_labels", c_void_p), ("n_match", c_void_p), ("n_counted", c_void_p)]
@@ -30,6 +36,7 @@ class CRvScore(ctypes.Structure):
 _F, _I = POINTER(c_float), POINTER(c_int32)
 _B = POINTER(CRvBeams)
 _S = POINTER(CRvScore)
+_M = POINTER(CRvMoves)
 SYMBOLS = [
     ("rv_abi_version", c_int32, []),
     ("rv_create", c_int32, [POINTER(CRvConfig), POINTER(c_void_p)]),
@@ -51,6 +58,10 @@ SYMBOLS = [
     ("rv_beam_search_submit_all", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _I]),
     ("rv_beam_search_collect_all", c_int32, [c_void_p, c_int32, _B, _I]),
     ("rv_beam_search_submit_all_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _B, _I]),
+    ("rv_beam_search_moves", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _B, _M, _I]),
+    ("rv_beam_search_moves_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _B, _M, _I]),
+    ("rv_beam_search_submit_moves", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _I]),
+    ("rv_beam_search_collect_moves", c_int32, [c_void_p, c_int32, _B, _M, _I]),
     ("rv_beam_search_flush", c_int32, [c_void_p]),
     ("rv_greedy_search", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
     ("rv_greedy_search_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),

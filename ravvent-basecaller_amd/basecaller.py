@@ -19,13 +19,17 @@ import torch
 
 from . import _capi, weights as _weights
 from .config import RvConfig, RAW_FEATURES, EVENT_FEATURES
-from .data_loader import nuc_tk, tokens_to_strings
+from .data_loader import _ASCII, nuc_tk, tokens_to_strings
 
 
 # What TFA's BeamSearchDecoder returns for a slab (rv_beam_search_all*, include/ravvent_hip.h): tokens [B,S,W] int32 the W
 # back-traced hypotheses, scores [B,S,W] the per-slot cumulative log-probabilities (not back-traced), path_scores [B,S,W] each
 # hypothesis's own cumulative log-probability, log_probs [B,W] / lengths [B,W] the final state's
 BeamHypotheses = collections.namedtuple("BeamHypotheses", "tokens scores path_scores log_probs lengths")
+
+# Where in the chunk's signal the tokens of BeamHypotheses.tokens come from (rv_beam_search_moves*, include/ravvent_hip.h: RvMoves):
+# six [B,S,W] tensors, column t of hypothesis w from the attention weights of the step that produced tokens[b, t, w]
+Moves = collections.namedtuple("Moves", "raw_pos raw_mass event_pos event_mass peak peak_weight")
 
 # What a forced decode or a scoring call leaves (rv_teacher_forced*, rv_score_logits; include/ravvent_hip.h: RvScore): sample_id [B,S]
 # int32 the argmax of logits [B,S,V]; nll [B,S] f32 the masked cross-entropy terms; nll_sum [B] f32, n_labels / n_match / n_counted [B] int32
@@ -278,6 +282,64 @@ class Basecaller:
         self.last_steps = S.value
         return self._beams_cut(bufs, S.value)
 
+    # ------------------------------------------------------------------ moves: where in the signal each called base lies
+    def _moves_bufs(self, B, steps, W, on_dev):
+        if on_dev:
+            mk = lambda dt: torch.empty((B, steps, W), dtype=dt, device=self.device)
+            f32, i32 = torch.float32, torch.int32
+        else:
+            mk = lambda dt: np.empty((B, steps, W), dt)
+            f32, i32 = np.float32, np.int32
+        return Moves(mk(f32), mk(f32), mk(f32), mk(f32), mk(i32), mk(f32))
+
+    @staticmethod
+    def _moves_struct(bufs):
+        ptr = lambda a: None if a is None else ctypes.c_void_p(a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data)
+        return _capi.CRvMoves(*[ptr(a) for a in bufs])
+
+    @staticmethod
+    def _moves_cut(bufs, S):
+        return Moves(*[(a if isinstance(a, torch.Tensor) else torch.from_numpy(a))[:, :S] for a in bufs])
+
+    def beam_search_moves(self, input_data, beam_width, max_output_len):
+        """`beam_search_hypotheses` with the position of every token in the chunk's signal (rv_beam_search_moves / _moves_dev) ->
+        (BeamHypotheses, Moves).  Moves: six [B,S,W] tensors -- raw_pos / event_pos f32: the attention-weighted mean sample / event
+        index of the step that produced tokens[b, t, w] (-1 where that segment carries no weight), raw_mass / event_mass f32: the
+        weight on each segment, peak int32 / peak_weight f32: the memory index (raw samples first, then events) of the largest
+        weight.  Columns past a hypothesis's length hold -1 / 0.  Host or device tensors follow the inputs; the BeamHypotheses is
+        `beam_search_hypotheses`'s byte for byte.  `base_positions` cuts a hypothesis's positions to its letters."""
+        keep, pr, pe, B, Tr, Te, on_dev = self._gather_inputs(input_data)
+        L, W = _as_int(max_output_len), int(beam_width)
+        steps = max(L - 1, 0)
+        S = ctypes.c_int32(0)
+        if on_dev:
+            torch.cuda.current_stream(self.device).synchronize()   # inputs ready before the library's stream reads them
+            bufs = self._beams_dev(B, steps, max(W, 0))
+        else:
+            bufs = self._beams_host(B, steps, max(W, 0))
+        mv = self._moves_bufs(B, steps, max(W, 0), on_dev)
+        st, sm = self._beams_struct(bufs), self._moves_struct(mv)
+        fn = self._lib.rv_beam_search_moves_dev if on_dev else self._lib.rv_beam_search_moves
+        self._check(fn(self._h, pr, pe, B, Tr, Te, W, L, ctypes.byref(st), ctypes.byref(sm), ctypes.byref(S)), "rv_beam_search_moves")
+        self.last_steps = S.value
+        return self._beams_cut(bufs, S.value), self._moves_cut(mv, S.value)
+
+    def base_positions(self, tokens, positions):
+        """The positions of the letters of one hypothesis: `tokens` [B,S] (e.g. BeamHypotheses.tokens[:, :, w]) and `positions` [B,S]
+        (the same slice of a Moves member) -> per chunk a 1-D array of the positions at the columns whose token
+        `tokens_to_nuc_sequences` keeps; element i belongs to letter i of that chunk's string."""
+        as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        tokens, positions = as_np(tokens), as_np(positions)
+        if tokens.ndim != 2 or positions.shape != tokens.shape:
+            raise ValueError(f"tokens and positions: two [B,S] arrays of one shape, got {tokens.shape} and {positions.shape}")
+        if self.tokenizer.word_index == nuc_tk.word_index:       # the table tokens_to_nuc_sequences maps through: 0 = dropped
+            table = _ASCII
+        else:
+            table = np.zeros(256, np.uint8)
+            table[:8] = self._call_lut()
+        kept = table[np.clip(tokens, 0, 255).astype(np.uint8)] != 0
+        return [positions[b][kept[b]] for b in range(tokens.shape[0])]
+
     # ------------------------------------------------------------------ the hot path, several slabs in flight
     def set_async_depth(self, depth: int):
         """Slab contexts the submit_* calls rotate through (1..16; default 2).  With several slabs in flight the GPU never idles
@@ -296,7 +358,7 @@ class Basecaller:
 
     supports_out = True       # submit_beam_search / beam_search_stream take caller-provided device outputs
 
-    def submit_beam_search(self, input_data, beam_width, max_output_len, out=None, out_ptrs=None, all_beams=False):
+    def submit_beam_search(self, input_data, beam_width, max_output_len, out=None, out_ptrs=None, all_beams=False, moves=False):
         """Queue `beam_search_prediction(input_data, ...)` without waiting for the GPU (rv_beam_search_submit / _submit_dev);
         returns a ticket for `collect`.  Results are byte-identical to the synchronous call.  Device inputs must stay untouched
         until the ticket is collected (the ticket keeps them alive).  `out` (device inputs only): a pair of contiguous device
@@ -305,11 +367,17 @@ class Basecaller:
         then returns only the step count) -- a loop that submits thousands of slabs into one buffer saves the per-slab tensor views.
         `all_beams`: queue `beam_search_hypotheses` instead (rv_beam_search_submit_all / _submit_all_dev); `out` is then its five
         device tensors (tokens, scores, path_scores [B, L-1, W], log_probs, lengths [B, W]) and `collect` returns a BeamHypotheses.
-        Such a slab is never coalesced with others."""
+        Such a slab is never coalesced with others.  `moves` (host inputs only): queue `beam_search_moves` instead
+        (rv_beam_search_submit_moves); `collect` returns its (BeamHypotheses, Moves)."""
         keep, pr, pe, B, Tr, Te, on_dev = self._gather_inputs(input_data)
         L, W = _as_int(max_output_len), int(beam_width)
         steps = max(L - 1, 0)
         t = ctypes.c_int32(-1)
+        if moves:
+            if on_dev or out is not None or out_ptrs is not None:
+                raise ValueError("moves=True takes host inputs and returns host results")
+            self._check(self._lib.rv_beam_search_submit_moves(self._h, pr, pe, B, Tr, Te, W, L, ctypes.byref(t)), "rv_beam_search_submit_moves")
+            return {"kind": "moves_host", "keep": keep, "B": B, "steps": steps, "W": max(W, 0), "ticket": t.value}
         if all_beams:
             if out_ptrs is not None:
                 raise ValueError("all_beams takes its outputs as tensors (out=)")
@@ -356,8 +424,17 @@ class Basecaller:
 
     def collect(self, call):
         """Wait for a `submit_beam_search` ticket -> (predicted_ids[:,:,0] [B,S] int32, scores[:,:,0] [B,S] f32), or the
-        BeamHypotheses of an `all_beams` ticket."""
+        BeamHypotheses of an `all_beams` ticket, or the (BeamHypotheses, Moves) of a `moves` ticket."""
         S = ctypes.c_int32(0)
+        if call["kind"] == "moves_host":
+            bufs = self._beams_host(call["B"], call["steps"], call["W"])
+            mv = self._moves_bufs(call["B"], call["steps"], call["W"], False)
+            st, sm = self._beams_struct(bufs), self._moves_struct(mv)
+            self._check(self._lib.rv_beam_search_collect_moves(self._h, call["ticket"], ctypes.byref(st), ctypes.byref(sm), ctypes.byref(S)),
+                        "rv_beam_search_collect_moves")
+            call["keep"] = None
+            self.last_steps = S.value
+            return self._beams_cut(bufs, S.value), self._moves_cut(mv, S.value)
         if call["kind"] in ("all_dev", "all_host"):
             if call["kind"] == "all_dev":
                 self._check(self._lib.rv_beam_search_collect_dev(self._h, call["ticket"], ctypes.byref(S)), "rv_beam_search_collect_dev")

@@ -221,7 +221,17 @@ struct DecState {
   // An id outside [0, V) adds no input row (tf.one_hot gives zeros); the persistent decode takes such calls only with V < RV_MAX_VOCAB
   // (last: the kernel-argument offsets of the members above are those of every earlier build)
   const int* forced;
+  // Moves (rv_beam_search_moves*): where in the memory each step's attention lay, one record per beam row as it
+  // is when the attention of the step runs (before the step's top-k reorders the rows), reduced on chip from the alignments the
+  // context product consumes.  step_moves [L-1,B,W,RV_MOVE_COLS]: raw_mass = sum_{t < Tr} a_t, raw_m1 = sum_{t < Tr} a_t t,
+  // event_mass = sum_{Tr <= t < Tm} a_t, event_m1 = sum_{Tr <= t < Tm} a_t (t - Tr), peak_weight = max_t a_t, peak_t = the first t
+  // holding it (as a float; -1 and NaN in the other five when the row's alignments are NaN: an all-padding chunk).  nullptr: every
+  // other call -- the kernels test the pointer at run time.  Tr: the split index (T_m in raw mode, 0 in event mode).
+  // moves_only (per-step kernels): this launch of k_dec_attend leaves after its softmax, having written the step's records alone
+  // (appended like `forced`: the offsets above stay)
+  float* step_moves; int Tr; int moves_only;
 };
+#define RV_MOVE_COLS 6
 hipError_t configure_decode_kernels();   // per-device dynamic-LDS opt-in; call after hipSetDevice; first error or hipSuccess
 void launch_dec_init(const DecState& d, hipStream_t s);
 // layer: which stacked cell; Wtok (one-hot embedding rows) is non-null for layer 0 only
@@ -257,6 +267,11 @@ void launch_dec_reduce_steps(const DecParts& p, hipStream_t s);   // S_dev[0] = 
 // (include/ravvent_hip.h: RvBeams).  path_scores, log_probs and lengths may be null: the kernel skips a null output.
 struct BeamsOut { int32_t* tokens; float* scores; float* path_scores; float* log_probs; int32_t* lengths; };
 void launch_dec_finalize_beams(const DecState& d, const BeamsOut& o, hipStream_t s);
+// The moves of a call (moves.hip, rv_beam_search_moves*): k_dec_finalize_moves runs behind k_dec_finalize_beams, one launch per decode
+// part, and back-traces the step_moves records like the tokens.  Six outputs [B,L-1,W], beam innermost (include/ravvent_hip.h:
+// RvMoves); the kernel skips a null output.
+struct MovesOut { float* raw_pos; float* raw_mass; float* event_pos; float* event_mass; int32_t* peak; float* peak_weight; };
+void launch_dec_finalize_moves(const DecState& d, const MovesOut& o, hipStream_t s);
 
 // ---------------------------------------------------------------- scoring (score.hip)
 // Masked sparse cross-entropy and masked token accuracy of label rows against logits (Basecaller.loss_function, basecaller.py:212-220;

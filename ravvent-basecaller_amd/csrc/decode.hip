@@ -226,6 +226,40 @@ __device__ __forceinline__ float wave_sum_fast(float v) {
   return ((a + b) + c) + e;
 }
 
+// ---- moves (DecState::step_moves): a beam row's record of one step, reduced from its alignments.  A lane adds its own steps in
+// ascending t, partial records merge pairwise in an order fixed by the lane / wave numbers alone; sums commute, and of two equal
+// peaks the smaller t stays, so both sides of a butterfly exchange end with the same bits.
+struct MoveAcc { float rm, r1, em, e1, pk; int pt; };
+__device__ __forceinline__ MoveAcc move_zero() { return MoveAcc{0.f, 0.f, 0.f, 0.f, -INFINITY, -1}; }
+__device__ __forceinline__ void move_add(MoveAcc& a, float al, int t, int Tr) {
+  // (selects, not a branch over the members: the compiler turns that into an indexed access of the record, in scratch.  Adding 0 and
+  // fma(0, t, x) leave a sum's bits alone)
+  const float ar = t < Tr ? al : 0.f, ae = t < Tr ? 0.f : al;
+  a.rm += ar; a.r1 = fmaf(ar, (float)t, a.r1);
+  a.em += ae; a.e1 = fmaf(ae, (float)(t - Tr), a.e1);
+  if (al > a.pk) { a.pk = al; a.pt = t; }      // strict: the first maximum; a NaN never enters
+}
+__device__ __forceinline__ void move_merge(MoveAcc& a, const MoveAcc& o) {
+  a.rm += o.rm; a.r1 += o.r1; a.em += o.em; a.e1 += o.e1;
+  if (o.pk > a.pk || (o.pk == a.pk && (unsigned)o.pt < (unsigned)a.pt)) { a.pk = o.pk; a.pt = o.pt; }
+}
+__device__ __forceinline__ MoveAcc move_shfl_xor(const MoveAcc& a, int x) {
+  return MoveAcc{__shfl_xor(a.rm, x), __shfl_xor(a.r1, x), __shfl_xor(a.em, x), __shfl_xor(a.e1, x), __shfl_xor(a.pk, x), __shfl_xor(a.pt, x)};
+}
+// No alignment was greater than -inf: the row is NaN (all-padding chunk) -- NaN in the five value columns whatever the segments hold.
+// z = pk - pk is that NaN (-inf - -inf) and +0 for every other row, and v + 0 is v for these non-negative values: no select, and no
+// NaN constant for the compiler to keep in a register through the persistent decode's step loop
+__device__ __forceinline__ void move_store(float* rec, const MoveAcc& a) {
+  const float z = a.pk - a.pk;
+  rec[0] = a.rm + z; rec[1] = a.r1 + z; rec[2] = a.em + z; rec[3] = a.e1 + z; rec[4] = a.pk + z;
+  rec[5] = (float)a.pt;
+}
+// one wave owns the row: lane `lane` holds the partial record of its steps
+__device__ __forceinline__ void move_wave_store(float* rec, MoveAcc a, int lane) {
+  for (int x = 32; x > 0; x >>= 1) { const MoveAcc o = move_shfl_xor(a, x); move_merge(a, o); }
+  if (lane == 0) move_store(rec, a);
+}
+
 constexpr int WB = RV_MAX_BEAM;
 constexpr int ATT_THREADS = 512;
 #ifndef RV_STAMP_WAVE
@@ -458,7 +492,7 @@ __global__ __launch_bounds__(ATT_THREADS) void k_dec_attend(DecState d, int step
 
   const int b = blockIdx.x, tid = threadIdx.x;
   if (step > 0 && d.nfin[step - 1] >= d.B) {      // whole batch finished earlier: propagate
-    if (tid == 0) atomicAdd(&d.nfin[step], 1);
+    if (tid == 0 && !d.moves_only) atomicAdd(&d.nfin[step], 1);      // (moves_only: the step's own attend, launched next, counts)
     return;
   }
   const size_t row0 = (size_t)b * W;
@@ -560,13 +594,17 @@ __global__ __launch_bounds__(ATT_THREADS) void k_dec_attend(DecState d, int step
         sum += e;
       }
       sum = wave_sum(sum);
+      MoveAcc mv = move_zero();
       for (int t = lane; t < Tm; t += 64) {
         const float a = sc[w * TmP + t] / sum;
         al[t * WB + w] = a;
         if (d.step_align) d.step_align[(((size_t)step * d.B + b) * W + w) * Tm + t] = a;
+        if (d.step_moves) move_add(mv, a, t, d.Tr);
       }
+      if (d.step_moves) move_wave_store(d.step_moves + (((size_t)step * d.B + b) * W + w) * RV_MOVE_COLS, mv, lane);   // moves: this wave owns the beam
     }
   }
+  if (d.moves_only) return;      // (uniform) a moves call beside the single-pass attend: the records were all this launch is for
   __syncthreads();
 
   // ---- D (math): context = sum_t alpha_t * values_t
@@ -996,6 +1034,68 @@ __device__ __forceinline__ void tap_align_image(const DecState& d, const float* 
   }
 }
 
+// The moves arguments of the call as the step loop reads them: from the LDS words the prologue left (k_dec_persist: s_moves), brought
+// into scalar registers for the length of the block that uses them
+__device__ __forceinline__ float* persist_moves_arg(float* const& s_moves, const int& s_Tr, int& Tr) {
+  const uint2 v = *reinterpret_cast<const uint2*>(&s_moves);
+  Tr = __builtin_amdgcn_readfirstlane(s_Tr);
+  const uint64_t a = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(v.y) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane(v.x);
+  return reinterpret_cast<float*>(a);
+}
+
+// Moves (DecState::step_moves) of a matrix-pipe form: the same read-back of the A image as the tap above, reduced instead of stored.
+// Wave w < W owns beam w and walks its T_m steps, lane l those with t % 64 == l; nothing but the six floats per beam leaves the chip.
+// These kernels hold 255 of 256 VGPRs through the step loop, so the record is not kept in six accumulators: one rolled pass over the
+// image per column -- the peak first (it says whether the row is NaN), then the four sums -- each with a handful of registers live
+// The shape is picked per form by what the register allocator makes of it, like the tap's: the forms reduce across the wave by DPP and
+// readlane (FAST), except Bahdanau (ATT 4) at beam 5, which by shuffles alone stays within its scratch bound (tests/test_build.py: 188 B
+// against 200).  At its other beams the shuffles cost that form up to 96 B more scratch than it had and 3.5 % of a call without moves
+// (beam 7); with FAST every instantiation but <3,8,1,4> (32 -> 56 B) spills no more than before the moves
+template <int W, int NIT, bool FAST>
+__device__ __forceinline__ void moves_from_image(const DecState& d, float* moves, int Tr, const float* part, int b, int step, int tid) {
+  auto wmax = [](float v) { if constexpr (FAST) return wave_max_fast(v); else return wave_max(v); };
+  auto wsum = [](float v) { if constexpr (FAST) return wave_sum_fast(v); else return wave_sum(v); };
+  const _Float16* aa = reinterpret_cast<const _Float16*>(part);
+  int t0 = tid;
+  asm volatile("" : "+v"(t0));     // nothing of this is hoisted out of the step loop (no registers held while the pointer is null)
+  const int lane = t0 & 63, w = __builtin_amdgcn_readfirstlane(t0 >> 6);      // (the wave's number, in a scalar register)
+  if (w >= W) return;
+  float* rec = moves + (((size_t)step * d.B + b) * W + w) * RV_MOVE_COLS;
+  const _Float16* row = aa + mx_row(w) * 8;
+  // The image holds 32 NIT steps: those from T_m on are padding and carry exactly 0 (NaN in a NaN row), so every pass walks the
+  // whole image -- a trip count the wave shares, no lane leaves a loop early (an exec mask saved per loop is two scalar registers, and
+  // the Bahdanau form spills those to memory)
+  constexpr int TRIPS = (32 * NIT + 63) / 64;
+  auto alpha = [&](int t) {
+    const int tc = min(t, 32 * NIT - 1);
+    const _Float16* q = row + (tc >> 3) * 128 + (tc & 7);
+    return ((float)q[0] + (float)q[8]) * (1.0f / 16384.f);
+  };
+  // the row's maximum (fmaxf drops a NaN: -inf stays for a NaN row), then the first t that holds it (t < 2^24: exact as a float)
+  float pk = -INFINITY;
+#pragma unroll 1
+  for (int i = 0; i < TRIPS; ++i) pk = fmaxf(pk, alpha(lane + 64 * i));
+  const float pmax = wmax(pk);
+  float nt = -INFINITY;            // minus the lane's first such t
+#pragma unroll 1
+  for (int i = 0; i < TRIPS; ++i) { const int t = lane + 64 * i; nt = fmaxf(nt, (alpha(t) == pmax && t < 32 * NIT) ? -(float)t : -INFINITY); }
+  const float pfirst = pmax == -INFINITY ? -1.0f : -wmax(nt);
+  const float z = pmax - pmax;     // NaN for a NaN row (no alignment was greater than -inf), +0 for every other: see move_store
+  if (lane == 0) { rec[4] = pmax + z; rec[5] = pfirst; }
+  auto segment = [&](int c, int lo, int hi, bool first_moment) {      // steps [lo, hi), weight 1 or t - lo
+    float acc = 0.f;
+#pragma unroll 1
+    for (int i = 0; i < TRIPS; ++i) {
+      const int t = lane + 64 * i;
+      const float al = (t >= lo && t < hi) ? alpha(t) : 0.f;
+      acc = fmaf(al, first_moment ? (float)(t - lo) : 1.0f, acc);
+    }
+    acc = wsum(acc);
+    if (lane == 0) rec[c] = acc + z;
+  };
+  segment(0, 0, Tr, false); segment(1, 0, Tr, true); segment(2, Tr, d.Tm, false); segment(3, Tr, d.Tm, true);
+}
+
 // The default form's own memory projection (option fused_memory; DecState::enc_rows): the chunk's [keys | U'] = enc_out . [W_mem | A_c]
 // computed by its decode workgroup straight into the resident fragments, instead of a GEMM launch that writes [B,T_m,256] floats
 // which this prologue would read back.  Every element keeps the chain of k_gemm_mem_split3 (gemm_f32.hip): k in eight steps of 32,
@@ -1360,6 +1460,11 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
   __shared__ __align__(16) float s_nh[(D == 1 && !T::MXC) ? RV_MAX_VOCAB * T::FCW : 4];
   __shared__ float s_lprob[WB];
   __shared__ int s_fin[WB], s_len[WB], s_parent[WB], s_tok[WB], s_allfin;
+  // moves: the call's records pointer and split index, parked here by the prologue.  Read from the kernel arguments inside the step
+  // loop they would be hoisted and hold three more scalar registers through it, which the forms at the edge of the register file pay
+  // for in spilled lanes; an LDS read per step holds none
+  __shared__ float* s_moves;
+  __shared__ int s_movesTr;
   __shared__ int s_qbig;                   // Bahdanau on the matrix pipe: some processed query of this step lies outside the fast form's range
 
   const int b = blockIdx.x, tid = threadIdx.x, Tm = d.Tm, V = d.V;
@@ -1475,7 +1580,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
     s_tok[tid] = (W == 1 && d.forced) ? persist_forced_tok(d, b, 0) : d.start_token; s_lprob[tid] = tid == 0 ? 0.f : -INFINITY;
     s_fin[tid] = 0; s_len[tid] = 0; s_parent[tid] = tid;
   }
-  if (tid == 0) s_allfin = 0;
+  if (tid == 0) { s_allfin = 0; s_moves = d.step_moves; s_movesTr = d.Tr; }
   for (int i = tid; i < V * RV_G; i += NT) zb[i] = Wtok[i] + bdec[i & (RV_G - 1)];   // W_dec[one_hot(v)] + b, resident
   if (W == 1 && d.forced) for (int i = tid; i < RV_G; i += NT) zb[V * RV_G + i] = bdec[i];      // row V (V < RV_MAX_VOCAB: ravvent_hip.cpp, persist_form): no input row, persist_forced_tok
   __syncthreads();
@@ -1490,6 +1595,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
     int tid = tid0;
     asm volatile("" : "+v"(tid));
     const int lane = tid & 63, wv = tid >> 6, sub = lane & 15, sid = tid >> 4, row = lane >> 4;
+    int mvTr = 0;
     RV_STAMP(d, step, 0);
     if (T::BAH && T::MXC && tid == 0) s_qbig = 0;              // (set again, if at all, after the gates' barrier; last read before this step's last barrier)
     // ================= gates of this step: the cell product was taken at the end of the previous step on the parent beams
@@ -1878,6 +1984,33 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
               if (it < NIT && t < Tm) out[(unsigned)(w0 * Tm + t)] = sc[p];
             }
           }
+          if (float* mvp = persist_moves_arg(s_moves, s_movesTr, mvTr)) {        // moves: the same fp32 alignments, reduced.  Lane (stream t0, half, beam w0) adds its rows, the two
+            // halves and the wave's four streams merge by butterflies (the beam stays in place), the eight waves through `ml`, idle
+            // from the merge's barrier above to the next step's softmax, in wave order
+            int t0 = sid, w0 = s8, hv = half, ln = lane, wq = wv;
+            asm volatile("" : "+v"(t0), "+v"(w0), "+v"(hv), "+v"(ln), "+v"(wq));   // (as the tap: nothing held while the pointer is null)
+            MoveAcc a = move_zero();
+#pragma unroll
+            for (int p = 0; p < T::NP; ++p) {
+              const int it = 2 * p + hv, t = t0 + 32 * it;
+              if (it < NIT && t < Tm) move_add(a, sc[p], t, mvTr);
+            }
+#pragma unroll
+            for (int x = 8; x <= 32; x <<= 1) { const MoveAcc o = move_shfl_xor(a, x); move_merge(a, o); }
+            if (ln < W) {
+              float* r = ml + (wq * WB + w0) * RV_MOVE_COLS;
+              r[0] = a.rm; r[1] = a.r1; r[2] = a.em; r[3] = a.e1; r[4] = a.pk; r[5] = __int_as_float(a.pt);
+            }
+            __syncthreads();
+            if (ln < W && wq == 0) {
+#pragma unroll 1
+              for (int g = 1; g < 8; ++g) {
+                const float* r = ml + (g * WB + w0) * RV_MOVE_COLS;
+                move_merge(a, MoveAcc{r[0], r[1], r[2], r[3], r[4], __float_as_int(r[5])});
+              }
+              move_store(mvp + (((size_t)step * d.B + b) * W + w0) * RV_MOVE_COLS, a);
+            }
+          }
         }
       }
       RV_STAMP(d, step, 5);
@@ -1900,6 +2033,7 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
         }
         __syncthreads();
         if (d.persist_align) tap_align_image<W, true>(d, part, b, step, tid);
+        if (float* mvp = persist_moves_arg(s_moves, s_movesTr, mvTr)) moves_from_image<W, NIT, W != 5>(d, mvp, mvTr, part, b, step, tid);
       } else {
         // ================= attention-layer context part = sum_t alpha_t * U'_t, one beam at a time (8-register accumulator)
         {
@@ -1982,6 +2116,9 @@ __global__ __launch_bounds__(512) void k_dec_persist(DecState d, const float* __
             } else attT[col * WB + kq + 4 * i] = av;
           }
       }
+      // moves: the alignment image is still whole here (`part` is next written behind this barrier), and the product's own registers are free
+      if constexpr (T::MXS)
+        if (float* mvp = persist_moves_arg(s_moves, s_movesTr, mvTr)) moves_from_image<W, NIT, true>(d, mvp, mvTr, part, b, step, tid);
       __syncthreads();
     }
     RV_STAMP(d, step, 8);

@@ -118,12 +118,16 @@ struct Call {
   bool whole_beam = false;                  // rv_beam_search_all* / rv_beam_search_submit_all*: every beam, through ...
   const RvBeams* beams = nullptr;           // ... these outputs (null: an asynchronous call with host outputs, named at its collect)
   const ForcedCall* forced = nullptr;       // rv_teacher_forced*
+  bool want_moves = false;                  // rv_beam_search_moves* / rv_beam_search_submit_moves (always with whole_beam): the moves too, through ...
+  const RvMoves* moves = nullptr;           // ... these outputs (null: an asynchronous call, named at its collect)
 };
 
 // What a recording needs beyond the call, resolved once before enqueue() (begin_all_beams, begin_forced, launch_group)
 struct CallParts {
   bool whole_beam = false;                  // k_dec_finalize_beams in k_dec_finalize's place, writing to ...
   BeamsOut beams{};                         // ... these device addresses (the caller's, or the context's d_beams)
+  bool moves = false;                       // the decode leaves step_moves records and k_dec_finalize_moves runs behind k_dec_finalize_beams, writing to ...
+  MovesOut moves_out{};                     // ... these device addresses (the caller's, or the context's d_moves)
   const int* labels = nullptr;              // a forced decode feeds these label rows [B,L] (device: the caller's, or d_forced) instead of its argmax
   ScoreArgs score{};                        // ... and scores them: omit_mask and the output addresses (device: the caller's, or the d_sc_* buffers; null = not asked for)
   const DecMembers* members = nullptr;      // the member table of a group's internal call
@@ -184,6 +188,10 @@ struct RvContext {
   // the whole beam (rv_beam_search_all*): device outputs and pinned staging of the host variants, [max_batch, max_output_len, max_beam]
   // and [max_batch, max_beam], allocated on this context's first such call (ensure_beam_buffers)
   BeamsOut d_beams{}, pin_beams{};
+  // moves (rv_beam_search_moves*): the decode's records [max_output_len - 1, max_batch, max_beam, RV_MOVE_COLS], allocated on this context's
+  // first such call (ensure_moves_buffers), and for the host variants the six outputs [max_batch, max_output_len, max_beam] with their staging
+  float* d_step_moves = nullptr;
+  MovesOut d_moves{}, pin_moves{};
   // forced decode and scoring (rv_teacher_forced*, rv_score_logits)
   int32_t* d_forced = nullptr;              // host variants: labels [max_batch, max_output_len] and the score outputs, allocated on this context's
   float *d_sc_nll = nullptr, *d_sc_sum = nullptr;   //   first such call (ensure_score_buffers): nll [max_batch, max_output_len], nll_sum [max_batch],
@@ -207,6 +215,7 @@ struct RvContext {
 
   // last call
   int lB = 0, lTm = 0, lL = 0, lS = 0, lgreedy = 0, ltaps = 0, lptaps = 0;
+  int lmoves = 0;                           // it was a moves call: "step_moves" holds its records
   SlabFacts fact;
   FormLog lforms;                           // the kernel instantiations it launched ("kernel_forms"); lforms_ok = 0: it ran as a slab graph
   int lforms_ok = 1;
@@ -218,7 +227,7 @@ struct RvContext {
   std::vector<RvContext*> kids;
   int inflight_hint = 1;                   // slabs the caller keeps in flight (1 for the synchronous entry points): sizes the workgroups
   int next_slot = 0, generation = 0;
-  struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false, all = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
+  struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false, all = false, moves = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
 
   // coalesced asynchronous calls (option "coalesce"): up to n consecutively submitted slabs of the default streamed path are decoded as ONE
   // internal call of sum(B) chunks on a GROUP context -- a child context whose buffers hold n x max_batch chunks -- so that the narrow
@@ -513,6 +522,15 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
 
 void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool profiled, FormLog* log) {
   const bool flash = h->fact.lflash != 0;
+  // A moves call whose steps take the single-pass attend, which never forms the alignments: the two-pass kernel runs first on the same
+  // rows and leaves after its softmax with the step's records (DecState::moves_only); the step itself is the single-pass kernel's, so
+  // the beam is what every other call's is
+  // With debug_taps on, the alignment tap of such a call is the two-pass launch's -- the alignments its records are reduced from -- and
+  // the single-pass kernel, which would store its raw scores to the same buffer, taps none
+  DecState dm = d, ds = d;
+  dm.moves_only = 1;
+  const bool moves_aside = d.step_moves && flash;
+  if (moves_aside) ds.step_align = nullptr;
   auto cells = [&](int step, bool prof) {
     for (int k = 0; k < d.depth; ++k) {
       const float* WcatT = h->img.WcatT + (size_t)k * RV_G * RV_E;
@@ -523,10 +541,12 @@ void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool pr
   for (int step = 0; step < d.L - 1; ++step) {
     if (profiled) {
       cells(step, true);
-      { Scope sc(h, "dec_attend"); launch_dec_attend(d, h->img.WmemT, flash, step, s, log); }
+      if (moves_aside) { Scope sc(h, "dec_attend_moves"); launch_dec_attend(dm, h->img.WmemT, false, step, s, log); }
+      { Scope sc(h, "dec_attend"); launch_dec_attend(ds, h->img.WmemT, flash, step, s, log); }
     } else {
       cells(step, false);
-      launch_dec_attend(d, h->img.WmemT, flash, step, s, log);
+      if (moves_aside) launch_dec_attend(dm, h->img.WmemT, false, step, s, log);
+      launch_dec_attend(ds, h->img.WmemT, flash, step, s, log);
     }
   }
 }
@@ -576,9 +596,10 @@ int enqueue(RvContext* h, const Call& stated, const CallParts& res) {
   const bool greedy = call.greedy, dev_out = call.dev_out, calls = call.lut != nullptr;
   HIPCHK(h, hipSetDevice(c.device));
   h->lB = B; h->fact.lW = W; h->lL = L; h->lS = 0; h->lgreedy = greedy; h->lTm = T_r + T_e; h->ltaps = h->opt.taps; h->lptaps = h->opt.ptaps;
+  h->lmoves = res.moves ? 1 : 0;
   h->lforms.n = 0; h->lforms.full = false; h->lforms_ok = 1;
   h->pend = RvContext::PendingCall{};
-  h->pend.busy = true; h->pend.greedy = greedy; h->pend.dev_out = dev_out; h->pend.calls = calls; h->pend.all = res.whole_beam;
+  h->pend.busy = true; h->pend.greedy = greedy; h->pend.dev_out = dev_out; h->pend.calls = calls; h->pend.all = res.whole_beam; h->pend.moves = res.moves;
   h->pend.B = B; h->pend.steps = std::max(L - 1, 0); h->pend.V = c.vocab; h->pend.Wd = greedy ? 1 : W;
   if (B == 0 || L <= 1) {
     h->pend.trivial = true;
@@ -749,7 +770,8 @@ int record_keys(RvContext* h, Slab& sl) {
   h->fact.lflash = (c.attention == RV_ATT_LUONG && h->opt.flash && W_eff <= 5) ? 1 : 0;   // wider beams: register budget -> two-pass
   // the persistent decode needs neither keys nor the per-step kernels
   const int persist_att = sl.persist_att = persist_form(h, greedy, W, Tm, sl.res.labels != nullptr);
-  h->fact.lkeys = ((!h->fact.lflash && persist_att < 0) || h->opt.taps) ? 1 : 0;
+  // (a moves call on the per-step kernels forms its alignments in the two-pass attend, beside the single-pass one where that runs the step)
+  h->fact.lkeys = ((!h->fact.lflash && persist_att < 0) || h->opt.taps || (sl.res.moves && persist_att < 0)) ? 1 : 0;
   if (h->fact.lkeys) {
     GemmArgs g{};
     g.A = h->enc_out; g.lda = RV_E; g.Bm = h->W_mem; g.ldb = RV_U; g.C = h->keys; g.ldc = RV_U;
@@ -808,6 +830,9 @@ int fill_dec_state(RvContext* h, Slab& sl) {
     if (need) HIPCHK(h, hipMemsetAsync(h->palign, 0xff, need * sizeof(float), s));
     d.persist_align = h->palign;
   }
+  d.step_moves = sl.res.moves ? h->d_step_moves : nullptr;
+  d.Tr = sl.call.T_r;      // (effective lengths: T_m in raw mode, 0 in event mode)
+  d.moves_only = 0;
   return RV_OK;
 }
 
@@ -859,6 +884,7 @@ int split_decode(RvContext* h, Slab& sl) {
     if (p.step_logits) p.step_logits += (size_t)steps * Wd * V * b0;
     if (p.step_align) p.step_align += (size_t)steps * Wd * Tm * b0;
     if (p.persist_align) p.persist_align += (size_t)steps * Wd * Tm * b0;
+    if (p.step_moves) p.step_moves += (size_t)steps * Wd * RV_MOVE_COLS * b0;
     p.nfin = d.nfin + g * (c.max_output_len + 1);
     parts.nfin[g] = p.nfin; parts.B[g] = p.B;
     if (!h->fact.lpersist) launch_dec_init(p, s);
@@ -930,7 +956,8 @@ int decode_steps(RvContext* h, Slab& sl) {
   DecState* part = sl.part;
   DecParts& parts = sl.parts;
   int& nsplit = sl.nsplit;
-  if (h->opt.graph && h->opt.profile != 2 && !d.forced) {      // (a forced decode launches its steps without replay: the label pointer is no part of the key)
+  // (a forced decode and a moves call launch their steps without replay: the label and the records pointers are no part of the key)
+  if (h->opt.graph && h->opt.profile != 2 && !d.forced && !d.step_moves) {
     GraphKey key{B, d.W, Tm, L, greedy ? 1 : 0, h->opt.taps * 2 + h->fact.lflash + 4 * h->opt.att_nt + 4096 * (d.step_logits ? 1 : 0) + 8192 * (d.persist_align ? 1 : 0), nsplit};   // every captured pointer that can change is in the key
     auto it = h->graphs.find(key);
     if (it == h->graphs.end()) {
@@ -992,6 +1019,20 @@ int finalize_and_score(RvContext* h, const Slab& sl) {
       }
     }
   }
+  if (sl.res.moves) {      // behind k_dec_finalize_beams, which left S for every part
+    Scope sc(h, "dec_finalize_moves");
+    for (int g = 0; g < parts.n; ++g) {
+      const size_t off = (parts.n == 1 ? 0 : (size_t)B * g / parts.n) * steps * Wd;
+      MovesOut o = sl.res.moves_out;
+      if (o.raw_pos) o.raw_pos += off;
+      if (o.raw_mass) o.raw_mass += off;
+      if (o.event_pos) o.event_pos += off;
+      if (o.event_mass) o.event_mass += off;
+      if (o.peak) o.peak += off;
+      if (o.peak_weight) o.peak_weight += off;
+      launch_dec_finalize_moves(sl.part[g], o, s);
+    }
+  }
   if (d.forced) {      // the forced decode's labels target[:, 1:] against the logits the finalize kernel just wrote
     ScoreArgs a = sl.res.score;
     a.logits = o2; a.labels = d.forced + 1; a.label_stride = L; a.B = B; a.S = steps; a.V = V; a.pad_token = c.pad_token; a.pred = nullptr;
@@ -1015,6 +1056,12 @@ int stage_outputs(RvContext* h, const Slab& sl) {
     if (o.path_scores) HIPCHK(h, hipMemcpyAsync(p.path_scores, o.path_scores, sizeof(float) * n, hipMemcpyDeviceToHost, s));
     if (o.log_probs) HIPCHK(h, hipMemcpyAsync(p.log_probs, o.log_probs, sizeof(float) * nb, hipMemcpyDeviceToHost, s));
     if (o.lengths) HIPCHK(h, hipMemcpyAsync(p.lengths, o.lengths, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, s));
+    if (sl.res.moves) {
+      const MovesOut &m = sl.res.moves_out, &q = h->pin_moves;
+      const void* src[6] = {m.raw_pos, m.raw_mass, m.event_pos, m.event_mass, m.peak, m.peak_weight};
+      void* dst[6] = {q.raw_pos, q.raw_mass, q.event_pos, q.event_mass, q.peak, q.peak_weight};
+      for (int i = 0; i < 6; ++i) if (src[i]) HIPCHK(h, hipMemcpyAsync(dst[i], src[i], 4 * n, hipMemcpyDeviceToHost, s));
+    }
   } else if (!dev_out && !calls) {
     HIPCHK(h, hipMemcpyAsync(h->pin_tok, sl.call.tokens, sizeof(int32_t) * B * steps, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(h->pin_out2, sl.call.out2, sizeof(float) * B * steps * (greedy ? V : 1), hipMemcpyDeviceToHost, s));
@@ -1044,7 +1091,8 @@ int record_slab(RvContext* h, const Call& call, const CallParts& res, const void
 }
 
 // The rest of a call: wait for the context's stream, hand the staged results to the caller's host buffers.
-int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr) {
+int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr,
+           const RvMoves* moves = nullptr) {
   if (!h || !S_out) return RV_EINVAL;
   if (!h->pend.busy) return fail(h, RV_ESTATE, "no call to collect on this context");
   const RvContext::PendingCall p = h->pend;
@@ -1052,6 +1100,11 @@ int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, in
   if (p.all != (beams != nullptr) && !(p.all && p.dev_out))      // (the ticket stays in flight)
     return fail(h, RV_EINVAL, p.all ? "this call hands out the whole beam: collect it with rv_beam_search_collect_all"
                                     : "rv_beam_search_collect_all takes the tickets of rv_beam_search_submit_all");
+  if (p.moves != (moves != nullptr) && !(p.moves && p.dev_out))      // (the ticket stays in flight)
+    return fail(h, RV_EINVAL, p.moves ? "this call hands out the moves: collect it with rv_beam_search_collect_moves"
+                                      : "rv_beam_search_collect_moves takes the tickets of rv_beam_search_submit_moves");
+  if (p.moves && !p.dev_out && !p.trivial && !moves->raw_pos && !moves->raw_mass && !moves->event_pos && !moves->event_mass && !moves->peak && !moves->peak_weight)
+    return fail(h, RV_EINVAL, "null output pointer");
   h->pend.busy = false;
   if (p.trivial) {
     if (p.all && !p.dev_out && beams) {      // the initial state
@@ -1078,6 +1131,12 @@ int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, in
     if (beams->path_scores) memcpy(beams->path_scores, q.path_scores, sizeof(float) * n);
     if (beams->log_probs) memcpy(beams->log_probs, q.log_probs, sizeof(float) * nb);
     if (beams->lengths) memcpy(beams->lengths, q.lengths, sizeof(int32_t) * nb);
+    if (p.moves) {
+      const MovesOut& m = h->pin_moves;
+      const void* src[6] = {m.raw_pos, m.raw_mass, m.event_pos, m.event_mass, m.peak, m.peak_weight};
+      void* dst[6] = {moves->raw_pos, moves->raw_mass, moves->event_pos, moves->event_mass, moves->peak, moves->peak_weight};
+      for (int i = 0; i < 6; ++i) if (dst[i]) memcpy(dst[i], src[i], 4 * n);
+    }
   } else if (!p.dev_out && !p.calls) {
     memcpy(tokens, h->pin_tok, sizeof(int32_t) * B * steps);
     memcpy(out2, h->pin_out2, sizeof(float) * B * steps * (p.greedy ? p.V : 1));
@@ -1129,6 +1188,48 @@ int begin_all_beams(RvContext* ctx, const Call& call, CallParts& res) {
     if (ab && !ab->lengths) res.beams.lengths = nullptr;
   }
   res.whole_beam = true;
+  return RV_OK;
+}
+
+// The records of a moves call and, for the host variants, its six device outputs and their pinned staging
+int ensure_moves_buffers(RvContext* h, bool host_outputs) {
+  const RvConfig& c = h->cfg;
+  HIPCHK(h, hipSetDevice(c.device));
+  if (!h->d_step_moves) TRY(dalloc(h, &h->d_step_moves, (size_t)std::max(c.max_output_len - 1, 1) * c.max_batch * c.max_beam * RV_MOVE_COLS));
+  if (!host_outputs) return RV_OK;
+  const size_t n = (size_t)c.max_batch * c.max_output_len * c.max_beam;
+  MovesOut& d = h->d_moves;
+  MovesOut& p = h->pin_moves;
+  // each buffer on its own test: a call that failed part-way leaves what it got, and the next one allocates only the rest
+  if (!d.raw_pos) TRY(dalloc(h, &d.raw_pos, n));
+  if (!d.raw_mass) TRY(dalloc(h, &d.raw_mass, n));
+  if (!d.event_pos) TRY(dalloc(h, &d.event_pos, n));
+  if (!d.event_mass) TRY(dalloc(h, &d.event_mass, n));
+  if (!d.peak) TRY(dalloc(h, &d.peak, n));
+  if (!d.peak_weight) TRY(dalloc(h, &d.peak_weight, n));
+  void** pins[6] = {(void**)&p.raw_pos, (void**)&p.raw_mass, (void**)&p.event_pos, (void**)&p.event_mass, (void**)&p.peak, (void**)&p.peak_weight};
+  for (void** q : pins)
+    if (!*q) HIPCHK(h, hipHostMalloc(q, n * 4, hipHostMallocDefault));
+  return RV_OK;
+}
+
+// Before enqueue() of a moves call on `ctx` (after begin_all_beams): its records, and where k_dec_finalize_moves writes.  call.moves
+// null = every output, to the context's own buffers (an asynchronous call: what is asked for is known at its collect)
+int begin_moves(RvContext* ctx, const Call& call, CallParts& res) {
+  const RvMoves* mv = call.moves;
+  TRY(ensure_moves_buffers(ctx, !call.dev_out));
+  if (call.dev_out) {
+    res.moves_out = MovesOut{mv->raw_pos, mv->raw_mass, mv->event_pos, mv->event_mass, mv->peak, mv->peak_weight};
+  } else {
+    res.moves_out = ctx->d_moves;
+    if (mv && !mv->raw_pos) res.moves_out.raw_pos = nullptr;
+    if (mv && !mv->raw_mass) res.moves_out.raw_mass = nullptr;
+    if (mv && !mv->event_pos) res.moves_out.event_pos = nullptr;
+    if (mv && !mv->event_mass) res.moves_out.event_mass = nullptr;
+    if (mv && !mv->peak) res.moves_out.peak = nullptr;
+    if (mv && !mv->peak_weight) res.moves_out.peak_weight = nullptr;
+  }
+  res.moves = true;
   return RV_OK;
 }
 
@@ -1250,10 +1351,11 @@ int run(RvContext* h, const Call& call, int32_t* S_out) {
   TRY(sync_context(h, &ctx));
   CallParts res;
   if (call.whole_beam) { const int rb = begin_all_beams(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
+  if (call.want_moves) { const int rb = begin_moves(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
   if (call.forced) { const int rb = begin_forced(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
   const int rc = enqueue(ctx, call, res);
   if (rc != RV_OK) { ctx->pend.busy = false; return relay(h, ctx, rc); }   // (ctx was idle on entry: the flag is this call's)
-  int rf = finish(ctx, call.tokens, call.out2, calls, S_out, call.beams);
+  int rf = finish(ctx, call.tokens, call.out2, calls, S_out, call.beams, call.moves);
   if (call.forced && rf == RV_OK) rf = fetch_scores(ctx, res.score, call.forced->out, call.dev_out, call.B, call.L - 1);
   if (ctx != h) h->lS = ctx->lS;
   return relay(h, ctx, rf);
@@ -1658,7 +1760,8 @@ void rv_destroy(rv_handle h) {
   if (h->step_align) hipFree(h->step_align);
   if (h->palign) hipFree(h->palign);
   for (void* p : {(void*)h->pin_raw, (void*)h->pin_ev, (void*)h->pin_tok, (void*)h->pin_out2, (void*)h->pin_S, (void*)h->pin_bases, (void*)h->pin_probs, (void*)h->pin_clen, (void*)h->pin_ptab,
-                  (void*)h->pin_beams.tokens, (void*)h->pin_beams.scores, (void*)h->pin_beams.path_scores, (void*)h->pin_beams.log_probs, (void*)h->pin_beams.lengths}) if (p) hipHostFree(p);
+                  (void*)h->pin_beams.tokens, (void*)h->pin_beams.scores, (void*)h->pin_beams.path_scores, (void*)h->pin_beams.log_probs, (void*)h->pin_beams.lengths,
+                  (void*)h->pin_moves.raw_pos, (void*)h->pin_moves.raw_mass, (void*)h->pin_moves.event_pos, (void*)h->pin_moves.event_mass, (void*)h->pin_moves.peak, (void*)h->pin_moves.peak_weight}) if (p) hipHostFree(p);
   for (void* p : h->allocs) hipFree(p);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
@@ -2088,6 +2191,7 @@ static int submit(rv_handle h, const Call& call, int32_t* ticket) {
   if (ctx != h) sync_child(ctx, h);
   CallParts res;
   if (call.whole_beam) { const int rb = begin_all_beams(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
+  if (call.want_moves) { const int rb = begin_moves(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
   const int rc = enqueue(ctx, call, res);
   if (rc != RV_OK) { ctx->pend.busy = false; return relay(h, ctx, rc); }
   h->next_slot = (slot + 1) % depth;
@@ -2095,17 +2199,19 @@ static int submit(rv_handle h, const Call& call, int32_t* ticket) {
   *ticket = ctx->pend.ticket;
   return RV_OK;
 }
-static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr) {
+static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr,
+                   const RvMoves* moves = nullptr) {
   if (!h || !S_out) return RV_EINVAL;
   const int slot = ticket & 15;
   if (ticket >= 0 && h->ticks[slot].busy && h->ticks[slot].ticket == ticket) {
+    if (moves) return fail(h, RV_EINVAL, "rv_beam_search_collect_moves takes the tickets of rv_beam_search_submit_moves");
     if (beams) return fail(h, RV_EINVAL, "rv_beam_search_collect_all takes the tickets of rv_beam_search_submit_all");      // (a group never holds one)
     return collect_group(h, slot, tokens, out2, calls, S_out);
   }
   if (ticket < 0 || slot > (int)h->kids.size()) return fail(h, RV_EINVAL, "unknown ticket %d", ticket);
   RvContext* ctx = slot == 0 ? h : h->kids[slot - 1];
   if (!ctx->pend.busy || ctx->pend.ticket != ticket) return fail(h, RV_ESTATE, "ticket %d is not in flight (collected already?)", ticket);
-  return relay(h, ctx, finish(ctx, tokens, out2, calls, S_out, beams));
+  return relay(h, ctx, finish(ctx, tokens, out2, calls, S_out, beams, moves));
 }
 int rv_beam_search_submit(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
                           int32_t* ticket) {
@@ -2171,6 +2277,38 @@ int rv_beam_search_submit_all_dev(rv_handle h, const float* d_raw, const float* 
   Call c = slab_call(d_raw, d_event, true, B, T_r, T_e, W, L);
   c.tokens = d_out->tokens; c.out2 = d_out->scores; c.whole_beam = true; c.beams = d_out;
   return submit(h, c, ticket);
+}
+
+// ---- the moves (k_dec_finalize_moves behind k_dec_finalize_beams): `out` as rv_beam_search_all's; every member of `moves` may be null, not all
+static bool moves_missing(const RvMoves* m, int B, int L) {      // (an empty tensor has no address)
+  return !m || (B > 0 && L > 1 && !m->raw_pos && !m->raw_mass && !m->event_pos && !m->event_mass && !m->peak && !m->peak_weight);
+}
+int rv_beam_search_moves(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                         const RvBeams* out, const RvMoves* moves, int32_t* S_out) {
+  if (!h) return RV_EINVAL;
+  if (beams_missing(out, B, L) || moves_missing(moves, B, L)) return fail(h, RV_EINVAL, "null output pointer");
+  Call c = slab_call(raw, event, false, B, T_r, T_e, W, L);
+  c.tokens = out->tokens; c.out2 = out->scores; c.whole_beam = true; c.beams = out; c.want_moves = true; c.moves = moves;
+  return run(h, c, S_out);
+}
+int rv_beam_search_moves_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
+                             int32_t L, const RvBeams* d_out, const RvMoves* d_moves, int32_t* S_out) {
+  if (!h) return RV_EINVAL;
+  if (beams_missing(d_out, B, L) || moves_missing(d_moves, B, L)) return fail(h, RV_EINVAL, "null output pointer");
+  Call c = slab_call(d_raw, d_event, true, B, T_r, T_e, W, L);
+  c.tokens = d_out->tokens; c.out2 = d_out->scores; c.whole_beam = true; c.beams = d_out; c.want_moves = true; c.moves = d_moves;
+  return run(h, c, S_out);
+}
+int rv_beam_search_submit_moves(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W,
+                                int32_t L, int32_t* ticket) {
+  Call c = slab_call(raw, event, false, B, T_r, T_e, W, L);
+  c.whole_beam = true; c.want_moves = true;
+  return submit(h, c, ticket);
+}
+int rv_beam_search_collect_moves(rv_handle h, int32_t ticket, const RvBeams* out, const RvMoves* moves, int32_t* S_out) {
+  if (!h) return RV_EINVAL;
+  if (!out || !moves) return fail(h, RV_EINVAL, "null output pointer");      // (all six null: refused at the ticket, which knows whether anything ran)
+  return collect(h, ticket, nullptr, nullptr, nullptr, S_out, out, moves);
 }
 
 int rv_beam_search_flush(rv_handle h) {
@@ -2290,6 +2428,10 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     if (!h->fact.lpersist) return fail(h, RV_ESTATE, "chunk_steps exist only after a persistent decode");
     src = h->d_chunk_steps; n = B; kind = 1;
   }
+  else if (!strcmp(name, "step_moves")) {
+    if (!h->lmoves || !h->d_step_moves) return fail(h, RV_ESTATE, "step_moves are the records of a moves call (rv_beam_search_moves*): the last call on this context was none");
+    src = h->d_step_moves; n = S * B * W * RV_MOVE_COLS;
+  }
   else if (!strcmp(name, "step_ids")) { src = d.step_ids; n = S * B * W; kind = 1; }
   else if (!strcmp(name, "parent_ids")) { src = d.parent_ids; n = S * B * W; kind = 1; }
   else if (!strcmp(name, "step_scores")) { src = d.step_scores; n = S * B * W; }
@@ -2308,7 +2450,7 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (kind == 0) {
     HIPCHK(h, hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (src == h->step_align && h->fact.lflash) {
+    if (src == h->step_align && h->fact.lflash && !h->lmoves) {      // (a moves call's tap is the two-pass launch's: alignments already)
       // the single-pass kernel taps raw log2-domain masked scores; normalise here (debug path only)
       for (size_t r = 0; r < n / Tm; ++r) {
         float* a = dst + r * Tm;
