@@ -21,7 +21,17 @@ Seeds of B, Braw, Bev and C, searched on the CPU as test_beams_gpu's docstring d
 returns the fp64 pass's step ids and parents on all six chunks of every one of the four shapes, and the fp64 records are not vacuous
 in the sense of test_beams_gpu._assert_not_vacuous (on all six chunks and on chunks 0 .. 4); the steps at which the chunks' beams are
 all finished: B [9, 7, 9, 4, 8, 9] (S = 9), Braw [4, 5, 5, 4, 9, 7], Bev [9, 9, 9, 4, 9, 9], C [4, 5, 5, 4, 5, 4] (S = 5).  The tests
-assert non-vacuity on the GPU's own records before they rely on a slab."""
+assert non-vacuity on the GPU's own records before they rely on a slab.
+  D      joint splits with the raw / event boundary where the per-segment reductions can go wrong (s_movesTr, persist_moves_arg:
+         DESIGN.md section 12): one raw sample (1 + 63, 1 + 351), one event (351 + 1), the boundary exactly on a 32-row group edge
+         (32 + 33, 64 + 192), and T_e >= T_r at the full 352 steps (176 + 176); L = 10 up to T_m = 256, L = 6 at 352.  The D shapes share
+         one handle per (attention, cells), sized for any split of 352 steps.
+Seeds of D (BOUNDARY_SEEDS), by the same search: the first slab seeds at which the twin returns the fp64 ids and parents on all six
+chunks and the fp64 records are not vacuous on all six and on chunks 0 .. 4 are 1, 2, 1, 3, 1, 2 in the order of SHAPES (the lower
+seeds fail only because their chunks finish together); the chunks' beams are all finished at 1 + 63 [9, 9, 7, 9, 9, 5], 32 + 33
+[5, 9, 5, 9, 6, 4], 64 + 192 [6, 9, 9, 9, 9, 9], 1 + 351 [5, 5, 4, 5, 5, 5], 351 + 1 [4, 5, 5, 5, 5, 5], 176 + 176 [5, 3, 5, 5, 5, 5].
+test_against_fp64 counts its witnesses of non-vacuity (a parent row whose position differs from the slot's by more than four times
+the tolerance) in the longer segment of a shape: with one raw sample every raw position is 0."""
 import ctypes
 
 import numpy as np
@@ -37,9 +47,12 @@ from test_parity_gpu import _near_tie_gap
 pytestmark = pytest.mark.gpu
 
 SHAPES = {"A": ("joint", 40, 8, 14), "B": ("joint", 61, 9, 10), "Braw": ("raw", 70, 0, 10), "Bev": ("event", 0, 33, 10),
-          "C": ("joint", 308, 44, 6)}
-NIT = {48: 2, 70: 8, 33: 2, 352: 11}          # the k_dec_persist band that serves T_m
+          "C": ("joint", 308, 44, 6),
+          "D1+63": ("joint", 1, 63, 10), "D32+33": ("joint", 32, 33, 10), "D64+192": ("joint", 64, 192, 10),
+          "D1+351": ("joint", 1, 351, 6), "D351+1": ("joint", 351, 1, 6), "D176+176": ("joint", 176, 176, 6)}
+NIT = {48: 2, 70: 8, 33: 2, 352: 11, 64: 2, 65: 8, 256: 8}          # the k_dec_persist band that serves T_m
 OTHER_SEEDS = (1, 1)                          # (weight seed, slab seed) of B, Braw, Bev, C: see the module docstring
+BOUNDARY_SEEDS = {"D1+63": 1, "D32+33": 2, "D64+192": 1, "D1+351": 3, "D351+1": 1, "D176+176": 2}     # slab seeds of the D shapes
 MX = dict(matrix_attention=1, matrix_cell=1)
 PERSIST_OPTS = dict(persistent_decode=1, use_graph=1, decode_split=1)
 # form -> (attention, decoder cells, options, the ATT of k_dec_persist it must run or None for the per-step kernels, beam widths on A)
@@ -50,12 +63,12 @@ MOVE_FORMS.update({
     "att2": ("luong", 1, dict(PERSIST_OPTS, matrix_attention=1, matrix_cell=0), 2, (1, 3, 5, 8)),
 })
 CASES = [(f, W, "A") for f, spec in MOVE_FORMS.items() for W in spec[4]] + \
-        [(f, 5, sh) for sh in ("B", "Braw", "Bev", "C") for f in MOVE_FORMS]
+        [(f, 5, sh) for sh in ("B", "Braw", "Bev", "C", *BOUNDARY_SEEDS) for f in MOVE_FORMS]
 FIELDS = M.FIELDS
 
 
 # ---------------------------------------------------------------------------------------------- handles and slabs: made once
-_HANDLES = {}
+_HANDLES, _BASECALLERS = {}, {}
 
 
 @pytest.fixture(scope="module")
@@ -64,8 +77,12 @@ def handles(rv):
         key = (shape, attention, D)
         if key not in _HANDLES:
             mode, TR, TE, L = SHAPES[shape]
-            wseed, sseed = SEEDS[(attention, D)] if shape == "A" else OTHER_SEEDS
-            bc, w = _handle(rv, mode, attention, D, wseed, Tr_max=max(TR, 1), Te_max=max(TE, 1), L=L, end_bias=END_BIAS)
+            wseed, sseed = SEEDS[(attention, D)] if shape == "A" else (OTHER_SEEDS[0], BOUNDARY_SEEDS.get(shape, OTHER_SEEDS[1]))
+            # the D shapes share one handle per (attention, cells): the same weights, room for every split of 352 steps
+            hkey, TRm, TEm, Lm = (("D", attention, D), 351, 351, 10) if shape in BOUNDARY_SEEDS else (key, max(TR, 1), max(TE, 1), L)
+            if hkey not in _BASECALLERS:
+                _BASECALLERS[hkey] = _handle(rv, mode, attention, D, wseed, Tr_max=TRm, Te_max=TEm, L=Lm, end_bias=END_BIAS)
+            bc, w = _BASECALLERS[hkey]
             raw, ev = _slab(mode, TR, TE, seed=sseed)
             praw, pev = raw.copy(), ev.copy()
             praw[5], pev[5] = 0.0, 0.0                # the same slab with its last chunk padding from end to end
@@ -74,9 +91,10 @@ def handles(rv):
             _HANDLES[key] = (bc, w, (raw, ev), (praw, pev))
         return _HANDLES[key]
     yield get
-    for bc, *_ in _HANDLES.values():
+    for bc, _ in _BASECALLERS.values():
         bc.close()
     _HANDLES.clear()
+    _BASECALLERS.clear()
 
 
 def _p(a):
@@ -260,17 +278,21 @@ def test_the_beam_is_untouched(handles, form, W):
 
 
 # ---------------------------------------------------------------------------------------------- 4
-@pytest.mark.parametrize("form", ["persistent", "per_step_graph"])
-def test_against_fp64(handles, oracle, form):
+@pytest.mark.parametrize("form,shape", [pytest.param(f, sh, id=f if sh == "A" else f"{f}-{sh}")
+                                        for sh in ("A", *BOUNDARY_SEEDS) for f in ("persistent", "per_step_graph")])
+def test_against_fp64(handles, oracle, form, shape):
     W = 5
     attention, D, opts, att, _ = MOVE_FORMS[form]
     assert (attention, D) == ("luong", 1)
-    mode, TR, TE, L = SHAPES["A"]
+    mode, TR, TE, L = SHAPES[shape]
     Tm = TR + TE
-    bc, w, (raw, ev), _ = handles("A", attention, D)
+    bc, w, (raw, ev), _ = handles(shape, attention, D)
     _set(bc, opts)
     r = _tapped_call(bc, _x(mode, raw, ev), W, L, Tm, att is not None)
+    form = form if shape == "A" else f"{form} {shape}"
     _assert_form(r["forms"], W, Tm, D, att, form, aside=True)      # per_step_graph: the records of the default per-step route
+    wseg = "raw" if TR >= TE else "event"                          # the witnesses of non-vacuity: positions in the longer segment
+    wcol = 0 if wseg == "raw" else 2
     end = bc.cfg.end_token
     taps = {}
     oracle.beam_search(w, bc.cfg.oracle_cfg(), raw, ev, W, L, dtype=np.float64, taps=taps)
@@ -315,10 +337,10 @@ def test_against_fp64(handles, oracle, form):
                 assert 0 <= pk < Tm and a64[t, b, row, pk] >= a64[t, b, row].max() - 2 * d, (tag, "peak", pk)
                 # non-vacuity: the parent row is not the slot, and the two rows' fp64 positions are told apart by the tolerance
                 s_ = int(slot[b, t, k])
-                if row != s_ and "raw" in tol_pos and rec64[t, b, s_, 0] > 0:
+                if row != s_ and wseg in tol_pos and rec64[t, b, s_, wcol] > 0:
                     tried += 1
-                    other = rec64[t, b, s_, 1] / rec64[t, b, s_, 0]
-                    witnesses += abs(other - ref["raw_pos"][b, t, k]) > 4 * tol_pos["raw"]
+                    other = rec64[t, b, s_, wcol + 1] / rec64[t, b, s_, wcol]
+                    witnesses += abs(other - ref[wseg + "_pos"][b, t, k]) > 4 * tol_pos[wseg]
     print(f"{form}: S = {r['S']} (fp64 {So}), left {left}, max |alpha - fp64| = {worst_d:.2e}, parent != slot cases {tried}, of which "
           f"the rows differ by more than 4 x tolerance: {witnesses}")
     assert witnesses > 0, (form, "no case tells the parent row from the slot", tried)
