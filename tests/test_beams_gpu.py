@@ -95,10 +95,11 @@ def _expect(oracle, ids, par, sc, cs, end):
                 ids=ids, par=par, cs=np.asarray(cs).astype(int), fin_at=fin_at)
 
 
-def _assert_not_vacuous(e, W, tag, rows=slice(None)):
-    """The records behind an expectation exercise the kernel: see the module docstring."""
+def _assert_not_vacuous(e, W, tag, rows=slice(None), finish_apart=True):
+    """The records behind an expectation exercise the kernel: see the module docstring.  finish_apart=False: a slab meant to run every
+    chunk to the last step (test_longest_output_gpu's "long" inputs), which states its own condition on the finishing steps."""
     cs, S = e["fin_at"][rows], e["tokens"].shape[1]
-    assert len(set(cs.tolist())) > 1 and cs.min() < S, (tag, "chunks finish together", cs.tolist(), S)
+    assert not finish_apart or (len(set(cs.tolist())) > 1 and cs.min() < S), (tag, "chunks finish together", cs.tolist(), S)
     if W == 1:
         return
     ident = np.arange(W)[None, None]

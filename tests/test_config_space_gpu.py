@@ -293,7 +293,7 @@ def _no_sentinel(*arrays):
         assert (a.view(np.uint8).reshape(-1, a.dtype.itemsize) != 0x7F).any(axis=1).all(), "an element the call did not write"
 
 
-def _beam_entry_points(bc, raw, ev, W):
+def _beam_entry_points(bc, raw, ev, W, L=L):
     """(name, tokens [B, L-1], scores [B, L-1], S) of every beam-search entry point on sentinel-filled buffers."""
     import torch
     lib, h, S = bc._lib, bc._h, ctypes.c_int32(-1)
@@ -326,7 +326,7 @@ def _beam_entry_points(bc, raw, ev, W):
     return out
 
 
-def _greedy_entry_points(bc, raw, ev, V):
+def _greedy_entry_points(bc, raw, ev, V, L=L):
     import torch
     lib, h, S = bc._lib, bc._h, ctypes.c_int32(-1)
     Bn, steps = raw.shape[0], L - 1
@@ -344,7 +344,7 @@ def _greedy_entry_points(bc, raw, ev, V):
     return out
 
 
-def _calls_entry_points(bc, raw, ev, W):
+def _calls_entry_points(bc, raw, ev, W, L=L):
     lib, h, S, t = bc._lib, bc._h, ctypes.c_int32(-1), ctypes.c_int32(-1)
     Bn, steps = raw.shape[0], L - 1
     dims = (Bn, raw.shape[1], ev.shape[1], W, L)
