@@ -48,6 +48,10 @@ void list_mx_forms(FormLog& log);
 void list_decode_forms(FormLog& log);
 
 // ---------------------------------------------------------------- K1: BiLSTM recurrence
+// Members of a coalesced call whose inputs are read where their callers left them (matrix-pipe layer 0 only): chunk b of the group with
+// row0[m] <= b < row0[m] + rows[m] is row b - row0[m] of x[m] [rows[m],T,F].  n = 0: every chunk is a row of RecArgs::x.
+#define RV_MAX_MEMBERS 8
+struct RecMembers { int n; int row0[RV_MAX_MEMBERS]; int rows[RV_MAX_MEMBERS]; const float* x[RV_MAX_MEMBERS]; };
 struct RecArgs {
   const float* x;        // F>0: chunk input [B,T,F];  F==0: pre-projected xw [B,T,2,512] (bias folded)
   const float* W[2];     // F>0: input kernel [F,512] per direction
@@ -73,6 +77,7 @@ struct RecArgs {
   int mask_T, mask_t0;   //   (the window is in LDS anyway; saves the slab a launch).  null = not asked for
   float pad;
   const void* const* ptab;   // matrix-pipe raw layer 0 only: non-null = read the chunk inputs' address from ptab[RV_PTAB_RAW] instead of `x`
+  RecMembers members;        // matrix-pipe layer 0 only: n > 0 = the chunks' inputs are rows of the members' own tensors, not of `x`
 };
 // Caller pointers of a slab call, read by the kernels through a small table in mapped pinned memory when the slab replays from a
 // hipGraph whose kernel arguments are frozen (ravvent_hip.cpp, option "slab_graph": one graph per slab context and call shape): the
@@ -256,7 +261,6 @@ void launch_dec_persist(const DecState& d, const float* Wcat /*[256,512]*/, cons
 // Members (persistent beam-search decode only): the slab is n slabs of the asynchronous calls decoded as one, back to back.  Member m
 // owns rows row0[m] .. row0[m] + rows[m] - 1: its S is the maximum of chunk_steps over those rows alone, goes to S_host[m], and its rows
 // are written through tokens[m] / out2[m] at the member's own row index.  n = 0: one member, the whole slab, the launcher's two pointers.
-#define RV_MAX_MEMBERS 8
 struct DecMembers { int n; int row0[RV_MAX_MEMBERS]; int rows[RV_MAX_MEMBERS]; int32_t* tokens[RV_MAX_MEMBERS]; float* out2[RV_MAX_MEMBERS]; };
 void launch_dec_finalize(const DecState& d, int32_t* tokens /*[B,L-1]*/, float* scores_or_logits, hipStream_t s, const void* const* ptab = nullptr,
                          const DecMembers* members = nullptr);

@@ -54,7 +54,7 @@ __device__ __forceinline__ float ror8_add(float v) {           // v + (v of the 
   return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, false));
 }
 
-template <int F, int CH>
+template <int F, int CH, bool MEM = false>
 __device__ __forceinline__ void rec_mx_body(const RecArgs& a) {
   static_assert(F == 0 || F == 1 || F == 5, "pre-projected inputs, or layer 0 on its F input features (raw samples: 1; events: 5)");
   static_assert(CH == 16 || CH == 8, "sixteen chunks per workgroup, or eight with both parts of h in the product's columns");
@@ -97,8 +97,15 @@ __device__ __forceinline__ void rec_mx_body(const RecArgs& a) {
       for (int r = 0; r < CH; ++r) {
         const int b = min(b0 + r, a.B - 1);
         const bool wm = a.mask && dir == 0 && b0 + r < a.B;     // utils.input_mask of this encoder's part (utils.py:26-32: all features != pad), once per chunk
+        const float* xb = xg;
+        int br = b;
+        if constexpr (MEM) {    // chunk b is a row of its member's own tensor (a workgroup's chunks may straddle members, so per chunk; scalar
+                                // 4-byte loads below: a member's tensor may sit at any float offset)
+          for (int m = 0; m < a.members.n; ++m)
+            if (b >= a.members.row0[m] && b < a.members.row0[m] + a.members.rows[m]) { xb = a.members.x[m]; br = b - a.members.row0[m]; }
+        }
         for (int i = tid; i < T; i += 512) {
-          const float* v = xg + ((size_t)b * T + i) * F;
+          const float* v = xb + ((size_t)br * T + i) * F;
 #pragma unroll
           for (int f = 0; f < F; ++f) xs[(r * T + i) * F + f] = v[f];
           if (wm) {
@@ -261,6 +268,12 @@ __device__ __forceinline__ void rec_mx_body(const RecArgs& a) {
 template <int F, int CH>
 __global__ __launch_bounds__(512) void k_lstm_rec_mx(RecArgs a) { rec_mx_body<F, CH>(a); }
 
+// The layer-0 forms (F > 0) for a coalesced call whose members' inputs stay where their callers hold them (RecArgs::members): the same body,
+// with the staging prologue resolving each chunk to its member's tensor.  Instantiations of their own, so that the step loops of the forms
+// above keep their instruction stream (the head of this file); they are logged as the (F, CH) form they are.
+template <int F, int CH>
+__global__ __launch_bounds__(512) void k_lstm_rec_mx_members(RecArgs a) { rec_mx_body<F, CH, true>(a); }
+
 // x . W + b for a layer-0 encoder with a handful of input features (the event encoder: F = 5), both directions:
 // xw [B*T, 2, 512].  One thread = 4 gate columns of one row; HBM-bound on its output (4 KB per chunk-timestep).
 template <int F>
@@ -314,6 +327,10 @@ hipError_t configure_mx_kernels() {
     using M = decltype(form);
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lstm_rec_mx<M::F, M::CH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess && first == hipSuccess) first = e;
+    if constexpr (M::F > 0) {
+      const hipError_t em = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lstm_rec_mx_members<M::F, M::CH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (em != hipSuccess && first == hipSuccess) first = em;
+    }
   });
   return first;
 }
@@ -323,7 +340,10 @@ void launch_lstm_rec_mx(const RecArgs& a, int F, hipStream_t s, bool rows8, Form
   for_each_mx_form([&](auto form) {
     using M = decltype(form);
     if (mx_serves<M>(F, CH)) {
-      hipLaunchKernelGGL((k_lstm_rec_mx<M::F, M::CH>), dim3((a.B + CH - 1) / CH, 2), dim3(512), mx_lds_bytes(M::F, a.T), s, a);
+      const dim3 grid((a.B + CH - 1) / CH, 2);
+      auto kernel = &k_lstm_rec_mx<M::F, M::CH>;
+      if constexpr (M::F > 0) { if (a.members.n > 0) kernel = &k_lstm_rec_mx_members<M::F, M::CH>; }
+      hipLaunchKernelGGL(kernel, grid, dim3(512), mx_lds_bytes(M::F, a.T), s, a);
       if (log) log->add(RV_K_LSTM_REC_MX, M::F, M::CH);
     }
   });

@@ -68,6 +68,8 @@ struct Options {
   int gen = 0;                              // (root) bumped by every rv_set_option / rv_load_weights: frozen arguments may have changed
   int async_depth = 2;                      // contexts the asynchronous entry points rotate through (1..RV_MAX_ASYNC)
   int coalesce = -1;                        // 0 / 1 off, n >= 2 slabs per group, -1 chosen from async_depth (coalesce_n)
+  int group_inplace = 1;                    // a group's layer-0 kernels read its members' device inputs where they are (no copies into the group's buffers)
+  int group_side_ev = -1;                   // a group's event encoder on a side stream beside its raw encoder: 0 / 1, -1 where the queues allow it (group_side_ev)
 };
 
 // Device images derived from the weights by rv_load_weights.  The handle owns them; a child context takes the addresses as a whole (create_child)
@@ -245,6 +247,8 @@ struct RvContext {
   uint8_t g_lut[RV_MAX_VOCAB] = {};
   int g_tslot[RV_MAX_MEMBERS] = {};
   DecMembers g_members{};                   // its member table: output addresses as the members come (submit_group), rows at its launch (launch_group)
+  bool g_inplace = false;                   // its members' device inputs are read in place (option "group_inplace"), through ...
+  RecMembers g_in[2]{};                     // ... these tables [raw, event]: addresses as the members come, rows at its launch
 };
 
 namespace {
@@ -425,6 +429,11 @@ bool rows8_wanted(const RvContext* h, int B) {
   return h->opt.wide < 0 && n >= 160 && n <= 512;
 }
 
+// Does layer 0 of this encoder take x . W + b in the lane of its matrix-pipe recurrence, from LDS windows of the chunks' inputs?
+bool lane_layer0(const RvContext* h, int F, int T) {
+  return F == 1 || (F == 5 && h->opt.lane_inproj && lstm_rec_mx_window_fits(T, 5));
+}
+
 void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int Tm, int t_off, hipStream_t s,
                  int l_begin = 0, int l_end = 1 << 30, const void* const* ptab = nullptr) {
   const int depth = h->cfg.enc_depth;
@@ -450,17 +459,18 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
       // matrix-pipe recurrence.  Raw layer 0 folds its one-feature input projection in; every other layer reads pre-projected
       // inputs xw [B,T,2,512]: event layer 0 from a small elementwise kernel, layers >= 1 from the split-f16 GEMM (both directions
       // and their biases in one launch, A read once).
-      if (l == 0 && (F == 1 || (F == 5 && h->opt.lane_inproj && lstm_rec_mx_window_fits(T, 5)))) {
+      if (l == 0 && lane_layer0(h, F, T)) {
         // layer 0 takes x . W + b in the lane, from LDS windows of its chunks' inputs: no projection launch, no xw round trip (round 4: the
         // event encoder's five features too -- the same fused multiply-adds in the same order as k_inproj_small: identical bits)
         a.x = x;
         for (int dr = 0; dr < 2; ++dr) { a.W[dr] = h->enc[e][0][dr].W; a.bias[dr] = h->enc[e][0][dr].b; }
         a.mask = h->mask; a.mask_T = Tm; a.mask_t0 = t_off; a.pad = h->cfg.padding_value;   // the layer-0 kernels leave the input mask too
         a.ptab = ptab;
+        if (h->g_inplace) a.members = h->g_in[e];      // (a group whose members' inputs stay where they are: launch_group)
         a.dbg_ts = (e == 0 && h->rec_ts_layer == 0) ? h->rec_ts : nullptr;     // (RV_REC_STAMPS=1: phase cycle sums of workgroup (0, 0))
         Scope sc(h, F == 1 ? "lstm_rec_raw_l0" : "lstm_rec_event_l0", s);
         launch_lstm_rec_mx(a, F, s, h->lrows8 != 0, &h->lforms);
-        a.dbg_ts = nullptr; a.ptab = nullptr; a.mask = nullptr;
+        a.dbg_ts = nullptr; a.ptab = nullptr; a.mask = nullptr; a.members.n = 0;
         continue;
       }
       if (l == 0) {
@@ -560,6 +570,7 @@ int persist_form(const RvContext* h, bool greedy, int W, int Tm, bool forced) {
 }
 
 int record_slab(RvContext* h, const Call& call, const CallParts& res, const void* const* ptab);
+bool group_side_ev(const RvContext* root);
 
 // The checks every call passes before anything is queued.  `ok` becomes the call with its effective lengths: T_r / T_e of an encoder
 // the mode does not use are 0 there, and everything past this point works on `ok`
@@ -735,12 +746,16 @@ int record_encoders(RvContext* h, const Slab& sl) {
     run_encoder(h, 0, xr, 1, B, T_r, Tm, 0, s, 1);
     HIPCHK(h, hipEventRecord(h->ev_join[0], sev));
     HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[0], 0));
-  } else if (h->lwide && use_raw && use_ev && h->inflight_hint <= 1 && !ptab && h->opt.profile == 0 && h->opt.side_ev) {
+  } else if (h->lwide && use_raw && use_ev && !ptab && h->opt.profile == 0 &&
+             ((h->inflight_hint <= 1 && h->opt.side_ev) || (h->g_cap > 0 && h->parent && group_side_ev(h->parent)))) {
     // One isolated slab on the matrix-pipe form: every encoder launch is 2 x ceil(B / 16) workgroups (32 of the chip's 256 CUs at B = 256), so
     // the event encoder's chain (four launches, ~0.15 ms at the C3 shape) runs on a side stream BESIDE the raw encoder's instead of in front of
     // it: the synchronous call's latency drops by that much.  (With several slabs in flight the other slabs fill the chip: one stream per
     // context then, no fork / join.)  The two encoders write disjoint time ranges of enc_out and of the mask and use their own xw / act / state
     // buffers: results are identical.
+    // A group of coalesced slabs forks the same way where the queues allow it (group_side_ev): with two groups in flight each one's next
+    // launch waits for its whole chain, and the event launches (2 x ceil(B / 16) workgroups: 160 of 256 CUs for five C3 slabs) need not be
+    // links of it.
     hipStream_t sev = side_stream(h, 0);
     HIPCHK(h, hipEventRecord(h->ev_fork, s));
     HIPCHK(h, hipStreamWaitEvent(sev, h->ev_fork, 0));       // inputs (H2D copies on s) are in place
@@ -1483,6 +1498,15 @@ int coalesce_n(const RvContext* h, int depth) {
   return depth < 8 ? 2 : std::min(depth / 2, 5);      // (C3 on 4 queues: depth 4 and 6 stream fastest with 2, depth 10 with 5)
 }
 
+// Does a group run its event encoder on a side stream beside its raw encoder (record_encoders)?  By default where every group context in
+// flight, ceil(depth / n) of them, gets a hardware queue for its own stream and one for its side stream (C3 at the defaults on 4 queues:
+// two groups of five; profiles/group_chain.md).
+bool group_side_ev(const RvContext* root) {
+  if (root->opt.group_side_ev >= 0) return root->opt.group_side_ev != 0;
+  const int depth = async_depth(root), n = coalesce_n(root, depth);
+  return 2 * ((depth + n - 1) / n) <= hw_queues();
+}
+
 int uncollected(const RvContext* h) {
   int n = h->pend.busy ? 1 : 0;
   for (const RvContext* k : h->kids) n += k->pend.busy ? 1 : 0;
@@ -1500,7 +1524,13 @@ void reset_group(RvContext* g) {
   g->g_n = 0; g->g_rows = 0; g->g_staged = 0; g->g_launched = false; g->g_synced = false; g->g_failed = RV_OK;
 }
 
-// Queue a group's internal call: its members' inputs are in d_raw / d_ev already (submit_group), back to back.
+// Can the layer-0 kernels of a group of this shape read their members' device inputs in place?  Only the matrix-pipe layer 0 with its
+// input projection in the lane resolves a chunk to its member (rec_mx_body); coalescible() has settled that for the raw encoder.
+bool inplace_serves(const RvContext* h, int T_e) {
+  return h->opt.group_inplace && (h->cfg.mode == RV_MODE_RAW || lane_layer0(h, 5, T_e));
+}
+
+// Queue a group's internal call: its members' inputs are in d_raw / d_ev already, back to back, or stay where the callers hold them (submit_group).
 int launch_group(RvContext* root, RvContext* g) {
   if (root->open_grp == g) root->open_grp = nullptr;
   if (g->g_launched) return g->g_failed;
@@ -1514,6 +1544,7 @@ int launch_group(RvContext* root, RvContext* g) {
   for (int i = 0; i < g->g_n; ++i) {
     const RvContext::Tick& t = root->ticks[g->g_tslot[i]];
     m.row0[i] = t.row0; m.rows[i] = t.B;
+    for (RecMembers& in : g->g_in) { in.n = g->g_n; in.row0[i] = t.row0; in.rows[i] = t.B; }
     if (!g->g_dev_out) { m.tokens[i] = g->out_tokens + (size_t)t.row0 * steps; m.out2[i] = g->out2 + (size_t)t.row0 * steps; }
   }
   Call call;
@@ -1562,12 +1593,14 @@ int submit_group(RvContext* h, int n, const Call& call, int32_t* ticket) {
       RvContext* k = nullptr;
       TRY(create_child(h, &k, n));
       k->g_cap = n;
+      if (group_side_ev(h)) side_stream(k, 0);      // (created with the context, as its buffers are: not at a group's first launch in mid-stream)
       reset_group(k);
       h->groups.push_back(k);
       if (!g) g = k;
     }
     reset_group(g);
     g->g_Tr = T_r; g->g_Te = T_e; g->g_W = W; g->g_L = L; g->g_dev_in = dev_in; g->g_dev_out = dev_out; g->g_calls = calls; g->g_B0 = B;
+    g->g_inplace = dev_in && inplace_serves(h, T_e);      // (the options cannot change under an open group: rv_set_option launches it)
     memset(g->g_lut, 0, sizeof g->g_lut);
     if (calls) memcpy(g->g_lut, lut, (size_t)c.vocab);
     h->open_grp = g;
@@ -1576,7 +1609,9 @@ int submit_group(RvContext* h, int n, const Call& call, int32_t* ticket) {
   for (int i = 0; i < RV_MAX_ASYNC && slot < 0; ++i) if (!h->ticks[i].busy) slot = i;
   if (slot < 0) return fail(h, RV_ESTATE, "no free ticket");      // (unreachable: at most async_depth <= RV_MAX_ASYNC are uncollected)
   const size_t row0 = (size_t)g->g_rows;
-  if (B > 0) {    // the member's inputs go to its rows of the group's input buffers now: the caller's host buffers are free on return
+  if (g->g_inplace) {   // device inputs stay valid and untouched until the ticket is collected (ravvent_hip.h): the layer-0 kernels read them there
+    g->g_in[0].x[g->g_n] = raw; g->g_in[1].x[g->g_n] = ev;
+  } else if (B > 0) {   // the member's inputs go to its rows of the group's input buffers now: the caller's host buffers are free on return
     const size_t nr = (size_t)B * T_r, ne = (size_t)B * T_e * 5;
     if (!dev_in) {
       if (nr) { memcpy(g->pin_raw + row0 * T_r, raw, sizeof(float) * nr); HIPCHK(h, hipMemcpyAsync(g->d_raw + row0 * T_r, g->pin_raw + row0 * T_r, sizeof(float) * nr, hipMemcpyHostToDevice, g->stream)); }
@@ -2319,6 +2354,8 @@ int rv_beam_search_flush(rv_handle h) {
 int rv_set_option(rv_handle h, const char* key, int32_t value) {
   if (!h || !key) return RV_EINVAL;
   flush_open_group(h);               // a group still filling was submitted under the options as they were
+  if (!strcmp(key, "group_inplace") && value != 0 && value != 1) return fail(h, RV_EINVAL, "group_inplace must be 0 or 1");
+  if (!strcmp(key, "group_side_ev") && (value < -1 || value > 1)) return fail(h, RV_EINVAL, "group_side_ev must be -1 (where the hardware queues allow it), 0 or 1");
   h->opt.gen++;                      // slab graphs captured under the old options are rebuilt on their next use
   if (!strcmp(key, "debug_taps")) h->opt.taps = value != 0;
   else if (!strcmp(key, "slab_graph")) h->opt.slab_graph = value != 0;
@@ -2326,6 +2363,8 @@ int rv_set_option(rv_handle h, const char* key, int32_t value) {
     if (value < -1 || value > RV_MAX_MEMBERS) return fail(h, RV_EINVAL, "coalesce must be -1 (chosen from async_depth), 0, 1 or 2..%d", RV_MAX_MEMBERS);
     h->opt.coalesce = value;
   }
+  else if (!strcmp(key, "group_inplace")) h->opt.group_inplace = value;
+  else if (!strcmp(key, "group_side_ev")) h->opt.group_side_ev = value;
   else if (!strcmp(key, "persist_taps")) h->opt.ptaps = value != 0;
   else if (!strcmp(key, "fused_memory")) h->opt.fused_mem = value != 0;
   else if (!strcmp(key, "use_graph")) h->opt.graph = value != 0;
