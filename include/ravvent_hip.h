@@ -11,10 +11,10 @@
  * is NOT thread-safe (the reference is single-threaded and synchronous:
  * ravvent_performance_evaluator.py:51-55); use one handle per GPU / per process.
  *
- * Synchronous calls -- rv_beam_search, rv_beam_search_dev, rv_beam_search_calls, rv_beam_search_all, rv_beam_search_all_dev,
+ * Synchronous calls -- rv_beam_search, rv_beam_search_dev, rv_beam_search_calls, rv_beam_search_windows, _windows_dev, _windows_calls, rv_beam_search_all, rv_beam_search_all_dev,
  * rv_greedy_search, rv_greedy_search_dev, rv_teacher_forced, rv_teacher_forced_dev, rv_score_logits, rv_load_weights, rv_get_tensor: results are complete when the call
  * returns, so a caller's wall-clock timers mean what they mean around the reference's methods.
- * Asynchronous calls -- rv_beam_search_submit, _submit_dev, _submit_calls, _submit_all, _submit_all_dev: they return once the
+ * Asynchronous calls -- rv_beam_search_submit, _submit_dev, _submit_calls, _submit_windows, _submit_windows_calls, _submit_all, _submit_all_dev: they return once the
  * slab is queued, or held for its group until one of the events listed at rv_beam_search_flush
  * (option "coalesce"); the matching rv_beam_search_collect* waits for it.  A synchronous call may be
  * made while tickets are in flight: it runs on an idle slab context of the handle (its own when
@@ -224,6 +224,54 @@ int rv_beam_search_collect_moves(rv_handle h, int32_t ticket, const RvBeams* out
  * that is still filling and returns at once (RV_OK also when there is none).  A launch that fails is reported by its tickets' collects. */
 int rv_beam_search_flush(rv_handle h);
 
+/* Reads and windows: beam search over chunks that are gathered on the chip from a read uploaded ONCE.  A chunk of
+ * the calls above is a padded row of a [B,T_r,1] / [B,T_e,5] tensor; at the evaluator's stride every sample of a read is copied into four
+ * to five such rows on the host and crosses the bus that often.  Here the read's two scaled tables go to the device as they are, and a
+ * chunk is a row of a small table of (start, length) windows into them.  These entry points were added without changing an existing one:
+ * RV_ABI_VERSION stays at 1.
+ *
+ * Reads.  raw: the standard-scaled samples f32 [n_raw] (NULL in event mode: ignored there); event: the scaled event features f32
+ * [n_event,5] (NULL in raw mode).  data_loader.prepare_windows produces both.
+ *   rv_read_put      host pointers; the tables are copied to pinned staging and uploaded on a copy stream of the handle: the caller may
+ *                    reuse its buffers on return, and the calls that use the read wait for the upload on the device (an event), not on the
+ *                    host.  A dropped read's buffers are kept: a put no larger than a buffer dropped earlier makes NO device allocation
+ *                    (rv_get_tensor("read_stats") counts them), so a streaming loop of put / calls / drop allocates only while it warms up
+ *   rv_read_put_dev  device addresses the caller keeps valid and untouched until the read is dropped; no copy is made
+ *   rv_read_drop     the id is dead from here on (a later put never returns it again).  RV_ESTATE while an uncollected ticket uses the read
+ * *read_id receives a non-negative id.  Up to 1,024 reads are alive at once.
+ *
+ * Window calls take a HOST table win [B,5] i32 with the columns (read_id, raw_start, raw_len, event_start, event_len), starts and lengths
+ * in samples / events; rows of one table may name different reads.  Chunk b is raw_len samples from raw_start followed by padding_value
+ * up to T_r, and event_len events from event_start followed by padding_value rows up to T_e: the result is byte for byte that of the
+ * chunk-tensor call on those padded rows (data_loader.expand_windows builds them), under every option.  The table is checked on the host
+ * BEFORE anything is queued; RV_EINVAL, with a message that names the row, for: an unknown read_id, a negative start or length, start +
+ * len beyond the read, raw_len > T_r or event_len > T_e.  The kernels therefore never index with an unchecked offset.  The columns of the
+ * segment the mode does not use are ignored.  B, T_r, T_e, W, L, the outputs and S_out: as for the call each one mirrors.
+ *   rv_beam_search_windows               synchronous, host outputs: rv_beam_search
+ *   rv_beam_search_windows_dev           synchronous, device outputs: rv_beam_search_dev
+ *   rv_beam_search_windows_calls         synchronous, fused post-processing: rv_beam_search_calls
+ *   rv_beam_search_submit_windows        asynchronous: the ticket is collected by rv_beam_search_collect
+ *   rv_beam_search_submit_windows_calls  asynchronous: the ticket is collected by rv_beam_search_collect_calls
+ * On the default path the layer-0 recurrence kernels read each chunk's window in their staging prologue (the forms "kernel_forms" lists
+ * for the chunk-tensor call, same rows); every other form -- "wide_recurrence" 0, "lane_projection" 0, the per-step decode, debug taps,
+ * profiling, a coalesced group with "group_inplace" 0 -- runs unchanged behind one launch of k_expand_windows, which writes the padded
+ * tensors into the context's input buffers (profile scope "expand_windows").  A window call is never replayed as a "slab_graph".  Window
+ * slabs of equal T_r, T_e, W, L, output kind and lut are coalesced under the rules at rv_beam_search_flush; a window slab and a
+ * chunk-tensor slab never share a group (each launches the group that is filling). */
+int rv_read_put(rv_handle h, const float* raw, size_t n_raw, const float* event, size_t n_event, int32_t* read_id);
+int rv_read_put_dev(rv_handle h, const float* d_raw, size_t n_raw, const float* d_event, size_t n_event, int32_t* read_id);
+int rv_read_drop(rv_handle h, int32_t read_id);
+int rv_beam_search_windows(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L, int32_t* tokens,
+                           float* scores, int32_t* S_out);
+int rv_beam_search_windows_dev(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                               int32_t* d_tokens, float* d_scores, int32_t* S_out);
+int rv_beam_search_windows_calls(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                 const uint8_t* lut, uint8_t* bases, int32_t* lengths, float* probs, int32_t* S_out);
+int rv_beam_search_submit_windows(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                  int32_t* ticket);
+int rv_beam_search_submit_windows_calls(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                        const uint8_t* lut, int32_t* ticket);
+
 /* Basecaller.greedy_search_prediction (basecaller.py:317-330): tokens = sample_id [B, L-1],
  * logits = rnn_output [B, L-1, vocab]; columns >= S are pad_token / 0. */
 int rv_greedy_search(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r,
@@ -375,6 +423,8 @@ int rv_set_option(rv_handle h, const char* key, int32_t value);
  *   "kernel_form_list" [n,5]      every instantiation the form lists hold, in the same rows, whatever the last call was
  *   "coalesce_stats"  [4]         of the handle since it was created: groups launched (option "coalesce"), slabs they held, members of the
  *                                 largest one, and the slabs per group the options and the environment give right now (1 = none)
+ *   "read_stats"      [5]         of the handle since it was created: device allocations made for reads (rv_read_put), reads alive, puts,
+ *                                 read slots (alive, or dropped with their buffers kept), launches of k_expand_windows
  * n_written receives the element count; fails with RV_EINVAL if dst is too small. */
 int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, size_t* n_written);
 

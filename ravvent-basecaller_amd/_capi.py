@@ -63,6 +63,14 @@ SYMBOLS = [
     ("rv_beam_search_submit_moves", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _I]),
     ("rv_beam_search_collect_moves", c_int32, [c_void_p, c_int32, _B, _M, _I]),
     ("rv_beam_search_flush", c_int32, [c_void_p]),
+    ("rv_read_put", c_int32, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, _I]),
+    ("rv_read_put_dev", c_int32, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, _I]),
+    ("rv_read_drop", c_int32, [c_void_p, c_int32]),
+    ("rv_beam_search_windows", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
+    ("rv_beam_search_windows_dev", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
+    ("rv_beam_search_windows_calls", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, _I]),
+    ("rv_beam_search_submit_windows", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _I]),
+    ("rv_beam_search_submit_windows_calls", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, _I]),
     ("rv_greedy_search", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
     ("rv_greedy_search_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
     ("rv_teacher_forced", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, _S]),

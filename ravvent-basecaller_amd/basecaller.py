@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from . import _capi, weights as _weights
+from . import _capi, data_loader as _dl, weights as _weights
 from .config import RvConfig, RAW_FEATURES, EVENT_FEATURES
 from .data_loader import _ASCII, nuc_tk, tokens_to_strings
 
@@ -34,6 +34,47 @@ Moves = collections.namedtuple("Moves", "raw_pos raw_mass event_pos event_mass p
 # What a forced decode or a scoring call leaves (rv_teacher_forced*, rv_score_logits; include/ravvent_hip.h: RvScore): sample_id [B,S]
 # int32 the argmax of logits [B,S,V]; nll [B,S] f32 the masked cross-entropy terms; nll_sum [B] f32, n_labels / n_match / n_counted [B] int32
 ForcedScores = collections.namedtuple("ForcedScores", "sample_id logits nll nll_sum n_labels n_match n_counted")
+
+
+def phred_qualities(probs) -> np.ndarray:
+    """Per-base probabilities -> Phred values u8: p clipped to [0, 1], round(-10 log10(max(1 - p, 1e-4))), clipped to [0, 40]."""
+    p = np.clip(np.asarray(probs, np.float64), 0.0, 1.0)
+    q = np.round(-10.0 * np.log10(np.maximum(1.0 - p, 1e-4)))
+    return np.clip(q, 0, 40).astype(np.uint8)
+
+
+class BasecallResult:
+    """What `Basecaller.basecall` returns for a read: seq, probs (the merger's per-base probabilities, f32), qualities (their
+    Phred values, u8), chunks_num."""
+    __slots__ = ("seq", "probs", "qualities", "chunks_num")
+
+    def __init__(self, seq, probs, chunks_num):
+        self.seq = seq
+        self.probs = np.asarray(probs, np.float32)
+        self.qualities = phred_qualities(self.probs)
+        self.chunks_num = int(chunks_num)
+
+    def to_fastq(self, name) -> str:
+        """Four lines: @name, the sequence, +, the qualities as chr(33 + Q)."""
+        return f"@{name}\n{self.seq}\n+\n{(self.qualities + 33).astype(np.uint8).tobytes().decode('ascii')}\n"
+
+
+class ReadHandle:
+    """A read on the device (Basecaller.put_read): `read_id` for the first column of a window table, `drop()` when done."""
+
+    def __init__(self, basecaller, read_id, n_raw, n_event, keep=None):
+        self._bc, self.read_id, self.n_raw, self.n_event, self._keep = basecaller, int(read_id), n_raw, n_event, keep
+
+    def table(self, windows) -> np.ndarray:
+        """windows i32 [n,4] (data_loader.prepare_windows) -> the [n,5] table of the window calls, this read's id in column 0."""
+        w = np.asarray(windows, np.int32).reshape(-1, 4)
+        return np.ascontiguousarray(np.column_stack((np.full(w.shape[0], self.read_id, np.int32), w)).astype(np.int32))
+
+    def drop(self):
+        """rv_read_drop; fails (RV_ESTATE) while an uncollected ticket uses the read.  A second drop does nothing."""
+        if self.read_id >= 0:
+            self._bc._check(self._bc._lib.rv_read_drop(self._bc._h, self.read_id), "rv_read_drop")
+            self.read_id, self._keep = -1, None
 
 
 def _as_int(x) -> int:
@@ -524,6 +565,157 @@ class Basecaller:
                     col(queue.pop(0))
                 except Exception:
                     pass
+
+    # ------------------------------------------------------------------ reads on the device, chunks as windows of them
+    def put_read(self, raw_sc, events_sc):
+        """Upload a read's scaled tables once (rv_read_put; torch device tensors: rv_read_put_dev, no copy) -> ReadHandle.
+        raw_sc f32 [N] (None in event mode), events_sc f32 [E,5] (None in raw mode): `data_loader.prepare_windows` makes both.
+        The handle's `table(windows)` turns that function's [n,4] windows into the [n,5] tables the window calls take."""
+        use_raw, use_ev = self.input_data_type != "event", self.input_data_type != "raw"
+        on_dev = any(isinstance(x, torch.Tensor) and x.is_cuda for x in (raw_sc, events_sc))
+
+        def prep(x, shape):
+            if x is None:
+                return None
+            if on_dev:
+                return torch.as_tensor(x).detach().to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
+            x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x
+            return np.ascontiguousarray(np.asarray(x, np.float32).reshape(shape))
+        r = prep(raw_sc, (-1,)) if use_raw else None
+        e = prep(events_sc, (-1, 5)) if use_ev else None
+        if (use_raw and r is None) or (use_ev and e is None):
+            raise ValueError(f"{self.input_data_type} mode needs " + ("raw_sc" if use_raw and r is None else "events_sc"))
+        ptr = lambda a: None if a is None else ctypes.c_void_p(a.data_ptr() if on_dev else a.ctypes.data)
+        n_raw, n_ev = (0 if r is None else int(r.shape[0])), (0 if e is None else int(e.shape[0]))
+        rid = ctypes.c_int32(-1)
+        if on_dev:
+            torch.cuda.current_stream(self.device).synchronize()   # the tables are complete before the library's streams read them
+            self._check(self._lib.rv_read_put_dev(self._h, ptr(r), n_raw, ptr(e), n_ev, ctypes.byref(rid)), "rv_read_put_dev")
+        else:
+            self._check(self._lib.rv_read_put(self._h, ptr(r), n_raw, ptr(e), n_ev, ctypes.byref(rid)), "rv_read_put")
+        return ReadHandle(self, rid.value, n_raw, n_ev, (r, e) if on_dev else None)
+
+    def _window_table(self, windows, T_r, T_e):
+        w = np.ascontiguousarray(np.asarray(windows, np.int32))
+        if w.ndim != 2 or w.shape[1] != 5:
+            raise ValueError(f"windows: expected [B,5] (read_id, raw_start, raw_len, event_start, event_len), got {w.shape}")
+        T_r = min(_dl.MAX_RAW_LEN, self.cfg.max_raw_len) if T_r is None else int(T_r)
+        T_e = min(_dl.MAX_EVENT_LEN, self.cfg.max_event_len) if T_e is None else int(T_e)
+        return w, w.ctypes.data_as(ctypes.c_void_p), int(w.shape[0]), T_r, T_e
+
+    def beam_search_windows(self, windows, beam_width, max_output_len, *, T_r=None, T_e=None, device_outputs=False):
+        """`beam_search_prediction` on chunks that are windows of reads put with `put_read` (rv_beam_search_windows / _dev):
+        windows i32 [B,5] = (read_id, raw_start, raw_len, event_start, event_len); chunk b is its windows padded to T_r / T_e
+        (default: the chunker's 200 / 30).  Byte-identical to the call on `data_loader.expand_windows` of the same rows."""
+        w, pw, B, T_r, T_e = self._window_table(windows, T_r, T_e)
+        L, W = _as_int(max_output_len), int(beam_width)
+        steps = max(L - 1, 0)
+        S = ctypes.c_int32(0)
+        if device_outputs:
+            tokens, scores = self._out_buffers("beam", B, steps, 1)
+            rc = self._lib.rv_beam_search_windows_dev(self._h, pw, B, T_r, T_e, W, L, ctypes.c_void_p(tokens.data_ptr()),
+                                                      ctypes.c_void_p(scores.data_ptr()), ctypes.byref(S))
+        else:
+            tk, sc = np.empty((B, steps), np.int32), np.empty((B, steps), np.float32)
+            rc = self._lib.rv_beam_search_windows(self._h, pw, B, T_r, T_e, W, L, tk.ctypes.data_as(ctypes.c_void_p),
+                                                  sc.ctypes.data_as(ctypes.c_void_p), ctypes.byref(S))
+            tokens, scores = torch.from_numpy(tk), torch.from_numpy(sc)
+        self._check(rc, "rv_beam_search_windows")
+        self.last_steps = S.value
+        return tokens[:, :S.value], scores[:, :S.value]
+
+    def beam_search_windows_call_arrays(self, windows, beam_width, max_output_len, *, T_r=None, T_e=None):
+        """`beam_search_call_arrays` on windows (rv_beam_search_windows_calls) -> (bases u8 [B,L-1], probs f32 [B,L-1], lengths i32 [B])."""
+        w, pw, B, T_r, T_e = self._window_table(windows, T_r, T_e)
+        L = _as_int(max_output_len)
+        steps = max(L - 1, 0)
+        lut = self._call_lut()
+        bases = np.zeros((B, steps), np.uint8); lens = np.zeros(B, np.int32); probs = np.zeros((B, steps), np.float32)
+        S = ctypes.c_int32(0)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self._lib.rv_beam_search_windows_calls(self._h, pw, B, T_r, T_e, int(beam_width), L, p(lut), p(bases), p(lens),
+                                                           p(probs), ctypes.byref(S)), "rv_beam_search_windows_calls")
+        self.last_steps = S.value
+        return bases, probs, lens
+
+    def submit_windows(self, windows, beam_width, max_output_len, calls=False, *, T_r=None, T_e=None):
+        """Queue `beam_search_windows` (calls=True: with the fused post-processing) without waiting for the GPU
+        (rv_beam_search_submit_windows / _windows_calls); the ticket goes to `collect` / `collect_calls`.  The reads the table
+        names cannot be dropped until the ticket is collected."""
+        w, pw, B, T_r, T_e = self._window_table(windows, T_r, T_e)
+        L = _as_int(max_output_len)
+        t = ctypes.c_int32(-1)
+        if calls:
+            lut = self._call_lut()
+            self._check(self._lib.rv_beam_search_submit_windows_calls(self._h, pw, B, T_r, T_e, int(beam_width), L,
+                                                                      lut.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t)),
+                        "rv_beam_search_submit_windows_calls")
+            return {"kind": "calls", "ticket": t.value, "B": B, "steps": max(L - 1, 0)}
+        self._check(self._lib.rv_beam_search_submit_windows(self._h, pw, B, T_r, T_e, int(beam_width), L, ctypes.byref(t)),
+                    "rv_beam_search_submit_windows")
+        return {"kind": "host", "keep": None, "ticket": t.value, "B": B, "steps": max(L - 1, 0)}
+
+    def beam_search_stream_windows(self, tables, beam_width, max_output_len, calls: bool = False, *, T_r=None, T_e=None):
+        """`beam_search_stream` over window tables: `async_depth` slabs in flight, each table's result in order."""
+        depth = getattr(self, "async_depth", 2)
+        col = self.collect_calls if calls else self.collect
+        queue = []
+        try:
+            for w in tables:
+                if len(queue) >= depth:
+                    yield col(queue.pop(0))
+                queue.append(self.submit_windows(w, beam_width, max_output_len, calls=calls, T_r=T_r, T_e=T_e))
+            while queue:
+                yield col(queue.pop(0))
+        finally:                       # (as beam_search_stream: no ticket may stay uncollected on the handle)
+            while queue:
+                try:
+                    col(queue.pop(0))
+                except Exception:
+                    pass
+
+    def _stream_window_calls(self, table, beam_width, L, chunk_size, T_r, T_e):
+        """The call arrays of a whole table, decoded in slabs of `chunk_size` rows with the handle's depth of them in flight."""
+        n, steps = int(table.shape[0]), max(L - 1, 0)
+        bases = np.zeros((n, steps), np.uint8); probs = np.zeros((n, steps), np.float32); lens = np.zeros(n, np.int32)
+        cuts = [(a, min(a + chunk_size, n)) for a in range(0, n, chunk_size)]
+        results = self.beam_search_stream_windows((table[a:b] for a, b in cuts), beam_width, L, calls=True, T_r=T_r, T_e=T_e)
+        for (a, b), (bs, pr, ln) in zip(cuts, results):
+            bases[a:b] = bs; probs[a:b] = pr; lens[a:b] = ln
+        return bases, probs, lens
+
+    def basecall(self, signal, stride=6, beam_width=5, max_output_len=None, chunk_size=1024):
+        """An unlabelled read's signal -> BasecallResult (seq, probs, qualities, chunks_num, to_fastq): `prepare_windows` without
+        labels, `put_read`, window slabs of `chunk_size` chunks streamed with the fused post-processing, the C++ merger, drop.
+        max_output_len None: the handle's."""
+        return self.basecall_many([signal], stride, beam_width, max_output_len, chunk_size)[0]
+
+    def basecall_many(self, signals, stride=6, beam_width=5, max_output_len=None, chunk_size=1024):
+        """`basecall` of several reads through shared slabs: the windows of all reads are queued into full slabs (a slab's rows may
+        name different reads) and each read is stitched from its own rows -> list of BasecallResult, equal to one `basecall` each."""
+        from . import merger as _merger
+        L = self.cfg.max_output_len if max_output_len is None else _as_int(max_output_len)
+        T_r, T_e = min(_dl.MAX_RAW_LEN, self.cfg.max_raw_len), min(_dl.MAX_EVENT_LEN, self.cfg.max_event_len)
+        reads, handles = [], []
+        try:
+            for sig in signals:
+                rw = _dl.prepare_windows(sig, stride=stride, max_raw_len=T_r, max_event_len=T_e)
+                reads.append(rw)
+                handles.append(self.put_read(rw.raw_sc, rw.events_sc))
+            n = [len(rw) for rw in reads]
+            off = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+            table = (np.concatenate([h.table(rw.windows) for h, rw in zip(handles, reads)]) if reads else np.zeros((0, 5), np.int32))
+            bases, probs, lens = self._stream_window_calls(table, beam_width, L, int(chunk_size), T_r, T_e)
+        finally:
+            for h in handles:
+                h.drop()
+        mg = _merger.Merger()
+        out = []
+        for i in range(len(reads)):
+            a, b = int(off[i]), int(off[i + 1])
+            seq, pr = mg.merge_arrays(bases[a:b], probs[a:b], lens[a:b]) if b > a else ("", np.zeros(0, np.float32))
+            out.append(BasecallResult(seq, pr, n[i]))
+        return out
 
     def greedy_search_prediction(self, input_data, max_output_len):
         """basecaller.py:317-330 -> (sample_id [B,S] int32, rnn_output logits [B,S,V] f32)."""

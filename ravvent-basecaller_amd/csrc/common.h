@@ -52,6 +52,10 @@ void list_decode_forms(FormLog& log);
 // row0[m] <= b < row0[m] + rows[m] is row b - row0[m] of x[m] [rows[m],T,F].  n = 0: every chunk is a row of RecArgs::x.
 #define RV_MAX_MEMBERS 8
 struct RecMembers { int n; int row0[RV_MAX_MEMBERS]; int rows[RV_MAX_MEMBERS]; const float* x[RV_MAX_MEMBERS]; };
+// A chunk as windows of a read that lies on the device once (rv_beam_search_windows*): raw_len samples from `raw`,
+// ev_len events of five features from `ev`.  The host resolves and bounds-checks every row against its read before anything is queued
+// (0 <= len <= T, the window inside the read); positions len .. T - 1 of the chunk are the padding value.
+struct RecWindow { const float* raw; const float* ev; int raw_len; int ev_len; };
 struct RecArgs {
   const float* x;        // F>0: chunk input [B,T,F];  F==0: pre-projected xw [B,T,2,512] (bias folded)
   const float* W[2];     // F>0: input kernel [F,512] per direction
@@ -78,6 +82,8 @@ struct RecArgs {
   float pad;
   const void* const* ptab;   // matrix-pipe raw layer 0 only: non-null = read the chunk inputs' address from ptab[RV_PTAB_RAW] instead of `x`
   RecMembers members;        // matrix-pipe layer 0 only: n > 0 = the chunks' inputs are rows of the members' own tensors, not of `x`
+  const RecWindow* windows;  // matrix-pipe layer 0 only: non-null = chunk b is the window windows[b] of a read (device table [B]), not a row of `x`
+                             // (last: the argument offsets of every member above are those of the builds before it)
 };
 // Caller pointers of a slab call, read by the kernels through a small table in mapped pinned memory when the slab replays from a
 // hipGraph whose kernel arguments are frozen (ravvent_hip.cpp, option "slab_graph": one graph per slab context and call shape): the
@@ -95,6 +101,10 @@ void launch_lstm_rec_proj(const RecArgs& a, int rows_per_block, hipStream_t s, F
 void launch_lstm_rec_mx(const RecArgs& a, int F, hipStream_t s, bool rows8 = false, FormLog* log = nullptr);   // rows8: eight chunks per workgroup (latency form)
 bool lstm_rec_mx_window_fits(int T, int F = 1);   // layer 0 with its input projection in the lane: do the input windows of a workgroup's chunks fit in LDS?
 hipError_t configure_mx_kernels();
+// The padded chunk tensors of a window table, written on the device (k_expand_windows): raw [B,T_r,1] from the rows' raw windows (null:
+// not asked for), ev [B,T_e,5] from their event windows; positions beyond a window's length take `pad`.  For every path whose layer-0
+// kernels read chunk tensors.
+void launch_expand_windows(const RecWindow* windows, int B, float* raw, int T_r, float* ev, int T_e, float pad, hipStream_t s);
 // xw [rows,2,512] = x [rows,F] . W_dir [F,512] + b_dir for a layer-0 encoder with F = 5 (or 1) input features, both directions
 // mask != null: also writes utils.input_mask of the rows, mask[(r / T) * mask_T + mask_t0 + r % T] = all(x[r, :] != pad)
 // xtab != null: x is read from xtab[RV_PTAB_EVENT] (F == 5) / xtab[RV_PTAB_RAW] (F == 1) on the device instead

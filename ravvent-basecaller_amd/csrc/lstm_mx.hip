@@ -54,7 +54,11 @@ __device__ __forceinline__ float ror8_add(float v) {           // v + (v of the 
   return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, false));
 }
 
-template <int F, int CH, bool MEM = false>
+// Where the staging prologue of a layer-0 form finds its chunks' inputs: rows of one chunk tensor, rows of the members' own tensors
+// (a coalesced call, RecArgs::members), or windows of reads (RecArgs::windows)
+enum { SRC_TENSOR = 0, SRC_MEMBERS = 1, SRC_WINDOWS = 2 };
+
+template <int F, int CH, int SRC = SRC_TENSOR>
 __device__ __forceinline__ void rec_mx_body(const RecArgs& a) {
   static_assert(F == 0 || F == 1 || F == 5, "pre-projected inputs, or layer 0 on its F input features (raw samples: 1; events: 5)");
   static_assert(CH == 16 || CH == 8, "sixteen chunks per workgroup, or eight with both parts of h in the product's columns");
@@ -99,7 +103,28 @@ __device__ __forceinline__ void rec_mx_body(const RecArgs& a) {
         const bool wm = a.mask && dir == 0 && b0 + r < a.B;     // utils.input_mask of this encoder's part (utils.py:26-32: all features != pad), once per chunk
         const float* xb = xg;
         int br = b;
-        if constexpr (MEM) {    // chunk b is a row of its member's own tensor (a workgroup's chunks may straddle members, so per chunk; scalar
+        if constexpr (SRC == SRC_WINDOWS) {    // chunk b is a window of a read: len real positions from the read's table, the padding value behind them.
+                                // The host has checked the window against its read and len <= T (resolve_windows); scalar 4-byte loads: a
+                                // window starts at any float offset.  The mask is the chunk tensor's: every feature != pad, so 0 beyond len
+          const RecWindow wr = a.windows[b];
+          const float* wp = F == 1 ? wr.raw : wr.ev;
+          const int len = F == 1 ? wr.raw_len : wr.ev_len;
+          for (int i = tid; i < T; i += 512) {
+            float v[F];
+#pragma unroll
+            for (int f = 0; f < F; ++f) v[f] = i < len ? wp[(size_t)i * F + f] : a.pad;
+#pragma unroll
+            for (int f = 0; f < F; ++f) xs[(r * T + i) * F + f] = v[f];
+            if (wm) {
+              bool real = true;
+#pragma unroll
+              for (int f = 0; f < F; ++f) real = real && v[f] != a.pad;
+              a.mask[(size_t)b * a.mask_T + a.mask_t0 + i] = real ? 1 : 0;
+            }
+          }
+          continue;
+        }
+        if constexpr (SRC == SRC_MEMBERS) {    // chunk b is a row of its member's own tensor (a workgroup's chunks may straddle members, so per chunk; scalar
                                 // 4-byte loads below: a member's tensor may sit at any float offset)
           for (int m = 0; m < a.members.n; ++m)
             if (b >= a.members.row0[m] && b < a.members.row0[m] + a.members.rows[m]) { xb = a.members.x[m]; br = b - a.members.row0[m]; }
@@ -272,7 +297,28 @@ __global__ __launch_bounds__(512) void k_lstm_rec_mx(RecArgs a) { rec_mx_body<F,
 // with the staging prologue resolving each chunk to its member's tensor.  Instantiations of their own, so that the step loops of the forms
 // above keep their instruction stream (the head of this file); they are logged as the (F, CH) form they are.
 template <int F, int CH>
-__global__ __launch_bounds__(512) void k_lstm_rec_mx_members(RecArgs a) { rec_mx_body<F, CH, true>(a); }
+__global__ __launch_bounds__(512) void k_lstm_rec_mx_members(RecArgs a) { rec_mx_body<F, CH, SRC_MEMBERS>(a); }
+
+// ... and for a call whose chunks are windows of reads (RecArgs::windows; a coalesced group of such calls too: its table is its
+// members' rows back to back, so no member lookup).  Logged as the (F, CH) form they are.
+template <int F, int CH>
+__global__ __launch_bounds__(512) void k_lstm_rec_mx_windows(RecArgs a) { rec_mx_body<F, CH, SRC_WINDOWS>(a); }
+
+// The padded chunk tensors of a window table for every path that reads chunk tensors (the packed-FMA recurrence, k_inproj_small, the
+// tapped and profiled calls): workgroup (b, seg) writes chunk b's raw [T_r,1] (seg 0) or event [T_e,5] (seg 1) row.  The rows were
+// checked on the host, like the windows kind of the recurrence; a null output is a segment the mode does not use.
+__global__ __launch_bounds__(256) void k_expand_windows(const RecWindow* __restrict__ win, float* __restrict__ raw, int T_r,
+                                                         float* __restrict__ ev, int T_e, float pad) {
+  const int b = blockIdx.x, seg = blockIdx.y;
+  const RecWindow w = win[b];
+  float* out = seg ? ev : raw;
+  if (!out) return;
+  const int F = seg ? 5 : 1, T = seg ? T_e : T_r;
+  const float* src = seg ? w.ev : w.raw;
+  const int n = (seg ? w.ev_len : w.raw_len) * F;
+  out += (size_t)b * T * F;
+  for (int i = threadIdx.x; i < T * F; i += 256) out[i] = i < n ? src[i] : pad;
+}
 
 // x . W + b for a layer-0 encoder with a handful of input features (the event encoder: F = 5), both directions:
 // xw [B*T, 2, 512].  One thread = 4 gate columns of one row; HBM-bound on its output (4 KB per chunk-timestep).
@@ -330,6 +376,8 @@ hipError_t configure_mx_kernels() {
     if constexpr (M::F > 0) {
       const hipError_t em = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lstm_rec_mx_members<M::F, M::CH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (em != hipSuccess && first == hipSuccess) first = em;
+      const hipError_t ew = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lstm_rec_mx_windows<M::F, M::CH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (ew != hipSuccess && first == hipSuccess) first = ew;
     }
   });
   return first;
@@ -342,11 +390,19 @@ void launch_lstm_rec_mx(const RecArgs& a, int F, hipStream_t s, bool rows8, Form
     if (mx_serves<M>(F, CH)) {
       const dim3 grid((a.B + CH - 1) / CH, 2);
       auto kernel = &k_lstm_rec_mx<M::F, M::CH>;
-      if constexpr (M::F > 0) { if (a.members.n > 0) kernel = &k_lstm_rec_mx_members<M::F, M::CH>; }
+      if constexpr (M::F > 0) {
+        if (a.windows) kernel = &k_lstm_rec_mx_windows<M::F, M::CH>;
+        else if (a.members.n > 0) kernel = &k_lstm_rec_mx_members<M::F, M::CH>;
+      }
       hipLaunchKernelGGL(kernel, grid, dim3(512), mx_lds_bytes(M::F, a.T), s, a);
       if (log) log->add(RV_K_LSTM_REC_MX, M::F, M::CH);
     }
   });
+}
+
+void launch_expand_windows(const RecWindow* windows, int B, float* raw, int T_r, float* ev, int T_e, float pad, hipStream_t s) {
+  if (B <= 0 || (!raw && !ev)) return;
+  hipLaunchKernelGGL(k_expand_windows, dim3(B, 2), dim3(256), 0, s, windows, raw, T_r, ev, T_e, pad);
 }
 
 void launch_inproj_small(const float* x, int rows, int F, const float* W0, const float* b0, const float* W1, const float* b1, float* xw,

@@ -122,6 +122,22 @@ struct Call {
   const ForcedCall* forced = nullptr;       // rv_teacher_forced*
   bool want_moves = false;                  // rv_beam_search_moves* / rv_beam_search_submit_moves (always with whole_beam): the moves too, through ...
   const RvMoves* moves = nullptr;           // ... these outputs (null: an asynchronous call, named at its collect)
+  // rv_beam_search_windows*: the chunks are windows of reads on the device (raw / ev unset, dev_in set).  As the entry point states it: its
+  // table's rows, resolved and checked against their reads (resolve_windows), in host memory; past enqueue()'s staging: the context's device
+  // copy of them.  win_expand (set by enqueue): the call takes a path whose layer-0 kernels read chunk tensors, so k_expand_windows writes
+  // them into the context's input buffers first and raw / ev name those
+  const RecWindow* windows = nullptr;
+  bool win_expand = false;
+};
+
+// A read on the device (rv_read_put*): its scaled samples [n_raw] and scaled events [n_ev,5].  owned: the buffers are the handle's (a
+// dropped read keeps them for the next put that fits); else the caller's (rv_read_put_dev).  users: uncollected tickets whose tables name it
+struct Read {
+  float *d_raw = nullptr, *d_ev = nullptr;
+  size_t n_raw = 0, n_ev = 0, cap_raw = 0, cap_ev = 0;      // cap_*: floats the owned buffers hold
+  float* pin = nullptr; size_t pin_cap = 0;                 // pinned staging of the upload: the caller's buffers are free when the put returns
+  bool live = false, owned = false, used = false;
+  int users = 0, id = -1;
 };
 
 // What a recording needs beyond the call, resolved once before enqueue() (begin_all_beams, begin_forced, launch_group)
@@ -249,6 +265,19 @@ struct RvContext {
   DecMembers g_members{};                   // its member table: output addresses as the members come (submit_group), rows at its launch (launch_group)
   bool g_inplace = false;                   // its members' device inputs are read in place (option "group_inplace"), through ...
   RecMembers g_in[2]{};                     // ... these tables [raw, event]: addresses as the members come, rows at its launch
+  bool g_win = false;                       // its members are window slabs: their rows stand back to back in pin_win (a window slab and a chunk-tensor slab never share a group)
+
+  // window calls (rv_beam_search_windows*): the resolved table of the call this context runs, [max_batch] rows -- written by the host into
+  // pinned staging when the call is queued (a group: as its members come), copied to the device in front of the call's first kernel
+  RecWindow *pin_win = nullptr, *d_win = nullptr;
+  // ... and of the handle (root): the reads, the stream and event of their uploads, and which reads each uncollected ticket uses
+  std::vector<Read> reads;
+  hipStream_t copy_stream = nullptr;
+  hipEvent_t ev_put = nullptr;              // recorded behind every upload: a window call's stream waits for it, the host never does
+  long long read_allocs = 0, read_puts = 0; // "read_stats": device allocations made for reads, puts
+  long long win_expands = 0;                // ... and launches of k_expand_windows
+  int read_gen = 0;
+  std::map<int, std::vector<int>> ticket_reads;
 };
 
 namespace {
@@ -435,7 +464,7 @@ bool lane_layer0(const RvContext* h, int F, int T) {
 }
 
 void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int Tm, int t_off, hipStream_t s,
-                 int l_begin = 0, int l_end = 1 << 30, const void* const* ptab = nullptr) {
+                 int l_begin = 0, int l_end = 1 << 30, const void* const* ptab = nullptr, const RecWindow* windows = nullptr) {
   const int depth = h->cfg.enc_depth;
   const int bt = pick_rows_per_block(B);
   for (int l = std::max(l_begin, 0); l < std::min(depth, l_end); ++l) {
@@ -467,10 +496,11 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
         a.mask = h->mask; a.mask_T = Tm; a.mask_t0 = t_off; a.pad = h->cfg.padding_value;   // the layer-0 kernels leave the input mask too
         a.ptab = ptab;
         if (h->g_inplace) a.members = h->g_in[e];      // (a group whose members' inputs stay where they are: launch_group)
+        a.windows = windows;                           // (a window call on the default path: the chunks are gathered from their reads in the lane)
         a.dbg_ts = (e == 0 && h->rec_ts_layer == 0) ? h->rec_ts : nullptr;     // (RV_REC_STAMPS=1: phase cycle sums of workgroup (0, 0))
         Scope sc(h, F == 1 ? "lstm_rec_raw_l0" : "lstm_rec_event_l0", s);
         launch_lstm_rec_mx(a, F, s, h->lrows8 != 0, &h->lforms);
-        a.dbg_ts = nullptr; a.ptab = nullptr; a.mask = nullptr; a.members.n = 0;
+        a.dbg_ts = nullptr; a.ptab = nullptr; a.mask = nullptr; a.members.n = 0; a.windows = nullptr;
         continue;
       }
       if (l == 0) {
@@ -588,7 +618,7 @@ int validate_call(RvContext* h, const Call& call, Call& ok) {
   if (use_ev && (T_e < 1 || T_e > c.max_event_len)) return fail(h, RV_EINVAL, "T_e=%d outside [1,%d]", T_e, c.max_event_len);
   if (W < 1 || W > c.max_beam || W > RV_MAX_BEAM) return fail(h, RV_EINVAL, "beam width %d outside [1,%d]", W, std::min(c.max_beam, RV_MAX_BEAM));
   if (L < 1 || L > c.max_output_len) return fail(h, RV_EINVAL, "max_output_len=%d outside [1,%d]", L, c.max_output_len);
-  if (B > 0 && ((use_raw && !raw) || (use_ev && !ev))) return fail(h, RV_EINVAL, "missing input pointer for this mode");   // (an empty device tensor has no address)
+  if (B > 0 && !ok.windows && ((use_raw && !raw) || (use_ev && !ev))) return fail(h, RV_EINVAL, "missing input pointer for this mode");   // (an empty device tensor has no address)
   if (T_r + T_e > 352) return fail(h, RV_EUNSUPPORTED, "attention memory of %d steps exceeds the 352 the decode kernel is built for", T_r + T_e);
   if (L > 64) return fail(h, RV_EUNSUPPORTED, "max_output_len %d exceeds 64", L);
   if (ok.dev_out && B > 0 && L > 1 && (!ok.tokens || !ok.out2)) return fail(h, RV_EINVAL, "null output pointer");
@@ -636,6 +666,19 @@ int enqueue(RvContext* h, const Call& stated, const CallParts& res) {
   const int form_B = res.form_B >= 0 ? res.form_B : B;      // a group takes the forms its first member would have got alone
   h->lwide = wide_recurrence(h, form_B, T_r) ? 1 : 0;
   h->lrows8 = h->lwide && rows8_wanted(h, form_B) ? 1 : 0;
+  const bool windowed = call.windows != nullptr;
+  if (windowed) {
+    // The table goes to this context's pinned staging now (a group's rows are there already: submit_group); its device copy is the first
+    // thing the recording queues (stage_inputs).  The default path gathers each chunk in the lane of its layer-0 recurrence; every other
+    // form -- the packed-FMA recurrence, "lane_projection" 0, the per-step decode, taps, profiling, a group with "group_inplace" 0 --
+    // runs unchanged behind k_expand_windows, which writes the padded chunk tensors into the context's input buffers
+    if (call.windows != h->pin_win) memcpy(h->pin_win, call.windows, sizeof(RecWindow) * (size_t)B);
+    call.windows = h->d_win;
+    const bool lane = h->lwide && (!use_ev || lane_layer0(h, 5, T_e)) && h->opt.profile == 0 && !h->opt.taps &&
+                      persist_form(h, greedy, W, T_r + T_e, res.labels != nullptr) >= 0 && !(h->g_cap > 0 && !h->opt.group_inplace);
+    call.win_expand = !lane;
+    if (call.win_expand) { call.raw = use_raw ? h->d_raw : nullptr; call.ev = use_ev ? h->d_ev : nullptr; }
+  }
   if ((!h->opt.fuse && c.enc_depth > 1) || h->lwide) {   // pre-projected tensors [max_batch, T_max, 2, 512]: allocated with the context (alloc_slab_buffers); this is a safety net
     if (use_raw && c.enc_depth > 1 && !h->xw[0]) TRY(dalloc(h, &h->xw[0], (size_t)c.max_batch * c.max_raw_len * 2 * RV_G));
     if (use_ev && !h->xw[1]) TRY(dalloc(h, &h->xw[1], (size_t)c.max_batch * c.max_event_len * 2 * RV_G));
@@ -651,7 +694,7 @@ int enqueue(RvContext* h, const Call& stated, const CallParts& res) {
     h->slab_graphs.clear();
     h->graph_gen = root->opt.gen;
   }
-  const bool graphable = root->opt.slab_graph && h->lwide && !h->lrows8 && persist_form(h, greedy, W, T_r + T_e, res.labels != nullptr) >= 0 && h->opt.profile == 0 && !h->opt.taps &&
+  const bool graphable = root->opt.slab_graph && !windowed && h->lwide && !h->lrows8 && persist_form(h, greedy, W, T_r + T_e, res.labels != nullptr) >= 0 && h->opt.profile == 0 && !h->opt.taps &&
                          !res.whole_beam && !res.labels && !h->opt.ptaps && !h->rec_ts && !h->dec_st.dbg_ts && h->d_ptab;
   if (!graphable) return record_slab(h, call, res, nullptr);
   h->lforms_ok = 0;                             // (a slab graph replays without the host launchers: "kernel_forms" answers RV_ESTATE)
@@ -706,6 +749,16 @@ int stage_inputs(RvContext* h, const Slab& sl) {
     if (use_raw) HIPCHK(h, hipMemcpyAsync(h->d_raw, h->pin_raw, sizeof(float) * B * T_r, hipMemcpyHostToDevice, s));
     if (use_ev) HIPCHK(h, hipMemcpyAsync(h->d_ev, h->pin_ev, sizeof(float) * B * T_e * 5, hipMemcpyHostToDevice, s));
   }
+  if (sl.call.windows) {   // a window call: its table, 24 bytes per chunk, behind the uploads of the reads it names
+    RvContext* root = h->parent ? h->parent : h;
+    if (root->ev_put) HIPCHK(h, hipStreamWaitEvent(s, root->ev_put, 0));
+    HIPCHK(h, hipMemcpyAsync(h->d_win, h->pin_win, sizeof(RecWindow) * (size_t)B, hipMemcpyHostToDevice, s));
+    if (sl.call.win_expand) {
+      Scope sc(h, "expand_windows");
+      root->win_expands += 1;
+      launch_expand_windows(h->d_win, B, use_raw ? h->d_raw : nullptr, T_r, use_ev ? h->d_ev : nullptr, T_e, c.padding_value, s);
+    }
+  }
   return RV_OK;
 }
 
@@ -716,6 +769,7 @@ int record_encoders(RvContext* h, const Slab& sl) {
   const int B = sl.call.B, T_r = sl.call.T_r, T_e = sl.call.T_e, Tm = sl.Tm;
   const float *xr = sl.call.raw, *xe = sl.call.ev;
   const void* const* ptab = sl.ptab;
+  const RecWindow* win = sl.call.win_expand ? nullptr : sl.call.windows;      // (only the matrix-pipe layer 0 with the projection in the lane takes windows: enqueue)
   hipStream_t s = h->stream;
   // ---- _encode_input (basecaller.py:395-416)
   // The mask is first read by the memory set-up / the decode: it runs on a side stream beside the encoders instead of in front
@@ -759,13 +813,13 @@ int record_encoders(RvContext* h, const Slab& sl) {
     hipStream_t sev = side_stream(h, 0);
     HIPCHK(h, hipEventRecord(h->ev_fork, s));
     HIPCHK(h, hipStreamWaitEvent(sev, h->ev_fork, 0));       // inputs (H2D copies on s) are in place
-    run_encoder(h, 1, xe, 5, B, T_e, Tm, T_r, sev);
+    run_encoder(h, 1, xe, 5, B, T_e, Tm, T_r, sev, 0, 1 << 30, nullptr, win);
     HIPCHK(h, hipEventRecord(h->ev_join[0], sev));
-    run_encoder(h, 0, xr, 1, B, T_r, Tm, 0, s);
+    run_encoder(h, 0, xr, 1, B, T_r, Tm, 0, s, 0, 1 << 30, nullptr, win);
     HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[0], 0));
   } else {
-    if (use_ev) run_encoder(h, 1, xe, 5, B, T_e, Tm, T_r, s, 0, 1 << 30, ptab);
-    if (use_raw) run_encoder(h, 0, xr, 1, B, T_r, Tm, 0, s, 0, 1 << 30, ptab);
+    if (use_ev) run_encoder(h, 1, xe, 5, B, T_e, Tm, T_r, s, 0, 1 << 30, ptab, win);
+    if (use_raw) run_encoder(h, 0, xr, 1, B, T_r, Tm, 0, s, 0, 1 << 30, ptab, win);
   }
 
   if (mask_aside) HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[2], 0));
@@ -1448,6 +1502,8 @@ int alloc_slab_buffers(RvContext* h) {
   HIPTRY(hipHostMalloc((void**)&h->pin_clen, B * sizeof(int), hipHostMallocDefault));
   // the table lives in mapped pinned memory: the three kernels that need a caller address read it over the host link once per workgroup
   // (a device copy refreshed by a memcpy node in front of the graph measured the same, and is one node more)
+  TRY(dalloc(h, &h->d_win, B));
+  HIPTRY(hipHostMalloc((void**)&h->pin_win, std::max<size_t>(B, 1) * sizeof(RecWindow), hipHostMallocDefault));
   HIPTRY(hipHostMalloc((void**)&h->pin_ptab, sizeof(void*) * RV_PTAB_N, hipHostMallocMapped));
   HIPTRY(hipHostGetDevicePointer((void**)&h->d_ptab, h->pin_ptab, 0));
   return RV_OK;
@@ -1552,6 +1608,7 @@ int launch_group(RvContext* root, RvContext* g) {
   call.B = g->g_rows; call.T_r = g->g_Tr; call.T_e = g->g_Te; call.W = g->g_W; call.L = g->g_L;
   call.tokens = g->out_tokens; call.out2 = g->out2; call.dev_out = g->g_dev_out;
   call.lut = g->g_calls ? g->g_lut : nullptr;
+  if (g->g_win) { call.raw = call.ev = nullptr; call.windows = g->pin_win; }
   CallParts res;
   res.members = &m;
   res.form_B = g->g_B0;
@@ -1571,9 +1628,10 @@ int submit_group(RvContext* h, int n, const Call& call, int32_t* ticket) {
   const bool dev_in = call.dev_in, dev_out = call.dev_out;
   const uint8_t* lut = call.lut;
   const bool calls = lut != nullptr;
+  const bool win = call.windows != nullptr;
   HIPCHK(h, hipSetDevice(c.device));
   RvContext* g = h->open_grp;
-  if (g && (g->g_cap != n || g->g_Tr != T_r || g->g_Te != T_e || g->g_W != W || g->g_L != L || g->g_dev_in != dev_in || g->g_dev_out != dev_out ||
+  if (g && (g->g_cap != n || g->g_win != win || g->g_Tr != T_r || g->g_Te != T_e || g->g_W != W || g->g_L != L || g->g_dev_in != dev_in || g->g_dev_out != dev_out ||
             g->g_calls != calls || (calls && memcmp(g->g_lut, lut, (size_t)c.vocab)))) {
     launch_group(h, g);                      // another shape or kind: the group goes as it is (a failure is its members' to collect)
     g = nullptr;
@@ -1600,7 +1658,8 @@ int submit_group(RvContext* h, int n, const Call& call, int32_t* ticket) {
     }
     reset_group(g);
     g->g_Tr = T_r; g->g_Te = T_e; g->g_W = W; g->g_L = L; g->g_dev_in = dev_in; g->g_dev_out = dev_out; g->g_calls = calls; g->g_B0 = B;
-    g->g_inplace = dev_in && inplace_serves(h, T_e);      // (the options cannot change under an open group: rv_set_option launches it)
+    g->g_win = win;
+    g->g_inplace = dev_in && !win && inplace_serves(h, T_e);      // (the options cannot change under an open group: rv_set_option launches it)
     memset(g->g_lut, 0, sizeof g->g_lut);
     if (calls) memcpy(g->g_lut, lut, (size_t)c.vocab);
     h->open_grp = g;
@@ -1609,7 +1668,9 @@ int submit_group(RvContext* h, int n, const Call& call, int32_t* ticket) {
   for (int i = 0; i < RV_MAX_ASYNC && slot < 0; ++i) if (!h->ticks[i].busy) slot = i;
   if (slot < 0) return fail(h, RV_ESTATE, "no free ticket");      // (unreachable: at most async_depth <= RV_MAX_ASYNC are uncollected)
   const size_t row0 = (size_t)g->g_rows;
-  if (g->g_inplace) {   // device inputs stay valid and untouched until the ticket is collected (ravvent_hip.h): the layer-0 kernels read them there
+  if (win) {            // the member's rows behind those of the members before it: the group's table needs no member lookup
+    if (B > 0) memcpy(g->pin_win + row0, call.windows, sizeof(RecWindow) * (size_t)B);
+  } else if (g->g_inplace) {   // device inputs stay valid and untouched until the ticket is collected (ravvent_hip.h): the layer-0 kernels read them there
     g->g_in[0].x[g->g_n] = raw; g->g_in[1].x[g->g_n] = ev;
   } else if (B > 0) {   // the member's inputs go to its rows of the group's input buffers now: the caller's host buffers are free on return
     const size_t nr = (size_t)B * T_r, ne = (size_t)B * T_e * 5;
@@ -1689,6 +1750,132 @@ Call slab_call(const float* raw, const float* event, bool on_device, int B, int 
   c.raw = raw; c.ev = event; c.dev_in = on_device; c.dev_out = on_device;
   c.B = B; c.T_r = T_r; c.T_e = T_e; c.W = W; c.L = L;
   return c;
+}
+
+// ---- reads and window tables (rv_read_put*, rv_beam_search_windows*)
+constexpr int RV_READ_SLOTS = 1024;         // read_id = generation << 10 | slot: an id that was dropped is never alive again
+
+Read* find_read(RvContext* h, int id) {
+  const int slot = id & (RV_READ_SLOTS - 1);
+  if (id < 0 || slot >= (int)h->reads.size()) return nullptr;
+  Read& r = h->reads[slot];
+  return r.live && r.id == id ? &r : nullptr;
+}
+
+// The table of a window call, checked row by row against the reads it names BEFORE anything is queued, so that no kernel ever indexes with
+// an unchecked offset: rows [B] as the kernels take them, ids = the reads used (each once).  The columns of the segment the mode does not
+// use are ignored (null address, length 0)
+int resolve_windows(RvContext* h, const int32_t* win, int B, int T_r, int T_e, std::vector<RecWindow>& rows, std::vector<int>& ids) {
+  const RvConfig& c = h->cfg;
+  const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
+  if (B < 0 || B > c.max_batch) return fail(h, RV_EINVAL, "B=%d outside [0,%d]", B, c.max_batch);
+  if (B > 0 && !win) return fail(h, RV_EINVAL, "null window table");
+  rows.assign((size_t)B, RecWindow{nullptr, nullptr, 0, 0});
+  for (int b = 0; b < B; ++b) {
+    const int32_t* w = win + (size_t)b * 5;
+    const Read* r = find_read(h, w[0]);
+    if (!r) return fail(h, RV_EINVAL, "window row %d: unknown read_id %d", b, w[0]);
+    if (use_raw) {
+      if (w[1] < 0 || w[2] < 0) return fail(h, RV_EINVAL, "window row %d: negative raw start or length (%d, %d)", b, w[1], w[2]);
+      if ((long long)w[1] + w[2] > (long long)r->n_raw) return fail(h, RV_EINVAL, "window row %d: raw window [%d, %lld) ends beyond the read's %zu samples", b, w[1], (long long)w[1] + w[2], r->n_raw);
+      if (w[2] > T_r) return fail(h, RV_EINVAL, "window row %d: raw_len %d exceeds T_r=%d", b, w[2], T_r);
+      rows[b].raw = r->d_raw + w[1]; rows[b].raw_len = w[2];
+    }
+    if (use_ev) {
+      if (w[3] < 0 || w[4] < 0) return fail(h, RV_EINVAL, "window row %d: negative event start or length (%d, %d)", b, w[3], w[4]);
+      if ((long long)w[3] + w[4] > (long long)r->n_ev) return fail(h, RV_EINVAL, "window row %d: event window [%d, %lld) ends beyond the read's %zu events", b, w[3], (long long)w[3] + w[4], r->n_ev);
+      if (w[4] > T_e) return fail(h, RV_EINVAL, "window row %d: event_len %d exceeds T_e=%d", b, w[4], T_e);
+      rows[b].ev = r->d_ev + (size_t)w[3] * 5; rows[b].ev_len = w[4];
+    }
+    if (std::find(ids.begin(), ids.end(), w[0]) == ids.end()) ids.push_back(w[0]);
+  }
+  return RV_OK;
+}
+
+// A window call as its entry point states it: device inputs (the reads), the outputs the entry point adds
+int windows_call(RvContext* h, const int32_t* win, int B, int T_r, int T_e, int W, int L, std::vector<RecWindow>& rows, std::vector<int>& ids, Call& c) {
+  if (!h) return RV_EINVAL;
+  TRY(resolve_windows(h, win, B, T_r, T_e, rows, ids));
+  c = slab_call(nullptr, nullptr, false, B, T_r, T_e, W, L);
+  c.dev_in = true;
+  static const RecWindow none{nullptr, nullptr, 0, 0};
+  c.windows = B > 0 ? rows.data() : &none;      // (an empty slab is still a window call)
+  return RV_OK;
+}
+
+// The reads an asynchronous window call uses stay put until its ticket is collected (rv_read_drop refuses)
+void hold_reads(RvContext* h, int ticket, const std::vector<int>& ids) {
+  for (int id : ids) if (Read* r = find_read(h, id)) r->users += 1;
+  h->ticket_reads[ticket] = ids;
+}
+void release_reads(RvContext* h, int ticket) {
+  auto it = h->ticket_reads.find(ticket);
+  if (it == h->ticket_reads.end()) return;
+  for (int id : it->second) if (Read* r = find_read(h, id)) r->users -= 1;
+  h->ticket_reads.erase(it);
+}
+
+int put_read(RvContext* h, const float* raw, size_t n_raw, const float* event, size_t n_event, bool on_device, int32_t* read_id) {
+  if (!h || !read_id) return RV_EINVAL;
+  *read_id = -1;
+  const RvConfig& c = h->cfg;
+  const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
+  if (!use_raw) { raw = nullptr; n_raw = 0; }
+  if (!use_ev) { event = nullptr; n_event = 0; }
+  if ((n_raw > 0 && !raw) || (n_event > 0 && !event)) return fail(h, RV_EINVAL, "missing read pointer for this mode");
+  if (n_raw > (size_t)INT32_MAX || n_event > (size_t)INT32_MAX / 5) return fail(h, RV_EINVAL, "read too long for 32-bit window offsets");
+  const size_t need_ev = n_event * 5;
+  // a slot: a dropped read whose buffers hold this one (the smallest such: no device allocation), else any dropped one, else a new one
+  int slot = -1;
+  if (!on_device)
+    for (size_t i = 0; i < h->reads.size(); ++i) {
+      const Read& r = h->reads[i];
+      if (r.live || !r.owned || r.cap_raw < n_raw || r.cap_ev < need_ev) continue;
+      if (slot < 0 || r.cap_raw + r.cap_ev < h->reads[slot].cap_raw + h->reads[slot].cap_ev) slot = (int)i;
+    }
+  for (size_t i = 0; i < h->reads.size() && slot < 0; ++i) if (!h->reads[i].live && (on_device || !h->reads[i].owned)) slot = (int)i;
+  for (size_t i = 0; i < h->reads.size() && slot < 0; ++i) if (!h->reads[i].live) slot = (int)i;
+  if (slot < 0) {
+    if ((int)h->reads.size() >= RV_READ_SLOTS) return fail(h, RV_ESTATE, "%d reads are alive: drop one first", RV_READ_SLOTS);
+    h->reads.emplace_back();
+    slot = (int)h->reads.size() - 1;
+  }
+  Read& r = h->reads[slot];
+  HIPCHK(h, hipSetDevice(c.device));
+  if (on_device) {
+    if (r.owned) { if (r.d_raw) hipFree(r.d_raw); if (r.d_ev) hipFree(r.d_ev); r.cap_raw = r.cap_ev = 0; }
+    r.owned = false;
+    r.d_raw = const_cast<float*>(raw); r.d_ev = const_cast<float*>(event);
+  } else {
+    if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    if (!h->ev_put) HIPCHK(h, hipEventCreateWithFlags(&h->ev_put, hipEventDisableTiming));
+    if (!r.owned) { r.d_raw = r.d_ev = nullptr; r.cap_raw = r.cap_ev = 0; r.owned = true; }
+    auto grow = [&](float** p, size_t* cap, size_t need) -> int {
+      if (need <= *cap) return RV_OK;
+      if (*p) { hipFree(*p); *p = nullptr; *cap = 0; }
+      if (hipMalloc((void**)p, need * sizeof(float)) != hipSuccess) return fail(h, RV_ENOMEM, "hipMalloc(%zu bytes) failed for a read", need * sizeof(float));
+      *cap = need; h->read_allocs += 1;
+      return RV_OK;
+    };
+    TRY(grow(&r.d_raw, &r.cap_raw, n_raw));
+    TRY(grow(&r.d_ev, &r.cap_ev, need_ev));
+    if (r.used) HIPCHK(h, hipEventSynchronize(h->ev_put));      // (the staging of a slot taken again: its earlier upload has left it)
+    if (n_raw + need_ev > r.pin_cap) {
+      if (r.pin) { hipHostFree(r.pin); r.pin = nullptr; r.pin_cap = 0; }
+      HIPCHK(h, hipHostMalloc((void**)&r.pin, (n_raw + need_ev) * sizeof(float), hipHostMallocDefault));
+      r.pin_cap = n_raw + need_ev;
+    }
+    if (n_raw) { memcpy(r.pin, raw, n_raw * sizeof(float)); HIPCHK(h, hipMemcpyAsync(r.d_raw, r.pin, n_raw * sizeof(float), hipMemcpyHostToDevice, h->copy_stream)); }
+    if (need_ev) { memcpy(r.pin + n_raw, event, need_ev * sizeof(float)); HIPCHK(h, hipMemcpyAsync(r.d_ev, r.pin + n_raw, need_ev * sizeof(float), hipMemcpyHostToDevice, h->copy_stream)); }
+    HIPCHK(h, hipEventRecord(h->ev_put, h->copy_stream));
+    r.used = true;
+  }
+  r.n_raw = n_raw; r.n_ev = n_event; r.live = true; r.users = 0;
+  h->read_gen = (h->read_gen + 1) & 0xFFFFF;
+  r.id = (h->read_gen << 10) | slot;
+  h->read_puts += 1;
+  *read_id = r.id;
+  return RV_OK;
 }
 
 }  // namespace
@@ -1794,10 +1981,13 @@ void rv_destroy(rv_handle h) {
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
   if (h->step_align) hipFree(h->step_align);
   if (h->palign) hipFree(h->palign);
-  for (void* p : {(void*)h->pin_raw, (void*)h->pin_ev, (void*)h->pin_tok, (void*)h->pin_out2, (void*)h->pin_S, (void*)h->pin_bases, (void*)h->pin_probs, (void*)h->pin_clen, (void*)h->pin_ptab,
+  for (void* p : {(void*)h->pin_raw, (void*)h->pin_ev, (void*)h->pin_tok, (void*)h->pin_out2, (void*)h->pin_S, (void*)h->pin_bases, (void*)h->pin_probs, (void*)h->pin_clen, (void*)h->pin_ptab, (void*)h->pin_win,
                   (void*)h->pin_beams.tokens, (void*)h->pin_beams.scores, (void*)h->pin_beams.path_scores, (void*)h->pin_beams.log_probs, (void*)h->pin_beams.lengths,
                   (void*)h->pin_moves.raw_pos, (void*)h->pin_moves.raw_mass, (void*)h->pin_moves.event_pos, (void*)h->pin_moves.event_mass, (void*)h->pin_moves.peak, (void*)h->pin_moves.peak_weight}) if (p) hipHostFree(p);
   for (void* p : h->allocs) hipFree(p);
+  for (Read& r : h->reads) { if (r.owned) { if (r.d_raw) hipFree(r.d_raw); if (r.d_ev) hipFree(r.d_ev); } if (r.pin) hipHostFree(r.pin); }
+  if (h->copy_stream) { hipStreamSynchronize(h->copy_stream); hipStreamDestroy(h->copy_stream); }
+  if (h->ev_put) hipEventDestroy(h->ev_put);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
 }
@@ -2241,12 +2431,16 @@ static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, co
   if (ticket >= 0 && h->ticks[slot].busy && h->ticks[slot].ticket == ticket) {
     if (moves) return fail(h, RV_EINVAL, "rv_beam_search_collect_moves takes the tickets of rv_beam_search_submit_moves");
     if (beams) return fail(h, RV_EINVAL, "rv_beam_search_collect_all takes the tickets of rv_beam_search_submit_all");      // (a group never holds one)
-    return collect_group(h, slot, tokens, out2, calls, S_out);
+    const int rc = collect_group(h, slot, tokens, out2, calls, S_out);
+    if (!(h->ticks[slot].busy && h->ticks[slot].ticket == ticket)) release_reads(h, ticket);      // (the ticket is gone: its reads may be dropped)
+    return rc;
   }
   if (ticket < 0 || slot > (int)h->kids.size()) return fail(h, RV_EINVAL, "unknown ticket %d", ticket);
   RvContext* ctx = slot == 0 ? h : h->kids[slot - 1];
   if (!ctx->pend.busy || ctx->pend.ticket != ticket) return fail(h, RV_ESTATE, "ticket %d is not in flight (collected already?)", ticket);
-  return relay(h, ctx, finish(ctx, tokens, out2, calls, S_out, beams, moves));
+  const int rc = relay(h, ctx, finish(ctx, tokens, out2, calls, S_out, beams, moves));
+  if (!(ctx->pend.busy && ctx->pend.ticket == ticket)) release_reads(h, ticket);
+  return rc;
 }
 int rv_beam_search_submit(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
                           int32_t* ticket) {
@@ -2274,6 +2468,63 @@ int rv_beam_search_submit_calls(rv_handle h, const float* raw, const float* even
 int rv_beam_search_collect_calls(rv_handle h, int32_t ticket, uint8_t* bases, int32_t* lengths, float* probs, int32_t* S_out) {
   const CallsOut c{nullptr, bases, lengths, probs};
   return collect(h, ticket, nullptr, nullptr, &c, S_out);
+}
+
+// ---- reads on the device, and beam search over windows of them
+int rv_read_put(rv_handle h, const float* raw, size_t n_raw, const float* event, size_t n_event, int32_t* read_id) {
+  return put_read(h, raw, n_raw, event, n_event, false, read_id);
+}
+int rv_read_put_dev(rv_handle h, const float* d_raw, size_t n_raw, const float* d_event, size_t n_event, int32_t* read_id) {
+  return put_read(h, d_raw, n_raw, d_event, n_event, true, read_id);
+}
+int rv_read_drop(rv_handle h, int32_t read_id) {
+  if (!h) return RV_EINVAL;
+  Read* r = find_read(h, read_id);
+  if (!r) return fail(h, RV_EINVAL, "unknown read_id %d", read_id);
+  if (r->users > 0) return fail(h, RV_ESTATE, "read %d is used by %d uncollected ticket(s): collect them first", read_id, r->users);
+  r->live = false;
+  if (!r->owned) { r->d_raw = r->d_ev = nullptr; }
+  return RV_OK;
+}
+int rv_beam_search_windows(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L, int32_t* tokens,
+                           float* scores, int32_t* S_out) {
+  std::vector<RecWindow> rows; std::vector<int> ids; Call c;
+  TRY(windows_call(h, win, B, T_r, T_e, W, L, rows, ids, c));
+  c.tokens = tokens; c.out2 = scores;
+  return run(h, c, S_out);
+}
+int rv_beam_search_windows_dev(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                               int32_t* d_tokens, float* d_scores, int32_t* S_out) {
+  std::vector<RecWindow> rows; std::vector<int> ids; Call c;
+  TRY(windows_call(h, win, B, T_r, T_e, W, L, rows, ids, c));
+  c.dev_out = true; c.tokens = d_tokens; c.out2 = d_scores;
+  return run(h, c, S_out);
+}
+int rv_beam_search_windows_calls(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                 const uint8_t* lut, uint8_t* bases, int32_t* lengths, float* probs, int32_t* S_out) {
+  std::vector<RecWindow> rows; std::vector<int> ids; Call c;
+  TRY(windows_call(h, win, B, T_r, T_e, W, L, rows, ids, c));
+  const CallsOut co{lut, bases, lengths, probs};
+  c.lut = lut; c.calls = &co;
+  return run(h, c, S_out);
+}
+int rv_beam_search_submit_windows(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                  int32_t* ticket) {
+  std::vector<RecWindow> rows; std::vector<int> ids; Call c;
+  TRY(windows_call(h, win, B, T_r, T_e, W, L, rows, ids, c));
+  TRY(submit(h, c, ticket));
+  hold_reads(h, *ticket, ids);
+  return RV_OK;
+}
+int rv_beam_search_submit_windows_calls(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                        const uint8_t* lut, int32_t* ticket) {
+  if (!lut) return h ? fail(h, RV_EINVAL, "null lut") : RV_EINVAL;
+  std::vector<RecWindow> rows; std::vector<int> ids; Call c;
+  TRY(windows_call(h, win, B, T_r, T_e, W, L, rows, ids, c));
+  c.lut = lut;
+  TRY(submit(h, c, ticket));
+  hold_reads(h, *ticket, ids);
+  return RV_OK;
 }
 
 // ---- the whole beam (k_dec_finalize_beams): tokens and scores are required, the other three outputs may be null
@@ -2425,6 +2676,14 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     if (!dst || dst_floats < 4) return fail(h, RV_EINVAL, "coalesce_stats needs 4 floats");
     dst[0] = (float)h->co_groups; dst[1] = (float)h->co_slabs; dst[2] = (float)h->co_largest;
     dst[3] = (float)coalesce_n(h, async_depth(h));
+    return RV_OK;
+  }
+  else if (!strcmp(name, "read_stats")) {       // device allocations made for reads, reads alive, puts, read slots (alive or kept for reuse), k_expand_windows launches
+    *n_written = 5;
+    if (!dst || dst_floats < 5) return fail(h, RV_EINVAL, "read_stats needs 5 floats");
+    long long alive = 0;
+    for (const Read& r : h->reads) alive += r.live ? 1 : 0;
+    dst[0] = (float)h->read_allocs; dst[1] = (float)alive; dst[2] = (float)h->read_puts; dst[3] = (float)h->reads.size(); dst[4] = (float)h->win_expands;
     return RV_OK;
   }
   else if (!strcmp(name, "rec_stamps")) {

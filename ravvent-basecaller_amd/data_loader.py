@@ -155,3 +155,90 @@ def load_data_from_single_signal_label(signal_path, label_path, stride):
     raw = np.loadtxt(signal_path, dtype=int)
     label = np.loadtxt(label_path, dtype=object)
     return snippets_to_slab(*prepare_snippets(raw, label[:, :2].astype(int), label[:, 2], stride))
+
+
+# ----------------------------------------------------------------------------------------------
+# The chunker in window form: a read's chunks as (start, length) windows of its two scaled tables, for the
+# rv_beam_search_windows* calls (include/ravvent_hip.h), which gather each window on the device from a read that is
+# uploaded once.  Same arithmetic as prepare_snippets: fp64 scaling, then ONE cast to f32 -- the cast pad_sequences
+# makes when it assigns an fp64 snippet into its float32 array (round to nearest even, element by element).
+class ReadWindows:
+    """raw_sc f32 [N], events_sc f32 [E,5], windows i32 [n,4] = (raw_start, raw_len, event_start, event_len) with the
+    lengths already clipped to max_raw_len / max_event_len (post-truncation), targets: the '$...^' strings or None."""
+    __slots__ = ("raw_sc", "events_sc", "windows", "targets")
+
+    def __init__(self, raw_sc, events_sc, windows, targets):
+        self.raw_sc, self.events_sc, self.windows, self.targets = raw_sc, events_sc, windows, targets
+
+    def __len__(self):
+        return int(self.windows.shape[0])
+
+    def expand(self, T_r=MAX_RAW_LEN, T_e=MAX_EVENT_LEN, pad=INPUT_PADDING):
+        return expand_windows(self.raw_sc, self.events_sc, self.windows, T_r, T_e, pad)
+
+
+def prepare_windows(raw, nuc_raw_ranges=None, nuc_reference_symbols=None, stride=6, max_raw_len=MAX_RAW_LEN,
+                    max_event_len=MAX_EVENT_LEN):
+    """prepare_snippets without the per-chunk copies -> ReadWindows.  nuc_raw_ranges None (an unlabelled read): every event
+    is kept, i.e. prepare_snippets given the one label range [first event's start, last event's end), which its trimming
+    lines leave as it is; targets is then None."""
+    from .event_detection import EventDetector
+    raw = np.asarray(raw)
+    st, ln, mu, sd = EventDetector(window_length1=ED_WINDOW_LENGTH_1, window_length2=ED_WINDOW_LENGTH_2).run_arrays(raw)
+    dmean = np.concatenate([[0.0], np.diff(mu)]) if len(mu) else np.zeros(0)
+    events = np.column_stack([st, st + ln, ln, mu, sd, mu ** 2, dmean]).astype(np.float64)
+    r = raw.reshape(-1, 1).astype(np.float64)
+    r_mean, r_scale = _standard_scale_fit(r)
+    raw_sc = ((r - r_mean) / r_scale).reshape(-1)
+    empty = ReadWindows(raw_sc.astype(np.float32), np.zeros((0, 5), np.float32), np.zeros((0, 4), np.int32),
+                        None if nuc_raw_ranges is None else [])
+    if events.shape[0] == 0:
+        return empty
+    ev_mean, ev_scale = _standard_scale_fit(events[:, 2:])
+    if nuc_raw_ranges is not None:
+        nuc_raw_ranges = np.asarray(nuc_raw_ranges)
+        keep = np.logical_and(events[:, 0] >= nuc_raw_ranges[0, 0], events[:, 1] <= nuc_raw_ranges[-1, 1])
+        events = events[keep]
+        events[0, 2] += events[0, 0] - nuc_raw_ranges[0, 0]
+        events[0, 0] = nuc_raw_ranges[0, 0]
+        events[-1, 2] = nuc_raw_ranges[-1, 1] - events[-1, 0]
+    events_ranges = compute_fitting_event_ranges(events[:, 2], stride, raw_max_len=max_raw_len)
+    events_sc = (events[:, 2:] - ev_mean) / ev_scale
+    if events_ranges.size == 0:
+        empty.events_sc = events_sc.astype(np.float32)
+        return empty
+    raw_ranges = np.column_stack((events[:, 0][events_ranges[:, 0]].astype(np.int32),
+                                  events[:, 0][events_ranges[:, 1] - 1].astype(np.int32)))
+    # what the slices raw_sc[a:b] / events_sc[i:j] hold (a slice ends at the table's end), cut to the padded lengths
+    N, E = raw_sc.shape[0], events_sc.shape[0]
+    ra = np.clip(raw_ranges[:, 0].astype(np.int64), 0, N)
+    rb = np.clip(raw_ranges[:, 1].astype(np.int64), 0, N)
+    ea = np.clip(events_ranges[:, 0].astype(np.int64), 0, E)
+    eb = np.clip(events_ranges[:, 1].astype(np.int64), 0, E)
+    windows = np.column_stack((ra, np.minimum(np.maximum(rb - ra, 0), max_raw_len),
+                               ea, np.minimum(np.maximum(eb - ea, 0), max_event_len))).astype(np.int32)
+    targets = None
+    if nuc_raw_ranges is not None:
+        ids_lens = nuc_raw_ranges[:, 1] - nuc_raw_ranges[:, 0]
+        id_seq = np.repeat(np.arange(nuc_raw_ranges.shape[0]), ids_lens)
+        if nuc_raw_ranges[0, 0] != 0:
+            id_seq = np.concatenate((np.full(nuc_raw_ranges[0, 0], -1), id_seq))
+        syms = np.asarray(nuc_reference_symbols)
+        targets = ["$" + "".join(syms[np.unique(id_seq[a:b])]) + "^" for a, b in raw_ranges]
+    return ReadWindows(raw_sc.astype(np.float32), np.ascontiguousarray(events_sc.astype(np.float32)), windows, targets)
+
+
+def expand_windows(raw_sc, events_sc, windows, T_r, T_e, pad=INPUT_PADDING):
+    """The padded chunk tensors of a window table, on the host: (raw [n,T_r,1] f32, event [n,T_e,5] f32), what
+    snippets_to_slab gives for the same chunks.  windows [n,4]; a length beyond T_r / T_e is cut there."""
+    raw_sc = np.asarray(raw_sc, np.float32).reshape(-1)
+    events_sc = np.asarray(events_sc, np.float32).reshape(-1, 5)
+    w = np.asarray(windows, np.int64).reshape(-1, 4)
+    n = w.shape[0]
+    raw = np.full((n, T_r, 1), pad, np.float32)
+    ev = np.full((n, T_e, 5), pad, np.float32)
+    for i, (a, la, e, le) in enumerate(w):
+        la, le = min(int(la), T_r), min(int(le), T_e)
+        raw[i, :la, 0] = raw_sc[a:a + la]
+        ev[i, :le] = events_sc[e:e + le]
+    return raw, ev

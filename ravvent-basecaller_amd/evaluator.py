@@ -16,8 +16,12 @@ from . import merger, utils
 
 class PerformanceEvaluator:
     def __init__(self, basecaller, stride: int = 6, fused_postprocessing: bool = True, pipelined_merge: bool = False,
-                 concurrent_slabs: int = 1):
+                 concurrent_slabs: int = 1, windows: bool = False):
         self.basecaller = basecaller
+        # True: `run_read` uploads the read once (Basecaller.put_read) and `run_slabs` feeds slabs of window tables
+        # (Basecaller.beam_search_stream_windows) in place of padded chunk arrays: same results, same result keys; t_data_loading
+        # then holds prepare_windows plus the put.  False (default): the padded arrays, as ever
+        self.windows = bool(windows)
         self.stride = stride           # ravvent_performance_evaluator.py:16
         # True (default since round 4): strings + per-base probabilities come straight from the device (rv_beam_search_calls) as
         # arrays, and the merge takes those arrays: no per-chunk Python object is built inside the timed phases (`nuc_preds` is put
@@ -61,6 +65,19 @@ class PerformanceEvaluator:
         ref_seq = "".join(list(np.asarray(labels)[:, 2]))
         samples_num = int(ranges_ids[-1, 1] - ranges_ids[0, 0])
         start = timer()
+        if self.windows:
+            rw = dl.prepare_windows(signal, ranges_ids, np.asarray(labels)[:, 2], self.stride)
+            nuc = dl.pad_sequences(dl.nuc_tk.texts_to_sequences(rw.targets), maxlen=None, value=dl.NUC_TOKEN_PAD, dtype="int64")
+            handle = self.basecaller.put_read(rw.raw_sc, rw.events_sc)
+            t_chunking = timer() - start
+            try:
+                res = self.run_slabs(None, None, nuc, bases_num=len(ref_seq), samples_num=samples_num, chunk_size=chunk_size,
+                                     beam_width=beam_width, window_table=handle.table(rw.windows))
+            finally:
+                handle.drop()
+            res["t_data_loading"] += t_chunking
+            res["total"] += t_chunking
+            return res
         slab = dl.snippets_to_slab(*dl.prepare_snippets(signal, ranges_ids, np.asarray(labels)[:, 2], self.stride))
         t_chunking = timer() - start
         res = self.run_slabs(*slab, bases_num=len(ref_seq), samples_num=samples_num, chunk_size=chunk_size,
@@ -70,9 +87,12 @@ class PerformanceEvaluator:
         return res
 
     def run_slabs(self, raw_snippets, event_snippets, nuc_tk_snippets, bases_num=None, samples_num=None,
-                  chunk_size: int = 1024, beam_width: int = 5):
+                  chunk_size: int = 1024, beam_width: int = 5, window_table=None):
         """The body of `run()` after data loading: inputs are the padded snippet arrays
-        `load_data_from_single_signal_label` would return (data_loader.py:113-126)."""
+        `load_data_from_single_signal_label` would return (data_loader.py:113-126).  window_table (windows=True): the chunks as
+        rows [n,5] of a window table over reads put on the basecaller (ReadHandle.table), in place of the two snippet arrays."""
+        if window_table is not None:
+            return self._run_window_slabs(np.asarray(window_table, np.int32), nuc_tk_snippets, bases_num, samples_num, chunk_size, beam_width)
         start = timer()
         data_chunks = list(zip(self._split_into_chunks(raw_snippets, chunk_size),
                                self._split_into_chunks(event_snippets, chunk_size),
@@ -126,6 +146,54 @@ class PerformanceEvaluator:
             flat, steps = bases.tobytes(), bases.shape[1]
             nuc_preds.extend((flat[i * steps:i * steps + int(n)].decode("ascii"), probs[i, :int(n)]) for i, n in enumerate(lens))
         n_chunks = int(raw_snippets.shape[0] if raw_snippets is not None else event_snippets.shape[0])
+        if bases_num is None:
+            bases_num = n_chunks * self.stride
+        return {
+            "bases_num": int(bases_num), "samples_num": samples_num, "chunks_num": n_chunks,
+            "t_data_loading": t_data_loading, "t_predicting": t_predicting,
+            "t_postprocessing": t_postprocessing, "t_merge": t_merge,
+            "total": t_data_loading + t_predicting + t_postprocessing + t_merge,
+            "total_processing": t_predicting + t_postprocessing + t_merge,
+            "nuc_preds": nuc_preds, "merged_seq": merged_seq,
+        }
+
+    def _run_window_slabs(self, table, nuc_tk_snippets, bases_num, samples_num, chunk_size, beam_width):
+        """`run_slabs` on a window table: the same slabs (rows of `chunk_size`), the same streamed calls, post-processing and merge."""
+        start = timer()
+        tables = [t for t in self._split_into_chunks(table, chunk_size) if t.shape[0] > 0]
+        L = int(nuc_tk_snippets.shape[1])
+        t_data_loading = timer() - start
+        results = self.basecaller.beam_search_stream_windows(iter(tables), beam_width, L, calls=self.fused_postprocessing)
+        nuc_preds, kept = [], []
+        t_predicting = t_postprocessing = 0.0
+        while True:
+            start = timer()
+            res = next(results, None)
+            t_predicting += timer() - start
+            if res is None:
+                break
+            start = timer()
+            if self.fused_postprocessing:
+                kept.append(res)
+            else:
+                pred_tokens, beam_scores = res
+                scores = utils.calc_prob_logits_beam_search_scores(beam_scores).numpy()
+                seqs = self.basecaller.tokens_to_nuc_sequences(pred_tokens)
+                nuc_preds.extend((seq, sc[:len(seq)]) for seq, sc in zip(seqs, scores))
+            t_postprocessing += timer() - start
+        start = timer()
+        if self.fused_postprocessing:
+            merged_seq = ""
+            if kept:
+                merged_seq = self.merger.merge_arrays(np.concatenate([a[0] for a in kept]), np.concatenate([a[1] for a in kept]),
+                                                      np.concatenate([a[2] for a in kept]))[0]
+        else:
+            merged_seq = self.merger.merge([merger.SeqLogitsPair(seq, lg) for seq, lg in nuc_preds]).seq if nuc_preds else ""
+        t_merge = timer() - start
+        for bases, probs, lens in kept:                          # per-chunk view for callers that want it (untimed)
+            flat, steps = bases.tobytes(), bases.shape[1]
+            nuc_preds.extend((flat[i * steps:i * steps + int(n)].decode("ascii"), probs[i, :int(n)]) for i, n in enumerate(lens))
+        n_chunks = int(table.shape[0])
         if bases_num is None:
             bases_num = n_chunks * self.stride
         return {
