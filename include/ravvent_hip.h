@@ -396,6 +396,25 @@ int rv_score_logits(rv_handle h, const float* logits, const int32_t* labels, int
  *                       prologue of its own workgroup, with the arithmetic of the split GEMM, straight into the resident fragments: no
  *                       `gemm_memory` launch and no [B,T_m,2u] tensor written and read back.  0 = the GEMM launch in front of the decode,
  *                       which every other form of the decode keeps in either case.  Results are identical bit for bit),
+ *          "weight_parts" (2/1, default 2; any other value fails with RV_EINVAL, and setting it with calls in flight with RV_ESTATE.
+ *                       In force from the next rv_load_weights.  2: every dense weight enters the matrix pipe as two f16 parts, fp32
+ *                       accuracy.  1: every weight tensor that rv_load_weights turns into a split-f16 image is first rounded to what
+ *                       the first f16 part of that image holds, float((_Float16)(w s)) / s under the image's own power-of-two scale
+ *                       s, and every image of the tensor is built from the rounded tensor: the recurrent kernels of the encoder, the
+ *                       input kernels of its layers >= 1 and [W_mem | A_c] per column (rv_round_weights), the decoder's folded cell
+ *                       kernel and output layer after their fold.  Biases, the layer-0 input kernels, the one-hot token rows of the
+ *                       cell kernel and attention_v stay fp32.  Served: the persistent decode of one decoder cell with Luong attention
+ *                       and "matrix_attention" / "matrix_cell" on, under every entry point and encoder option; anything else -- any
+ *                       decoder depth other than 1, Bahdanau attention, "persistent_decode" / "flash_attend" / "matrix_attention" /
+ *                       "matrix_cell" 0, "debug_taps" 1 -- fails with RV_EUNSUPPORTED.  The second parts of the Wc16 / Wl16 images
+ *                       are exactly zero in this mode.  Those of the per-column images (Ua, Wh, Wx16, Wmp16, Wkp16) are zero too,
+ *                       with one exception: where a column's largest element rounds up to a power of two, the packer scales the
+ *                       rounded column by half the scale it was rounded under, and an element below 2^-26 of that maximum may then
+ *                       leave a non-zero second part; both parts together still hold the rounded weight exactly),
+ *          "one_part_kernels" (0/1, default 1; meaningful under "weight_parts" 1 only: the decode runs k_dec_persist_1p, one MFMA and
+ *                       half the weight stream per (k-step, gate) pair, where the one-part list holds a form for the call -- beam widths
+ *                       1 and 5.  0 = the two-part kernels on the images whose second parts are zero.  Results are identical bit for
+ *                       bit but for the sign of a zero),
  *          "profile"    (0 off; 1: hipEvents around every launch outside the decode graph and around
  *                       the graph as a whole; 2: no graph, events around every kernel; 3: events around the decode
  *                       launch only -- the persistent decode kernel or the decode graph). */
@@ -421,6 +440,11 @@ int rv_set_option(rv_handle h, const char* key, int32_t value);
  *                                 it; a per-step decode replayed from its captured hipGraph reports the forms of the capture.  After a call
  *                                 that ran as a slab graph (option "slab_graph") it fails with RV_ESTATE
  *   "kernel_form_list" [n,5]      every instantiation the form lists hold, in the same rows, whatever the last call was
+ *   "kernel_form_list_1p" [n,5]   the one-part forms of the persistent decode (option "weight_parts" 1), a list of their own: rows
+ *                                 (8, W, NIT, 1, ATT) for k_dec_persist_1p<W, NIT, ATT>.  "kernel_forms" reports a launched one under
+ *                                 the same kernel id 8
+ *   "group_kernel_forms" [n,5]    the instantiations the last coalesced group of asynchronous calls (option "coalesce") launched on its
+ *                                 own context, in the same rows; empty before the first group
  *   "coalesce_stats"  [4]         of the handle since it was created: groups launched (option "coalesce"), slabs they held, members of the
  *                                 largest one, and the slabs per group the options and the environment give right now (1 = none)
  *   "read_stats"      [5]         of the handle since it was created: device allocations made for reads (rv_read_put), reads alive, puts,
@@ -442,6 +466,14 @@ int rv_reset_profile(rv_handle h);
 int rv_detect_events(const double* raw, size_t n, int32_t window_length1, int32_t window_length2,
                      double threshold1, double threshold2, double peak_height, int64_t* start,
                      int64_t* length, double* mean, double* stdv, size_t capacity, size_t* n_events);
+
+/* Option "weight_parts" 1 on the host (pure CPU, needs no handle): dst receives the blob src (n_floats = the config's weight
+ * count, else RV_EINVAL) with its blob-level tensors rounded as rv_load_weights rounds them in that mode -- per column, s = the
+ * power of two that brings the column's largest |w| into [2^13, 2^14), w <- float((_Float16)(w s)) / s: U of every encoder layer
+ * and direction over its 128 rows, W of encoder layers >= 1 over 256 rows, W_mem and A_c (rows u..3u-1 of the attention layer) over
+ * 256 rows.  Every other tensor is copied as it is (the decoder's folded kernels are rounded after their fold, by the loader, and
+ * are no rounding of a blob slice).  The loader runs this same code.  dst may be src. */
+int rv_round_weights(const RvConfig* cfg, const float* src, float* dst, size_t n_floats);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,7 @@ SYMBOLS = [
     ("rv_reset_profile", c_int32, [c_void_p]),
     ("rv_detect_events", c_int32, [c_void_p, c_size_t, c_int32, c_int32, c_double, c_double, c_double,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]),
+    ("rv_round_weights", c_int32, [c_void_p, c_void_p, c_void_p, c_size_t]),
     # include/ravvent_merge.h
     ("rv_merge_calls", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                  c_int64, POINTER(c_int64)]),

@@ -135,6 +135,7 @@ class Basecaller:
         rc = self._lib.rv_create(ctypes.byref(ccfg), ctypes.byref(self._h))
         _capi.check(self._lib, None, rc, "rv_create")
         self.optimizer = None
+        self._weight_parts = 2
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -162,6 +163,7 @@ class Basecaller:
         self._check(self._lib.rv_load_weights(self._h, blob.ctypes.data_as(ctypes.c_void_p), blob.size),
                     "rv_load_weights")
         self._blob = blob
+        self._parts_loaded = self.weight_parts       # the mode the images in force were built in
 
     def clone(self):
         """A second handle on the same device with the same configuration and weights (own stream, own buffers): two handles
@@ -174,10 +176,40 @@ class Basecaller:
         ccfg = self.cfg.to_c()
         rc = self._lib.rv_create(ctypes.byref(ccfg), ctypes.byref(other._h))
         _capi.check(self._lib, None, rc, "rv_create")
+        # the mode travels with the clone: its images are built in the mode this handle's were LOADED in, and its option then says
+        # what this handle's option says (the two differ after set_option("weight_parts", n) without a reload)
+        loaded = getattr(self, "_parts_loaded", 2)
         if getattr(self, "_blob", None) is not None:
+            if loaded != 2:
+                other._check(self._lib.rv_set_option(other._h, b"weight_parts", loaded), "rv_set_option(weight_parts)")
             other._check(self._lib.rv_load_weights(other._h, self._blob.ctypes.data_as(ctypes.c_void_p), self._blob.size),
                          "rv_load_weights")
+        if self.weight_parts != (loaded if getattr(self, "_blob", None) is not None else 2):
+            other._check(self._lib.rv_set_option(other._h, b"weight_parts", self.weight_parts), "rv_set_option(weight_parts)")
         return other
+
+    @property
+    def weight_parts(self) -> int:
+        """f16 parts each dense weight keeps (option ``weight_parts``, as set: in force from the next load of weights): 2 = fp32-exact
+        weights, 1 = the half-precision weight mode.  ``weight_parts_loaded`` is the mode the weights in force were loaded in."""
+        return getattr(self, "_weight_parts", 2)
+
+    @property
+    def weight_parts_loaded(self) -> int:
+        return getattr(self, "_parts_loaded", 2)
+
+    def set_weight_parts(self, n: int):
+        """2 (default): every dense weight enters the matrix pipe as two f16 parts.  1: every such weight is rounded to its first
+        part (include/ravvent_hip.h, option ``weight_parts``) -- a model with slightly other weights, decoded
+        with half the weight stream.  Weights already loaded are loaded again from the kept blob, so the mode is in force when this
+        returns.  Fails while asynchronous calls are in flight."""
+        self._check(self._lib.rv_set_option(self._h, b"weight_parts", int(n)), "rv_set_option(weight_parts)")
+        self._weight_parts = int(n)
+        if getattr(self, "_blob", None) is not None:
+            self._check(self._lib.rv_load_weights(self._h, self._blob.ctypes.data_as(ctypes.c_void_p), self._blob.size),
+                        "rv_load_weights")
+            self._parts_loaded = int(n)          # (only once the reload has succeeded)
+        return self
 
     def load_weights(self, path):
         """ravvent_performance_evaluator.py:107.  `path` is either a TF-format checkpoint prefix as Keras writes it
@@ -203,6 +235,8 @@ class Basecaller:
             warnings.warn(f"rv_set_option({key}): {msg.decode() if msg else rc}", RuntimeWarning, stacklevel=2)
             return
         self._check(rc, f"rv_set_option({key})")
+        if key == "weight_parts":
+            self._weight_parts = int(value)
 
     # ------------------------------------------------------------------ input plumbing
     def _split_inputs(self, input_data):

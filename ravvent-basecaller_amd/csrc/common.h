@@ -24,6 +24,7 @@ enum {
   RV_K_LSTM_REC_PROJ = 5,      // k_lstm_rec_proj<BT, SB>
   RV_K_LSTM_REC_MX = 6,        // k_lstm_rec_mx<F, CH>
   RV_K_INPROJ_SMALL = 7,       // k_inproj_small<F>
+  RV_K_DEC_PERSIST_1P = 8,     // k_dec_persist_1p<W, NIT, ATT>: (W, NIT, 1, ATT); launched under option weight_parts 1 only
 };
 #define RV_FORM_ROWS 512
 struct FormLog {
@@ -46,6 +47,7 @@ struct FormLog {
 void list_rec_forms(FormLog& log);
 void list_mx_forms(FormLog& log);
 void list_decode_forms(FormLog& log);
+void list_decode_forms_1p(FormLog& log);   // the one-part forms of the persistent decode: a list of their own ("kernel_form_list_1p")
 
 // ---------------------------------------------------------------- K1: BiLSTM recurrence
 // Members of a coalesced call whose inputs are read where their callers left them (matrix-pipe layer 0 only): chunk b of the group with
@@ -266,7 +268,10 @@ void launch_dec_attend(const DecState& d, const float* WmemT, bool flash, int st
 int dec_persist_form(int attention, int depth, int W, int Tm, bool greedy, bool matrix_attention, bool matrix_cell);
 void launch_dec_persist(const DecState& d, const float* Wcat /*[256,512]*/, const float* Wtok /*[V,512]*/,
                         const float* bdec /*[512]*/, const float* Wcat1, const float* bdec1, const float* Nh, hipStream_t s,
-                        FormLog* log = nullptr);
+                        FormLog* log = nullptr, const uint16_t* Wc16p1 = nullptr, const uint16_t* Wl16p1 = nullptr);
+// Wc16p1 / Wl16p1 (option weight_parts 1; both or neither): the first f16 parts of the Wc16 / Wl16 images on their own.  Where the
+// one-part list holds a form for the call, k_dec_persist_1p runs on them in k_dec_persist's place; elsewhere k_dec_persist runs on
+// d's two-part images, whose second parts are zero then -- the same results bit for bit, but for the sign of a zero
 // ptab != null: the two output addresses are read from ptab[RV_PTAB_TOKENS] / ptab[RV_PTAB_OUT2] on the device instead
 // Members (persistent beam-search decode only): the slab is n slabs of the asynchronous calls decoded as one, back to back.  Member m
 // owns rows row0[m] .. row0[m] + rows[m] - 1: its S is the maximum of chunk_steps over those rows alone, goes to S_host[m], and its rows

@@ -70,6 +70,9 @@ struct Options {
   int coalesce = -1;                        // 0 / 1 off, n >= 2 slabs per group, -1 chosen from async_depth (coalesce_n)
   int group_inplace = 1;                    // a group's layer-0 kernels read its members' device inputs where they are (no copies into the group's buffers)
   int group_side_ev = -1;                   // a group's event encoder on a side stream beside its raw encoder: 0 / 1, -1 where the queues allow it (group_side_ev)
+  int weight_parts = 2;                     // option "weight_parts": f16 parts a weight image keeps of each weight, as of the next rv_load_weights (round_blob_weights)
+  int parts_loaded = 2;                     // ... and what the images in force were built with
+  int one_part = 1;                         // option "one_part_kernels": weight_parts 1 decodes with k_dec_persist_1p where a form exists (0: the two-part kernels on the zero-lo images)
 };
 
 // Device images derived from the weights by rv_load_weights.  The handle owns them; a child context takes the addresses as a whole (create_child)
@@ -89,6 +92,8 @@ struct WeightImages {
   float* Wcat2 = nullptr;                   // (one decoder cell): [W_a ; U + A_h W_a] [256][512]
   float* Nh = nullptr;                      // (one decoder cell): A_h W_fc [128][V]
   uint16_t* Wc16 = nullptr;                 // (one decoder cell): Wcat2 as two f16 parts in MFMA B-fragment order (DecState::Wc16)
+  uint16_t* Wc16p1 = nullptr;               // weight_parts 1: the first parts of Wc16 alone, [wave][pair][64 lanes][8 f16] (k_dec_persist_1p)
+  uint16_t* Wl16p1 = nullptr;               // ... and of Wl16, [8 k-steps][64 lanes][8 f16]
   uint16_t* Wmp16 = nullptr;                // Wmp as two f16 parts in MFMA fragment order + column factors (launch_gemm_mem_split)
   uint16_t* Wkp16 = nullptr;                // the W_mem half of those parts, columns permuted into key-tile rows (DecState::Wkp16)
   float* WcatT = nullptr;                   // ([W_dec[V:] ; U_dec])^T, [512][256]
@@ -237,6 +242,7 @@ struct RvContext {
   SlabFacts fact;
   FormLog lforms;                           // the kernel instantiations it launched ("kernel_forms"); lforms_ok = 0: it ran as a slab graph
   int lforms_ok = 1;
+  FormLog gforms;                           // (root) the instantiations the last coalesced group launched on its own context ("group_kernel_forms")
   std::map<GraphKey, FormLog> graph_forms;  // ... those a captured decode graph of `graphs` launches (recorded at its capture)
 
   // asynchronous calls (rv_beam_search_submit* / rv_beam_search_collect*): the handle owns `kids` more slab contexts -- own stream,
@@ -380,6 +386,29 @@ void bind_weights(RvContext* h) {
   h->W_att = p; p += (d + 2 * u) * d;
   h->W_fc = p; p += d * V;
   h->b_fc = p; p += V;
+}
+
+// Option weight_parts 1, the tensors that are a slice of the blob (same walk as bind_weights): each column rounded to what the first
+// f16 part of its split image holds (rv_round_column) -- U of every encoder layer and direction over its 128 rows, W of encoder
+// layers >= 1 over 256 rows, W_mem and A_c (rows u .. 3u - 1 of the attention layer) over 256 rows.  Everything else stays as it is;
+// the folded tensors (cell kernel, output layer) are rounded after their fold by rv_load_weights.  Host code, no device.
+void round_blob_weights(const RvConfig& c, float* blob) {
+  const size_t u = c.enc_units, d = c.dec_units, V = c.vocab;
+  float* p = blob;
+  for (int e = 0; e < 2; ++e)
+    for (int l = 0; l < c.enc_depth; ++l) {
+      const size_t F = l > 0 ? 2 * u : (e == 0 ? 1 : 5);
+      for (int dr = 0; dr < 2; ++dr) {
+        if (l > 0) for (size_t n = 0; n < 4 * u; ++n) rv_round_column(p + n, 4 * u, (int)F);
+        p += F * 4 * u;
+        for (size_t n = 0; n < 4 * u; ++n) rv_round_column(p + n, 4 * u, (int)u);
+        p += u * 4 * u + 4 * u;
+      }
+    }
+  for (int k = 0; k < c.dec_depth; ++k) p += ((k == 0 ? V + d : d) + d + 1) * 4 * d;
+  for (size_t n = 0; n < d; ++n) rv_round_column(p + n, d, (int)(2 * u));        // W_mem
+  p += 2 * u * d + d * d + d;                                                      // (W_q, attention_v)
+  for (size_t n = 0; n < d; ++n) rv_round_column(p + d * d + n, d, (int)(2 * u));  // A_c
 }
 
 // ---- profiling: bracket a launch with events on the launch stream
@@ -622,6 +651,12 @@ int validate_call(RvContext* h, const Call& call, Call& ok) {
   if (T_r + T_e > 352) return fail(h, RV_EUNSUPPORTED, "attention memory of %d steps exceeds the 352 the decode kernel is built for", T_r + T_e);
   if (L > 64) return fail(h, RV_EUNSUPPORTED, "max_output_len %d exceeds 64", L);
   if (ok.dev_out && B > 0 && L > 1 && (!ok.tokens || !ok.out2)) return fail(h, RV_EINVAL, "null output pointer");
+  // weight_parts 1: only the decode whose every weight comes from an image of a rounded tensor -- the persistent decode of one cell
+  // with Luong attention and the cell product on the matrix pipe (ATT 3: Wkp16 / Wmp16, Wc16, Wl16).  The per-step kernels and the
+  // other persistent forms read the cell kernel, the attention layer or the output layer from the blob, which holds them unrounded
+  if ((h->parent ? h->parent : h)->opt.parts_loaded == 1 && (c.dec_depth != 1 || persist_form(h, ok.greedy, W, T_r + T_e, ok.forced != nullptr) != 3))
+    return fail(h, RV_EUNSUPPORTED, "weight_parts 1 serves the persistent decode of one decoder cell with Luong attention and the cell product on the matrix "
+                "pipe only (options persistent_decode, flash_attend, matrix_attention, matrix_cell at 1, debug_taps 0): this call would read unrounded weights");
   return RV_OK;
 }
 
@@ -990,9 +1025,11 @@ int decode_persist(RvContext* h, Slab& sl) {
   d.values = h->mem2; part[0].values = h->mem2;
   d.mx_kscale = h->mx_kscale; d.mx_kdescale = std::ldexp(1.0f, -14) / h->mx_kscale;
   d.mx_uscale = h->mx_uscale; d.mx_udescale = std::ldexp(1.0f, -14) / h->mx_uscale;
+  const bool p1 = h->opt.parts_loaded == 1 && h->opt.one_part && persist_att == 3 && d.depth == 1;
   Scope sc(h, "dec_persist", nullptr, true);
   launch_dec_persist(d, d.depth > 1 ? h->dec[0].W + (size_t)V * RV_G : h->img.Wcat2, h->dec[0].W, h->dec[0].b,
-                     d.depth > 1 ? h->dec[1].W : nullptr, d.depth > 1 ? h->dec[1].b : nullptr, h->img.Nh, s, &h->lforms);
+                     d.depth > 1 ? h->dec[1].W : nullptr, d.depth > 1 ? h->dec[1].b : nullptr, h->img.Nh, s, &h->lforms,
+                     p1 ? h->img.Wc16p1 : nullptr, p1 ? h->img.Wl16p1 : nullptr);
   return RV_OK;
 }
 
@@ -1613,6 +1650,7 @@ int launch_group(RvContext* root, RvContext* g) {
   res.members = &m;
   res.form_B = g->g_B0;
   const int rc = enqueue(g, call, res);
+  root->gforms = g->lforms;
   g->pend.busy = false;                      // (the tickets live in the root's table)
   if (rc != RV_OK) g->g_failed = rc;
   return relay(root, g, rc);
@@ -1940,6 +1978,8 @@ int rv_create(const RvConfig* cfg, rv_handle* out) {
   TRY(dalloc(h, &h->img.Wc16, (size_t)2 * 3 * RV_U * RV_G));      // (two cells: 384 rows)
   if (c.dec_depth == 2) TRY(dalloc(h, &h->img.W1c16, (size_t)2 * RV_E * RV_G));
   TRY(dalloc(h, &h->img.Wl16, (size_t)2 * RV_E * 16));
+  TRY(dalloc(h, &h->img.Wc16p1, (size_t)RV_E * RV_G));
+  TRY(dalloc(h, &h->img.Wl16p1, (size_t)RV_E * 16));
   TRY(dalloc(h, &h->img.Wq16, (size_t)2 * RV_U * RV_U));
   TRY(dalloc(h, &h->img.Wcat2, (size_t)RV_E * RV_G));
   TRY(dalloc(h, &h->img.Nh, (size_t)RV_U * RV_MAX_VOCAB));
@@ -1994,6 +2034,16 @@ void rv_destroy(rv_handle h) {
 
 size_t rv_weight_count(rv_handle h) { return h ? h->n_w : 0; }
 
+int rv_round_weights(const RvConfig* cfg, const float* src, float* dst, size_t n_floats) {
+  if (!cfg || !src || !dst) return RV_EINVAL;
+  const RvConfig& c = *cfg;
+  if (c.enc_units != RV_U || c.dec_units != RV_U || c.dec_depth < 1 || c.dec_depth > 4 || c.enc_depth < 1 || c.enc_depth > 8 ||
+      c.vocab < 2 || c.vocab > RV_MAX_VOCAB || n_floats != weight_count(c)) return RV_EINVAL;
+  if (dst != src) memmove(dst, src, n_floats * sizeof(float));
+  round_blob_weights(c, dst);
+  return RV_OK;
+}
+
 int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
   if (!h) return RV_EINVAL;
   if (!blob) return fail(h, RV_EINVAL, "null weight blob");
@@ -2003,6 +2053,15 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
   for (RvContext* k : h->kids) if (k->pend.busy) return fail(h, RV_ESTATE, "collect the calls in flight before loading weights");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   h->opt.gen++;                      // (weight-derived scalars travel by value in the decode's kernel arguments)
+  // weight_parts 1: every image below -- and the device copy of the blob -- is built from the blob with its blob-level tensors rounded
+  const bool one_part = h->opt.weight_parts == 1;
+  std::vector<float> rounded;
+  if (one_part) {
+    rounded.assign(blob, blob + n_floats);
+    round_blob_weights(h->cfg, rounded.data());
+    blob = rounded.data();
+  }
+  h->opt.parts_loaded = h->opt.weight_parts;
   HIPCHK(h, hipMemcpyAsync(h->d_w, blob, n_floats * sizeof(float), hipMemcpyHostToDevice, h->stream));
   {   // derived layout for the decoder cell kernel: the input-kernel rows that multiply a dense input
       // (rows V.. of W_0; all of W_k for k >= 1) followed by U_k form a contiguous [256][512] matrix in
@@ -2191,17 +2250,37 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
           for (int j = 0; j < RV_U; ++j) acc += (double)blob[ah + (size_t)i * RV_U + j] * (double)blob[fc + (size_t)j * V + v];
           nh[(size_t)i * V + v] = (float)acc;
         }
+      // the scales of the matrix-pipe images of both folded tensors (Wc16, Wl16 below): rows divided by the factor their input's f16
+      // image carries (exact: powers of two), then one power-of-two scale for the tensor
+      auto xs = [&](int k) { return k < RV_U ? h->mx_uscale : 16384.f; };
+      float mx = 0.f;
+      for (int k = 0; k < KR; ++k)
+        for (int n = 0; n < RV_G; ++n) mx = std::max(mx, std::fabs(w2[(size_t)k * RV_G + n] / xs(k)));
+      int ex = 0;
+      if (mx > 0.f && std::isfinite(mx)) std::frexp(mx, &ex);
+      const float T = std::ldexp(1.0f, 14 - ex);
+      std::vector<float> fcw(blob + fc, blob + fc + (size_t)RV_U * V);      // W_fc, the output layer's upper half
+      auto wl = [&](int k, int v) -> float {
+        if (v >= V) return 0.f;
+        return (k < RV_U ? fcw[(size_t)k * V + v] : nh[(size_t)(k - RV_U) * V + v]) / xs(k);
+      };
+      float ml = 0.f;
+      for (int k = 0; k < RV_E; ++k)
+        for (int v = 0; v < V; ++v) ml = std::max(ml, std::fabs(wl(k, v)));
+      int el = 0;
+      if (ml > 0.f && std::isfinite(ml)) std::frexp(ml, &el);
+      const float Tl = std::ldexp(1.0f, 14 - el);
+      if (one_part) {   // weight_parts 1: both folded tensors rounded to the first f16 part of those images, under the scales just taken
+                        // (kept for the packing below), so that their fp32 images (Wcat2, Nh) carry the same numbers
+        for (int k = 0; k < KR; ++k)
+          for (int n = 0; n < RV_G; ++n) w2[(size_t)k * RV_G + n] = rv_round_to_first_part(w2[(size_t)k * RV_G + n] / xs(k), T) * xs(k);
+        for (int k = 0; k < RV_E; ++k)
+          for (int v = 0; v < V; ++v)
+            (k < RV_U ? fcw[(size_t)k * V + v] : nh[(size_t)(k - RV_U) * V + v]) = rv_round_to_first_part(wl(k, v), Tl) * xs(k);
+      }
       if (!two) HIPCHK(h, hipMemcpy(h->img.Wcat2, w2.data(), w2.size() * sizeof(float), hipMemcpyHostToDevice));     // (the packed-FMA form of one cell)
       HIPCHK(h, hipMemcpy(h->img.Nh, nh.data(), nh.size() * sizeof(float), hipMemcpyHostToDevice));
-      {   // the same kernel for the matrix-pipe cell product (DecState::Wc16): rows divided by the factor their input's f16 image
-          // carries (exact: powers of two), one power-of-two scale for the tensor, two f16 parts in B-fragment order per wave
-        auto xs = [&](int k) { return k < RV_U ? h->mx_uscale : 16384.f; };
-        float mx = 0.f;
-        for (int k = 0; k < KR; ++k)
-          for (int n = 0; n < RV_G; ++n) mx = std::max(mx, std::fabs(w2[(size_t)k * RV_G + n] / xs(k)));
-        int ex = 0;
-        if (mx > 0.f && std::isfinite(mx)) std::frexp(mx, &ex);
-        const float T = std::ldexp(1.0f, 14 - ex);
+      {   // the same kernel for the matrix-pipe cell product (DecState::Wc16): two f16 parts in B-fragment order per wave
         h->mx_cdescale = 1.0f / T;
         const int NP = KR / 8;                              // (k-step, gate) pairs per wave: 32, or 48 with two cells
         std::vector<uint16_t> img((size_t)2 * KR * RV_G);
@@ -2218,6 +2297,11 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
                 img[(((((size_t)wv * NP + pr) * 2 + 1) * 64) + ln) * 8 + j] = lb;
               }
         HIPCHK(h, hipMemcpy(h->img.Wc16, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        if (one_part && !two) {   // the first parts alone (the second are zero), [wave][pair][64 lanes][8 f16]: k_dec_persist_1p
+          std::vector<uint16_t> p1((size_t)RV_E * RV_G);
+          for (size_t fr = 0; fr < (size_t)8 * NP; ++fr) memcpy(&p1[fr * 512], &img[fr * 1024], 512 * sizeof(uint16_t));
+          HIPCHK(h, hipMemcpy(h->img.Wc16p1, p1.data(), p1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        }
         if (two) {   // cell 1's kernels on h_0 (W_1) and on h_1 (U_1): DecState::W1c16, rows divided by the 2^14 their inputs' images carry
           const size_t w1 = (size_t)(h->dec[1].W - h->d_w), u1 = (size_t)(h->dec[1].U - h->d_w);
           float m1 = 0.f;
@@ -2242,16 +2326,6 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
           HIPCHK(h, hipMemcpy(h->img.W1c16, i1.data(), i1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
         // the output layer on the same [ctx' | h] image: logits = ctx' . W_fc + h . (A_h W_fc) + b_fc; columns >= V are zero
-        auto wl = [&](int k, int v) -> float {
-          if (v >= V) return 0.f;
-          return (k < RV_U ? blob[fc + (size_t)k * V + v] : nh[(size_t)(k - RV_U) * V + v]) / xs(k);
-        };
-        float ml = 0.f;
-        for (int k = 0; k < RV_E; ++k)
-          for (int v = 0; v < V; ++v) ml = std::max(ml, std::fabs(wl(k, v)));
-        int el = 0;
-        if (ml > 0.f && std::isfinite(ml)) std::frexp(ml, &el);
-        const float Tl = std::ldexp(1.0f, 14 - el);
         h->mx_ldescale = 1.0f / Tl;
         std::vector<uint16_t> li((size_t)2 * RV_E * 16);
         for (int ks = 0; ks < 8; ++ks)
@@ -2265,6 +2339,11 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
               li[(((size_t)ks * 2 + 1) * 64 + ln) * 8 + j] = lb;
             }
         HIPCHK(h, hipMemcpy(h->img.Wl16, li.data(), li.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        if (one_part) {   // its first parts alone, [8 k-steps][64 lanes][8 f16]
+          std::vector<uint16_t> p1((size_t)RV_E * 16);
+          for (int ks = 0; ks < 8; ++ks) memcpy(&p1[(size_t)ks * 512], &li[(size_t)ks * 1024], 512 * sizeof(uint16_t));
+          HIPCHK(h, hipMemcpy(h->img.Wl16p1, p1.data(), p1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        }
         if (!two) {   // Bahdanau's query layer W_q [128][128] for the matrix pipe (DecState::Wq16): one power-of-two scale, two f16 parts, per-wave B fragments
           const size_t qo = (size_t)(h->W_q - h->d_w);
           float mq = 0.f;
@@ -2607,8 +2686,16 @@ int rv_set_option(rv_handle h, const char* key, int32_t value) {
   flush_open_group(h);               // a group still filling was submitted under the options as they were
   if (!strcmp(key, "group_inplace") && value != 0 && value != 1) return fail(h, RV_EINVAL, "group_inplace must be 0 or 1");
   if (!strcmp(key, "group_side_ev") && (value < -1 || value > 1)) return fail(h, RV_EINVAL, "group_side_ev must be -1 (where the hardware queues allow it), 0 or 1");
+  if (!strcmp(key, "weight_parts")) {
+    if (value != 1 && value != 2) return fail(h, RV_EINVAL, "weight_parts must be 2 (each weight as two f16 parts) or 1 (rounded to its first part)");
+    if (uncollected(h)) return fail(h, RV_ESTATE, "collect the calls in flight before setting weight_parts");
+    for (RvContext* k : h->kids) if (k->pend.busy) return fail(h, RV_ESTATE, "collect the calls in flight before setting weight_parts");
+  }
+  if (!strcmp(key, "one_part_kernels") && value != 0 && value != 1) return fail(h, RV_EINVAL, "one_part_kernels must be 0 or 1");
   h->opt.gen++;                      // slab graphs captured under the old options are rebuilt on their next use
-  if (!strcmp(key, "debug_taps")) h->opt.taps = value != 0;
+  if (!strcmp(key, "weight_parts")) h->opt.weight_parts = value;      // (in force from the next rv_load_weights)
+  else if (!strcmp(key, "one_part_kernels")) h->opt.one_part = value;
+  else if (!strcmp(key, "debug_taps")) h->opt.taps = value != 0;
   else if (!strcmp(key, "slab_graph")) h->opt.slab_graph = value != 0;
   else if (!strcmp(key, "coalesce")) {
     if (value < -1 || value > RV_MAX_MEMBERS) return fail(h, RV_EINVAL, "coalesce must be -1 (chosen from async_depth), 0, 1 or 2..%d", RV_MAX_MEMBERS);
@@ -2695,12 +2782,17 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     for (int i = 0; i < 24; ++i) dst[i] = (float)ts[i];
     return RV_OK;
   }
-  else if (!strcmp(name, "kernel_forms") || !strcmp(name, "kernel_form_list")) {
+  else if (!strcmp(name, "kernel_forms") || !strcmp(name, "kernel_form_list") || !strcmp(name, "kernel_form_list_1p") || !strcmp(name, "group_kernel_forms")) {
     FormLog all;
     const FormLog* f = &h->lforms;
     if (!strcmp(name, "kernel_form_list")) {
       list_rec_forms(all); list_mx_forms(all); list_decode_forms(all);
       f = &all;
+    } else if (!strcmp(name, "kernel_form_list_1p")) {
+      list_decode_forms_1p(all);
+      f = &all;
+    } else if (!strcmp(name, "group_kernel_forms")) {
+      f = &h->gforms;
     } else if (!h->lforms_ok) {
       return fail(h, RV_ESTATE, "kernel_forms: the last call replayed a slab graph (option slab_graph), which launches nothing on the host");
     }

@@ -13,6 +13,23 @@
 // RV_WMP16_SLOT (ncb = 1) / RV_WX16_SLOT (ncb = 4) uint16.  Column c = 256 cb + 16 nt + n: lane (n, kq = lane / 16) of tile nt,
 // k-step ks holds s_c W[32 ks + 8 kq + j][c], j = 0..7, part 0 = its f16 rounding, part 1 = the f16 rounding of what that left
 // (s_c W is exact: s_c is the power of two that brings the column's largest |w| into [2^13, 2^14); 2^14 for a zero or non-finite one).
+// The power of two s that brings a column's largest |w| (mx) into [2^13, 2^14); 2^14 for a zero or non-finite one: the scale of every
+// per-column split-f16 image (below, and the Ua / Wh packers of rv_load_weights)
+inline float rv_column_scale(float mx) {
+  int ex = 0;
+  if (mx > 0.f && std::isfinite(mx)) std::frexp(mx, &ex);    // mx = m 2^ex, m in [0.5, 1)
+  return std::ldexp(1.0f, 14 - ex);
+}
+// Option weight_parts 1: one weight rounded to what the first f16 part of its image holds under the image's scale s (a power of two)
+inline float rv_round_to_first_part(float w, float s) { return (float)(_Float16)(w * s) / s; }
+// ... and a column of `rows` elements (stride ld) under its own scale
+inline void rv_round_column(float* w, size_t ld, int rows) {
+  float mx = 0.f;
+  for (int k = 0; k < rows; ++k) mx = std::max(mx, std::fabs(w[(size_t)k * ld]));
+  const float s = rv_column_scale(mx);
+  for (int k = 0; k < rows; ++k) w[(size_t)k * ld] = rv_round_to_first_part(w[(size_t)k * ld], s);
+}
+
 template <class ColOffset>
 inline void rv_pack_split_image(const float* w, size_t ld, int ncb, ColOffset col, uint16_t* img) {
   const size_t block = (size_t)2 * 256 * 256;               // uint16 per column block

@@ -155,6 +155,7 @@ class PerformanceEvaluator:
             "total": t_data_loading + t_predicting + t_postprocessing + t_merge,
             "total_processing": t_predicting + t_postprocessing + t_merge,
             "nuc_preds": nuc_preds, "merged_seq": merged_seq,
+            "weight_parts": int(getattr(self.basecaller, "weight_parts_loaded", 2)),
         }
 
     def _run_window_slabs(self, table, nuc_tk_snippets, bases_num, samples_num, chunk_size, beam_width):
@@ -203,6 +204,7 @@ class PerformanceEvaluator:
             "total": t_data_loading + t_predicting + t_postprocessing + t_merge,
             "total_processing": t_predicting + t_postprocessing + t_merge,
             "nuc_preds": nuc_preds, "merged_seq": merged_seq,
+            "weight_parts": int(getattr(self.basecaller, "weight_parts_loaded", 2)),
         }
 
     # ------------------------------------------------------------------ BASELINE configs 4/5: one read over N GPUs
@@ -255,6 +257,7 @@ class PerformanceEvaluator:
             "t_merge": t_merge, "total": t_predicting + t_gather + t_merge,
             "total_processing": t_predicting + t_gather + t_merge,
             "call_arrays": (g_bases, g_probs, g_lens), "merged_seq": merged_seq,
+            "weight_parts": int(getattr(self.basecaller, "weight_parts_loaded", 2)),
         }
 
     def decode_range(self, raw_snippets, event_snippets, lo: int, hi: int, max_output_len: int, chunk_size: int = 1024,
@@ -315,6 +318,7 @@ class PerformanceEvaluator:
             "t_data_loading": t_data_loading, "t_predicting": t_predicting, "t_postprocessing": 0.0, "t_merge": t_merge,
             "total": t_data_loading + t_predicting + t_merge, "total_processing": t_predicting + t_merge,
             "nuc_preds": nuc_preds, "merged_seq": merged_seq,
+            "weight_parts": int(getattr(self.basecaller, "weight_parts_loaded", 2)),
         }
 
     def run_many(self, reads, chunk_size: int = 1024, beam_width: int = 5, max_output_len: int | None = None,

@@ -84,6 +84,24 @@ def unpack(cfg: RvConfig, blob: np.ndarray) -> dict:
     return flat
 
 
+def rounded_view(cfg: RvConfig, flat: dict) -> dict:
+    """The flat dict with its blob-level tensors rounded as option ``weight_parts`` 1 rounds them (``rv_round_weights``, the code the
+    loader runs; no device): ``U`` of every encoder layer and direction, ``W`` of encoder layers >= 1, ``W_mem`` and rows u..3u-1 of
+    ``W_att``, each column to ``float16(w s) / s`` under the power of two ``s`` that brings the column's largest |w| into
+    [2^13, 2^14).  Every other tensor is returned as it is.  The decoder's folded kernels are rounded after their fold, inside the
+    loader, so this view is the model the encoder and the attention memory compute exactly and the decode computes to that rounding."""
+    import ctypes
+    from . import _capi
+    lib = _capi.load_library()
+    blob = pack(cfg, flat)
+    out = np.empty_like(blob)
+    ccfg = cfg.to_c()
+    rc = lib.rv_round_weights(ctypes.byref(ccfg), blob.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p), blob.size)
+    if rc != 0:
+        raise ValueError(f"rv_round_weights failed ({rc}): the configuration or the blob's size is not one the library accepts")
+    return unpack(cfg, out)
+
+
 def save(path: str, cfg: RvConfig, flat: dict) -> None:
     np.savez(path, **{k: np.asarray(v, np.float32) for k, v in flat.items()})
 
