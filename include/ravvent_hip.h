@@ -80,12 +80,24 @@ int rv_abi_version(void);
 
 /* Basecaller.__init__: allocates every device buffer, streams and graphs for the max shapes. */
 int rv_create(const RvConfig* cfg, rv_handle* out);
+/* The same for a cell family of the reference's rnn_type (basecaller.py:18-46, 85-89).  rv_create means RV_RNN_BILSTM.
+ * RV_RNN_BIGRU: Bidirectional GRUCell encoders and a StackedRNNCells(GRUCell) decoder, Keras defaults (reset_after = True, gates
+ * z, r, h): every cell of the blob is W[F,3u] U[u,3u] b[2,3u] (ravvent-basecaller_amd/weights.py).  Added without changing an
+ * existing entry point or RvConfig: RV_ABI_VERSION stays at 1.  A GRU handle serves every mode, both attentions, enc_depth 1..8,
+ * dec_depth 1..4, beam 1..8 and greedy search, the whole beam, teacher-forced scoring, moves, the asynchronous calls (never
+ * coalesced), window calls (behind k_expand_windows) and the debug taps.  Its encoders run k_gru_rec_mx (matrix pipe, sixteen
+ * chunks per workgroup) and its decode the per-step kernels with k_dec_cell_gru as the cell; there is no persistent GRU decode.
+ * rv_set_option on such a handle fails with RV_EUNSUPPORTED for "weight_parts" 1, "wide_recurrence" other than 1,
+ * "lane_projection" 0 and "slab_graph" 1 (no GRU kernel stands behind them); options that only pick LSTM forms or configure the
+ * persistent decode are accepted and do nothing.  Any other value of `rnn` fails with RV_EUNSUPPORTED. */
+enum { RV_RNN_BILSTM = 0, RV_RNN_BIGRU = 1 };
+int rv_create_rnn(const RvConfig* cfg, int32_t rnn, rv_handle* out);
 void rv_destroy(rv_handle h);
 
 /* Message of the last failing call on this handle (h == NULL: last rv_create failure). */
 const char* rv_last_error(rv_handle h);
 
-/* Number of fp32 values rv_load_weights expects for this handle's config. */
+/* Number of fp32 values rv_load_weights expects for this handle's config and cell family. */
 size_t rv_weight_count(rv_handle h);
 
 /* Basecaller.load_weights (ravvent_performance_evaluator.py:107): flat little-endian fp32
@@ -436,10 +448,13 @@ int rv_set_option(rv_handle h, const char* key, int32_t value);
  *   "kernel_forms"    [n,5]       the kernel instantiations the handle's own context launched in its last call, each once, as rows
  *                                 (kernel, p1, p2, p3, p4), unused parameters 0: kernel 0 k_dec_persist (W, NIT, D, ATT), 1 k_dec_attend_flash
  *                                 (W, NT), 2 k_dec_attend (W, TB), 3 k_lstm_rec (BT, F), 4 k_lstm_rec_tw (BT, F), 5 k_lstm_rec_proj (BT, SB),
- *                                 6 k_lstm_rec_mx (F, CH), 7 k_inproj_small (F).  Noted by the walk of each kernel's form list that launches
+ *                                 6 k_lstm_rec_mx (F, CH), 7 k_inproj_small (F), 8 k_dec_persist_1p (below), 9 k_gru_rec_mx (F, CH),
+ *                                 10 k_dec_cell_gru (no parameters), the last two on a GRU handle only.  Noted by the walk of each kernel's form list that launches
  *                                 it; a per-step decode replayed from its captured hipGraph reports the forms of the capture.  After a call
  *                                 that ran as a slab graph (option "slab_graph") it fails with RV_ESTATE
- *   "kernel_form_list" [n,5]      every instantiation the form lists hold, in the same rows, whatever the last call was
+ *   "kernel_form_list" [n,5]      every instantiation the form lists hold, in the same rows, whatever the last call was.  It answers for
+ *                                 the handle's family: a BiLSTM handle lists what it always did; a GRU handle (rv_create_rnn) lists the
+ *                                 k_gru_rec_mx forms and k_dec_cell_gru in place of the LSTM recurrences and the persistent decode
  *   "kernel_form_list_1p" [n,5]   the one-part forms of the persistent decode (option "weight_parts" 1), a list of their own: rows
  *                                 (8, W, NIT, 1, ATT) for k_dec_persist_1p<W, NIT, ATT>.  "kernel_forms" reports a launched one under
  *                                 the same kernel id 8

@@ -40,6 +40,7 @@ _M = POINTER(CRvMoves)
 SYMBOLS = [
     ("rv_abi_version", c_int32, []),
     ("rv_create", c_int32, [POINTER(CRvConfig), POINTER(c_void_p)]),
+    ("rv_create_rnn", c_int32, [POINTER(CRvConfig), c_int32, POINTER(c_void_p)]),
     ("rv_destroy", None, [c_void_p]),
     ("rv_last_error", c_char_p, [c_void_p]),
     ("rv_weight_count", c_size_t, [c_void_p]),

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _capi, data_loader as _dl, weights as _weights
-from .config import RvConfig, RAW_FEATURES, EVENT_FEATURES
+from .config import RvConfig, RAW_FEATURES, EVENT_FEATURES, RNNS
 from .data_loader import _ASCII, nuc_tk, tokens_to_strings
 
 
@@ -95,13 +95,17 @@ class Basecaller:
         (basecaller.py:158).  Keyword-only extras size device memory (``max_beam``: the widest beam
         the handle will be asked for, 1..8).
 
+        ``rnn_type``: 'bilstm' (BiLSTM encoders, LSTM decoder cells) or 'bigru' (BiGRU encoders, GRU decoder cells; Keras GRUCell
+        defaults, DESIGN.md section 15 -- served on the per-step decode).  'lstm' and 'gru' raise NotImplementedError.
+
         The reference hard-codes Luong attention when it builds its Decoder
         (basecaller.py:194) and only stores ``attention_type`` (:201); that behaviour is kept
         unless ``honor_attention_type=True`` selects the Bahdanau mechanism that
         ``Decoder(attention_type='bahdanau')`` builds (basecaller.py:131-132)."""
-        if rnn_type != "bilstm":
+        if rnn_type not in ("bilstm", "bigru"):
             raise NotImplementedError(
-                f"rnn_type={rnn_type!r}: only the BiLSTM encoder / LSTM decoder of the north-star path is built")
+                f"rnn_type={rnn_type!r}: the bidirectional families are built ('bilstm': BiLSTM encoder / LSTM decoder; 'bigru': "
+                f"BiGRU encoder / GRU decoder), the unidirectional ones are not")
         if input_data_type not in ("raw", "event", "joint"):
             raise ValueError(f"input_data_type {input_data_type!r}")
         self.batch_sz = batch_sz
@@ -127,17 +131,25 @@ class Basecaller:
             start_token=int(self.output_start_token), end_token=int(self.output_end_token),
             pad_token=int(self.output_padding_token), padding_value=float(input_padding_value),
             max_batch=max_batch, max_raw_len=max_raw_len, max_event_len=max_event_len,
-            max_output_len=max_output_len, max_beam=int(max_beam), device=device)
+            max_output_len=max_output_len, max_beam=int(max_beam), device=device, rnn=rnn_type)
         self.device = torch.device("cuda", device)
         self._lib = _capi.load_library()
-        self._h = ctypes.c_void_p()
-        ccfg = self.cfg.to_c()
-        rc = self._lib.rv_create(ctypes.byref(ccfg), ctypes.byref(self._h))
-        _capi.check(self._lib, None, rc, "rv_create")
+        self._h = self._create_handle()
         self.optimizer = None
         self._weight_parts = 2
 
     # ------------------------------------------------------------------ lifecycle
+    def _create_handle(self):
+        """A handle of this configuration's cell family: rv_create for the BiLSTM, rv_create_rnn for every other one."""
+        h = ctypes.c_void_p()
+        ccfg = self.cfg.to_c()
+        if self.cfg.rnn == "bilstm":
+            rc, what = self._lib.rv_create(ctypes.byref(ccfg), ctypes.byref(h)), "rv_create"
+        else:
+            rc, what = self._lib.rv_create_rnn(ctypes.byref(ccfg), RNNS[self.cfg.rnn], ctypes.byref(h)), "rv_create_rnn"
+        _capi.check(self._lib, None, rc, what)
+        return h
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self._lib.rv_destroy(self._h)
@@ -172,10 +184,7 @@ class Basecaller:
         for k, v in self.__dict__.items():
             if k not in ("_h", "_outs"):
                 setattr(other, k, v)
-        other._h = ctypes.c_void_p()
-        ccfg = self.cfg.to_c()
-        rc = self._lib.rv_create(ctypes.byref(ccfg), ctypes.byref(other._h))
-        _capi.check(self._lib, None, rc, "rv_create")
+        other._h = self._create_handle()
         # the mode travels with the clone: its images are built in the mode this handle's were LOADED in, and its option then says
         # what this handle's option says (the two differ after set_option("weight_parts", n) without a reload)
         loaded = getattr(self, "_parts_loaded", 2)

@@ -381,6 +381,9 @@ def flat_from_tensors(tensors: dict, cfg: RvConfig) -> dict:
             if not np.array_equal(flat[name], np.asarray(arr, np.float32)):
                 raise ValueError(f"{name}: keys {seen[name]!r} and {key!r} disagree")
             continue
+        if cfg.rnn == "bigru" and name.endswith(".b") and len(layout[name]) == 2 and tuple(arr.shape) == (layout[name][1],):
+            raise ValueError(f"{key}: bias of shape {tuple(arr.shape)} is a GRU built with reset_after=False, which is unsupported: "
+                             f"{name} needs {tuple(layout[name])} (reset_after=True: input and recurrent bias rows)")
         if tuple(arr.shape) != tuple(layout[name]):
             raise ValueError(f"{key}: shape {tuple(arr.shape)}, the configured model needs {tuple(layout[name])} for {name}")
         flat[name], seen[name] = np.asarray(arr, np.float32), key
@@ -403,7 +406,7 @@ def is_tf_checkpoint(path: str) -> bool:
 
 
 def main(argv=None):
-    """python -m ravvent_basecaller_amd.checkpoint manifest [out.json] | convert <tf_prefix> <out.npz> [enc_depth dec_depth mode]"""
+    """python -m ravvent_basecaller_amd.checkpoint manifest [out.json] | convert <tf_prefix> <out.npz> [enc_depth dec_depth mode rnn]"""
     import sys
     argv = list(sys.argv[1:] if argv is None else argv)
     if argv and argv[0] == "manifest":
@@ -417,7 +420,7 @@ def main(argv=None):
         return 0
     if argv and argv[0] == "convert" and len(argv) >= 3:
         cfg = RvConfig(enc_depth=int(argv[3]) if len(argv) > 3 else 2, dec_depth=int(argv[4]) if len(argv) > 4 else 1,
-                       mode=argv[5] if len(argv) > 5 else "joint")
+                       mode=argv[5] if len(argv) > 5 else "joint", rnn=argv[6] if len(argv) > 6 else "bilstm")
         _weights.save(argv[2], cfg, flat_from_checkpoint(argv[1], cfg))
         return 0
     print(main.__doc__)

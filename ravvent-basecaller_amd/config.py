@@ -12,6 +12,8 @@ from dataclasses import dataclass
 
 MODE_RAW, MODE_EVENT, MODE_JOINT = 0, 1, 2
 ATT_LUONG, ATT_BAHDANAU = 0, 1
+RNN_BILSTM, RNN_BIGRU = 0, 1
+RNNS = {"bilstm": RNN_BILSTM, "bigru": RNN_BIGRU}
 MODES = {"raw": MODE_RAW, "event": MODE_EVENT, "joint": MODE_JOINT}
 ATTENTIONS = {"luong": ATT_LUONG, "bahdanau": ATT_BAHDANAU}
 
@@ -61,6 +63,7 @@ class RvConfig:
     max_output_len: int = 64
     max_beam: int = 8
     device: int = 0
+    rnn: str = "bilstm"            # cell family: 'bilstm' (rv_create) or 'bigru' (rv_create_rnn); travels beside the C record, not in it
 
     def to_c(self) -> CRvConfig:
         return CRvConfig(

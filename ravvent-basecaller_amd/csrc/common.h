@@ -25,6 +25,8 @@ enum {
   RV_K_LSTM_REC_MX = 6,        // k_lstm_rec_mx<F, CH>
   RV_K_INPROJ_SMALL = 7,       // k_inproj_small<F>
   RV_K_DEC_PERSIST_1P = 8,     // k_dec_persist_1p<W, NIT, ATT>: (W, NIT, 1, ATT); launched under option weight_parts 1 only
+  RV_K_GRU_REC_MX = 9,         // k_gru_rec_mx<F, CH> (a GRU handle only: rv_create_rnn)
+  RV_K_DEC_CELL_GRU = 10,      // k_dec_cell_gru: no parameters
 };
 #define RV_FORM_ROWS 512
 struct FormLog {
@@ -117,6 +119,37 @@ hipError_t configure_rec_kernels();   // dynamic-LDS opt-in of the recurrence ke
 // layer 0 stages its chunks' whole input windows in LDS: does a window of T steps x F features fit with that many rows per workgroup?
 bool lstm_rec_window_fits(int F, int rows_per_block, int T);
 
+// ---------------------------------------------------------------- K1g / D1g: the BiGRU family (gru_mx.hip)
+#define RV_GG 384         // 3 gates (z, r, h) x RV_U
+// Arguments of k_gru_rec_mx, a struct of its own: RecArgs travels by value into every LSTM recurrence kernel and stays as it is.
+struct GruRecArgs {
+  const float* x;          // F>0: chunk input [B,T,F];  F==0: pre-projected xw [B,T,2,384] = x . W + b[0]
+  const float* W[2];       // F>0: input kernel [F,384] per direction
+  const float* b[2];       // [2,384] per direction: row 0 the input bias (read by the F > 0 forms), row 1 the recurrent bias (every form)
+  const uint16_t* Ua[2];   // U^T as MFMA A fragments, [8 waves][3 gates][4 k-steps][2 parts][64 lanes][8 f16] of the column-scaled kernel,
+                           // then 384 floats 2^-14 / s_r (RV_GRU_UA_SLOT uint16 per direction)
+  const float* h0[2];      // initial state [B,128] or nullptr (zeros); |h0| <= 1
+  float* hT[2];            // final state [B,128]
+  float* out;              // [B,out_T,256]; direction d writes columns [128d,128d+128) at time out_t0+t
+  int out_T, out_t0;
+  int B, T;
+  uint8_t* mask;           // F>0: also leaves utils.input_mask of its chunks at mask[b * mask_T + mask_t0 + t]; null = not asked for
+  int mask_T, mask_t0;
+  float pad;
+};
+#define RV_GRU_UA_SLOT ((size_t)2 * RV_U * RV_GG + 2 * RV_GG)
+// the split GEMM's image of a [256 x 768] input kernel (both directions, three column blocks of 256) and its 768 column factors
+#define RV_GRU_WX16_SLOT ((size_t)2 * RV_E * 2 * RV_GG + 2 * 2 * RV_GG)
+void list_gru_forms(FormLog& log);
+hipError_t configure_gru_kernels();
+bool gru_rec_mx_window_fits(int T, int F);     // layer 0: do the input windows of a workgroup's sixteen chunks fit in LDS?
+void launch_gru_rec_mx(const GruRecArgs& a, int F, hipStream_t s, FormLog* log = nullptr);   // F in {0, 1, 5}
+struct DecState;
+// the GRU cell of the per-step decode, where launch_dec_cell launches k_dec_cell: WcatT [512,256] = column tiles z, r, [W_h ; 0],
+// [0 ; U_h] of ([W_in ; U])^T, Wtok [V,384] (cell 0's one-hot rows, null for the cells above), bias [2,384]
+void launch_dec_cell_gru(const DecState& d, int layer, const float* WcatT, const float* Wtok, const float* bias, int step, hipStream_t s,
+                         FormLog* log = nullptr);
+
 // ---------------------------------------------------------------- K0/K2: fp32 MFMA GEMM
 struct GemmArgs {
   const float* A; int lda;     // [M,K]
@@ -141,7 +174,8 @@ void launch_gemm_mem_split(const float* A, int M, const uint16_t* img, float* C,
 // The same kernel over `ncb` column blocks of 256: C[M, ldc] (columns 256 cb ..) = A[M,256] . W_cb[256,256] (+ bias[256 cb ..]);
 // img = [ncb][8 k-steps][16 tiles][2 parts][64 lanes][8 f16], then 256 ncb floats 2^-14 / s_n.  A workgroup takes the ncb blocks of a
 // row tile one after the other, so A comes from HBM once.  The input projection of encoder layers >= 1 for the matrix-pipe
-// recurrence: ncb = 4 (two directions x 512 gate columns), ldc = 1024, bias = [b_fwd | b_bwd].
+// recurrence: ncb = 4 (two directions x 512 gate columns), ldc = 1024, bias = [b_fwd | b_bwd]; of the BiGRU family: ncb = 3 (two
+// directions x 384), ldc = 768 (RV_GRU_WX16_SLOT), on the weight-stationary form only.
 #define RV_WX16_SLOT ((size_t)2 * RV_E * 2 * RV_G + 2 * 2 * RV_G)
 hipError_t configure_gemm_kernels();   // dynamic-LDS opt-in of the weight-stationary split GEMM
 void launch_gemm_split_blocks(const float* A, int M, const uint16_t* img, int ncb, const float* bias, float* C, int ldc, hipStream_t s);

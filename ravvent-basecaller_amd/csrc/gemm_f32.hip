@@ -494,7 +494,8 @@ void launch_gemm_split_blocks(const float* A, int M, const uint16_t* img, int nc
 #endif
   // ncb == 1 (the attention-memory projection, N = 256) stays on form (3): with two column halves a workgroup would load its 128 KB of
   // weights for some twenty 32-row tiles, and the load shows (0.056 vs 0.052 ms at C3)
-  if (!old_form && !dbg && ncb > 1) {
+  // (ncb == 3, the BiGRU family's [256 x 768] input kernel, has this form alone: the diagnostic switches above do not apply to it)
+  if ((!old_form && !dbg && ncb > 1) || ncb == 3) {
     // row groups: 8 k with 8 k x 2 ncb ~ 256 workgroups, but no more groups than there is work for their waves
     const int nch = 2 * ncb, ntile = (M + 31) / 32, nw = RV_WS_THREADS / 64;
     int k = 256 / (8 * nch);
@@ -506,7 +507,7 @@ void launch_gemm_split_blocks(const float* A, int M, const uint16_t* img, int nc
   const dim3 grid(nt128 < 256 ? nt128 : 256), block(384);
   if (ncb == 1) hipLaunchKernelGGL(k_gemm_mem_split3<1>, grid, block, 0, s, A, M, img, C, nt128, dbg, ldc, bias);
   else if (ncb == 4) hipLaunchKernelGGL(k_gemm_mem_split3<4>, grid, block, 0, s, A, M, img, C, nt128, dbg, ldc, bias);
-  else abort();   // (internal: 1 = attention memory, 4 = both directions of an encoder layer)
+  else abort();   // (internal: 1 = attention memory, 4 = both directions of a BiLSTM layer; 3 = of a BiGRU layer never gets here)
 }
 void launch_gemm_mem_split(const float* A, int M, const uint16_t* img, float* C, hipStream_t s) {
   launch_gemm_split_blocks(A, M, img, 1, nullptr, C, RV_E, s);

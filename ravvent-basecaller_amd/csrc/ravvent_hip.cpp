@@ -97,6 +97,11 @@ struct WeightImages {
   uint16_t* Wmp16 = nullptr;                // Wmp as two f16 parts in MFMA fragment order + column factors (launch_gemm_mem_split)
   uint16_t* Wkp16 = nullptr;                // the W_mem half of those parts, columns permuted into key-tile rows (DecState::Wkp16)
   float* WcatT = nullptr;                   // ([W_dec[V:] ; U_dec])^T, [512][256]
+  // a GRU handle (rv_create_rnn, RV_RNN_BIGRU) holds these and WmemT alone
+  uint16_t* gUa = nullptr;                  // recurrent kernels as MFMA A fragments + column factors, [enc][layer][dir][RV_GRU_UA_SLOT]
+  uint16_t* gWx16 = nullptr;                // input kernels of encoder layers >= 1, both directions, as three B slabs of the split GEMM, [enc][layer-1][RV_GRU_WX16_SLOT]
+  float* gbx = nullptr;                     // [b[0]_fwd | b[0]_bwd] of those layers, [enc][layer-1][768]
+  float* gWcatT = nullptr;                  // decoder cells for k_dec_cell_gru: column tiles z, r, [W_h ; 0], [0 ; U_h] of ([W_in ; U])^T, [cell][512][256]
 };
 
 // What a recording leaves behind for rv_get_tensor beside lB .. lptaps; a slab graph stores them at its capture and puts them back at every replay
@@ -161,6 +166,7 @@ struct CallParts {
 
 struct RvContext {
   RvConfig cfg{};
+  int rnn = RV_RNN_BILSTM;                  // cell family (rv_create_rnn); a child context takes its parent's
   hipStream_t stream = nullptr;
   std::string err;
   std::vector<void*> allocs;
@@ -342,17 +348,19 @@ inline float bf16_value(uint16_t b) {
   return x;
 }
 
-size_t weight_count(const RvConfig& c) {
+// Per cell of the blob: W[F, G u]  U[u, G u]  b[NB, G u] -- LSTM: G = 4 gates, one bias row; GRU: G = 3, input and recurrent bias rows
+size_t weight_count(const RvConfig& c, int rnn = RV_RNN_BILSTM) {
   const size_t u = c.enc_units, d = c.dec_units, V = c.vocab;
+  const size_t G = rnn == RV_RNN_BIGRU ? 3 : 4, NB = rnn == RV_RNN_BIGRU ? 2 : 1;
   size_t n = 0;
   for (int e = 0; e < 2; ++e)
     for (int l = 0; l < c.enc_depth; ++l) {
       const size_t F = l > 0 ? 2 * u : (e == 0 ? 1 : 5);
-      n += 2 * (F * 4 * u + u * 4 * u + 4 * u);
+      n += 2 * (F * G * u + u * G * u + NB * G * u);
     }
   for (int k = 0; k < c.dec_depth; ++k) {
     const size_t fin = k == 0 ? V + d : d;
-    n += fin * 4 * d + d * 4 * d + 4 * d;
+    n += fin * G * d + d * G * d + NB * G * d;
   }
   n += 2 * u * d + d * d + d + (d + 2 * u) * d + d * V + V;
   return n;
@@ -361,6 +369,7 @@ size_t weight_count(const RvConfig& c) {
 void bind_weights(RvContext* h) {
   const RvConfig& c = h->cfg;
   const size_t u = c.enc_units, d = c.dec_units, V = c.vocab;
+  const size_t G = h->rnn == RV_RNN_BIGRU ? 3 : 4, NB = h->rnn == RV_RNN_BIGRU ? 2 : 1;      // (weight_count)
   const float* p = h->d_w;
   for (int e = 0; e < 2; ++e) {
     h->enc[e].assign(c.enc_depth, std::vector<LstmW>(2));
@@ -368,17 +377,17 @@ void bind_weights(RvContext* h) {
       const size_t F = l > 0 ? 2 * u : (e == 0 ? 1 : 5);
       for (int dr = 0; dr < 2; ++dr) {
         LstmW& w = h->enc[e][l][dr];
-        w.W = p; p += F * 4 * u;
-        w.U = p; p += u * 4 * u;
-        w.b = p; p += 4 * u;
+        w.W = p; p += F * G * u;
+        w.U = p; p += u * G * u;
+        w.b = p; p += NB * G * u;
       }
     }
   }
   h->dec.assign(c.dec_depth, LstmW{});
   for (int k = 0; k < c.dec_depth; ++k) {
-    h->dec[k].W = p; p += (k == 0 ? V + d : d) * 4 * d;
-    h->dec[k].U = p; p += d * 4 * d;
-    h->dec[k].b = p; p += 4 * d;
+    h->dec[k].W = p; p += (k == 0 ? V + d : d) * G * d;
+    h->dec[k].U = p; p += d * G * d;
+    h->dec[k].b = p; p += NB * G * d;
   }
   h->W_mem = p; p += 2 * u * d;
   h->W_q = p; p += d * d;
@@ -492,8 +501,46 @@ bool lane_layer0(const RvContext* h, int F, int T) {
   return F == 1 || (F == 5 && h->opt.lane_inproj && lstm_rec_mx_window_fits(T, 5));
 }
 
+// Encoder.call of a GRU handle: k_gru_rec_mx on every layer.  Layer 0 takes x . W + b[0] in the lane and leaves the input mask; layers
+// >= 1 read xw [B,T,2,384] from the split-f16 GEMM over three column blocks (both directions and their input biases in one launch).
+// State sets hold h only: layer l + 1 starts from layer l's two final states.
+void run_gru_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int Tm, int t_off, hipStream_t s, int l_begin, int l_end) {
+  const int depth = h->cfg.enc_depth;
+  for (int l = std::max(l_begin, 0); l < std::min(depth, l_end); ++l) {
+    const bool last = l == depth - 1;
+    GruRecArgs a{};
+    a.B = B; a.T = T;
+    a.out = last ? h->enc_out : h->act[e][l & 1]; a.out_T = last ? Tm : T; a.out_t0 = last ? t_off : 0;
+    const int rd = (l & 1) ^ 1, wr = l & 1;     // state sets: layer l reads set rd, writes set wr
+    for (int dr = 0; dr < 2; ++dr) {
+      const LstmW& w = h->enc[e][l][dr];
+      a.W[dr] = w.W; a.b[dr] = w.b;
+      a.Ua[dr] = h->img.gUa + ((size_t)(e * depth + l) * 2 + dr) * RV_GRU_UA_SLOT;
+      a.h0[dr] = l > 0 ? h->st[e][rd][2 * dr] : nullptr;
+      a.hT[dr] = h->st[e][wr][2 * dr];
+    }
+    if (l == 0) {
+      a.x = x;
+      a.mask = h->mask; a.mask_T = Tm; a.mask_t0 = t_off; a.pad = h->cfg.padding_value;
+      Scope sc(h, F == 1 ? "gru_rec_raw_l0" : "gru_rec_event_l0", s);
+      launch_gru_rec_mx(a, F, s, &h->lforms);
+      continue;
+    }
+    {
+      const size_t slot = (size_t)(e * (depth - 1) + (l - 1));
+      Scope sc(h, e == 0 ? "gemm_inproj_raw" : "gemm_inproj_event", s);
+      launch_gemm_split_blocks(h->act[e][(l - 1) & 1], B * T, h->img.gWx16 + slot * RV_GRU_WX16_SLOT, 3, h->img.gbx + slot * 2 * RV_GG, h->xw[e],
+                               2 * RV_GG, s);
+    }
+    a.x = h->xw[e];
+    Scope sc(h, e == 0 ? "gru_rec_raw_l1p" : "gru_rec_event_l1p", s);
+    launch_gru_rec_mx(a, 0, s, &h->lforms);
+  }
+}
+
 void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int Tm, int t_off, hipStream_t s,
                  int l_begin = 0, int l_end = 1 << 30, const void* const* ptab = nullptr, const RecWindow* windows = nullptr) {
+  if (h->rnn == RV_RNN_BIGRU) return run_gru_encoder(h, e, x, F, B, T, Tm, t_off, s, l_begin, l_end);      // (never with ptab or windows: enqueue)
   const int depth = h->cfg.enc_depth;
   const int bt = pick_rows_per_block(B);
   for (int l = std::max(l_begin, 0); l < std::min(depth, l_end); ++l) {
@@ -602,6 +649,12 @@ void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool pr
   if (moves_aside) ds.step_align = nullptr;
   auto cells = [&](int step, bool prof) {
     for (int k = 0; k < d.depth; ++k) {
+      if (h->rnn == RV_RNN_BIGRU) {
+        const float* Wg = h->img.gWcatT + (size_t)k * RV_G * RV_E;
+        if (prof) { Scope sc(h, "dec_cell_gru"); launch_dec_cell_gru(d, k, Wg, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s, log); }
+        else launch_dec_cell_gru(d, k, Wg, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s, log);
+        continue;
+      }
       const float* WcatT = h->img.WcatT + (size_t)k * RV_G * RV_E;
       if (prof) { Scope sc(h, "dec_cell"); launch_dec_cell(d, k, WcatT, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s); }
       else launch_dec_cell(d, k, WcatT, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s);
@@ -622,6 +675,7 @@ void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool pr
 
 // The form of the one-launch persistent decode this call takes (dec_persist_form), or -1: the per-step kernels
 int persist_form(const RvContext* h, bool greedy, int W, int Tm, bool forced) {
+  if (h->rnn != RV_RNN_BILSTM) return -1;                // (a GRU handle decodes per step: no persistent GRU kernel)
   if (!h->opt.persist || !h->opt.flash || h->opt.taps) return -1;
   const RvConfig& c = h->cfg;
   if (forced && c.vocab >= RV_MAX_VOCAB) return -1;      // (a forced decode keeps a bias-only row behind the vocabulary's in the resident token table)
@@ -699,8 +753,9 @@ int enqueue(RvContext* h, const Call& stated, const CallParts& res) {
   if (!dev_out || !call.out2) call.out2 = h->out2;
 
   const int form_B = res.form_B >= 0 ? res.form_B : B;      // a group takes the forms its first member would have got alone
-  h->lwide = wide_recurrence(h, form_B, T_r) ? 1 : 0;
-  h->lrows8 = h->lwide && rows8_wanted(h, form_B) ? 1 : 0;
+  const bool gru = h->rnn == RV_RNN_BIGRU;               // its one recurrence is the sixteen-chunk matrix-pipe kernel, whatever the slab
+  h->lwide = gru || wide_recurrence(h, form_B, T_r) ? 1 : 0;
+  h->lrows8 = !gru && h->lwide && rows8_wanted(h, form_B) ? 1 : 0;
   const bool windowed = call.windows != nullptr;
   if (windowed) {
     // The table goes to this context's pinned staging now (a group's rows are there already: submit_group); its device copy is the first
@@ -968,7 +1023,7 @@ int split_decode(RvContext* h, Slab& sl) {
   if (!h->fact.lpersist) {
     for (int k = 0; k < d.depth; ++k) {     // get_initial_state: all zeros (basecaller.py:305); the persistent kernel keeps state in LDS
       HIPCHK(h, hipMemsetAsync(d.xh + k * d.ls_xh, 0, sizeof(float) * N * RV_E, s));
-      HIPCHK(h, hipMemsetAsync(d.c + k * d.ls_c, 0, sizeof(float) * N * RV_U, s));
+      if (h->rnn == RV_RNN_BILSTM) HIPCHK(h, hipMemsetAsync(d.c + k * d.ls_c, 0, sizeof(float) * N * RV_U, s));      // (a GRU cell has no c)
     }
   }
   const int Wd = d.W;
@@ -1491,10 +1546,10 @@ int alloc_slab_buffers(RvContext* h) {
   if (use_ev) TRY(dalloc(h, &h->xw[1], B * Te * 2 * RV_G));
   for (int e = 0; e < 2; ++e)
     for (int st = 0; st < 2; ++st)
-      for (int k = 0; k < 4; ++k) TRY(dalloc(h, &h->st[e][st][k], B * RV_U));
+      for (int k = 0; k < 4; k += h->rnn == RV_RNN_BIGRU ? 2 : 1) TRY(dalloc(h, &h->st[e][st][k], B * RV_U));      // (a GRU's sets hold h only)
   TRY(dalloc(h, &h->enc_out, B * Tm * RV_E));
   TRY(dalloc(h, &h->keys, B * Tm * RV_U));
-  TRY(dalloc(h, &h->mem2, B * Tm * RV_E));
+  if (h->rnn == RV_RNN_BILSTM) TRY(dalloc(h, &h->mem2, B * Tm * RV_E));      // (the persistent decode's projected memory)
   DecState& d = h->dec_st;
 #ifdef RV_DIAG   // timing ablations that INVALIDATE results: only in `make diag` builds (libravvent_hip_diag.so), never in the product library
   if (const char* e = getenv("RV_ATT_STOP")) d.dbg_stop = atoi(e);
@@ -1552,6 +1607,7 @@ int create_child(RvContext* p, RvContext** out, int slabs = 1) {
   h->cfg = p->cfg;
   h->cfg.max_batch *= slabs;                // (a group context of the coalesced calls: room for `slabs` slabs back to back)
   h->parent = p;
+  h->rnn = p->rnn;
   // (stream priorities -- the contexts at the runtime's three levels in turn, so that slabs submitted together leave lockstep -- measured
   //  no gain at the driver's 20 steps and 4 % less once the stream has settled: tools/stream_ab.py, round 4)
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return fail(p, RV_EHIP, "hipStreamCreate failed for an asynchronous context"); }
@@ -1916,6 +1972,90 @@ int put_read(RvContext* h, const float* raw, size_t n_raw, const float* event, s
   return RV_OK;
 }
 
+// The device images of a GRU handle (rv_load_weights), from the host blob: every cell W[F,384] U[128,384] b[2,384], gates z, r, h
+int load_gru_images(RvContext* h, const float* blob) {
+  const RvConfig& c = h->cfg;
+  // recurrent kernels as MFMA A fragments of U^T for k_gru_rec_mx: wave w, gate g, k-step ks, part p, lane (m = lane % 16, kq = lane / 16)
+  // holds s_r U[32 ks + 8 kq + j][r], r = 128 g + 16 w + m (s_r: rv_column_scale of the column), then the 384 factors 2^-14 / s_r
+  for (int e = 0; e < 2; ++e)
+    for (int l = 0; l < c.enc_depth; ++l)
+      for (int dr = 0; dr < 2; ++dr) {
+        const size_t off = (size_t)(h->enc[e][l][dr].U - h->d_w);
+        std::vector<uint16_t> ua(RV_GRU_UA_SLOT);
+        float cs[RV_GG];
+        for (int r = 0; r < RV_GG; ++r) {
+          float mx = 0.f;
+          for (int k = 0; k < RV_U; ++k) mx = std::max(mx, std::fabs(blob[off + (size_t)k * RV_GG + r]));
+          cs[r] = rv_column_scale(mx);
+        }
+        for (int w = 0; w < 8; ++w)
+          for (int g = 0; g < 3; ++g)
+            for (int ks = 0; ks < 4; ++ks)
+              for (int ln = 0; ln < 64; ++ln)
+                for (int j = 0; j < 8; ++j) {
+                  const int r = g * RV_U + 16 * w + (ln & 15);
+                  const float v = blob[off + (size_t)(32 * ks + 8 * (ln >> 4) + j) * RV_GG + r] * cs[r];   // exact
+                  const _Float16 hi = (_Float16)v;
+                  const _Float16 lo = (_Float16)(v - (float)hi);
+                  uint16_t hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
+                  const size_t base = ((((size_t)w * 3 + g) * 4 + ks) * 2) * 64 * 8;
+                  ua[base + (size_t)ln * 8 + j] = hb;
+                  ua[base + 64 * 8 + (size_t)ln * 8 + j] = lb;
+                }
+        for (int r = 0; r < RV_GG; ++r) { const float f = std::ldexp(1.0f, -14) / cs[r]; memcpy(&ua[(size_t)2 * RV_U * RV_GG + 2 * r], &f, 4); }
+        HIPCHK(h, hipMemcpy(h->img.gUa + ((size_t)(e * c.enc_depth + l) * 2 + dr) * RV_GRU_UA_SLOT, ua.data(), ua.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+      }
+  // encoder layers >= 1: the [256 x 768] input kernel of both directions ([fwd z r h | bwd z r h]) as three column blocks of the split
+  // GEMM (rv_pack_split_image: the kernel and the packer take any block count), and the input biases b[0] of both directions
+  for (int e = 0; e < 2; ++e)
+    for (int l = 1; l < c.enc_depth; ++l) {
+      std::vector<uint16_t> img(RV_GRU_WX16_SLOT);
+      std::vector<float> b2(2 * RV_GG);
+      size_t off[2];
+      for (int dr = 0; dr < 2; ++dr) {
+        const size_t boff = (size_t)(h->enc[e][l][dr].b - h->d_w);
+        off[dr] = (size_t)(h->enc[e][l][dr].W - h->d_w);
+        for (int n = 0; n < RV_GG; ++n) b2[(size_t)dr * RV_GG + n] = blob[boff + n];
+      }
+      rv_pack_split_image(blob, RV_GG, 3, [&](int cc) { return off[cc / RV_GG] + (size_t)(cc % RV_GG); }, img.data());
+      const size_t slot = (size_t)(e * (c.enc_depth - 1) + (l - 1));
+      HIPCHK(h, hipMemcpy(h->img.gWx16 + slot * RV_GRU_WX16_SLOT, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(h->img.gbx + slot * 2 * RV_GG, b2.data(), b2.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+  {   // decoder cells for k_dec_cell_gru: ([W_in ; U])^T as four column tiles of 128 -- z, r, [W_h ; 0], [0 ; U_h] -- [512][256], so
+      // that the candidate gate's input and recurrent parts leave the one product apart (W_in: the rows of W behind cell 0's one-hot rows)
+    std::vector<float> t((size_t)RV_G * RV_E);
+    for (int k = 0; k < c.dec_depth; ++k) {
+      const size_t wo = (size_t)(h->dec[k].W - h->d_w) + (k == 0 ? (size_t)c.vocab * RV_GG : 0), uo = (size_t)(h->dec[k].U - h->d_w);
+      for (int tile = 0; tile < 4; ++tile)
+        for (int n = 0; n < RV_U; ++n)
+          for (int kk = 0; kk < RV_E; ++kk) {
+            const int col = (tile < 2 ? tile : 2) * RV_U + n;
+            const bool in_half = kk < RV_U;
+            float v = in_half ? blob[wo + (size_t)kk * RV_GG + col] : blob[uo + (size_t)(kk - RV_U) * RV_GG + col];
+            if ((tile == 2 && !in_half) || (tile == 3 && in_half)) v = 0.f;
+            t[((size_t)tile * RV_U + n) * RV_E + kk] = v;
+          }
+      HIPCHK(h, hipMemcpy(h->img.gWcatT + (size_t)k * RV_G * RV_E, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+  }
+  const size_t moff = (size_t)(h->W_mem - h->d_w);       // W_mem [256][128] -> [128][256]
+  std::vector<float> m((size_t)RV_U * RV_E);
+  for (int i = 0; i < RV_E; ++i)
+    for (int j = 0; j < RV_U; ++j) m[(size_t)j * RV_E + i] = blob[moff + (size_t)i * RV_U + j];
+  HIPCHK(h, hipMemcpy(h->img.WmemT, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice));
+  return RV_OK;
+}
+
+// rv_set_option on a GRU handle: the values no GRU kernel stands behind
+int refuse_gru_option(RvContext* h, const char* key, int value) {
+  const bool bad = (!strcmp(key, "weight_parts") && value == 1) || (!strcmp(key, "wide_recurrence") && value != 1) ||
+                   (!strcmp(key, "lane_projection") && value == 0) || (!strcmp(key, "slab_graph") && value != 0);
+  if (!bad) return RV_OK;
+  return fail(h, RV_EUNSUPPORTED, "%s %d is not served on a bigru handle: its encoders run the sixteen-chunk matrix-pipe GRU recurrence with the "
+              "layer-0 projection in the lane, its weights keep two f16 parts, and its decode runs per step outside a slab graph", key, value);
+}
+
 }  // namespace
 
 // Loading the library is the earliest point a C caller reaches: ask the HIP runtime for 16 hardware queues (the asynchronous calls keep up
@@ -1931,10 +2071,15 @@ int rv_abi_version(void) { return RV_ABI_VERSION; }
 
 const char* rv_last_error(rv_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-int rv_create(const RvConfig* cfg, rv_handle* out) {
+int rv_create(const RvConfig* cfg, rv_handle* out) { return rv_create_rnn(cfg, RV_RNN_BILSTM, out); }
+
+int rv_create_rnn(const RvConfig* cfg, int32_t rnn, rv_handle* out) {
   if (!cfg || !out) return fail(nullptr, RV_EINVAL, "null argument");
   *out = nullptr;
   const RvConfig& c = *cfg;
+  if (rnn != RV_RNN_BILSTM && rnn != RV_RNN_BIGRU)
+    return fail(nullptr, RV_EUNSUPPORTED, "rnn %d: RV_RNN_BILSTM (0) and RV_RNN_BIGRU (1) are built; the unidirectional families are not", (int)rnn);
+  const bool gru = rnn == RV_RNN_BIGRU;
   if (c.enc_units != RV_U || c.dec_units != RV_U)
     return fail(nullptr, RV_EUNSUPPORTED, "this build is specialised for enc_units = dec_units = 128 (got %d, %d)", c.enc_units, c.dec_units);
   if (c.dec_depth < 1 || c.dec_depth > 4)
@@ -1948,7 +2093,12 @@ int rv_create(const RvConfig* cfg, rv_handle* out) {
   for (int t : {c.start_token, c.end_token, c.pad_token})
     if (t < 0 || t >= c.vocab) return fail(nullptr, RV_EINVAL, "token id %d outside vocab", t);
 
-  {   // layer 0 keeps a workgroup's input windows in LDS (160 KB): reject maximum shapes no kernel variant can launch
+  if (gru) {   // k_gru_rec_mx stages the input windows of its sixteen chunks in LDS
+    if (c.mode != RV_MODE_EVENT && !gru_rec_mx_window_fits(c.max_raw_len, 1))
+      return fail(nullptr, RV_EUNSUPPORTED, "bigru: max_raw_len %d exceeds the 160 KB of LDS the layer-0 recurrence stages its sixteen input windows in", c.max_raw_len);
+    if (c.mode != RV_MODE_RAW && !gru_rec_mx_window_fits(c.max_event_len, 5))
+      return fail(nullptr, RV_EUNSUPPORTED, "bigru: max_event_len %d exceeds the 160 KB of LDS the layer-0 recurrence stages its sixteen input windows in", c.max_event_len);
+  } else {   // layer 0 keeps a workgroup's input windows in LDS (160 KB): reject maximum shapes no kernel variant can launch
     const int bt = pick_rows_per_block(c.max_batch);
     if (c.mode != RV_MODE_EVENT && !lstm_rec_window_fits(1, bt, c.max_raw_len))
       return fail(nullptr, RV_EUNSUPPORTED, "max_raw_len %d with max_batch %d (%d chunks per workgroup) exceeds the 160 KB of LDS the layer-0 recurrence stages its input windows in", c.max_raw_len, c.max_batch, bt);
@@ -1962,15 +2112,29 @@ int rv_create(const RvConfig* cfg, rv_handle* out) {
 
   RvContext* h = new RvContext();
   h->cfg = c;
+  h->rnn = rnn;
   auto init = [&]() -> int {
   HIPTRY(hipSetDevice(c.device));
   HIPTRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   HIPTRY(configure_decode_kernels());    // a refused LDS opt-in would otherwise surface as an opaque launch error later
-  HIPTRY(configure_rec_kernels());
-  HIPTRY(configure_mx_kernels());
+  if (!gru) {                            // (a GRU handle launches neither LSTM recurrence)
+    HIPTRY(configure_rec_kernels());
+    HIPTRY(configure_mx_kernels());
+  }
   HIPTRY(configure_gemm_kernels());
-  h->n_w = weight_count(c);
+  h->n_w = weight_count(c, rnn);
   TRY(dalloc(h, &h->d_w, h->n_w));
+  if (gru) {   // the GRU images and none of the LSTM-only ones (WmemT: the attend kernels' key projection, family-independent)
+    HIPTRY(configure_gru_kernels());
+    TRY(dalloc(h, &h->img.gUa, (size_t)2 * c.enc_depth * 2 * RV_GRU_UA_SLOT));
+    if (c.enc_depth > 1) TRY(dalloc(h, &h->img.gWx16, (size_t)2 * (c.enc_depth - 1) * RV_GRU_WX16_SLOT));
+    if (c.enc_depth > 1) TRY(dalloc(h, &h->img.gbx, (size_t)2 * (c.enc_depth - 1) * 2 * RV_GG));
+    TRY(dalloc(h, &h->img.gWcatT, (size_t)c.dec_depth * RV_G * RV_E));
+    TRY(dalloc(h, &h->img.WmemT, (size_t)RV_U * RV_E));
+    bind_weights(h);
+    TRY(alloc_slab_buffers(h));
+    return RV_OK;
+  }
   TRY(dalloc(h, &h->img.WcatT, (size_t)c.dec_depth * RV_G * RV_E));
   TRY(dalloc(h, &h->img.Wmp, (size_t)RV_E * RV_E));
   TRY(dalloc(h, &h->img.Wmp16, RV_WMP16_SLOT));
@@ -2063,6 +2227,12 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
   }
   h->opt.parts_loaded = h->opt.weight_parts;
   HIPCHK(h, hipMemcpyAsync(h->d_w, blob, n_floats * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (h->rnn == RV_RNN_BIGRU) {
+    TRY(load_gru_images(h, blob));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->loaded = true;
+    return RV_OK;
+  }
   {   // derived layout for the decoder cell kernel: the input-kernel rows that multiply a dense input
       // (rows V.. of W_0; all of W_k for k >= 1) followed by U_k form a contiguous [256][512] matrix in
       // the blob; the kernel wants it column-major ([512][256]).
@@ -2684,6 +2854,7 @@ int rv_beam_search_flush(rv_handle h) {
 int rv_set_option(rv_handle h, const char* key, int32_t value) {
   if (!h || !key) return RV_EINVAL;
   flush_open_group(h);               // a group still filling was submitted under the options as they were
+  if (h->rnn == RV_RNN_BIGRU) TRY(refuse_gru_option(h, key, value));
   if (!strcmp(key, "group_inplace") && value != 0 && value != 1) return fail(h, RV_EINVAL, "group_inplace must be 0 or 1");
   if (!strcmp(key, "group_side_ev") && (value < -1 || value > 1)) return fail(h, RV_EINVAL, "group_side_ev must be -1 (where the hardware queues allow it), 0 or 1");
   if (!strcmp(key, "weight_parts")) {
@@ -2785,7 +2956,13 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
   else if (!strcmp(name, "kernel_forms") || !strcmp(name, "kernel_form_list") || !strcmp(name, "kernel_form_list_1p") || !strcmp(name, "group_kernel_forms")) {
     FormLog all;
     const FormLog* f = &h->lforms;
-    if (!strcmp(name, "kernel_form_list")) {
+    if (!strcmp(name, "kernel_form_list") && h->rnn == RV_RNN_BIGRU) {      // the list answers for the handle's family
+      FormLog dec;
+      list_gru_forms(all); list_decode_forms(dec);
+      for (int i = 0; i < dec.n; ++i)      // (the attend kernels; no persistent GRU decode)
+        if (dec.row[i][0] != RV_K_DEC_PERSIST) all.add(dec.row[i][0], dec.row[i][1], dec.row[i][2], dec.row[i][3], dec.row[i][4]);
+      f = &all;
+    } else if (!strcmp(name, "kernel_form_list")) {
       list_rec_forms(all); list_mx_forms(all); list_decode_forms(all);
       f = &all;
     } else if (!strcmp(name, "kernel_form_list_1p")) {

@@ -10,6 +10,9 @@ Blob order (all matrices row-major ``[in, out]`` exactly as Keras stores kernels
   for k in decoder cells: Wd[in_k,4d]  Ud[d,4d]  bd[4d]      (in_0 = vocab + d, in_k = d)
   W_mem[2u,d]   W_q[d,d]  v_att[d]  (both always present; used only by Bahdanau)
   W_att[d+2u,d] W_fc[d,V] b_fc[V]
+
+``cfg.rnn == 'bigru'`` (Keras GRUCell, reset_after=True, gates z, r, h): every cell is W[F,3u]  U[u,3u]  b[2,3u] in the same
+order, row 0 of b the input bias and row 1 the recurrent bias; everything behind the cells is the same.
 """
 from __future__ import annotations
 
@@ -24,20 +27,28 @@ def _enc_in_features(cfg: RvConfig, enc: str, layer: int) -> int:
     return RAW_FEATURES if enc == "raw" else EVENT_FEATURES
 
 
+def _gates(cfg: RvConfig) -> int:
+    if cfg.rnn not in ("bilstm", "bigru"):
+        raise ValueError(f"rnn {cfg.rnn!r}: 'bilstm' or 'bigru'")
+    return 3 if cfg.rnn == "bigru" else 4
+
+
 def blob_layout(cfg: RvConfig):
     """[(name, shape)] in blob order."""
     u, d, V = cfg.enc_units, cfg.dec_units, cfg.vocab
+    g = _gates(cfg)
+    bias = (lambda n: (2, g * n)) if cfg.rnn == "bigru" else (lambda n: (g * n,))
     out = []
     for enc in ("raw", "event"):
         for l in range(cfg.enc_depth):
             F = _enc_in_features(cfg, enc, l)
             for dr in ("fwd", "bwd"):
                 p = f"enc_{enc}.{l}.{dr}"
-                out += [(p + ".W", (F, 4 * u)), (p + ".U", (u, 4 * u)), (p + ".b", (4 * u,))]
+                out += [(p + ".W", (F, g * u)), (p + ".U", (u, g * u)), (p + ".b", bias(u))]
     for k in range(cfg.dec_depth):
         fin = V + d if k == 0 else d
         p = f"dec_cells.{k}"
-        out += [(p + ".W", (fin, 4 * d)), (p + ".U", (d, 4 * d)), (p + ".b", (4 * d,))]
+        out += [(p + ".W", (fin, g * d)), (p + ".U", (d, g * d)), (p + ".b", bias(d))]
     out += [("W_mem", (2 * u, d)), ("W_q", (d, d)), ("v_att", (d,)),
             ("W_att", (d + 2 * u, d)), ("W_fc", (d, V)), ("b_fc", (V,))]
     return out
@@ -145,7 +156,7 @@ def init_weights(cfg: RvConfig, seed: int = 22, scheme: str = "keras", gain: flo
 
     scheme 'keras': the Keras defaults the reference relies on -- Glorot-uniform kernels
       (/root/reference/basecaller.py:23,86), orthogonal recurrent kernels, zero bias with
-      unit forget-gate bias; default seed 22 as /root/reference/ravvent.py:9.
+      unit forget-gate bias (bigru: zero biases); default seed 22 as /root/reference/ravvent.py:9.
     scheme 'hash' : splitmix64 uniforms scaled like Glorot; exactly reproducible, used for the
       committed golden fixtures.
     ``gain`` scales the attention/output matrices ("peaky" variant: larger logit margins).
@@ -154,7 +165,9 @@ def init_weights(cfg: RvConfig, seed: int = 22, scheme: str = "keras", gain: flo
     rng = np.random.default_rng(seed)
     for i, (name, shape) in enumerate(blob_layout(cfg)):
         leaf = name.rsplit(".", 1)[-1]
-        if leaf == "b" and name != "b_fc":
+        if leaf == "b" and name != "b_fc" and cfg.rnn == "bigru":
+            a = np.zeros(shape)                                # both bias rows zero: a GRU has no forget gate
+        elif leaf == "b" and name != "b_fc":
             b = np.zeros(shape)
             q = shape[0] // 4
             b[q:2 * q] = 1.0                                   # unit_forget_bias
