@@ -4,7 +4,7 @@
 // (/root/reference/basecaller.py:296-330).  No CPU compute path exists in this library.
 #include "../../include/ravvent_hip.h"
 #include "common.h"
-#include "split_image.h"
+#include "weight_images.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -75,34 +75,14 @@ struct Options {
   int one_part = 1;                         // option "one_part_kernels": weight_parts 1 decodes with k_dec_persist_1p where a form exists (0: the two-part kernels on the zero-lo images)
 };
 
-// Device images derived from the weights by rv_load_weights.  The handle owns them; a child context takes the addresses as a whole (create_child)
+// Device images derived from the weights (weight_images.h lists them; rv_load_weights uploads what build_weight_images returns).  The
+// handle owns them; a child context takes the addresses as a whole (create_child)
 struct WeightImages {
-  float* WmemT = nullptr;                   // W_mem^T [128][256]
-  float* Up = nullptr;                      // recurrent kernels in the recurrence kernels' register order, [enc][layer][dir][65536]
-  float* Wp = nullptr;                      // input kernels of encoder layers >= 1 as MFMA B fragments, [enc][layer-1][dir][131072]
-  uint16_t* Wsb = nullptr;                  // the same kernels cut into three bf16 parts, [enc][layer-1][dir][32 tiles][3 parts][8 k-steps][64 lanes][8]
-  uint16_t* Wh = nullptr;                   // ... as two f16 parts of the column-scaled kernels + 512 column factors, [enc][layer-1][dir][RV_WH_SLOT]
-  uint16_t* Wl16 = nullptr;                 // (one decoder cell): [W_fc ; A_h W_fc] as MFMA B fragments (DecState::Wl16)
-  uint16_t* Wq16 = nullptr;                 // (Bahdanau, one decoder cell): W_q as MFMA B fragments (DecState::Wq16)
-  uint16_t* W1c16 = nullptr;                // (two decoder cells): [W_1 | U_1] as MFMA B fragments (DecState::W1c16)
-  uint16_t* Ua = nullptr;                   // recurrent kernels as MFMA A fragments (two f16 parts) + row factors, [enc][layer][dir][RV_UA_SLOT]
-  uint16_t* Wx16 = nullptr;                 // input kernels of encoder layers >= 1, both directions, as the split GEMM's B slabs, [enc][layer-1][RV_WX16_SLOT]
-  float* bx2 = nullptr;                     // [b_fwd | b_bwd] of those layers, [enc][layer-1][1024]
-  float* Wmp = nullptr;                     // [W_mem | A_c] [256][256] (A_c = W_att rows 128..383): projection of the attention memory for the persistent decode
-  float* Wcat2 = nullptr;                   // (one decoder cell): [W_a ; U + A_h W_a] [256][512]
-  float* Nh = nullptr;                      // (one decoder cell): A_h W_fc [128][V]
-  uint16_t* Wc16 = nullptr;                 // (one decoder cell): Wcat2 as two f16 parts in MFMA B-fragment order (DecState::Wc16)
-  uint16_t* Wc16p1 = nullptr;               // weight_parts 1: the first parts of Wc16 alone, [wave][pair][64 lanes][8 f16] (k_dec_persist_1p)
-  uint16_t* Wl16p1 = nullptr;               // ... and of Wl16, [8 k-steps][64 lanes][8 f16]
-  uint16_t* Wmp16 = nullptr;                // Wmp as two f16 parts in MFMA fragment order + column factors (launch_gemm_mem_split)
-  uint16_t* Wkp16 = nullptr;                // the W_mem half of those parts, columns permuted into key-tile rows (DecState::Wkp16)
-  float* WcatT = nullptr;                   // ([W_dec[V:] ; U_dec])^T, [512][256]
-  // a GRU handle (rv_create_rnn, RV_RNN_BIGRU) holds these and WmemT alone
-  uint16_t* gUa = nullptr;                  // recurrent kernels as MFMA A fragments + column factors, [enc][layer][dir][RV_GRU_UA_SLOT]
-  uint16_t* gWx16 = nullptr;                // input kernels of encoder layers >= 1, both directions, as three B slabs of the split GEMM, [enc][layer-1][RV_GRU_WX16_SLOT]
-  float* gbx = nullptr;                     // [b[0]_fwd | b[0]_bwd] of those layers, [enc][layer-1][768]
-  float* gWcatT = nullptr;                  // decoder cells for k_dec_cell_gru: column tiles z, r, [W_h ; 0], [0 ; U_h] of ([W_in ; U])^T, [cell][512][256]
+#define X(T, name, count) T* name = nullptr;
+  RV_WEIGHT_IMAGES(X)
+#undef X
 };
+static_assert(wimg::U == RV_U && wimg::E == RV_E && wimg::MAX_VOCAB == RV_MAX_VOCAB, "weight_images.h restates common.h");
 
 // What a recording leaves behind for rv_get_tensor beside lB .. lptaps; a slab graph stores them at its capture and puts them back at every replay
 struct SlabFacts {
@@ -179,11 +159,7 @@ struct RvContext {
   std::vector<LstmW> dec;                   // stacked decoder cells
   WeightImages img;                         // derived from the weights; a child context holds its parent's addresses
   const float *W_mem = nullptr, *W_q = nullptr, *v_att = nullptr, *W_att = nullptr, *W_fc = nullptr, *b_fc = nullptr;
-  float mx_cdescale = 1.f;                  // 1 / the power-of-two scale of the Wc16 image (set by rv_load_weights)
-  float mx_ldescale = 1.f;                  // ... of the Wl16 image
-  float mx_qdescale = 1.f;
-  float mx_c1descale = 1.f;
-  float mx_kscale = 1.f, mx_uscale = 1.f;   // powers of two from the bounds of [keys | U'] = enc_out . Wmp (set by rv_load_weights)
+  wimg::ImageScales scales;                 // the weight-derived scalars of the decode (set by rv_load_weights)
 
   Options opt;
   int dbg_role = 0;                         // timing probe (RV_DBG_ROLE): 1 = no projection math, 2 = no recurrence math
@@ -336,88 +312,18 @@ int dalloc(RvContext* h, T** p, size_t count) {
   return RV_OK;
 }
 
-#define RV_WH_SLOT ((size_t)2 * RV_E * RV_G + 2 * RV_G)   // uint16 per (encoder, layer, direction) of d_Wh
-// bf16 with round-to-nearest-even, and back (finite inputs: the weights)
-inline uint16_t bf16_rne(float x) {
-  uint32_t u; memcpy(&u, &x, 4);
-  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-inline float bf16_value(uint16_t b) {
-  const uint32_t u = (uint32_t)b << 16;
-  float x; memcpy(&x, &u, 4);
-  return x;
-}
-
-// Per cell of the blob: W[F, G u]  U[u, G u]  b[NB, G u] -- LSTM: G = 4 gates, one bias row; GRU: G = 3, input and recurrent bias rows
-size_t weight_count(const RvConfig& c, int rnn = RV_RNN_BILSTM) {
-  const size_t u = c.enc_units, d = c.dec_units, V = c.vocab;
-  const size_t G = rnn == RV_RNN_BIGRU ? 3 : 4, NB = rnn == RV_RNN_BIGRU ? 2 : 1;
-  size_t n = 0;
-  for (int e = 0; e < 2; ++e)
-    for (int l = 0; l < c.enc_depth; ++l) {
-      const size_t F = l > 0 ? 2 * u : (e == 0 ? 1 : 5);
-      n += 2 * (F * G * u + u * G * u + NB * G * u);
-    }
-  for (int k = 0; k < c.dec_depth; ++k) {
-    const size_t fin = k == 0 ? V + d : d;
-    n += fin * G * d + d * G * d + NB * G * d;
-  }
-  n += 2 * u * d + d * d + d + (d + 2 * u) * d + d * V + V;
-  return n;
-}
-
 void bind_weights(RvContext* h) {
-  const RvConfig& c = h->cfg;
-  const size_t u = c.enc_units, d = c.dec_units, V = c.vocab;
-  const size_t G = h->rnn == RV_RNN_BIGRU ? 3 : 4, NB = h->rnn == RV_RNN_BIGRU ? 2 : 1;      // (weight_count)
-  const float* p = h->d_w;
+  const wimg::BlobLayout lay(h->cfg, h->rnn);
+  auto dev = [&](const wimg::CellOffsets& o) { return LstmW{h->d_w + o.W, h->d_w + o.U, h->d_w + o.b}; };
   for (int e = 0; e < 2; ++e) {
-    h->enc[e].assign(c.enc_depth, std::vector<LstmW>(2));
-    for (int l = 0; l < c.enc_depth; ++l) {
-      const size_t F = l > 0 ? 2 * u : (e == 0 ? 1 : 5);
-      for (int dr = 0; dr < 2; ++dr) {
-        LstmW& w = h->enc[e][l][dr];
-        w.W = p; p += F * G * u;
-        w.U = p; p += u * G * u;
-        w.b = p; p += NB * G * u;
-      }
-    }
+    h->enc[e].assign(h->cfg.enc_depth, std::vector<LstmW>(2));
+    for (int l = 0; l < h->cfg.enc_depth; ++l)
+      for (int dr = 0; dr < 2; ++dr) h->enc[e][l][dr] = dev(lay.cell(e, l, dr));
   }
-  h->dec.assign(c.dec_depth, LstmW{});
-  for (int k = 0; k < c.dec_depth; ++k) {
-    h->dec[k].W = p; p += (k == 0 ? V + d : d) * G * d;
-    h->dec[k].U = p; p += d * G * d;
-    h->dec[k].b = p; p += NB * G * d;
-  }
-  h->W_mem = p; p += 2 * u * d;
-  h->W_q = p; p += d * d;
-  h->v_att = p; p += d;
-  h->W_att = p; p += (d + 2 * u) * d;
-  h->W_fc = p; p += d * V;
-  h->b_fc = p; p += V;
-}
-
-// Option weight_parts 1, the tensors that are a slice of the blob (same walk as bind_weights): each column rounded to what the first
-// f16 part of its split image holds (rv_round_column) -- U of every encoder layer and direction over its 128 rows, W of encoder
-// layers >= 1 over 256 rows, W_mem and A_c (rows u .. 3u - 1 of the attention layer) over 256 rows.  Everything else stays as it is;
-// the folded tensors (cell kernel, output layer) are rounded after their fold by rv_load_weights.  Host code, no device.
-void round_blob_weights(const RvConfig& c, float* blob) {
-  const size_t u = c.enc_units, d = c.dec_units, V = c.vocab;
-  float* p = blob;
-  for (int e = 0; e < 2; ++e)
-    for (int l = 0; l < c.enc_depth; ++l) {
-      const size_t F = l > 0 ? 2 * u : (e == 0 ? 1 : 5);
-      for (int dr = 0; dr < 2; ++dr) {
-        if (l > 0) for (size_t n = 0; n < 4 * u; ++n) rv_round_column(p + n, 4 * u, (int)F);
-        p += F * 4 * u;
-        for (size_t n = 0; n < 4 * u; ++n) rv_round_column(p + n, 4 * u, (int)u);
-        p += u * 4 * u + 4 * u;
-      }
-    }
-  for (int k = 0; k < c.dec_depth; ++k) p += ((k == 0 ? V + d : d) + d + 1) * 4 * d;
-  for (size_t n = 0; n < d; ++n) rv_round_column(p + n, d, (int)(2 * u));        // W_mem
-  p += 2 * u * d + d * d + d;                                                      // (W_q, attention_v)
-  for (size_t n = 0; n < d; ++n) rv_round_column(p + d * d + n, d, (int)(2 * u));  // A_c
+  h->dec.clear();
+  for (const wimg::CellOffsets& o : lay.dec) h->dec.push_back(dev(o));
+  h->W_mem = h->d_w + lay.W_mem; h->W_q = h->d_w + lay.W_q; h->v_att = h->d_w + lay.v_att;
+  h->W_att = h->d_w + lay.W_att; h->W_fc = h->d_w + lay.W_fc; h->b_fc = h->d_w + lay.b_fc;
 }
 
 // ---- profiling: bracket a launch with events on the launch stream
@@ -610,7 +516,7 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
         a.dbg_role = h->dbg_role;
         for (int dr = 0; dr < 2; ++dr) {
           a.Wp[dr] = h->img.Wp + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * RV_E * RV_G;
-          a.Wh[dr] = h->opt.split_proj == 2 ? h->img.Wh + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * RV_WH_SLOT : nullptr;
+          a.Wh[dr] = h->opt.split_proj == 2 ? h->img.Wh + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * wimg::WH_SLOT : nullptr;
           a.Wsb[dr] = h->opt.split_proj == 1 ? h->img.Wsb + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * 3 * RV_E * RV_G : nullptr;
           a.bias[dr] = h->enc[e][l][dr].b;
         }
@@ -1014,8 +920,8 @@ int split_decode(RvContext* h, Slab& sl) {
   nsplit = (greedy || h->opt.taps || B < 64) ? 1 : std::min(std::max(h->opt.split, 1), 4);
   d.chunk_steps = nullptr;
   d.persist_att = persist_att;
-  d.Wc16 = h->img.Wc16; d.mx_cdescale = h->mx_cdescale; d.Wl16 = h->img.Wl16; d.mx_ldescale = h->mx_ldescale;
-  d.Wq16 = h->img.Wq16; d.mx_qdescale = h->mx_qdescale; d.W1c16 = h->img.W1c16; d.mx_c1descale = h->mx_c1descale;
+  d.Wc16 = h->img.Wc16; d.mx_cdescale = h->scales.cdescale; d.Wl16 = h->img.Wl16; d.mx_ldescale = h->scales.ldescale;
+  d.Wq16 = h->img.Wq16; d.mx_qdescale = h->scales.qdescale; d.W1c16 = h->img.W1c16; d.mx_c1descale = h->scales.c1descale;
   h->fact.lpersist = persist_att >= 0 ? 1 : 0;
   h->fact.lmem2_stale = 0;
   if (h->fact.lpersist) { nsplit = 1; d.chunk_steps = h->d_chunk_steps; }
@@ -1078,8 +984,8 @@ int decode_persist(RvContext* h, Slab& sl) {
     else launch_gemm_f32(g, false, s);
   }
   d.values = h->mem2; part[0].values = h->mem2;
-  d.mx_kscale = h->mx_kscale; d.mx_kdescale = std::ldexp(1.0f, -14) / h->mx_kscale;
-  d.mx_uscale = h->mx_uscale; d.mx_udescale = std::ldexp(1.0f, -14) / h->mx_uscale;
+  d.mx_kscale = h->scales.kscale; d.mx_kdescale = std::ldexp(1.0f, -14) / h->scales.kscale;
+  d.mx_uscale = h->scales.uscale; d.mx_udescale = std::ldexp(1.0f, -14) / h->scales.uscale;
   const bool p1 = h->opt.parts_loaded == 1 && h->opt.one_part && persist_att == 3 && d.depth == 1;
   Scope sc(h, "dec_persist", nullptr, true);
   launch_dec_persist(d, d.depth > 1 ? h->dec[0].W + (size_t)V * RV_G : h->img.Wcat2, h->dec[0].W, h->dec[0].b,
@@ -1622,8 +1528,7 @@ int create_child(RvContext* p, RvContext** out, int slabs = 1) {
 
 // options and weight-derived scalars of the parent, as of now
 void sync_child(RvContext* k, const RvContext* p) {
-  k->loaded = p->loaded; k->mx_kscale = p->mx_kscale; k->mx_uscale = p->mx_uscale;
-  k->mx_cdescale = p->mx_cdescale; k->mx_ldescale = p->mx_ldescale; k->mx_qdescale = p->mx_qdescale; k->mx_c1descale = p->mx_c1descale;
+  k->loaded = p->loaded; k->scales = p->scales;
   k->opt = p->opt;
   k->opt.taps = 0; k->opt.ptaps = 0;      // debug taps belong to the synchronous calls
   k->inflight_hint = p->inflight_hint;
@@ -1972,78 +1877,12 @@ int put_read(RvContext* h, const float* raw, size_t n_raw, const float* event, s
   return RV_OK;
 }
 
-// The device images of a GRU handle (rv_load_weights), from the host blob: every cell W[F,384] U[128,384] b[2,384], gates z, r, h
-int load_gru_images(RvContext* h, const float* blob) {
-  const RvConfig& c = h->cfg;
-  // recurrent kernels as MFMA A fragments of U^T for k_gru_rec_mx: wave w, gate g, k-step ks, part p, lane (m = lane % 16, kq = lane / 16)
-  // holds s_r U[32 ks + 8 kq + j][r], r = 128 g + 16 w + m (s_r: rv_column_scale of the column), then the 384 factors 2^-14 / s_r
-  for (int e = 0; e < 2; ++e)
-    for (int l = 0; l < c.enc_depth; ++l)
-      for (int dr = 0; dr < 2; ++dr) {
-        const size_t off = (size_t)(h->enc[e][l][dr].U - h->d_w);
-        std::vector<uint16_t> ua(RV_GRU_UA_SLOT);
-        float cs[RV_GG];
-        for (int r = 0; r < RV_GG; ++r) {
-          float mx = 0.f;
-          for (int k = 0; k < RV_U; ++k) mx = std::max(mx, std::fabs(blob[off + (size_t)k * RV_GG + r]));
-          cs[r] = rv_column_scale(mx);
-        }
-        for (int w = 0; w < 8; ++w)
-          for (int g = 0; g < 3; ++g)
-            for (int ks = 0; ks < 4; ++ks)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int j = 0; j < 8; ++j) {
-                  const int r = g * RV_U + 16 * w + (ln & 15);
-                  const float v = blob[off + (size_t)(32 * ks + 8 * (ln >> 4) + j) * RV_GG + r] * cs[r];   // exact
-                  const _Float16 hi = (_Float16)v;
-                  const _Float16 lo = (_Float16)(v - (float)hi);
-                  uint16_t hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
-                  const size_t base = ((((size_t)w * 3 + g) * 4 + ks) * 2) * 64 * 8;
-                  ua[base + (size_t)ln * 8 + j] = hb;
-                  ua[base + 64 * 8 + (size_t)ln * 8 + j] = lb;
-                }
-        for (int r = 0; r < RV_GG; ++r) { const float f = std::ldexp(1.0f, -14) / cs[r]; memcpy(&ua[(size_t)2 * RV_U * RV_GG + 2 * r], &f, 4); }
-        HIPCHK(h, hipMemcpy(h->img.gUa + ((size_t)(e * c.enc_depth + l) * 2 + dr) * RV_GRU_UA_SLOT, ua.data(), ua.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-      }
-  // encoder layers >= 1: the [256 x 768] input kernel of both directions ([fwd z r h | bwd z r h]) as three column blocks of the split
-  // GEMM (rv_pack_split_image: the kernel and the packer take any block count), and the input biases b[0] of both directions
-  for (int e = 0; e < 2; ++e)
-    for (int l = 1; l < c.enc_depth; ++l) {
-      std::vector<uint16_t> img(RV_GRU_WX16_SLOT);
-      std::vector<float> b2(2 * RV_GG);
-      size_t off[2];
-      for (int dr = 0; dr < 2; ++dr) {
-        const size_t boff = (size_t)(h->enc[e][l][dr].b - h->d_w);
-        off[dr] = (size_t)(h->enc[e][l][dr].W - h->d_w);
-        for (int n = 0; n < RV_GG; ++n) b2[(size_t)dr * RV_GG + n] = blob[boff + n];
-      }
-      rv_pack_split_image(blob, RV_GG, 3, [&](int cc) { return off[cc / RV_GG] + (size_t)(cc % RV_GG); }, img.data());
-      const size_t slot = (size_t)(e * (c.enc_depth - 1) + (l - 1));
-      HIPCHK(h, hipMemcpy(h->img.gWx16 + slot * RV_GRU_WX16_SLOT, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-      HIPCHK(h, hipMemcpy(h->img.gbx + slot * 2 * RV_GG, b2.data(), b2.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-  {   // decoder cells for k_dec_cell_gru: ([W_in ; U])^T as four column tiles of 128 -- z, r, [W_h ; 0], [0 ; U_h] -- [512][256], so
-      // that the candidate gate's input and recurrent parts leave the one product apart (W_in: the rows of W behind cell 0's one-hot rows)
-    std::vector<float> t((size_t)RV_G * RV_E);
-    for (int k = 0; k < c.dec_depth; ++k) {
-      const size_t wo = (size_t)(h->dec[k].W - h->d_w) + (k == 0 ? (size_t)c.vocab * RV_GG : 0), uo = (size_t)(h->dec[k].U - h->d_w);
-      for (int tile = 0; tile < 4; ++tile)
-        for (int n = 0; n < RV_U; ++n)
-          for (int kk = 0; kk < RV_E; ++kk) {
-            const int col = (tile < 2 ? tile : 2) * RV_U + n;
-            const bool in_half = kk < RV_U;
-            float v = in_half ? blob[wo + (size_t)kk * RV_GG + col] : blob[uo + (size_t)(kk - RV_U) * RV_GG + col];
-            if ((tile == 2 && !in_half) || (tile == 3 && in_half)) v = 0.f;
-            t[((size_t)tile * RV_U + n) * RV_E + kk] = v;
-          }
-      HIPCHK(h, hipMemcpy(h->img.gWcatT + (size_t)k * RV_G * RV_E, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-  }
-  const size_t moff = (size_t)(h->W_mem - h->d_w);       // W_mem [256][128] -> [128][256]
-  std::vector<float> m((size_t)RV_U * RV_E);
-  for (int i = 0; i < RV_E; ++i)
-    for (int j = 0; j < RV_U; ++j) m[(size_t)j * RV_E + i] = blob[moff + (size_t)i * RV_U + j];
-  HIPCHK(h, hipMemcpy(h->img.WmemT, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice));
+// One host image to the device (rv_load_weights), in pieces of 1 MiB: the runtime stages a copy from pageable memory of up to a few MiB
+// through its own pinned buffer, and pins the pages of a larger one first, which takes longer than the copy
+int upload_image(RvContext* h, void* dst, const void* src, size_t bytes) {
+  const size_t piece = (size_t)1 << 20;
+  for (size_t at = 0; at < bytes; at += piece)
+    HIPCHK(h, hipMemcpy((char*)dst + at, (const char*)src + at, std::min(piece, bytes - at), hipMemcpyHostToDevice));
   return RV_OK;
 }
 
@@ -2122,42 +1961,16 @@ int rv_create_rnn(const RvConfig* cfg, int32_t rnn, rv_handle* out) {
     HIPTRY(configure_mx_kernels());
   }
   HIPTRY(configure_gemm_kernels());
-  h->n_w = weight_count(c, rnn);
+  h->n_w = wimg::BlobLayout(c, rnn).total;
   TRY(dalloc(h, &h->d_w, h->n_w));
-  if (gru) {   // the GRU images and none of the LSTM-only ones (WmemT: the attend kernels' key projection, family-independent)
-    HIPTRY(configure_gru_kernels());
-    TRY(dalloc(h, &h->img.gUa, (size_t)2 * c.enc_depth * 2 * RV_GRU_UA_SLOT));
-    if (c.enc_depth > 1) TRY(dalloc(h, &h->img.gWx16, (size_t)2 * (c.enc_depth - 1) * RV_GRU_WX16_SLOT));
-    if (c.enc_depth > 1) TRY(dalloc(h, &h->img.gbx, (size_t)2 * (c.enc_depth - 1) * 2 * RV_GG));
-    TRY(dalloc(h, &h->img.gWcatT, (size_t)c.dec_depth * RV_G * RV_E));
-    TRY(dalloc(h, &h->img.WmemT, (size_t)RV_U * RV_E));
-    bind_weights(h);
-    TRY(alloc_slab_buffers(h));
-    return RV_OK;
-  }
-  TRY(dalloc(h, &h->img.WcatT, (size_t)c.dec_depth * RV_G * RV_E));
-  TRY(dalloc(h, &h->img.Wmp, (size_t)RV_E * RV_E));
-  TRY(dalloc(h, &h->img.Wmp16, RV_WMP16_SLOT));
-  TRY(dalloc(h, &h->img.Wkp16, RV_WKP16_SLOT));
-  TRY(dalloc(h, &h->img.Wc16, (size_t)2 * 3 * RV_U * RV_G));      // (two cells: 384 rows)
-  if (c.dec_depth == 2) TRY(dalloc(h, &h->img.W1c16, (size_t)2 * RV_E * RV_G));
-  TRY(dalloc(h, &h->img.Wl16, (size_t)2 * RV_E * 16));
-  TRY(dalloc(h, &h->img.Wc16p1, (size_t)RV_E * RV_G));
-  TRY(dalloc(h, &h->img.Wl16p1, (size_t)RV_E * 16));
-  TRY(dalloc(h, &h->img.Wq16, (size_t)2 * RV_U * RV_U));
-  TRY(dalloc(h, &h->img.Wcat2, (size_t)RV_E * RV_G));
-  TRY(dalloc(h, &h->img.Nh, (size_t)RV_U * RV_MAX_VOCAB));
-  TRY(dalloc(h, &h->img.Up, (size_t)2 * c.enc_depth * 2 * RV_U * RV_G));
-  TRY(dalloc(h, &h->img.Ua, (size_t)2 * c.enc_depth * 2 * RV_UA_SLOT));
-  if (c.enc_depth > 1) TRY(dalloc(h, &h->img.Wx16, (size_t)2 * (c.enc_depth - 1) * RV_WX16_SLOT));
-  if (c.enc_depth > 1) TRY(dalloc(h, &h->img.bx2, (size_t)2 * (c.enc_depth - 1) * 2 * RV_G));
-  if (c.enc_depth > 1) TRY(dalloc(h, &h->img.Wp, (size_t)2 * (c.enc_depth - 1) * 2 * RV_E * RV_G));
-  if (c.enc_depth > 1) TRY(dalloc(h, &h->img.Wh, (size_t)2 * (c.enc_depth - 1) * 2 * RV_WH_SLOT));
-  if (c.enc_depth > 1) TRY(dalloc(h, &h->img.Wsb, (size_t)2 * (c.enc_depth - 1) * 2 * 3 * RV_E * RV_G));
+  if (gru) HIPTRY(configure_gru_kernels());
+  const wimg::ImageCounts cnt = wimg::image_counts(c, rnn);
+#define X(T, name, count) if (cnt.name) TRY(dalloc(h, &h->img.name, cnt.name));
+  RV_WEIGHT_IMAGES(X)
+#undef X
 #ifdef RV_DIAG
   if (const char* e = getenv("RV_DBG_ROLE")) h->dbg_role = atoi(e);
 #endif
-  TRY(dalloc(h, &h->img.WmemT, (size_t)RV_U * RV_E));
   bind_weights(h);
   TRY(alloc_slab_buffers(h));
   return RV_OK;
@@ -2202,9 +2015,9 @@ int rv_round_weights(const RvConfig* cfg, const float* src, float* dst, size_t n
   if (!cfg || !src || !dst) return RV_EINVAL;
   const RvConfig& c = *cfg;
   if (c.enc_units != RV_U || c.dec_units != RV_U || c.dec_depth < 1 || c.dec_depth > 4 || c.enc_depth < 1 || c.enc_depth > 8 ||
-      c.vocab < 2 || c.vocab > RV_MAX_VOCAB || n_floats != weight_count(c)) return RV_EINVAL;
+      c.vocab < 2 || c.vocab > RV_MAX_VOCAB || n_floats != wimg::BlobLayout(c, RV_RNN_BILSTM).total) return RV_EINVAL;
   if (dst != src) memmove(dst, src, n_floats * sizeof(float));
-  round_blob_weights(c, dst);
+  wimg::round_blob_weights(c, dst);
   return RV_OK;
 }
 
@@ -2217,333 +2030,20 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
   for (RvContext* k : h->kids) if (k->pend.busy) return fail(h, RV_ESTATE, "collect the calls in flight before loading weights");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   h->opt.gen++;                      // (weight-derived scalars travel by value in the decode's kernel arguments)
-  // weight_parts 1: every image below -- and the device copy of the blob -- is built from the blob with its blob-level tensors rounded
-  const bool one_part = h->opt.weight_parts == 1;
+  // weight_parts 1: every image -- and the device copy of the blob -- is built from the blob with its blob-level tensors rounded
   std::vector<float> rounded;
-  if (one_part) {
+  if (h->opt.weight_parts == 1) {
     rounded.assign(blob, blob + n_floats);
-    round_blob_weights(h->cfg, rounded.data());
+    wimg::round_blob_weights(h->cfg, rounded.data());
     blob = rounded.data();
   }
   h->opt.parts_loaded = h->opt.weight_parts;
   HIPCHK(h, hipMemcpyAsync(h->d_w, blob, n_floats * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (h->rnn == RV_RNN_BIGRU) {
-    TRY(load_gru_images(h, blob));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->loaded = true;
-    return RV_OK;
-  }
-  {   // derived layout for the decoder cell kernel: the input-kernel rows that multiply a dense input
-      // (rows V.. of W_0; all of W_k for k >= 1) followed by U_k form a contiguous [256][512] matrix in
-      // the blob; the kernel wants it column-major ([512][256]).
-    std::vector<float> t((size_t)RV_G * RV_E);
-    for (int l = 0; l < h->cfg.dec_depth; ++l) {
-      const size_t off = (size_t)(h->dec[l].W - h->d_w) + (l == 0 ? (size_t)h->cfg.vocab * RV_G : 0);
-      for (int k = 0; k < RV_E; ++k)
-        for (int n = 0; n < RV_G; ++n) t[(size_t)n * RV_E + k] = blob[off + (size_t)k * RV_G + n];
-      HIPCHK(h, hipMemcpy(h->img.WcatT + (size_t)l * RV_G * RV_E, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    // every encoder layer: U [128][512] -> [32 i][512 threads][4 slots] (thread = 4 j + kq holds k = 32 kq + i, slot r = gate (kq + r) & 3)
-    for (int e = 0; e < 2; ++e)
-      for (int l = 0; l < h->cfg.enc_depth; ++l)
-        for (int dr = 0; dr < 2; ++dr) {
-          const size_t off = (size_t)(h->enc[e][l][dr].U - h->d_w);
-          std::vector<float> up((size_t)RV_U * RV_G);
-          for (int i = 0; i < 32; ++i)
-            for (int tid = 0; tid < 512; ++tid) {
-              const int j = tid >> 2, kq = tid & 3;
-              for (int r = 0; r < 4; ++r)
-                up[((size_t)i * 512 + tid) * 4 + r] = blob[off + (size_t)(32 * kq + i) * RV_G + ((kq + r) & 3) * RV_U + j];
-            }
-          float* dst = h->img.Up + ((size_t)(e * h->cfg.enc_depth + l) * 2 + dr) * RV_U * RV_G;
-          HIPCHK(h, hipMemcpy(dst, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-    // ... and as MFMA A fragments of U^T for the matrix-pipe recurrence: wave w, gate g, k-step ks, part p, lane (m = lane%16, kq = lane/16)
-    // holds s_r U[32 ks + 8 kq + j][r], r = 128 g + 16 w + m (s_r: power of two, the column's largest element into [2^13, 2^14))
-    for (int e = 0; e < 2; ++e)
-      for (int l = 0; l < h->cfg.enc_depth; ++l)
-        for (int dr = 0; dr < 2; ++dr) {
-          const size_t off = (size_t)(h->enc[e][l][dr].U - h->d_w);
-          std::vector<uint16_t> ua(RV_UA_SLOT);
-          float cs[RV_G];
-          for (int r = 0; r < RV_G; ++r) {
-            float mx = 0.f;
-            for (int k = 0; k < RV_U; ++k) mx = std::max(mx, std::fabs(blob[off + (size_t)k * RV_G + r]));
-            int ex = 0;
-            if (mx > 0.f && std::isfinite(mx)) std::frexp(mx, &ex);
-            cs[r] = std::ldexp(1.0f, 14 - ex);
-          }
-          for (int w = 0; w < 8; ++w)
-            for (int g = 0; g < 4; ++g)
-              for (int ks = 0; ks < 4; ++ks)
-                for (int ln = 0; ln < 64; ++ln)
-                  for (int j = 0; j < 8; ++j) {
-                    const int r = g * RV_U + 16 * w + (ln & 15);
-                    const float v = blob[off + (size_t)(32 * ks + 8 * (ln >> 4) + j) * RV_G + r] * cs[r];   // exact
-                    const _Float16 hi = (_Float16)v;
-                    const _Float16 lo = (_Float16)(v - (float)hi);
-                    uint16_t hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
-                    const size_t base = ((((size_t)w * 4 + g) * 4 + ks) * 2) * 64 * 8;
-                    ua[base + (size_t)ln * 8 + j] = hb;
-                    ua[base + 64 * 8 + (size_t)ln * 8 + j] = lb;
-                  }
-          for (int r = 0; r < RV_G; ++r) { const float f = std::ldexp(1.0f, -14) / cs[r]; memcpy(&ua[(size_t)2 * RV_U * RV_G + 2 * r], &f, 4); }
-          HIPCHK(h, hipMemcpy(h->img.Ua + ((size_t)(e * h->cfg.enc_depth + l) * 2 + dr) * RV_UA_SLOT, ua.data(), ua.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        }
-    // encoder layers >= 1, both directions' input kernels as the split GEMM's B slabs: column block cb = 2 dir + half holds columns
-    // 256 half .. of direction dir; [cb][8 k-steps][16 tiles][2 parts][64 lanes][8 f16] of the column-scaled kernel, then 1024 factors
-    for (int e = 0; e < 2; ++e)
-      for (int l = 1; l < h->cfg.enc_depth; ++l) {
-        std::vector<uint16_t> img(RV_WX16_SLOT);
-        std::vector<float> b2(2 * RV_G);
-        size_t off[2];
-        for (int dr = 0; dr < 2; ++dr) {
-          const size_t boff = (size_t)(h->enc[e][l][dr].b - h->d_w);
-          off[dr] = (size_t)(h->enc[e][l][dr].W - h->d_w);
-          for (int n = 0; n < RV_G; ++n) b2[(size_t)dr * RV_G + n] = blob[boff + n];
-        }
-        rv_pack_split_image(blob, RV_G, 4, [&](int c) { return off[c / RV_G] + (size_t)(c % RV_G); }, img.data());
-        const size_t slot = (size_t)(e * (h->cfg.enc_depth - 1) + (l - 1));
-        HIPCHK(h, hipMemcpy(h->img.Wx16 + slot * RV_WX16_SLOT, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(h->img.bx2 + slot * 2 * RV_G, b2.data(), b2.size() * sizeof(float), hipMemcpyHostToDevice));
-      }
-    // encoder layers >= 1: W [256][512] -> [32 column tiles][16 k-groups][64 lanes][4]: lane (q = lane/16, col = lane%16)
-    // of tile nt finds W[16 g + 4 i + q][16 nt + col] for its 4 MFMAs i of k-group g in one float4 (lstm_rec.hip)
-    for (int e = 0; e < 2; ++e)
-      for (int l = 1; l < h->cfg.enc_depth; ++l)
-        for (int dr = 0; dr < 2; ++dr) {
-          const size_t off = (size_t)(h->enc[e][l][dr].W - h->d_w);
-          for (int nt = 0; nt < 32; ++nt)
-            for (int g = 0; g < 16; ++g)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int i = 0; i < 4; ++i)
-                  t[(((size_t)nt * 16 + g) * 64 + ln) * 4 + i] = blob[off + (size_t)(16 * g + 4 * i + (ln >> 4)) * RV_G + 16 * nt + (ln & 15)];
-          float* dst = h->img.Wp + ((size_t)(e * (h->cfg.enc_depth - 1) + (l - 1)) * 2 + dr) * RV_E * RV_G;
-          HIPCHK(h, hipMemcpy(dst, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-          // ... and as bf16 parts: lane (kq = lane/16, col = lane%16) of tile nt, k-step ks holds W[32 ks + 8 kq + j][16 nt + col], j = 0..7
-          std::vector<uint16_t> sb((size_t)3 * RV_E * RV_G);
-          for (int nt = 0; nt < 32; ++nt)
-            for (int ks = 0; ks < 8; ++ks)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int j = 0; j < 8; ++j) {
-                  float r = blob[off + (size_t)(32 * ks + 8 * (ln >> 4) + j) * RV_G + 16 * nt + (ln & 15)];
-                  for (int part = 0; part < 3; ++part) {
-                    const uint16_t b = bf16_rne(r);
-                    sb[((((size_t)nt * 3 + part) * 8 + ks) * 64 + ln) * 8 + j] = b;
-                    r -= bf16_value(b);                    // exact
-                  }
-                }
-          // ... and as two f16 parts of s_n W (s_n: power of two, column maximum into [2^13, 2^14]), then the factors 2^-14 / s_n
-          std::vector<uint16_t> wh(RV_WH_SLOT);
-          float cs[RV_G];
-          for (int n = 0; n < RV_G; ++n) {
-            float mx = 0.f;
-            for (int k = 0; k < RV_E; ++k) mx = std::max(mx, std::fabs(blob[off + (size_t)k * RV_G + n]));
-            int ex = 0;
-            if (mx > 0.f && std::isfinite(mx)) std::frexp(mx, &ex);     // mx = m 2^ex, m in [0.5, 1)
-            cs[n] = std::ldexp(1.0f, 14 - ex);                           // s_n; mx s_n in [2^13, 2^14)
-          }
-          for (int nt = 0; nt < 32; ++nt)
-            for (int ks = 0; ks < 8; ++ks)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int j = 0; j < 8; ++j) {
-                  const int n = 16 * nt + (ln & 15);
-                  const float v = blob[off + (size_t)(32 * ks + 8 * (ln >> 4) + j) * RV_G + n] * cs[n];   // exact
-                  const _Float16 hi = (_Float16)v;
-                  const _Float16 lo = (_Float16)((v - (float)hi) * 2048.f);
-                  uint16_t hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
-                  wh[((((size_t)nt * 2 + 0) * 8 + ks) * 64 + ln) * 8 + j] = hb;
-                  wh[((((size_t)nt * 2 + 1) * 8 + ks) * 64 + ln) * 8 + j] = lb;
-                }
-          for (int n = 0; n < RV_G; ++n) { const float f = std::ldexp(1.0f, -14) / cs[n]; memcpy(&wh[(size_t)2 * RV_E * RV_G + 2 * n], &f, 4); }
-          HIPCHK(h, hipMemcpy(h->img.Wh + ((size_t)(e * (h->cfg.enc_depth - 1) + (l - 1)) * 2 + dr) * RV_WH_SLOT, wh.data(), wh.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-          uint16_t* dsb = h->img.Wsb + ((size_t)(e * (h->cfg.enc_depth - 1) + (l - 1)) * 2 + dr) * 3 * RV_E * RV_G;
-          HIPCHK(h, hipMemcpy(dsb, sb.data(), sb.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        }
-    {   // [W_mem | A_c] [256][256]: column block 0 = W_mem (keys), column block 1 = rows 128..383 of the attention layer
-        // (its context part), so that enc_out . Wmp = [keys | image of the values under the attention layer]
-      const size_t mo = (size_t)(h->W_mem - h->d_w), ao = (size_t)(h->W_att - h->d_w) + (size_t)RV_U * RV_U;
-      std::vector<float> wmp((size_t)RV_E * RV_E);
-      for (int kk = 0; kk < RV_E; ++kk)
-        for (int n = 0; n < RV_U; ++n) {
-          wmp[(size_t)kk * RV_E + n] = blob[mo + (size_t)kk * RV_U + n];
-          wmp[(size_t)kk * RV_E + RV_U + n] = blob[ao + (size_t)kk * RV_U + n];
-        }
-      HIPCHK(h, hipMemcpy(h->img.Wmp, wmp.data(), wmp.size() * sizeof(float), hipMemcpyHostToDevice));
-      {   // |enc_out| <= 1, so |key_tu| <= sum_k |W_mem[k][u]| and |U'_tn| <= sum_k |A_c[k][n]|: the largest column sums bound both
-        double bk = 0.0, bu = 0.0;
-        for (int n = 0; n < RV_E; ++n) {
-          double cs = 0.0;
-          for (int kk = 0; kk < RV_E; ++kk) cs += std::fabs((double)wmp[(size_t)kk * RV_E + n]);
-          if (n < RV_U) bk = std::max(bk, cs); else bu = std::max(bu, cs);
-        }
-        auto pow2_scale = [](double bound) { int ex = 0; if (bound > 0.0 && std::isfinite(bound)) std::frexp(bound * 1.0001, &ex); return std::ldexp(1.0f, 14 - ex); };
-        h->mx_kscale = pow2_scale(bk); h->mx_uscale = pow2_scale(bu);
-      }
-      std::vector<uint16_t> img(RV_WMP16_SLOT);
-      rv_pack_split_image(wmp.data(), RV_E, 1, [](int c) { return (size_t)c; }, img.data());
-      HIPCHK(h, hipMemcpy(h->img.Wmp16, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-      // the same f16 parts of the W_mem half, for the decode's own projection (DecState::Wkp16): lane (i, kq) of key tile 2 ks + y
-      // takes what lane (c % 16, kq) of column tile c / 16 holds, c = 32 ks + 8 (i / 4) + 4 y + i % 4
-      std::vector<uint16_t> kimg(RV_WKP16_SLOT);
-      for (int st = 0; st < 8; ++st)
-        for (int t8 = 0; t8 < 8; ++t8)
-          for (int part = 0; part < 2; ++part)
-            for (int ln = 0; ln < 64; ++ln) {
-              const int i = ln & 15, q = ln >> 4, c = 32 * (t8 >> 1) + 8 * (i >> 2) + 4 * (t8 & 1) + (i & 3);
-              memcpy(&kimg[((((size_t)st * 8 + t8) * 2 + part) * 64 + ln) * 8],
-                     &img[((((size_t)st * 16 + c / 16) * 2 + part) * 64 + 16 * q + c % 16) * 8], 8 * sizeof(uint16_t));
-            }
-      HIPCHK(h, hipMemcpy(h->img.Wkp16, kimg.data(), kimg.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    }
-    if (h->cfg.dec_depth <= 2) {
-      // attention = h . A_h + ctx' (h = the top cell's output); its h part is folded into what consumes the attention vector (products in double):
-      //   one cell : next cell input  [ctx' | h] . [W_a ; U + A_h W_a],                 logits  ctx' . W_fc + h . (A_h W_fc) + b
-      //   two cells: cell 0's input   [ctx' | h_1 | h_0] . [W_a ; A_h W_a ; U_0],       logits  ctx' . W_fc + h_1 . (A_h W_fc) + b
-      const int V = h->cfg.vocab;
-      const bool two = h->cfg.dec_depth == 2;
-      const int KR = two ? 3 * RV_U : RV_E;                 // rows of cell 0's folded kernel
-      const size_t wa = (size_t)(h->dec[0].W - h->d_w) + (size_t)V * RV_G, uo = (size_t)(h->dec[0].U - h->d_w);
-      const size_t ah = (size_t)(h->W_att - h->d_w), fc = (size_t)(h->W_fc - h->d_w);
-      std::vector<float> w2((size_t)KR * RV_G), nh((size_t)RV_U * RV_MAX_VOCAB, 0.f);
-      for (int i = 0; i < RV_U; ++i)
-        for (int n = 0; n < RV_G; ++n) {
-          w2[(size_t)i * RV_G + n] = blob[wa + (size_t)i * RV_G + n];
-          double acc = two ? 0.0 : (double)blob[uo + (size_t)i * RV_G + n];
-          for (int j = 0; j < RV_U; ++j) acc += (double)blob[ah + (size_t)i * RV_U + j] * (double)blob[wa + (size_t)j * RV_G + n];
-          w2[(size_t)(RV_U + i) * RV_G + n] = (float)acc;
-          if (two) w2[(size_t)(2 * RV_U + i) * RV_G + n] = blob[uo + (size_t)i * RV_G + n];
-        }
-      for (int i = 0; i < RV_U; ++i)
-        for (int v = 0; v < V; ++v) {
-          double acc = 0.0;
-          for (int j = 0; j < RV_U; ++j) acc += (double)blob[ah + (size_t)i * RV_U + j] * (double)blob[fc + (size_t)j * V + v];
-          nh[(size_t)i * V + v] = (float)acc;
-        }
-      // the scales of the matrix-pipe images of both folded tensors (Wc16, Wl16 below): rows divided by the factor their input's f16
-      // image carries (exact: powers of two), then one power-of-two scale for the tensor
-      auto xs = [&](int k) { return k < RV_U ? h->mx_uscale : 16384.f; };
-      float mx = 0.f;
-      for (int k = 0; k < KR; ++k)
-        for (int n = 0; n < RV_G; ++n) mx = std::max(mx, std::fabs(w2[(size_t)k * RV_G + n] / xs(k)));
-      int ex = 0;
-      if (mx > 0.f && std::isfinite(mx)) std::frexp(mx, &ex);
-      const float T = std::ldexp(1.0f, 14 - ex);
-      std::vector<float> fcw(blob + fc, blob + fc + (size_t)RV_U * V);      // W_fc, the output layer's upper half
-      auto wl = [&](int k, int v) -> float {
-        if (v >= V) return 0.f;
-        return (k < RV_U ? fcw[(size_t)k * V + v] : nh[(size_t)(k - RV_U) * V + v]) / xs(k);
-      };
-      float ml = 0.f;
-      for (int k = 0; k < RV_E; ++k)
-        for (int v = 0; v < V; ++v) ml = std::max(ml, std::fabs(wl(k, v)));
-      int el = 0;
-      if (ml > 0.f && std::isfinite(ml)) std::frexp(ml, &el);
-      const float Tl = std::ldexp(1.0f, 14 - el);
-      if (one_part) {   // weight_parts 1: both folded tensors rounded to the first f16 part of those images, under the scales just taken
-                        // (kept for the packing below), so that their fp32 images (Wcat2, Nh) carry the same numbers
-        for (int k = 0; k < KR; ++k)
-          for (int n = 0; n < RV_G; ++n) w2[(size_t)k * RV_G + n] = rv_round_to_first_part(w2[(size_t)k * RV_G + n] / xs(k), T) * xs(k);
-        for (int k = 0; k < RV_E; ++k)
-          for (int v = 0; v < V; ++v)
-            (k < RV_U ? fcw[(size_t)k * V + v] : nh[(size_t)(k - RV_U) * V + v]) = rv_round_to_first_part(wl(k, v), Tl) * xs(k);
-      }
-      if (!two) HIPCHK(h, hipMemcpy(h->img.Wcat2, w2.data(), w2.size() * sizeof(float), hipMemcpyHostToDevice));     // (the packed-FMA form of one cell)
-      HIPCHK(h, hipMemcpy(h->img.Nh, nh.data(), nh.size() * sizeof(float), hipMemcpyHostToDevice));
-      {   // the same kernel for the matrix-pipe cell product (DecState::Wc16): two f16 parts in B-fragment order per wave
-        h->mx_cdescale = 1.0f / T;
-        const int NP = KR / 8;                              // (k-step, gate) pairs per wave: 32, or 48 with two cells
-        std::vector<uint16_t> img((size_t)2 * KR * RV_G);
-        for (int wv = 0; wv < 8; ++wv)
-          for (int pr = 0; pr < NP; ++pr)
-            for (int ln = 0; ln < 64; ++ln)
-              for (int j = 0; j < 8; ++j) {
-                const int ks = pr >> 2, g = pr & 3, k = 32 * ks + 8 * (ln >> 4) + j, n = RV_U * g + 16 * wv + (ln & 15);
-                const float v = (w2[(size_t)k * RV_G + n] / xs(k)) * T;
-                const _Float16 hi = (_Float16)v;
-                const _Float16 lo = (_Float16)(v - (float)hi);
-                uint16_t hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
-                img[(((((size_t)wv * NP + pr) * 2 + 0) * 64) + ln) * 8 + j] = hb;
-                img[(((((size_t)wv * NP + pr) * 2 + 1) * 64) + ln) * 8 + j] = lb;
-              }
-        HIPCHK(h, hipMemcpy(h->img.Wc16, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        if (one_part && !two) {   // the first parts alone (the second are zero), [wave][pair][64 lanes][8 f16]: k_dec_persist_1p
-          std::vector<uint16_t> p1((size_t)RV_E * RV_G);
-          for (size_t fr = 0; fr < (size_t)8 * NP; ++fr) memcpy(&p1[fr * 512], &img[fr * 1024], 512 * sizeof(uint16_t));
-          HIPCHK(h, hipMemcpy(h->img.Wc16p1, p1.data(), p1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        }
-        if (two) {   // cell 1's kernels on h_0 (W_1) and on h_1 (U_1): DecState::W1c16, rows divided by the 2^14 their inputs' images carry
-          const size_t w1 = (size_t)(h->dec[1].W - h->d_w), u1 = (size_t)(h->dec[1].U - h->d_w);
-          float m1 = 0.f;
-          for (size_t i = 0; i < (size_t)RV_U * RV_G; ++i) m1 = std::max(m1, std::max(std::fabs(blob[w1 + i]), std::fabs(blob[u1 + i])) / 16384.f);
-          int e1 = 0;
-          if (m1 > 0.f && std::isfinite(m1)) std::frexp(m1, &e1);
-          const float T1 = std::ldexp(1.0f, 14 - e1);
-          h->mx_c1descale = 1.0f / T1;
-          std::vector<uint16_t> i1((size_t)2 * RV_E * RV_G);
-          for (int wv = 0; wv < 8; ++wv)
-            for (int pr = 0; pr < 32; ++pr)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int j = 0; j < 8; ++j) {
-                  const int ks = (pr & 15) >> 2, g = pr & 3, k = 32 * ks + 8 * (ln >> 4) + j, n = RV_U * g + 16 * wv + (ln & 15);
-                  const float v = (blob[(pr < 16 ? w1 : u1) + (size_t)k * RV_G + n] / 16384.f) * T1;
-                  const _Float16 hi = (_Float16)v;
-                  const _Float16 lo = (_Float16)(v - (float)hi);
-                  uint16_t hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
-                  i1[(((((size_t)wv * 32 + pr) * 2 + 0) * 64) + ln) * 8 + j] = hb;
-                  i1[(((((size_t)wv * 32 + pr) * 2 + 1) * 64) + ln) * 8 + j] = lb;
-                }
-          HIPCHK(h, hipMemcpy(h->img.W1c16, i1.data(), i1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        }
-        // the output layer on the same [ctx' | h] image: logits = ctx' . W_fc + h . (A_h W_fc) + b_fc; columns >= V are zero
-        h->mx_ldescale = 1.0f / Tl;
-        std::vector<uint16_t> li((size_t)2 * RV_E * 16);
-        for (int ks = 0; ks < 8; ++ks)
-          for (int ln = 0; ln < 64; ++ln)
-            for (int j = 0; j < 8; ++j) {
-              const float v = wl(32 * ks + 8 * (ln >> 4) + j, ln & 15) * Tl;
-              const _Float16 hi = (_Float16)v;
-              const _Float16 lo = (_Float16)(v - (float)hi);
-              uint16_t hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
-              li[(((size_t)ks * 2 + 0) * 64 + ln) * 8 + j] = hb;
-              li[(((size_t)ks * 2 + 1) * 64 + ln) * 8 + j] = lb;
-            }
-        HIPCHK(h, hipMemcpy(h->img.Wl16, li.data(), li.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        if (one_part) {   // its first parts alone, [8 k-steps][64 lanes][8 f16]
-          std::vector<uint16_t> p1((size_t)RV_E * 16);
-          for (int ks = 0; ks < 8; ++ks) memcpy(&p1[(size_t)ks * 512], &li[(size_t)ks * 1024], 512 * sizeof(uint16_t));
-          HIPCHK(h, hipMemcpy(h->img.Wl16p1, p1.data(), p1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        }
-        if (!two) {   // Bahdanau's query layer W_q [128][128] for the matrix pipe (DecState::Wq16): one power-of-two scale, two f16 parts, per-wave B fragments
-          const size_t qo = (size_t)(h->W_q - h->d_w);
-          float mq = 0.f;
-          for (size_t i = 0; i < (size_t)RV_U * RV_U; ++i) mq = std::max(mq, std::fabs(blob[qo + i]));
-          int eq = 0;
-          if (mq > 0.f && std::isfinite(mq)) std::frexp(mq, &eq);
-          const float Tq = std::ldexp(1.0f, 14 - eq);
-          h->mx_qdescale = std::ldexp(1.0f, -14) / Tq;
-          std::vector<uint16_t> qi((size_t)2 * RV_U * RV_U);
-          for (int wv = 0; wv < 8; ++wv)
-            for (int ks = 0; ks < 4; ++ks)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int j = 0; j < 8; ++j) {
-                  const float v = blob[qo + (size_t)(32 * ks + 8 * (ln >> 4) + j) * RV_U + 16 * wv + (ln & 15)] * Tq;
-                  const _Float16 hi = (_Float16)v;
-                  const _Float16 lo = (_Float16)(v - (float)hi);
-                  uint16_t hb, lb; memcpy(&hb, &hi, 2); memcpy(&lb, &lo, 2);
-                  qi[((((size_t)wv * 4 + ks) * 2 + 0) * 64 + ln) * 8 + j] = hb;
-                  qi[((((size_t)wv * 4 + ks) * 2 + 1) * 64 + ln) * 8 + j] = lb;
-                }
-          HIPCHK(h, hipMemcpy(h->img.Wq16, qi.data(), qi.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        }
-      }
-    }
-    const size_t moff = (size_t)(h->W_mem - h->d_w);       // W_mem [256][128] -> [128][256]
-    std::vector<float> m((size_t)RV_U * RV_E);
-    for (int i = 0; i < RV_E; ++i)
-      for (int j = 0; j < RV_U; ++j) m[(size_t)j * RV_E + i] = blob[moff + (size_t)i * RV_U + j];
-    HIPCHK(h, hipMemcpy(h->img.WmemT, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
+  const wimg::HostImages im = wimg::build_weight_images(h->cfg, h->rnn, h->opt.weight_parts, blob);
+  h->scales = im.scales;
+#define X(T, name, count) TRY(upload_image(h, h->img.name, im.name.data(), im.name.size() * sizeof(T)));
+  RV_WEIGHT_IMAGES(X)
+#undef X
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->loaded = true;
   return RV_OK;
