@@ -1,5 +1,5 @@
 // Device probe of the projection GEMMs (csrc/gemm_f32.hip): k_gemm_f32<2,2,16> through launch_gemm_f32 with the three argument sets
-// the library uses, and k_gemm_mem_split3<1> / k_gemm_ws through launch_gemm_split_blocks with ncb = 1 / 4, on chosen A, W, bias and M.
+// the library uses, and k_gemm_mem_split3<1> / k_gemm_ws through launch_gemm_split_blocks with ncb = 1 / 3 and 4, on chosen A, W, bias and M.
 // Built by `make libravvent_gemmprobe.so` in csrc with the library's flags and linked with the library's gemm_f32.o and its weight-image
 // packer (csrc/split_image.h); tests/test_gemm_probe_gpu.py loads it through ctypes and holds the kernels to numpy fp64.
 //
@@ -61,7 +61,7 @@ extern "C" int rv_gemm_probe_guard_rows() { return RV_PROBE_GUARD; }
 
 // The weight image alone (host code; no device needed): W [256][ld] (ld >= 256 ncb) -> img, RV_WMP16_SLOT / RV_WX16_SLOT uint16
 extern "C" int rv_gemm_probe_pack(const float* W, int ld, int ncb, uint16_t* img) {
-  if ((ncb != 1 && ncb != 4) || ld < RV_E * ncb) return -1;
+  if ((ncb != 1 && ncb != 3 && ncb != 4) || ld < RV_E * ncb) return -1;
   rv_pack_split_image(W, (size_t)ld, ncb, [](int c) { return (size_t)c; }, img);
   return 0;
 }
@@ -104,10 +104,12 @@ extern "C" int rv_gemm_probe_f32(int set, const float* A, int M, const float* W0
 }
 
 // launch_gemm_split_blocks: C [M][ldc] (columns 0 .. 256 ncb) = A [M][256] . W [256][256 ncb] (+ bias [256 ncb], may be null), with W
-// packed by rv_pack_split_image first.  ncb = 1: k_gemm_mem_split3<1>; ncb = 4: k_gemm_ws.  ldc >= 256 ncb, a multiple of 4.
+// packed by rv_pack_split_image first.  ncb = 1: k_gemm_mem_split3<1> (the attention-memory projection); ncb = 3: k_gemm_ws over six
+// half column blocks (both directions of a BiGRU layer >= 1, N = 768); ncb = 4: k_gemm_ws over eight (of a BiLSTM layer >= 1, N = 1024).
+// ldc >= 256 ncb, a multiple of 4.
 // C_out [M + guard][ldc].
 extern "C" int rv_gemm_probe_split(int ncb, const float* A, int M, const float* W, const float* bias, int ldc, uint32_t fill, float* C_out) {
-  if ((ncb != 1 && ncb != 4) || M <= 0 || !A || !W || !C_out || ldc < RV_E * ncb || ldc % 4) return -1;
+  if ((ncb != 1 && ncb != 3 && ncb != 4) || M <= 0 || !A || !W || !C_out || ldc < RV_E * ncb || ldc % 4) return -1;
   hipError_t e = configure_once();
   if (e != hipSuccess) return (int)e;
   const int N = RV_E * ncb;

@@ -4,7 +4,9 @@
   k_gemm_f32<2,2,16>   through launch_gemm_f32 with the library's three argument sets: "keys" (N = 128, row mask, plain grid),
                        "memory" (N = 256, xcd_remap) and "inproj" (N = 512, both directions as two problems, biases, ldc = 1024, xcd_remap);
   k_gemm_mem_split3<1> through launch_gemm_split_blocks with ncb = 1 ("split1": the default attention-memory projection);
-  k_gemm_ws            through launch_gemm_split_blocks with ncb = 4 ("ws": the default input projection of encoder layers >= 1).
+  k_gemm_ws            through launch_gemm_split_blocks with ncb = 4 ("ws": the default input projection of encoder layers >= 1)
+                       and with ncb = 3 ("ws3": N = 768, the input projection of a BiGRU layer >= 1 -- six half column blocks, so the
+                       workgroup id is taken modulo a non-power of two, and up to five row-group multiples where ncb = 4 has four).
 
 Reference and bound.  ref = A64 @ W64 + b in fp64; the fp32 chain twin is the k-ordered chain the kernel file's header says the
 f32 kernel is: acc = fl32(acc + a_k w_k), k = 0..255 (product and sum in fp64, rounded once per step), + b rounded once more.  The
@@ -15,7 +17,9 @@ except the classes of A named in SPLIT_TERM_CLASSES on the split kernels, which 
 Rows.  A[r] = base[r % NBASE]: reference and twin exist for the NBASE base rows only, every row of C is held to the first row with
 the same base row BIT FOR BIT (a row's arithmetic does not depend on the tile, wave or lane that ran it), and those first rows to
 the reference.  The row counts come from the launchers' arithmetic, restated below.  The probe surrounds C with guard rows and, where
-ldc > N, guard columns, all prefilled with one NaN pattern: the guards must keep it and no element of [M, N] may."""
+ldc > N, guard columns, all prefilled with one NaN pattern: the guards must keep it and no element of [M, N] may.  For "ws3" this is
+what shows that each of the six 128-column halves of C is written by some workgroup and that none of them lands outside [M, 768]: a
+half skipped or taken twice by `ch = (id >> 3) % nch` leaves the pattern in its columns (run_kernel)."""
 import ctypes
 import os
 
@@ -41,15 +45,17 @@ FILL = 0x7FC5A5A5                 # the prefill of C: a NaN no arithmetic produc
 SPLIT_TERM = 3 * 2.0 ** -22
 SPLIT_TERM_CLASSES = ("scale20", "scale30", "onehot")
 
-KERNELS = ("keys", "memory", "inproj", "split1", "ws")
-NCOLS = {"keys": 128, "memory": 256, "inproj": 1024, "split1": 256, "ws": 1024}
-IS_SPLIT = {"keys": False, "memory": False, "inproj": False, "split1": True, "ws": True}
+KERNELS = ("keys", "memory", "inproj", "split1", "ws", "ws3")
+NCOLS = {"keys": 128, "memory": 256, "inproj": 1024, "split1": 256, "ws": 1024, "ws3": 768}
+IS_SPLIT = {"keys": False, "memory": False, "inproj": False, "split1": True, "ws": True, "ws3": True}
+WS_NCB = {"ws": 4, "ws3": 3}      # column blocks of the two k_gemm_ws entries
 
 
 # ---------------------------------------------------------------- the launchers' arithmetic (csrc/gemm_f32.hip), restated
-def ws_geometry(M):
-    """launch_gemm_split_blocks, ncb = 4 -> k_gemm_ws: (k, ntile, tiles of the busiest wave)."""
-    nch, nw = 2 * 4, 768 // 64
+def ws_geometry(M, ncb=4):
+    """launch_gemm_split_blocks, ncb = 4 or 3 -> k_gemm_ws: (k, ntile, tiles of the busiest wave).  ncb = 4: eight half column blocks,
+    k starts at 256 / 64 = 4; ncb = 3: six, k starts at 256 / 48 = 5."""
+    nch, nw = 2 * ncb, 768 // 64
     ntile = (M + 31) // 32
     k = 256 // (8 * nch)
     while k > 1 and 8 * (k - 1) * nw >= ntile:
@@ -58,24 +64,26 @@ def ws_geometry(M):
     return k, ntile, (ntile + tstride - 1) // tstride
 
 
-def _ws_rows():
+def _ws_rows(ncb=4):
+    geo = lambda m: ws_geometry(m, ncb)
     small = [1, 8, 9, 31, 32, 33, 32 * 8 - 1, 32 * 8 + 1]                       # ... ntile 8 and 9
-    assert [ws_geometry(m)[1] for m in small[-2:]] == [8, 9]
+    assert [geo(m)[1] for m in small[-2:]] == [8, 9]
     edges = []
-    kmax = ws_geometry(1 << 20)[0]
+    kmax = geo(1 << 20)[0]
+    assert kmax == {4: 4, 3: 5}[ncb]                                            # ncb = 3 reaches a row-group multiple ncb = 4 never does
     for k in range(1, kmax):                                                    # the largest M that still selects k row-group multiples
-        m = max(m for m in range(32, 1 << 15, 32) if ws_geometry(m)[0] == k)
-        assert ws_geometry(m + 1)[0] == k + 1
+        m = max(m for m in range(32, 1 << 15, 32) if geo(m)[0] == k)
+        assert geo(m + 1)[0] == k + 1
         edges.append(m)
-    m = max(m for m in range(32, 1 << 16, 32) if ws_geometry(m)[2] == 1)        # the largest M without a second tile per wave
-    assert ws_geometry(m) == (kmax, 96 * kmax, 1) and ws_geometry(m + 1)[2] == 2
+    m = max(m for m in range(32, 1 << 16, 32) if geo(m)[2] == 1)                # the largest M without a second tile per wave
+    assert geo(m) == (kmax, 96 * kmax, 1) and geo(m + 1)[2] == 2
     edges.append(m)
     large = []
     for m in edges:                                                             # M % 32 == 0, in 1..8 (past the edge), in 9..31 (before it)
         large += [m - 15, m, m + 1]
-    m3 = min(m for m in range(32, 1 << 16, 32) if ws_geometry(m + 1)[2] == 3)   # ... and past a third tile: the three residues again
+    m3 = min(m for m in range(32, 1 << 16, 32) if geo(m + 1)[2] == 3)           # ... and past a third tile: the three residues again
     large += [m3 + 1, m3 + 32 + 20, m3 + 64]
-    assert all(ws_geometry(m)[2] == 3 for m in large[-3:])
+    assert all(geo(m)[2] == 3 for m in large[-3:])
     assert {m % 32 == 0 for m in large} == {True, False} and any(1 <= m % 32 <= 8 for m in large) and any(m % 32 >= 9 for m in large)
     return small + large
 
@@ -90,7 +98,7 @@ def _f32_rows():
     return [1, bm - 1, bm, bm + 1, pad * bm, pad * bm + 1, 3 * pad * bm + 1]
 
 
-ROW_CASES = ([("ws", m) for m in _ws_rows()] + [("split1", m) for m in _split1_rows()]
+ROW_CASES = ([("ws", m) for m in _ws_rows(4)] + [("ws3", m) for m in _ws_rows(3)] + [("split1", m) for m in _split1_rows()]
              + [(kern, m) for kern in ("keys", "memory", "inproj") for m in _f32_rows()])
 
 
@@ -150,6 +158,7 @@ def run_kernel(kern, A, W, bias, mask=None, guard_cols=0):
     assert (bits[M:] == FILL).all(), f"{kern}, M = {M}: a guard row was written"
     assert (bits[:, N:] == FILL).all(), f"{kern}, M = {M}: a guard column was written"
     inside = bits[:M, :N] == FILL
+    # (relied on for "ws3", nch = 6: every one of the six 128-column halves written, by whichever workgroup `% nch` gives it to)
     assert not inside.any(), f"{kern}, M = {M}: {int(inside.sum())} elements never written, first at {np.argwhere(inside)[:4].tolist()}"
     return C[:M, :N]
 

@@ -207,3 +207,32 @@ def test_case_biases_are_observable(rv):
     d = float(np.abs((z * h + (1 - z) * outside) - G.gru_cell(x, h, W, U, b)).max())
     print(f"b[1]_h outside r * (.): h' moves by {d:.2e}")
     assert d > 1e-2
+
+
+# ---------------------------------------------------------------------------------------------- the adversarial weights reach their regime
+@pytest.mark.parametrize("saturate", [False, True], ids=["plain", "saturated"])
+@pytest.mark.parametrize("col_gain", C.ADV_GAINS)
+def test_adversarial_encoder_recipe_reaches_its_regime(rv, col_gain, saturate):
+    """On the reference alone: with saturation more than 0.3 of |enc_output| lies within 2^-20 of 1 (the 2^14 image of h at its edge);
+    without it the gained columns' recurrent pre-activations exceed 10 somewhere.  |h| <= 1 in fp64 and in the twin's own arithmetic,
+    and the twin's error is finite: the probe is one an honest fp32 evaluation passes."""
+    a = C.adversarial_encoder(rv, col_gain, saturate)
+    print(f"adversarial encoder gain {col_gain:g} {'saturated' if saturate else 'plain'}: saturated share {a['saturated']:.3f}, "
+          f"largest gained pre-activation {a['preact']:.1f}, twin enc_output {a['twin']['enc_output']:.1e} keys {a['twin']['keys']:.1e}")
+    assert np.abs(a["enc_output"]).max() <= 1.0 and a["mask"].any(axis=1).all()
+    if saturate:
+        assert a["saturated"] > 0.3, a["saturated"]
+    else:
+        assert a["preact"] > 10.0, a["preact"]
+    assert all(np.isfinite(v) for v in a["twin"].values())
+
+
+@pytest.mark.parametrize("dec_depth", [1, 2])
+def test_adversarial_decoder_recipe_is_a_fair_probe(rv, dec_depth):
+    """On the reference alone: every chunk runs all L - 1 steps, and the fp32 twin leaves the fp64 beam on at most B // 4 chunks (_stays,
+    inside adversarial_decoder) at the L of ADV_DEC; the gained h columns' recurrent pre-activations reach tens."""
+    a = C.adversarial_decoder(rv, dec_depth)
+    c = a["case"]
+    assert a["taps"]["step_ids"].shape[0] == c.L - 1 and c.L <= 16
+    print(f"adversarial decoder dec_depth {dec_depth}: twin " + ", ".join(f"{k} {v:.1e}" for k, v in a["twin"].items()))
+    assert all(np.isfinite(v) for v in a["twin"].values())

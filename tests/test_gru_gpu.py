@@ -8,10 +8,16 @@ kernels can go wrong:
   chain-*   layer l + 1 starting from layer l's final states, and the three-block input GEMM at M = 119 (a partial row tile), 300, 60;
   cell-*    k_dec_cell_gru's 64-row workgroup at N = B W = 1, 64, 65, one to three stacked cells, both attentions;
   search-*  greedy and beam 1, 2, 5, 8 on one slab of seventeen chunks;
-  allpad-*  one chunk that is padding from end to end: NaN where the reference has NaN, its neighbours untouched.
+  allpad-*  one chunk that is padding from end to end: NaN where the reference has NaN, its neighbours untouched;
+  lds-*     the layer-0 event form's dynamic LDS on either side of 64 KB (T_e = 115, 116: where the opt-in of configure_gru_kernels starts to
+            matter) and at the decode's 352 steps;
+  long-*    the F = 1 form and the F = 0 input ring over 352 steps, the chunker's 200 + 30 (k = 2 of the three-block GEMM), 100 + 252 with
+            T_m = 352 through the per-step attend, and the two-pass Bahdanau attend at T_m = 352 under a GRU cell;
+  gemm-k5   raw M = 13,000: the three-block GEMM with k = 5 row-group multiples, the geometry of the shipped 1024 x 200 shape.
 Every case holds enc_output, mask, keys, step logits and step alignments to TOL of fp64 and to TWIN_K x the fp32 twin + TWIN_C; a
 chunk may leave the fp64 decode only through a near-tie narrower than twice the logits bound.  Then the outer interfaces, one case each,
-and the refusals."""
+the refusals (options; windows that do not fit the 160 KB of LDS, both sides of each edge), and adversarial weights: the split-f16 image
+of U and the 2^14 image of h under large and tiny rows, gained columns and saturated activations; the decoder cell under a gain of 50."""
 import numpy as np
 import pytest
 
@@ -27,7 +33,7 @@ def _open(rv, c, **kw):
     bc = rv.Basecaller(128, 128, 128, rv.data_loader.nuc_tk, c.mode, 0.0, encoder_depth=c.enc_depth, decoder_depth=c.dec_depth,
                        rnn_type="bigru", attention_type=c.attention, honor_attention_type=True, max_batch=kw.get("max_batch", c.B),
                        max_raw_len=max(c.Tr, 1), max_event_len=max(c.Te, 1), max_output_len=kw.get("L", c.L), max_beam=kw.get("max_beam", max(c.W, 1)))
-    flat, _ = C.weights(rv, c.enc_depth, c.dec_depth, c.mode, c.attention)
+    flat = kw.get("flat") or C.weights(rv, c.enc_depth, c.dec_depth, c.mode, c.attention)[0]
     bc.set_weights_flat(flat)
     return bc
 
@@ -99,7 +105,7 @@ def test_case_against_fp64_and_twin(rv, name):
             assert np.array_equal(np.isnan(sc), np.isnan(r["out"][1])), name
     assert len(left) <= len(keep) // 4, (name, "chunks that left the fp64 decode", left)
     err.update(e)
-    print(f"{name}: " + ", ".join(f"{k} {v:.2e}" for k, v in err.items()))
+    print(f"{name}: " + ", ".join(f"{k} {v:.2e}" for k, v in err.items()) + f"; chunks that left the fp64 decode: {[keep[i] for i in left]}")
     for k, v in err.items():
         assert v < TOL, (name, k, v)
     _assert_twin(err, twin, name)
@@ -351,3 +357,140 @@ def test_refused_options_and_a_bilstm_handle_beside(rv, world):
     import ctypes
     ccfg, h = bc.cfg.to_c(), ctypes.c_void_p()
     assert bc._lib.rv_create_rnn(ctypes.byref(ccfg), 2, ctypes.byref(h)) == -5 and not h, "a family that is not built: RV_EUNSUPPORTED, no handle"
+
+
+# ---------------------------------------------------------------------------------------------- windows that do not fit in LDS
+def _gru_lds_bytes(F, T):
+    """gru_lds_bytes of csrc/gru_mx.hip, restated: the h image (16 KB), 384 factors and 384 recurrent biases, and for a layer-0 form
+    (F > 0) its F + 1 rows of 384 input weights / biases and the sixteen chunks' windows of T steps x F features, as floats."""
+    return 16384 + 4 * (2 * 384 + ((F + 1) * 384 + 16 * T * F if F > 0 else 0))
+
+
+LDS_LIMIT = 160 * 1024
+DECODE_STEPS = 352                  # the attention memory the decode kernels are built for
+
+
+def _last_fit(F):
+    return max(T for T in range(1, 1 << 14) if _gru_lds_bytes(F, T) <= LDS_LIMIT)
+
+
+def test_windows_beyond_the_lds_are_refused_and_the_last_that_fit_work(rv):
+    """rv_create_rnn on both sides of each LDS edge of k_gru_rec_mx's layer-0 forms: the first max_event_len / max_raw_len that does not
+    fit is RV_EUNSUPPORTED by name, with no handle; the last that fits gives a handle that works at the decode's 352 steps, returns the
+    bytes of a handle sized to the call, refuses T_m = 353 by name and works on.  (The case names lds-event-T115 / T116 are the two sides
+    of 64 KB by the same formula.)"""
+    import ctypes
+    te, tr = _last_fit(5), _last_fit(1)
+    assert _gru_lds_bytes(5, te) <= LDS_LIMIT < _gru_lds_bytes(5, te + 1) and (te, tr) == (422, 2208)
+    assert _gru_lds_bytes(1, tr) == LDS_LIMIT < _gru_lds_bytes(1, tr + 1), "2208 samples take the 160 KB exactly"
+    assert _gru_lds_bytes(5, 115) < 64 * 1024 < _gru_lds_bytes(5, 116) and _gru_lds_bytes(5, DECODE_STEPS) == 141312
+    lib = rv._capi.load_library()
+    for mode, key, T in (("event", "max_event_len", te + 1), ("joint", "max_event_len", te + 1), ("raw", "max_raw_len", tr + 1),
+                         ("joint", "max_raw_len", tr + 1)):
+        cfg = rv.config.RvConfig(mode=mode, rnn="bigru", max_batch=2, **{key: T})
+        ccfg, h = cfg.to_c(), ctypes.c_void_p()
+        rc = lib.rv_create_rnn(ctypes.byref(ccfg), 1, ctypes.byref(h))
+        msg = (lib.rv_last_error(None) or b"").decode()
+        assert rc == -5 and not h, (mode, key, T, rc)
+        assert "bigru" in msg and key in msg and str(T) in msg and "160 KB" in msg, (mode, key, msg)
+    # the longest raw window that fits: a handle, and a call at the decode's limit on it
+    long_raw = C.BY_NAME["long-raw-T352"]
+    r = C.fp64(rv, long_raw.name)
+    bc = rv.Basecaller(128, 128, 128, rv.data_loader.nuc_tk, "raw", 0.0, encoder_depth=long_raw.enc_depth, rnn_type="bigru", max_batch=2,
+                       max_raw_len=tr, max_output_len=long_raw.L)
+    bc.set_weights_flat(C.weights(rv, long_raw.enc_depth, 1, "raw", "luong")[0])
+    assert long_raw.Tr == DECODE_STEPS
+    tok, lg = (a.numpy() for a in bc.greedy_search_prediction(r["raw"][:2], long_raw.L))
+    (og, olg), o = C.sliced(r["out"], r["taps"], [0, 1])
+    e, _ = _greedy_errors(tok, lg, None, og, olg, o)
+    print(f"max_raw_len {tr}, T_r {DECODE_STEPS}: step logits {e['step_logits']:.2e} from fp64")
+    assert tok.shape[0] == 2 and e["step_logits"] < TOL
+    bc.close()
+    # the longest event window that fits: the bytes of the handle sized to the call; 353 steps refused by name; the next call right
+    c = C.BY_NAME["lds-event-T352"]
+    r = C.fp64(rv, c.name)
+    assert c.Te == DECODE_STEPS and c.mode == "event"
+    sized = _open(rv, c)
+    want = [a.numpy().copy() for a in sized.beam_search_prediction(r["ev"], c.W, c.L)]
+    sized.close()
+    big = rv.Basecaller(128, 128, 128, rv.data_loader.nuc_tk, "event", 0.0, encoder_depth=c.enc_depth, rnn_type="bigru", max_batch=c.B,
+                        max_event_len=te, max_output_len=c.L, max_beam=c.W)
+    big.set_weights_flat(C.weights(rv, c.enc_depth, c.dec_depth, c.mode, c.attention)[0])
+    for again in range(2):
+        got = [a.numpy() for a in big.beam_search_prediction(r["ev"], c.W, c.L)]
+        assert got[0].shape == want[0].shape and np.array_equal(got[0], want[0]) and np.array_equal(_bits(got[1]), _bits(want[1])), again
+        if again == 0:
+            over = np.concatenate([r["ev"], r["ev"][:, :1]], axis=1)
+            assert over.shape[1] == DECODE_STEPS + 1 <= te
+            with pytest.raises(rv._capi.RavventHipError) as ex:
+                big.beam_search_prediction(over, c.W, c.L)
+            assert "RV_EUNSUPPORTED" in str(ex.value) and str(DECODE_STEPS) in str(ex.value) and str(DECODE_STEPS + 1) in str(ex.value), str(ex.value)
+    big.close()
+
+
+# ---------------------------------------------------------------------------------------------- adversarial weights
+@pytest.mark.parametrize("saturate", [False, True], ids=["plain", "saturated"])
+@pytest.mark.parametrize("col_gain", C.ADV_GAINS)
+def test_encoder_adversarial_recurrent_kernel(rv, col_gain, saturate):
+    """k_gru_rec_mx (F = 1, 5 and 0; both directions, two layers, 150 + 25 steps) on the recipes of gru_cases.adversarial_encoder: in every
+    encoder cell's U one row x 30, one row x 1e-5, a z column and two h columns x 8 or x 50; with `saturate` the first 64 units' z gates
+    closed and their candidates at +-1, so that half of h sits on the edge the 2^14 image rests on.  The regime is asserted on the
+    reference; then enc_output is finite, nowhere beyond 1 in size, within TOL of fp64 and within TWIN_K x the fp32 twin + TWIN_C -- the
+    one relative bound: the family has no second recurrence form to compare with.  The keys likewise.  An activation that is accurate
+    absolutely but not relatively (tanh as 2 sigmoid(2x) - 1) passes every other GRU case and fails here, as the BiLSTM kernels once did."""
+    a = C.adversarial_encoder(rv, col_gain, saturate)
+    if saturate:
+        assert a["saturated"] > 0.3, a["saturated"]
+    else:
+        assert a["preact"] > 10.0, a["preact"]
+    c = C._c("adversarial-enc", C.ADV_B, "joint", C.ADV_TR, C.ADV_TE, enc_depth=2, W=3, L=6)
+    bc = _open(rv, c, flat=a["flat"])
+    bc.set_option("debug_taps", 1)
+    bc.beam_search_prediction((a["raw"], a["ev"]), c.W, c.L)
+    Tm = c.Tr + c.Te
+    enc = bc.get_tensor("enc_output").reshape(c.B, Tm, 256)
+    keys = bc.get_tensor("keys").reshape(c.B, Tm, 128)
+    assert (bc.get_tensor("mask").reshape(c.B, Tm) == a["mask"]).all()
+    forms = {tuple(int(v) for v in row) for row in bc.get_tensor("kernel_forms").reshape(-1, 5)}
+    assert {f for f in forms if f[0] == 9} == {(9, F, 16, 0, 0) for F in (0, 1, 5)}, sorted(forms)
+    bc.close()
+    assert np.isfinite(enc).all() and np.isfinite(keys).all()
+    assert np.abs(enc).max() <= 1.0, float(np.abs(enc).max())
+    err = _memory_errors(enc, keys, a)
+    tag = f"adversarial encoder gain {col_gain:g} {'saturated' if saturate else 'plain'}"
+    print(f"{tag}: " + ", ".join(f"{k} {v:.2e} (twin {a['twin'][k]:.2e})" for k, v in err.items()) + f"; saturated share {a['saturated']:.3f}, pre-activation {a['preact']:.1f}")
+    for k, v in err.items():
+        assert v < TOL, (tag, k, v, a["twin"][k])
+    _assert_twin(err, a["twin"], tag)
+
+
+@pytest.mark.parametrize("dec_depth", [1, 2])
+def test_decoder_cell_adversarial_recurrent_kernel(rv, dec_depth):
+    """k_dec_cell_gru, one and two stacked cells, on gru_cases.adversarial_decoder: two h-gate columns of each cell's U x 50, one row x 30,
+    one row x 1e-5, the end token suppressed so that all L - 1 steps run.  Step logits and alignments over the steps that agree with the
+    fp64 beam within TOL and within TWIN_K x the fp32 twin + TWIN_C; a chunk that leaves the fp64 beam does so through a near-tie, and at
+    most B // 4 do (the twin meets that cap: test_gru.py)."""
+    a = C.adversarial_decoder(rv, dec_depth)
+    c, o, twin = a["case"], a["taps"], a["twin"]
+    bc = _open(rv, c, flat=a["flat"])
+    bc.set_option("debug_taps", 1)
+    tok, sc = (x.numpy() for x in bc.beam_search_prediction((a["raw"], a["ev"]), c.W, c.L))
+    S, B, W, Tm = tok.shape[1], c.B, c.W, c.Tr + c.Te
+    assert S == c.L - 1 == o["step_ids"].shape[0]
+    lgs = bc.get_tensor("step_logits").reshape(S, B, W, 7)
+    al = bc.get_tensor("step_alignments").reshape(S, B, W, Tm)
+    ids = bc.get_tensor("step_ids").reshape(S, B, W).astype(np.int64)
+    par = bc.get_tensor("parent_ids").reshape(S, B, W).astype(np.int64)
+    forms = {tuple(int(v) for v in row) for row in bc.get_tensor("kernel_forms").reshape(-1, 5)}
+    assert (10, 0, 0, 0, 0) in forms, sorted(forms)
+    bc.close()
+    assert np.isfinite(lgs).all() and np.isfinite(al).all()
+    err, left = _beam_errors(lgs, al, ids, par, np.full(B, S), None, o, a["out"][1])
+    for i in left:
+        gap = _near_tie_gap(G, o["step_logits"][:, i], W, a["cfg"]["end_token"])
+        assert gap < _tie_bound(twin), (c.name, i, "left the fp64 beam with no near-tie", gap)
+    assert len(left) <= B // 4, (c.name, "chunks that left the fp64 decode", left)
+    print(f"{c.name}: " + ", ".join(f"{k} {v:.2e}" for k, v in err.items()) + f"; chunks that left: {left}")
+    for k, v in err.items():
+        assert v < TOL, (c.name, k, v)
+    _assert_twin(err, twin, c.name)

@@ -68,7 +68,7 @@ def special_weights(rng, N):
     return W
 
 
-@pytest.mark.parametrize("ncb", [1, 4])
+@pytest.mark.parametrize("ncb", [1, 3, 4])          # the attention memory; both directions of a BiGRU layer; of a BiLSTM layer
 @pytest.mark.parametrize("kind", ["ordinary", "special"])
 def test_split_image_matches_documented_layout(ncb, kind):
     rng = np.random.default_rng(100 * ncb + len(kind))
