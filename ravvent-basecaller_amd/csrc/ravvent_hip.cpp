@@ -43,8 +43,7 @@ struct SlabKey {
   }
 };
 
-// What rv_set_option sets.  A child context takes its parent's as a whole (sync_child); slab_graph, async_depth, coalesce and gen are
-// read from the handle (root) only, so their copies on a child mean nothing.
+// What rv_set_option sets, on the handle.  A slab context reads them through its handle while it queues a call (enqueue), never later
 struct Options {
   int split = 1;                            // concurrent decode sub-slabs (1..4); measured neutral at B=256
   int att_nt = 0;
@@ -65,7 +64,7 @@ struct Options {
   int slab_graph = 0;                       // option "slab_graph": off by default -- measured (tools/graph_ab.py, C3, depth 10): a submit costs the host
                                             // 22-27 us instead of 43-48, but the replayed slabs stream 1.5-3 % SLOWER (354-361 k against 361-370 k chunks/s
                                             // settled; the runtime's per-node barrier packets), and the host is not what bounds the stream
-  int gen = 0;                              // (root) bumped by every rv_set_option / rv_load_weights: frozen arguments may have changed
+  int gen = 0;                              // bumped by every rv_set_option / rv_load_weights: frozen arguments may have changed
   int async_depth = 2;                      // contexts the asynchronous entry points rotate through (1..RV_MAX_ASYNC)
   int coalesce = -1;                        // 0 / 1 off, n >= 2 slabs per group, -1 chosen from async_depth (coalesce_n)
   int group_inplace = 1;                    // a group's layer-0 kernels read its members' device inputs where they are (no copies into the group's buffers)
@@ -76,7 +75,7 @@ struct Options {
 };
 
 // Device images derived from the weights (weight_images.h lists them; rv_load_weights uploads what build_weight_images returns).  The
-// handle owns them; a child context takes the addresses as a whole (create_child)
+// handle owns them; every slab context reads them there
 struct WeightImages {
 #define X(T, name, count) T* name = nullptr;
   RV_WEIGHT_IMAGES(X)
@@ -142,14 +141,32 @@ struct CallParts {
   int form_B = -1;                          // the B that picks the kernel forms (a group: its first member's), -1 = the call's own
 };
 
+// Which kernels a call runs: decided once, before anything is queued (plan_call), and carried by the recording (Slab)
+struct Plan {
+  bool wide = false;                        // encoder recurrences on the matrix pipe (lstm_mx.hip; a GRU handle: always) ...
+  bool rows8 = false;                       // ... with eight chunks per workgroup (the latency form)
+  int persist = -1;                         // the form of the one-launch persistent decode (dec_persist_form), or -1: the per-step kernels
+  bool flash = false;                       // single-pass Luong attend (wider beams: register budget -> two-pass)
+  bool keys = false;                        // the key GEMM runs: the two-pass attend, the "keys" debug tap, a moves call on the per-step kernels
+  bool win_lane = false;                    // a window call gathers its chunks in the lane of the layer-0 recurrence (else behind k_expand_windows)
+  bool graphable = false;                   // the call replays as a slab graph (option "slab_graph")
+};
+
+struct SlabCtx;
+struct Group;
+
+// One uncollected slab of a coalesced group; `done`: its group has run, S is final
+struct Tick { bool busy = false, done = false, dev_out = false, calls = false; int ticket = -1, member = 0, B = 0, row0 = 0, steps = 0, S = 0; Group* grp = nullptr; };
+
 }  // namespace
 
+// The handle a caller holds: the weights and what is derived from them, the options, the slab contexts and groups its calls run on,
+// the tickets and the reads.  Nothing of a call in flight lives here (SlabCtx, Group)
 struct RvContext {
   RvConfig cfg{};
-  int rnn = RV_RNN_BILSTM;                  // cell family (rv_create_rnn); a child context takes its parent's
-  hipStream_t stream = nullptr;
+  int rnn = RV_RNN_BILSTM;                  // cell family (rv_create_rnn)
   std::string err;
-  std::vector<void*> allocs;
+  std::vector<void*> allocs;                // the blob and the images
 
   // weights
   float* d_w = nullptr;
@@ -157,19 +174,62 @@ struct RvContext {
   bool loaded = false;
   std::vector<std::vector<LstmW>> enc[2];   // [enc][layer][dir]
   std::vector<LstmW> dec;                   // stacked decoder cells
-  WeightImages img;                         // derived from the weights; a child context holds its parent's addresses
+  WeightImages img;                         // derived from the weights
   const float *W_mem = nullptr, *W_q = nullptr, *v_att = nullptr, *W_att = nullptr, *W_fc = nullptr, *b_fc = nullptr;
   wimg::ImageScales scales;                 // the weight-derived scalars of the decode (set by rv_load_weights)
 
   Options opt;
   int dbg_role = 0;                         // timing probe (RV_DBG_ROLE): 1 = no projection math, 2 = no recurrence math
+  std::map<std::string, ProfEntry> prof;
+
+  // Slab contexts by slot -- own stream, own buffers -- so that several slabs are in flight on the GPU at once.  Slot 0 exists from
+  // rv_create_rnn on and serves the synchronous calls, the debug taps and rv_get_tensor; the asynchronous calls (rv_beam_search_submit* /
+  // rv_beam_search_collect*) rotate through slots 0 .. async_depth - 1, created on the first submit that needs them
+  std::vector<SlabCtx*> slabs;
+  int inflight_hint = 1;                    // slabs the caller keeps in flight (1 for the synchronous entry points): sizes the workgroups
+  int next_slot = 0, generation = 0;
+  int lS = 0;                               // S of the last call rv_get_tensor answers for (DESIGN.md section 16 has the one quirk)
+
+  // coalesced asynchronous calls (option "coalesce"): up to n consecutively submitted slabs of the default streamed path are decoded as ONE
+  // internal call of sum(B) chunks on a group's context, whose buffers hold n x max_batch chunks -- so that the narrow recurrence launches
+  // are n times as wide and a handle fills the chip from few hardware queues.  Tickets stay per slab (`ticks`).
+  std::vector<Group*> groups;               // created when a slab finds none idle
+  Group* open_grp = nullptr;                // the group that still takes members: filled, not launched
+  Tick ticks[RV_MAX_ASYNC];
+  long long co_groups = 0, co_slabs = 0, co_largest = 0;     // "coalesce_stats": groups launched, slabs in them, members of the largest
+  FormLog gforms;                           // the instantiations the last coalesced group launched on its own context ("group_kernel_forms")
+
+  // window calls (rv_beam_search_windows*): the reads, the stream and event of their uploads, and which reads each uncollected ticket uses
+  std::vector<Read> reads;
+  hipStream_t copy_stream = nullptr;
+  hipEvent_t ev_put = nullptr;              // recorded behind every upload: a window call's stream waits for it, the host never does
+  long long read_allocs = 0, read_puts = 0; // "read_stats": device allocations made for reads, puts
+  long long win_expands = 0;                // ... and launches of k_expand_windows
+  int read_gen = 0;
+  std::map<int, std::vector<int>> ticket_reads;
+};
+
+namespace {
+
+// What one slab in flight needs: a stream, the per-slab buffers, the decode state and graphs, the last call's facts and one pending
+// call.  Options, weights, images and scales are its handle's
+struct SlabCtx {
+  RvContext* h = nullptr;
+  int slot = 0;                             // its place in h->slabs (-1: a group's context)
+  Group* grp = nullptr;                     // the group it belongs to (null: a plain slab context)
+  int cap = 0;                              // chunks its buffers hold: the handle's max_batch (a group's context: times its members)
+  hipStream_t stream = nullptr;
+  std::vector<void*> allocs;
   hipStream_t side[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-  int* d_chunk_steps = nullptr;
-  int lwide = 0;
-  int lrows8 = 0;                           // this call's matrix-pipe recurrences take eight chunks per workgroup (the latency form of lstm_mx.hip)
-  float* mem2 = nullptr;                    // [B,Tm,256] = enc_out . Wmp: keys | attention-layer image of the values
 
+  // Debug taps and rv_get_tensor belong to slot 0: every other context runs with both tap options off, whatever the handle says
+  bool own() const { return slot == 0; }
+  int taps() const { return own() ? h->opt.taps : 0; }
+  int ptaps() const { return own() ? h->opt.ptaps : 0; }
+
+  int* d_chunk_steps = nullptr;
+  float* mem2 = nullptr;                    // [B,Tm,256] = enc_out . Wmp: keys | attention-layer image of the values
   // encoder buffers
   float *d_raw = nullptr, *d_ev = nullptr;
   uint8_t* mask = nullptr;
@@ -190,23 +250,22 @@ struct RvContext {
   uint8_t *d_bases = nullptr, *pin_bases = nullptr;
   float *d_probs = nullptr, *pin_probs = nullptr;
   int *d_clen = nullptr, *pin_clen = nullptr;
-  // the whole beam (rv_beam_search_all*): device outputs and pinned staging of the host variants, [max_batch, max_output_len, max_beam]
-  // and [max_batch, max_beam], allocated on this context's first such call (ensure_beam_buffers)
+  // the whole beam (rv_beam_search_all*): device outputs and pinned staging of the host variants, [cap, max_output_len, max_beam]
+  // and [cap, max_beam], allocated on this context's first such call (ensure_beam_buffers)
   BeamsOut d_beams{}, pin_beams{};
-  // moves (rv_beam_search_moves*): the decode's records [max_output_len - 1, max_batch, max_beam, RV_MOVE_COLS], allocated on this context's
-  // first such call (ensure_moves_buffers), and for the host variants the six outputs [max_batch, max_output_len, max_beam] with their staging
+  // moves (rv_beam_search_moves*): the decode's records [max_output_len - 1, cap, max_beam, RV_MOVE_COLS], allocated on this context's
+  // first such call (ensure_moves_buffers), and for the host variants the six outputs [cap, max_output_len, max_beam] with their staging
   float* d_step_moves = nullptr;
   MovesOut d_moves{}, pin_moves{};
   // forced decode and scoring (rv_teacher_forced*, rv_score_logits)
-  int32_t* d_forced = nullptr;              // host variants: labels [max_batch, max_output_len] and the score outputs, allocated on this context's
-  float *d_sc_nll = nullptr, *d_sc_sum = nullptr;   //   first such call (ensure_score_buffers): nll [max_batch, max_output_len], nll_sum [max_batch],
-  int32_t* d_sc_cnt = nullptr;              //   n_labels | n_match | n_counted [3][max_batch]
+  int32_t* d_forced = nullptr;              // host variants: labels [cap, max_output_len] and the score outputs, allocated on this context's
+  float *d_sc_nll = nullptr, *d_sc_sum = nullptr;   //   first such call (ensure_score_buffers): nll [cap, max_output_len], nll_sum [cap],
+  int32_t* d_sc_cnt = nullptr;              //   n_labels | n_match | n_counted [3][cap]
 
   long long* rec_ts = nullptr;              // diagnostic: per-wave cycle sums of the raw layer-0 recurrence (RV_REC_STAMPS=1) or of its fused layer 1 (=2)
   int rec_ts_layer = 0;
-  std::map<std::string, ProfEntry> prof;
   struct Pending { std::string name; hipEvent_t a, b; };
-  std::vector<Pending> pending;
+  std::vector<Pending> pending;             // profile events in flight: drained into the handle's profile when the call is finished
   std::vector<hipEvent_t> ev_pool;
   std::map<GraphKey, hipGraphExec_t> graphs;
   // one hipGraph per slab context and call shape: the whole slab (ten launches on the default path) replays as ONE hipGraphLaunch.
@@ -216,59 +275,36 @@ struct RvContext {
   std::map<SlabKey, SlabGraph> slab_graphs;
   const void** d_ptab = nullptr;
   const void** pin_ptab = nullptr;
-  int graph_gen = 0;                        // the opt.gen (of the root) this context's slab graphs were captured under
+  int graph_gen = 0;                        // the handle's opt.gen this context's slab graphs were captured under
 
   // last call
-  int lB = 0, lTm = 0, lL = 0, lS = 0, lgreedy = 0, ltaps = 0, lptaps = 0;
+  int lB = 0, lTm = 0, lL = 0, lgreedy = 0, ltaps = 0, lptaps = 0;
   int lmoves = 0;                           // it was a moves call: "step_moves" holds its records
   SlabFacts fact;
   FormLog lforms;                           // the kernel instantiations it launched ("kernel_forms"); lforms_ok = 0: it ran as a slab graph
   int lforms_ok = 1;
-  FormLog gforms;                           // (root) the instantiations the last coalesced group launched on its own context ("group_kernel_forms")
   std::map<GraphKey, FormLog> graph_forms;  // ... those a captured decode graph of `graphs` launches (recorded at its capture)
-
-  // asynchronous calls (rv_beam_search_submit* / rv_beam_search_collect*): the handle owns `kids` more slab contexts -- own stream,
-  // own buffers, the PARENT's weights and derived images -- so that several slabs are in flight on the GPU at once
-  RvContext* parent = nullptr;
-  std::vector<RvContext*> kids;
-  int inflight_hint = 1;                   // slabs the caller keeps in flight (1 for the synchronous entry points): sizes the workgroups
-  int next_slot = 0, generation = 0;
   struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false, all = false, moves = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
 
-  // coalesced asynchronous calls (option "coalesce"): up to n consecutively submitted slabs of the default streamed path are decoded as ONE
-  // internal call of sum(B) chunks on a GROUP context -- a child context whose buffers hold n x max_batch chunks -- so that the narrow
-  // recurrence launches are n times as wide and a handle fills the chip from few hardware queues.  Tickets stay per slab (`ticks`).
-  std::vector<RvContext*> groups;           // (root) group contexts, created when a slab finds none idle
-  RvContext* open_grp = nullptr;            // (root) the group that still takes members: filled, not launched
-  struct Tick { bool busy = false, done = false, dev_out = false, calls = false; int ticket = -1, member = 0, B = 0, row0 = 0, steps = 0, S = 0; RvContext* grp = nullptr; };
-  Tick ticks[RV_MAX_ASYNC];                 // (root) one per uncollected slab of a group; `done`: its group has run, S is final
-  long long co_groups = 0, co_slabs = 0, co_largest = 0;     // (root) "coalesce_stats": groups launched, slabs in them, members of the largest
-  // ... of a group context
-  int g_cap = 0, g_n = 0, g_rows = 0, g_staged = 0, g_failed = RV_OK;     // members it takes / holds, chunks they add up to, members whose results wait in its staging
-  bool g_launched = false, g_synced = false, g_dev_in = false, g_dev_out = false, g_calls = false;
-  int g_Tr = 0, g_Te = 0, g_W = 0, g_L = 0;
-  int g_B0 = 0;                             // its first member's B: the group takes the kernel forms that member would have got alone
-  uint8_t g_lut[RV_MAX_VOCAB] = {};
-  int g_tslot[RV_MAX_MEMBERS] = {};
-  DecMembers g_members{};                   // its member table: output addresses as the members come (submit_group), rows at its launch (launch_group)
-  bool g_inplace = false;                   // its members' device inputs are read in place (option "group_inplace"), through ...
-  RecMembers g_in[2]{};                     // ... these tables [raw, event]: addresses as the members come, rows at its launch
-  bool g_win = false;                       // its members are window slabs: their rows stand back to back in pin_win (a window slab and a chunk-tensor slab never share a group)
-
-  // window calls (rv_beam_search_windows*): the resolved table of the call this context runs, [max_batch] rows -- written by the host into
+  // window calls (rv_beam_search_windows*): the resolved table of the call this context runs, [cap] rows -- written by the host into
   // pinned staging when the call is queued (a group: as its members come), copied to the device in front of the call's first kernel
   RecWindow *pin_win = nullptr, *d_win = nullptr;
-  // ... and of the handle (root): the reads, the stream and event of their uploads, and which reads each uncollected ticket uses
-  std::vector<Read> reads;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_put = nullptr;              // recorded behind every upload: a window call's stream waits for it, the host never does
-  long long read_allocs = 0, read_puts = 0; // "read_stats": device allocations made for reads, puts
-  long long win_expands = 0;                // ... and launches of k_expand_windows
-  int read_gen = 0;
-  std::map<int, std::vector<int>> ticket_reads;
 };
 
-namespace {
+// A group of coalesced slabs: the context its internal call runs on, and what its members add up to
+struct Group {
+  SlabCtx* ctx = nullptr;
+  int cap = 0, n = 0, rows = 0, staged = 0, failed = RV_OK;     // members it takes / holds, chunks they add up to, members whose results wait in its staging
+  bool launched = false, synced = false, dev_in = false, dev_out = false, calls = false;
+  int Tr = 0, Te = 0, W = 0, L = 0;
+  int B0 = 0;                               // its first member's B: the group takes the kernel forms that member would have got alone
+  uint8_t lut[RV_MAX_VOCAB] = {};
+  int tslot[RV_MAX_MEMBERS] = {};
+  DecMembers members{};                     // its member table: output addresses as the members come (submit_group), rows at its launch (launch_group)
+  bool inplace = false;                     // its members' device inputs are read in place (option "group_inplace"), through ...
+  RecMembers in[2]{};                       // ... these tables [raw, event]: addresses as the members come, rows at its launch
+  bool win = false;                         // its members are window slabs: their rows stand back to back in pin_win (a window slab and a chunk-tensor slab never share a group)
+};
 
 int fail(RvContext* h, int code, const char* fmt, ...) {
   char buf[512];
@@ -288,12 +324,6 @@ int fail(RvContext* h, int code, const char* fmt, ...) {
 // rv_create and the context's buffers: the short form of HIPCHK's message
 #define HIPTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(h, RV_EHIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
 
-// The outcome of a call that ran on context `ctx` of handle h: rv_last_error answers from the handle
-int relay(RvContext* h, const RvContext* ctx, int rc) {
-  if (rc != RV_OK && ctx != h) h->err = ctx->err;
-  return rc;
-}
-
 int async_depth(const RvContext* h) { return std::min(std::max(h->opt.async_depth, 1), RV_MAX_ASYNC); }
 
 // The next ticket of handle h for `slot` (a slab context, or an entry of `ticks`)
@@ -302,15 +332,18 @@ int issue_ticket(RvContext* h, int slot) {
   return (h->generation << 4) | slot;
 }
 
+// Device memory owned by the handle or by one of its slab contexts; a failure is the handle's
 template <class T>
-int dalloc(RvContext* h, T** p, size_t count) {
+int dalloc(RvContext* h, std::vector<void*>& owned, T** p, size_t count) {
   void* q = nullptr;
   hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
   if (e != hipSuccess) return fail(h, RV_ENOMEM, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
-  h->allocs.push_back(q);
+  owned.push_back(q);
   *p = static_cast<T*>(q);
   return RV_OK;
 }
+template <class T> int dalloc(RvContext* h, T** p, size_t count) { return dalloc(h, h->allocs, p, count); }
+template <class T> int dalloc(SlabCtx* cx, T** p, size_t count) { return dalloc(cx->h, cx->allocs, p, count); }
 
 void bind_weights(RvContext* h) {
   const wimg::BlobLayout lay(h->cfg, h->rnn);
@@ -328,15 +361,15 @@ void bind_weights(RvContext* h) {
 
 // ---- profiling: bracket a launch with events on the launch stream
 struct Scope {
-  RvContext* h; const char* name; hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st;
+  SlabCtx* cx; const char* name; hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st;
   // profile 3: only the decode launches (the dominant kernel) are bracketed, so that the timed region of bench.py
   // carries two events per slab instead of two per launch (the per-launch events cost 2.6 % of a C3 slab)
-  Scope(RvContext* h_, const char* n, hipStream_t st_ = nullptr, bool decode = false)
-      : h(h_), name(n), on(h_->opt.profile != 0 && (h_->opt.profile != 3 || decode)), st(st_ ? st_ : h_->stream) {
+  Scope(SlabCtx* x_, const char* n, hipStream_t st_ = nullptr, bool decode = false)
+      : cx(x_), name(n), on(x_->h->opt.profile != 0 && (x_->h->opt.profile != 3 || decode)), st(st_ ? st_ : x_->stream) {
     if (!on) return;
     auto get = [&]() {
       hipEvent_t e;
-      if (!h->ev_pool.empty()) { e = h->ev_pool.back(); h->ev_pool.pop_back(); }
+      if (!cx->ev_pool.empty()) { e = cx->ev_pool.back(); cx->ev_pool.pop_back(); }
       else hipEventCreate(&e);
       return e;
     };
@@ -346,31 +379,30 @@ struct Scope {
   ~Scope() {
     if (!on) return;
     hipEventRecord(b, st);
-    h->pending.push_back({name, a, b});
+    cx->pending.push_back({name, a, b});
   }
 };
 
-void drain_profile(RvContext* h) {
-  RvContext* root = h->parent ? h->parent : h;
-  for (auto& p : h->pending) {
+void drain_profile(SlabCtx* cx) {
+  for (auto& p : cx->pending) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-      ProfEntry& e = root->prof[p.name];
+      ProfEntry& e = cx->h->prof[p.name];
       e.ms += ms; e.n += 1;
     }
-    h->ev_pool.push_back(p.a); h->ev_pool.push_back(p.b);
+    cx->ev_pool.push_back(p.a); cx->ev_pool.push_back(p.b);
   }
-  h->pending.clear();
+  cx->pending.clear();
 }
 
 // Side stream g of a context, created on first use.  Highest priority: their few workgroups should take CU slots as soon as they free up.
-hipStream_t side_stream(RvContext* h, int g) {
-  if (!h->side[g]) {
+hipStream_t side_stream(SlabCtx* cx, int g) {
+  if (!cx->side[g]) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (hipStreamCreateWithPriority(&h->side[g], hipStreamNonBlocking, hi) != hipSuccess) { h->side[g] = nullptr; return h->stream; }   // (degrades to in-order)
+    if (hipStreamCreateWithPriority(&cx->side[g], hipStreamNonBlocking, hi) != hipSuccess) { cx->side[g] = nullptr; return cx->stream; }   // (degrades to in-order)
   }
-  return h->side[g];
+  return cx->side[g];
 }
 
 int pick_rows_per_block(int B) {
@@ -410,48 +442,50 @@ bool lane_layer0(const RvContext* h, int F, int T) {
 // Encoder.call of a GRU handle: k_gru_rec_mx on every layer.  Layer 0 takes x . W + b[0] in the lane and leaves the input mask; layers
 // >= 1 read xw [B,T,2,384] from the split-f16 GEMM over three column blocks (both directions and their input biases in one launch).
 // State sets hold h only: layer l + 1 starts from layer l's two final states.
-void run_gru_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int Tm, int t_off, hipStream_t s, int l_begin, int l_end) {
+void run_gru_encoder(SlabCtx* cx, int e, const float* x, int F, int B, int T, int Tm, int t_off, hipStream_t s, int l_begin, int l_end) {
+  RvContext* const h = cx->h;
   const int depth = h->cfg.enc_depth;
   for (int l = std::max(l_begin, 0); l < std::min(depth, l_end); ++l) {
     const bool last = l == depth - 1;
     GruRecArgs a{};
     a.B = B; a.T = T;
-    a.out = last ? h->enc_out : h->act[e][l & 1]; a.out_T = last ? Tm : T; a.out_t0 = last ? t_off : 0;
+    a.out = last ? cx->enc_out : cx->act[e][l & 1]; a.out_T = last ? Tm : T; a.out_t0 = last ? t_off : 0;
     const int rd = (l & 1) ^ 1, wr = l & 1;     // state sets: layer l reads set rd, writes set wr
     for (int dr = 0; dr < 2; ++dr) {
       const LstmW& w = h->enc[e][l][dr];
       a.W[dr] = w.W; a.b[dr] = w.b;
       a.Ua[dr] = h->img.gUa + ((size_t)(e * depth + l) * 2 + dr) * RV_GRU_UA_SLOT;
-      a.h0[dr] = l > 0 ? h->st[e][rd][2 * dr] : nullptr;
-      a.hT[dr] = h->st[e][wr][2 * dr];
+      a.h0[dr] = l > 0 ? cx->st[e][rd][2 * dr] : nullptr;
+      a.hT[dr] = cx->st[e][wr][2 * dr];
     }
     if (l == 0) {
       a.x = x;
-      a.mask = h->mask; a.mask_T = Tm; a.mask_t0 = t_off; a.pad = h->cfg.padding_value;
-      Scope sc(h, F == 1 ? "gru_rec_raw_l0" : "gru_rec_event_l0", s);
-      launch_gru_rec_mx(a, F, s, &h->lforms);
+      a.mask = cx->mask; a.mask_T = Tm; a.mask_t0 = t_off; a.pad = h->cfg.padding_value;
+      Scope sc(cx, F == 1 ? "gru_rec_raw_l0" : "gru_rec_event_l0", s);
+      launch_gru_rec_mx(a, F, s, &cx->lforms);
       continue;
     }
     {
       const size_t slot = (size_t)(e * (depth - 1) + (l - 1));
-      Scope sc(h, e == 0 ? "gemm_inproj_raw" : "gemm_inproj_event", s);
-      launch_gemm_split_blocks(h->act[e][(l - 1) & 1], B * T, h->img.gWx16 + slot * RV_GRU_WX16_SLOT, 3, h->img.gbx + slot * 2 * RV_GG, h->xw[e],
+      Scope sc(cx, e == 0 ? "gemm_inproj_raw" : "gemm_inproj_event", s);
+      launch_gemm_split_blocks(cx->act[e][(l - 1) & 1], B * T, h->img.gWx16 + slot * RV_GRU_WX16_SLOT, 3, h->img.gbx + slot * 2 * RV_GG, cx->xw[e],
                                2 * RV_GG, s);
     }
-    a.x = h->xw[e];
-    Scope sc(h, e == 0 ? "gru_rec_raw_l1p" : "gru_rec_event_l1p", s);
-    launch_gru_rec_mx(a, 0, s, &h->lforms);
+    a.x = cx->xw[e];
+    Scope sc(cx, e == 0 ? "gru_rec_raw_l1p" : "gru_rec_event_l1p", s);
+    launch_gru_rec_mx(a, 0, s, &cx->lforms);
   }
 }
 
-void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int Tm, int t_off, hipStream_t s,
+void run_encoder(SlabCtx* cx, const Plan& plan, int e, const float* x, int F, int B, int T, int Tm, int t_off, hipStream_t s,
                  int l_begin = 0, int l_end = 1 << 30, const void* const* ptab = nullptr, const RecWindow* windows = nullptr) {
-  if (h->rnn == RV_RNN_BIGRU) return run_gru_encoder(h, e, x, F, B, T, Tm, t_off, s, l_begin, l_end);      // (never with ptab or windows: enqueue)
+  RvContext* const h = cx->h;
+  if (h->rnn == RV_RNN_BIGRU) return run_gru_encoder(cx, e, x, F, B, T, Tm, t_off, s, l_begin, l_end);      // (never with ptab or windows: enqueue)
   const int depth = h->cfg.enc_depth;
   const int bt = pick_rows_per_block(B);
   for (int l = std::max(l_begin, 0); l < std::min(depth, l_end); ++l) {
     const bool last = l == depth - 1;
-    float* out = last ? h->enc_out : h->act[e][l & 1];
+    float* out = last ? cx->enc_out : cx->act[e][l & 1];
     RecArgs a{};
     a.B = B; a.T = T;
     a.out = out; a.out_T = last ? Tm : T; a.out_t0 = last ? t_off : 0;
@@ -461,12 +495,12 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
       a.U[dr] = w.U;
       a.Up[dr] = h->img.Up + ((size_t)(e * depth + l) * 2 + dr) * RV_U * RV_G;
       a.Ua[dr] = h->img.Ua + ((size_t)(e * depth + l) * 2 + dr) * RV_UA_SLOT;
-      a.h0[dr] = l > 0 ? h->st[e][rd][2 * dr] : nullptr;
-      a.c0[dr] = l > 0 ? h->st[e][rd][2 * dr + 1] : nullptr;
-      a.hT[dr] = h->st[e][wr][2 * dr];
-      a.cT[dr] = h->st[e][wr][2 * dr + 1];
+      a.h0[dr] = l > 0 ? cx->st[e][rd][2 * dr] : nullptr;
+      a.c0[dr] = l > 0 ? cx->st[e][rd][2 * dr + 1] : nullptr;
+      a.hT[dr] = cx->st[e][wr][2 * dr];
+      a.cT[dr] = cx->st[e][wr][2 * dr + 1];
     }
-    if (h->lwide) {
+    if (plan.wide) {
       // matrix-pipe recurrence.  Raw layer 0 folds its one-feature input projection in; every other layer reads pre-projected
       // inputs xw [B,T,2,512]: event layer 0 from a small elementwise kernel, layers >= 1 from the split-f16 GEMM (both directions
       // and their biases in one launch, A read once).
@@ -475,42 +509,42 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
         // event encoder's five features too -- the same fused multiply-adds in the same order as k_inproj_small: identical bits)
         a.x = x;
         for (int dr = 0; dr < 2; ++dr) { a.W[dr] = h->enc[e][0][dr].W; a.bias[dr] = h->enc[e][0][dr].b; }
-        a.mask = h->mask; a.mask_T = Tm; a.mask_t0 = t_off; a.pad = h->cfg.padding_value;   // the layer-0 kernels leave the input mask too
+        a.mask = cx->mask; a.mask_T = Tm; a.mask_t0 = t_off; a.pad = h->cfg.padding_value;   // the layer-0 kernels leave the input mask too
         a.ptab = ptab;
-        if (h->g_inplace) a.members = h->g_in[e];      // (a group whose members' inputs stay where they are: launch_group)
+        if (cx->grp && cx->grp->inplace) a.members = cx->grp->in[e];    // (a group whose members' inputs stay where they are: launch_group)
         a.windows = windows;                           // (a window call on the default path: the chunks are gathered from their reads in the lane)
-        a.dbg_ts = (e == 0 && h->rec_ts_layer == 0) ? h->rec_ts : nullptr;     // (RV_REC_STAMPS=1: phase cycle sums of workgroup (0, 0))
-        Scope sc(h, F == 1 ? "lstm_rec_raw_l0" : "lstm_rec_event_l0", s);
-        launch_lstm_rec_mx(a, F, s, h->lrows8 != 0, &h->lforms);
+        a.dbg_ts = (e == 0 && cx->rec_ts_layer == 0) ? cx->rec_ts : nullptr;     // (RV_REC_STAMPS=1: phase cycle sums of workgroup (0, 0))
+        Scope sc(cx, F == 1 ? "lstm_rec_raw_l0" : "lstm_rec_event_l0", s);
+        launch_lstm_rec_mx(a, F, s, plan.rows8, &cx->lforms);
         a.dbg_ts = nullptr; a.ptab = nullptr; a.mask = nullptr; a.members.n = 0; a.windows = nullptr;
         continue;
       }
       if (l == 0) {
-        Scope sc(h, e == 0 ? "inproj_raw_l0" : "inproj_event_l0", s);
-        launch_inproj_small(x, B * T, F, h->enc[e][0][0].W, h->enc[e][0][0].b, h->enc[e][0][1].W, h->enc[e][0][1].b, h->xw[e],
-                            h->mask, T, Tm, t_off, h->cfg.padding_value, s, ptab, &h->lforms);
+        Scope sc(cx, e == 0 ? "inproj_raw_l0" : "inproj_event_l0", s);
+        launch_inproj_small(x, B * T, F, h->enc[e][0][0].W, h->enc[e][0][0].b, h->enc[e][0][1].W, h->enc[e][0][1].b, cx->xw[e],
+                            cx->mask, T, Tm, t_off, h->cfg.padding_value, s, ptab, &cx->lforms);
       } else {
-        Scope sc(h, e == 0 ? "gemm_inproj_raw" : "gemm_inproj_event", s);
-        launch_gemm_split_blocks(h->act[e][(l - 1) & 1], B * T, h->img.Wx16 + (size_t)(e * (depth - 1) + (l - 1)) * RV_WX16_SLOT, 4,
-                                 h->img.bx2 + (size_t)(e * (depth - 1) + (l - 1)) * 2 * RV_G, h->xw[e], 2 * RV_G, s);
+        Scope sc(cx, e == 0 ? "gemm_inproj_raw" : "gemm_inproj_event", s);
+        launch_gemm_split_blocks(cx->act[e][(l - 1) & 1], B * T, h->img.Wx16 + (size_t)(e * (depth - 1) + (l - 1)) * RV_WX16_SLOT, 4,
+                                 h->img.bx2 + (size_t)(e * (depth - 1) + (l - 1)) * 2 * RV_G, cx->xw[e], 2 * RV_G, s);
       }
-      a.x = h->xw[e];
-      a.dbg_ts = (e == 0 && l == 1 && h->rec_ts_layer == 1) ? h->rec_ts : nullptr;    // (RV_REC_STAMPS=2)
-      Scope sc(h, l == 0 ? "lstm_rec_event_l0" : (e == 0 ? "lstm_rec_raw_l1p" : "lstm_rec_event_l1p"), s);
-      launch_lstm_rec_mx(a, 0, s, h->lrows8 != 0, &h->lforms);
+      a.x = cx->xw[e];
+      a.dbg_ts = (e == 0 && l == 1 && cx->rec_ts_layer == 1) ? cx->rec_ts : nullptr;    // (RV_REC_STAMPS=2)
+      Scope sc(cx, l == 0 ? "lstm_rec_event_l0" : (e == 0 ? "lstm_rec_raw_l1p" : "lstm_rec_event_l1p"), s);
+      launch_lstm_rec_mx(a, 0, s, plan.rows8, &cx->lforms);
       a.dbg_ts = nullptr;
       continue;
     }
     if (l == 0) {
       a.x = x;
       for (int dr = 0; dr < 2; ++dr) { a.W[dr] = h->enc[e][0][dr].W; a.bias[dr] = h->enc[e][0][dr].b; }
-      Scope sc(h, e == 0 ? "lstm_rec_raw_l0" : "lstm_rec_event_l0", s);
+      Scope sc(cx, e == 0 ? "lstm_rec_raw_l0" : "lstm_rec_event_l0", s);
       a.tail_wave = h->opt.tail_wave;
-      a.dbg_ts = (e == 0 && h->rec_ts_layer == 0) ? h->rec_ts : nullptr;
-      launch_lstm_rec(a, F, bt, s, &h->lforms);
+      a.dbg_ts = (e == 0 && cx->rec_ts_layer == 0) ? cx->rec_ts : nullptr;
+      launch_lstm_rec(a, F, bt, s, &cx->lforms);
       a.dbg_ts = nullptr;
     } else {
-      const float* in = h->act[e][(l - 1) & 1];
+      const float* in = cx->act[e][(l - 1) & 1];
       if (h->opt.fuse) {   // x . W + b on the matrix pipe inside the recurrence kernel: no K0 launch, no xw tensor
         a.x = in;
         a.dbg_role = h->dbg_role;
@@ -520,30 +554,30 @@ void run_encoder(RvContext* h, int e, const float* x, int F, int B, int T, int T
           a.Wsb[dr] = h->opt.split_proj == 1 ? h->img.Wsb + ((size_t)(e * (depth - 1) + (l - 1)) * 2 + dr) * 3 * RV_E * RV_G : nullptr;
           a.bias[dr] = h->enc[e][l][dr].b;
         }
-        a.dbg_ts = (e == 0 && l == 1 && h->rec_ts_layer == 1) ? h->rec_ts : nullptr;
-        Scope sc(h, e == 0 ? "lstm_rec_raw_l1p" : "lstm_rec_event_l1p", s);
-        launch_lstm_rec_proj(a, bt, s, &h->lforms);
+        a.dbg_ts = (e == 0 && l == 1 && cx->rec_ts_layer == 1) ? cx->rec_ts : nullptr;
+        Scope sc(cx, e == 0 ? "lstm_rec_raw_l1p" : "lstm_rec_event_l1p", s);
+        launch_lstm_rec_proj(a, bt, s, &cx->lforms);
         continue;
       }
       {   // both directions in ONE launch (same A): 2x the workgroups -> less round quantisation
         GemmArgs g{};
         g.A = in; g.lda = RV_E; g.ldb = RV_G; g.ldc = 2 * RV_G;
         g.M = B * T; g.N = RV_G; g.K = RV_E;
-        g.Bm = h->enc[e][l][0].W; g.bias = h->enc[e][l][0].b; g.C = h->xw[e];
-        g.Bm1 = h->enc[e][l][1].W; g.bias1 = h->enc[e][l][1].b; g.C1 = h->xw[e] + RV_G;
+        g.Bm = h->enc[e][l][0].W; g.bias = h->enc[e][l][0].b; g.C = cx->xw[e];
+        g.Bm1 = h->enc[e][l][1].W; g.bias1 = h->enc[e][l][1].b; g.C1 = cx->xw[e] + RV_G;
         g.xcd_remap = 1;
-        Scope sc(h, e == 0 ? "gemm_inproj_raw" : "gemm_inproj_event", s);
+        Scope sc(cx, e == 0 ? "gemm_inproj_raw" : "gemm_inproj_event", s);
         launch_gemm_f32(g, false, s);
       }
-      a.x = h->xw[e];
-      Scope sc(h, e == 0 ? "lstm_rec_raw_l1p" : "lstm_rec_event_l1p", s);
-      launch_lstm_rec(a, 0, bt, s, &h->lforms);
+      a.x = cx->xw[e];
+      Scope sc(cx, e == 0 ? "lstm_rec_raw_l1p" : "lstm_rec_event_l1p", s);
+      launch_lstm_rec(a, 0, bt, s, &cx->lforms);
     }
   }
 }
 
-void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool profiled, FormLog* log) {
-  const bool flash = h->fact.lflash != 0;
+void launch_decode_steps(SlabCtx* cx, const DecState& d, bool flash, hipStream_t s, bool profiled, FormLog* log) {
+  RvContext* const h = cx->h;
   // A moves call whose steps take the single-pass attend, which never forms the alignments: the two-pass kernel runs first on the same
   // rows and leaves after its softmax with the step's records (DecState::moves_only); the step itself is the single-pass kernel's, so
   // the beam is what every other call's is
@@ -557,20 +591,20 @@ void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool pr
     for (int k = 0; k < d.depth; ++k) {
       if (h->rnn == RV_RNN_BIGRU) {
         const float* Wg = h->img.gWcatT + (size_t)k * RV_G * RV_E;
-        if (prof) { Scope sc(h, "dec_cell_gru"); launch_dec_cell_gru(d, k, Wg, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s, log); }
+        if (prof) { Scope sc(cx, "dec_cell_gru"); launch_dec_cell_gru(d, k, Wg, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s, log); }
         else launch_dec_cell_gru(d, k, Wg, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s, log);
         continue;
       }
       const float* WcatT = h->img.WcatT + (size_t)k * RV_G * RV_E;
-      if (prof) { Scope sc(h, "dec_cell"); launch_dec_cell(d, k, WcatT, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s); }
+      if (prof) { Scope sc(cx, "dec_cell"); launch_dec_cell(d, k, WcatT, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s); }
       else launch_dec_cell(d, k, WcatT, k == 0 ? h->dec[0].W : nullptr, h->dec[k].b, step, s);
     }
   };
   for (int step = 0; step < d.L - 1; ++step) {
     if (profiled) {
       cells(step, true);
-      if (moves_aside) { Scope sc(h, "dec_attend_moves"); launch_dec_attend(dm, h->img.WmemT, false, step, s, log); }
-      { Scope sc(h, "dec_attend"); launch_dec_attend(ds, h->img.WmemT, flash, step, s, log); }
+      if (moves_aside) { Scope sc(cx, "dec_attend_moves"); launch_dec_attend(dm, h->img.WmemT, false, step, s, log); }
+      { Scope sc(cx, "dec_attend"); launch_dec_attend(ds, h->img.WmemT, flash, step, s, log); }
     } else {
       cells(step, false);
       if (moves_aside) launch_dec_attend(dm, h->img.WmemT, false, step, s, log);
@@ -580,21 +614,49 @@ void launch_decode_steps(RvContext* h, const DecState& d, hipStream_t s, bool pr
 }
 
 // The form of the one-launch persistent decode this call takes (dec_persist_form), or -1: the per-step kernels
-int persist_form(const RvContext* h, bool greedy, int W, int Tm, bool forced) {
+int persist_form(const SlabCtx* cx, bool greedy, int W, int Tm, bool forced) {
+  const RvContext* const h = cx->h;
   if (h->rnn != RV_RNN_BILSTM) return -1;                // (a GRU handle decodes per step: no persistent GRU kernel)
-  if (!h->opt.persist || !h->opt.flash || h->opt.taps) return -1;
+  if (!h->opt.persist || !h->opt.flash || cx->taps()) return -1;
   const RvConfig& c = h->cfg;
   if (forced && c.vocab >= RV_MAX_VOCAB) return -1;      // (a forced decode keeps a bias-only row behind the vocabulary's in the resident token table)
   return dec_persist_form(c.attention, c.dec_depth, greedy ? 1 : W, Tm, greedy, h->opt.mx_att, h->opt.mx_cell);
 }
 
-int record_slab(RvContext* h, const Call& call, const CallParts& res, const void* const* ptab);
-bool group_side_ev(const RvContext* root);
+// The plan of a validated call on context cx, under the handle's options as they are now
+Plan plan_call(const SlabCtx* cx, const Call& call, const CallParts& res) {
+  const RvContext* const h = cx->h;
+  const Options& o = h->opt;
+  const int form_B = res.form_B >= 0 ? res.form_B : call.B;      // a group takes the forms its first member would have got alone
+  const bool gru = h->rnn == RV_RNN_BIGRU;                        // its one recurrence is the sixteen-chunk matrix-pipe kernel, whatever the slab
+  const bool quiet = o.profile == 0 && !cx->taps();
+  Plan p;
+  p.wide = gru || wide_recurrence(h, form_B, call.T_r);
+  p.rows8 = !gru && p.wide && rows8_wanted(h, form_B);
+  p.persist = persist_form(cx, call.greedy, call.W, call.T_r + call.T_e, res.labels != nullptr);
+  // ---- setup_memory (basecaller.py:303): keys = (enc_output * mask) . W_mem.  The single-pass Luong attend never reads keys
+  //      (score_t = values_t . (W_mem q)), and the persistent decode needs neither keys nor the per-step kernels; a moves call on the
+  //      per-step kernels forms its alignments in the two-pass attend, beside the single-pass one where that runs the step
+  p.flash = h->cfg.attention == RV_ATT_LUONG && o.flash && (call.greedy ? 1 : call.W) <= 5;      // wider beams: register budget -> two-pass
+  p.keys = (!p.flash && p.persist < 0) || cx->taps() || (res.moves && p.persist < 0);
+  // A window call: the default path gathers each chunk in the lane of its layer-0 recurrence; every other form -- the packed-FMA
+  // recurrence, "lane_projection" 0, the per-step decode, taps, profiling, a group with "group_inplace" 0 -- runs unchanged behind
+  // k_expand_windows, which writes the padded chunk tensors into the context's input buffers
+  p.win_lane = call.windows && p.wide && (h->cfg.mode == RV_MODE_RAW || lane_layer0(h, 5, call.T_e)) && quiet && p.persist >= 0 &&
+               !(cx->grp && !o.group_inplace);
+  // A slab graph: the default path only -- matrix-pipe recurrences + persistent decode, no profiling, no taps
+  p.graphable = o.slab_graph && !call.windows && p.wide && !p.rows8 && p.persist >= 0 && quiet && !res.whole_beam && !res.labels &&
+                !cx->ptaps() && !cx->rec_ts && !cx->dec_st.dbg_ts && cx->d_ptab;
+  return p;
+}
+
+int record_slab(SlabCtx* cx, const Call& call, const CallParts& res, const Plan& plan, const void* const* ptab);
+bool group_side_ev(const RvContext* h);
 
 // The checks every call passes before anything is queued.  `ok` becomes the call with its effective lengths: T_r / T_e of an encoder
 // the mode does not use are 0 there, and everything past this point works on `ok`
-int validate_call(RvContext* h, const Call& call, Call& ok) {
-  const RvConfig& c = h->cfg;
+int validate_call(SlabCtx* cx, const Call& call, Call& ok) {
+  RvContext* const h = cx->h; const RvConfig& c = h->cfg;
   if (!h->loaded) return fail(h, RV_ESTATE, "no weights loaded (call rv_load_weights first)");
   const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
   ok = call;
@@ -602,7 +664,7 @@ int validate_call(RvContext* h, const Call& call, Call& ok) {
   if (!use_ev) ok.T_e = 0;
   const int B = ok.B, T_r = ok.T_r, T_e = ok.T_e, W = ok.W, L = ok.L;
   const float *raw = ok.raw, *ev = ok.ev;
-  if (B < 0 || B > c.max_batch) return fail(h, RV_EINVAL, "B=%d outside [0,%d]", B, c.max_batch);
+  if (B < 0 || B > cx->cap) return fail(h, RV_EINVAL, "B=%d outside [0,%d]", B, cx->cap);      // (a group's context: its members' slabs together)
   if (use_raw && (T_r < 1 || T_r > c.max_raw_len)) return fail(h, RV_EINVAL, "T_r=%d outside [1,%d]", T_r, c.max_raw_len);
   if (use_ev && (T_e < 1 || T_e > c.max_event_len)) return fail(h, RV_EINVAL, "T_e=%d outside [1,%d]", T_e, c.max_event_len);
   if (W < 1 || W > c.max_beam || W > RV_MAX_BEAM) return fail(h, RV_EINVAL, "beam width %d outside [1,%d]", W, std::min(c.max_beam, RV_MAX_BEAM));
@@ -614,31 +676,31 @@ int validate_call(RvContext* h, const Call& call, Call& ok) {
   // weight_parts 1: only the decode whose every weight comes from an image of a rounded tensor -- the persistent decode of one cell
   // with Luong attention and the cell product on the matrix pipe (ATT 3: Wkp16 / Wmp16, Wc16, Wl16).  The per-step kernels and the
   // other persistent forms read the cell kernel, the attention layer or the output layer from the blob, which holds them unrounded
-  if ((h->parent ? h->parent : h)->opt.parts_loaded == 1 && (c.dec_depth != 1 || persist_form(h, ok.greedy, W, T_r + T_e, ok.forced != nullptr) != 3))
+  if (h->opt.parts_loaded == 1 && (c.dec_depth != 1 || persist_form(cx, ok.greedy, W, T_r + T_e, ok.forced != nullptr) != 3))
     return fail(h, RV_EUNSUPPORTED, "weight_parts 1 serves the persistent decode of one decoder cell with Luong attention and the cell product on the matrix "
                 "pipe only (options persistent_decode, flash_attend, matrix_attention, matrix_cell at 1, debug_taps 0): this call would read unrounded weights");
   return RV_OK;
 }
 
 // Everything of a call up to (not including) the wait for the stream: launches and the D2H copies into pinned staging.
-int enqueue(RvContext* h, const Call& stated, const CallParts& res) {
-  if (!h) return RV_EINVAL;
-  const RvConfig& c = h->cfg;
-  if (h->pend.busy) return fail(h, RV_ESTATE, "this context still holds an uncollected call");
+int enqueue(SlabCtx* cx, const Call& stated, const CallParts& res) {
+  RvContext* const h = cx->h; const RvConfig& c = h->cfg;
+  if (cx->pend.busy) return fail(h, RV_ESTATE, "this context still holds an uncollected call");
   const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
   Call call;
-  TRY(validate_call(h, stated, call));
+  TRY(validate_call(cx, stated, call));
   const int B = call.B, T_r = call.T_r, T_e = call.T_e, W = call.W, L = call.L;
   const bool greedy = call.greedy, dev_out = call.dev_out, calls = call.lut != nullptr;
   HIPCHK(h, hipSetDevice(c.device));
-  h->lB = B; h->fact.lW = W; h->lL = L; h->lS = 0; h->lgreedy = greedy; h->lTm = T_r + T_e; h->ltaps = h->opt.taps; h->lptaps = h->opt.ptaps;
-  h->lmoves = res.moves ? 1 : 0;
-  h->lforms.n = 0; h->lforms.full = false; h->lforms_ok = 1;
-  h->pend = RvContext::PendingCall{};
-  h->pend.busy = true; h->pend.greedy = greedy; h->pend.dev_out = dev_out; h->pend.calls = calls; h->pend.all = res.whole_beam; h->pend.moves = res.moves;
-  h->pend.B = B; h->pend.steps = std::max(L - 1, 0); h->pend.V = c.vocab; h->pend.Wd = greedy ? 1 : W;
+  cx->lB = B; cx->fact.lW = W; cx->lL = L; cx->lgreedy = greedy; cx->lTm = T_r + T_e; cx->ltaps = cx->taps(); cx->lptaps = cx->ptaps();
+  cx->lmoves = res.moves ? 1 : 0;
+  if (cx->own()) h->lS = 0;
+  cx->lforms.n = 0; cx->lforms.full = false; cx->lforms_ok = 1;
+  cx->pend = SlabCtx::PendingCall{};
+  cx->pend.busy = true; cx->pend.greedy = greedy; cx->pend.dev_out = dev_out; cx->pend.calls = calls; cx->pend.all = res.whole_beam; cx->pend.moves = res.moves;
+  cx->pend.B = B; cx->pend.steps = std::max(L - 1, 0); cx->pend.V = c.vocab; cx->pend.Wd = greedy ? 1 : W;
   if (B == 0 || L <= 1) {
-    h->pend.trivial = true;
+    cx->pend.trivial = true;
     if (res.whole_beam && dev_out && B > 0) {      // nothing is launched: the initial state goes to the caller's device buffers by plain copies
       std::vector<float> lp((size_t)B * W, -INFINITY);
       for (int b = 0; b < B; ++b) lp[(size_t)b * W] = 0.f;
@@ -650,74 +712,59 @@ int enqueue(RvContext* h, const Call& stated, const CallParts& res) {
 
   // From here on `call` names device memory throughout: the inputs the encoders read and the outputs the finalize kernel writes
   // (dev_in / dev_out still say whose they are, so which copies the recording adds)
-  hipStream_t s = h->stream;
+  hipStream_t s = cx->stream;
   if (!call.dev_in) {   // host -> pinned staging (CPU memcpy); the H2D copies are part of the slab's stream work (record_slab)
-    if (use_raw) { memcpy(h->pin_raw, call.raw, sizeof(float) * B * T_r); call.raw = h->d_raw; }
-    if (use_ev) { memcpy(h->pin_ev, call.ev, sizeof(float) * B * T_e * 5); call.ev = h->d_ev; }
+    if (use_raw) { memcpy(cx->pin_raw, call.raw, sizeof(float) * B * T_r); call.raw = cx->d_raw; }
+    if (use_ev) { memcpy(cx->pin_ev, call.ev, sizeof(float) * B * T_e * 5); call.ev = cx->d_ev; }
   }
-  if (!dev_out || !call.tokens) call.tokens = h->out_tokens;
-  if (!dev_out || !call.out2) call.out2 = h->out2;
+  if (!dev_out || !call.tokens) call.tokens = cx->out_tokens;
+  if (!dev_out || !call.out2) call.out2 = cx->out2;
 
-  const int form_B = res.form_B >= 0 ? res.form_B : B;      // a group takes the forms its first member would have got alone
-  const bool gru = h->rnn == RV_RNN_BIGRU;               // its one recurrence is the sixteen-chunk matrix-pipe kernel, whatever the slab
-  h->lwide = gru || wide_recurrence(h, form_B, T_r) ? 1 : 0;
-  h->lrows8 = !gru && h->lwide && rows8_wanted(h, form_B) ? 1 : 0;
-  const bool windowed = call.windows != nullptr;
-  if (windowed) {
+  const Plan plan = plan_call(cx, call, res);
+  if (call.windows) {
     // The table goes to this context's pinned staging now (a group's rows are there already: submit_group); its device copy is the first
-    // thing the recording queues (stage_inputs).  The default path gathers each chunk in the lane of its layer-0 recurrence; every other
-    // form -- the packed-FMA recurrence, "lane_projection" 0, the per-step decode, taps, profiling, a group with "group_inplace" 0 --
-    // runs unchanged behind k_expand_windows, which writes the padded chunk tensors into the context's input buffers
-    if (call.windows != h->pin_win) memcpy(h->pin_win, call.windows, sizeof(RecWindow) * (size_t)B);
-    call.windows = h->d_win;
-    const bool lane = h->lwide && (!use_ev || lane_layer0(h, 5, T_e)) && h->opt.profile == 0 && !h->opt.taps &&
-                      persist_form(h, greedy, W, T_r + T_e, res.labels != nullptr) >= 0 && !(h->g_cap > 0 && !h->opt.group_inplace);
-    call.win_expand = !lane;
-    if (call.win_expand) { call.raw = use_raw ? h->d_raw : nullptr; call.ev = use_ev ? h->d_ev : nullptr; }
-  }
-  if ((!h->opt.fuse && c.enc_depth > 1) || h->lwide) {   // pre-projected tensors [max_batch, T_max, 2, 512]: allocated with the context (alloc_slab_buffers); this is a safety net
-    if (use_raw && c.enc_depth > 1 && !h->xw[0]) TRY(dalloc(h, &h->xw[0], (size_t)c.max_batch * c.max_raw_len * 2 * RV_G));
-    if (use_ev && !h->xw[1]) TRY(dalloc(h, &h->xw[1], (size_t)c.max_batch * c.max_event_len * 2 * RV_G));
+    // thing the recording queues (stage_inputs)
+    if (call.windows != cx->pin_win) memcpy(cx->pin_win, call.windows, sizeof(RecWindow) * (size_t)B);
+    call.windows = cx->d_win;
+    call.win_expand = !plan.win_lane;
+    if (call.win_expand) { call.raw = use_raw ? cx->d_raw : nullptr; call.ev = use_ev ? cx->d_ev : nullptr; }
   }
 
-  // ---- one hipGraph per slab context and call shape (option "slab_graph"): the default path -- matrix-pipe recurrences + persistent
-  // decode, no profiling, no taps -- replays as ONE hipGraphLaunch instead of ten launches (a submit's host time is what the GPU waits
-  // for whenever the slabs in flight finish together).  All kernel arguments are frozen at capture; the caller's addresses of THIS
-  // call go through the pointer table (mapped pinned memory, written here, read by the kernels).
-  RvContext* root = h->parent ? h->parent : h;
-  if (h->graph_gen != root->opt.gen) {          // an option or the weights changed since the capture: frozen arguments may be stale
-    for (auto& kv : h->slab_graphs) hipGraphExecDestroy(kv.second.exec);
-    h->slab_graphs.clear();
-    h->graph_gen = root->opt.gen;
+  // ---- one hipGraph per slab context and call shape (option "slab_graph"): the default path replays as ONE hipGraphLaunch instead
+  // of ten launches (a submit's host time is what the GPU waits for whenever the slabs in flight finish together).  All kernel arguments
+  // are frozen at capture; the caller's addresses of THIS call go through the pointer table (mapped pinned memory, written here, read by
+  // the kernels).
+  if (cx->graph_gen != h->opt.gen) {            // an option or the weights changed since the capture: frozen arguments may be stale
+    for (auto& kv : cx->slab_graphs) hipGraphExecDestroy(kv.second.exec);
+    cx->slab_graphs.clear();
+    cx->graph_gen = h->opt.gen;
   }
-  const bool graphable = root->opt.slab_graph && !windowed && h->lwide && !h->lrows8 && persist_form(h, greedy, W, T_r + T_e, res.labels != nullptr) >= 0 && h->opt.profile == 0 && !h->opt.taps &&
-                         !res.whole_beam && !res.labels && !h->opt.ptaps && !h->rec_ts && !h->dec_st.dbg_ts && h->d_ptab;
-  if (!graphable) return record_slab(h, call, res, nullptr);
-  h->lforms_ok = 0;                             // (a slab graph replays without the host launchers: "kernel_forms" answers RV_ESTATE)
-  h->pin_ptab[RV_PTAB_RAW] = call.raw; h->pin_ptab[RV_PTAB_EVENT] = call.ev; h->pin_ptab[RV_PTAB_TOKENS] = call.tokens; h->pin_ptab[RV_PTAB_OUT2] = call.out2;
+  if (!plan.graphable) return record_slab(cx, call, res, plan, nullptr);
+  cx->lforms_ok = 0;                             // (a slab graph replays without the host launchers: "kernel_forms" answers RV_ESTATE)
+  cx->pin_ptab[RV_PTAB_RAW] = call.raw; cx->pin_ptab[RV_PTAB_EVENT] = call.ev; cx->pin_ptab[RV_PTAB_TOKENS] = call.tokens; cx->pin_ptab[RV_PTAB_OUT2] = call.out2;
   SlabKey key{B, T_r, T_e, W, L, (greedy ? 1 : 0) | (calls ? 2 : 0) | (call.dev_in ? 0 : 4) | (dev_out ? 0 : 8), 0};
   if (calls) memcpy(&key.lut, call.lut, std::min<size_t>(sizeof key.lut, (size_t)c.vocab));
-  auto it = h->slab_graphs.find(key);
-  if (it == h->slab_graphs.end()) {
-    if (h->slab_graphs.size() >= 16) {          // bound the cache (callers with ever-changing slab shapes)
-      for (auto& kv : h->slab_graphs) hipGraphExecDestroy(kv.second.exec);
-      h->slab_graphs.clear();
+  auto it = cx->slab_graphs.find(key);
+  if (it == cx->slab_graphs.end()) {
+    if (cx->slab_graphs.size() >= 16) {          // bound the cache (callers with ever-changing slab shapes)
+      for (auto& kv : cx->slab_graphs) hipGraphExecDestroy(kv.second.exec);
+      cx->slab_graphs.clear();
     }
     hipGraph_t graph = nullptr;
     HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int rc = record_slab(h, call, res, h->d_ptab);
+    const int rc = record_slab(cx, call, res, plan, cx->d_ptab);
     const hipError_t ce = hipStreamEndCapture(s, &graph);      // (always: the stream must leave capture mode whatever record_slab said)
     if (rc != RV_OK) { if (graph) hipGraphDestroy(graph); return rc; }
     HIPCHK(h, ce);
-    RvContext::SlabGraph g;
+    SlabCtx::SlabGraph g;
     const hipError_t ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
     HIPCHK(h, ie);
-    g.fact = h->fact;
-    it = h->slab_graphs.emplace(key, g).first;
+    g.fact = cx->fact;
+    it = cx->slab_graphs.emplace(key, g).first;
   }
-  const RvContext::SlabGraph& g = it->second;
-  h->fact = g.fact;
+  const SlabCtx::SlabGraph& g = it->second;
+  cx->fact = g.fact;
   HIPCHK(h, hipGraphLaunch(g.exec, s));
   return RV_OK;
 }
@@ -726,9 +773,9 @@ int enqueue(RvContext* h, const Call& stated, const CallParts& res) {
 struct Slab {
   const Call& call;
   const CallParts& res;
+  const Plan& plan;
   const void* const* ptab;      // non-null: the call is being captured into a slab graph
   int Tm, steps;
-  int persist_att = -1;         // persist_form of the call
   DecState d{};                 // the whole slab's decode ...
   int nsplit = 1;
   DecState part[4];             // ... and its sub-slabs (one part unless the per-step decode splits)
@@ -736,51 +783,51 @@ struct Slab {
 };
 
 // Phase 1 of a recording: the inputs of a host caller, pinned staging -> device
-int stage_inputs(RvContext* h, const Slab& sl) {
-  const RvConfig& c = h->cfg;
+int stage_inputs(SlabCtx* cx, const Slab& sl) {
+  RvContext* const h = cx->h; const RvConfig& c = h->cfg;
   const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
   const int B = sl.call.B, T_r = sl.call.T_r, T_e = sl.call.T_e;
-  hipStream_t s = h->stream;
+  hipStream_t s = cx->stream;
   if (!sl.call.dev_in) {   // pinned staging -> device
-    if (use_raw) HIPCHK(h, hipMemcpyAsync(h->d_raw, h->pin_raw, sizeof(float) * B * T_r, hipMemcpyHostToDevice, s));
-    if (use_ev) HIPCHK(h, hipMemcpyAsync(h->d_ev, h->pin_ev, sizeof(float) * B * T_e * 5, hipMemcpyHostToDevice, s));
+    if (use_raw) HIPCHK(h, hipMemcpyAsync(cx->d_raw, cx->pin_raw, sizeof(float) * B * T_r, hipMemcpyHostToDevice, s));
+    if (use_ev) HIPCHK(h, hipMemcpyAsync(cx->d_ev, cx->pin_ev, sizeof(float) * B * T_e * 5, hipMemcpyHostToDevice, s));
   }
   if (sl.call.windows) {   // a window call: its table, 24 bytes per chunk, behind the uploads of the reads it names
-    RvContext* root = h->parent ? h->parent : h;
-    if (root->ev_put) HIPCHK(h, hipStreamWaitEvent(s, root->ev_put, 0));
-    HIPCHK(h, hipMemcpyAsync(h->d_win, h->pin_win, sizeof(RecWindow) * (size_t)B, hipMemcpyHostToDevice, s));
+    if (h->ev_put) HIPCHK(h, hipStreamWaitEvent(s, h->ev_put, 0));
+    HIPCHK(h, hipMemcpyAsync(cx->d_win, cx->pin_win, sizeof(RecWindow) * (size_t)B, hipMemcpyHostToDevice, s));
     if (sl.call.win_expand) {
-      Scope sc(h, "expand_windows");
-      root->win_expands += 1;
-      launch_expand_windows(h->d_win, B, use_raw ? h->d_raw : nullptr, T_r, use_ev ? h->d_ev : nullptr, T_e, c.padding_value, s);
+      Scope sc(cx, "expand_windows");
+      h->win_expands += 1;
+      launch_expand_windows(cx->d_win, B, use_raw ? cx->d_raw : nullptr, T_r, use_ev ? cx->d_ev : nullptr, T_e, c.padding_value, s);
     }
   }
   return RV_OK;
 }
 
 // Phase 2: the input mask and the two encoders, on one of three stream arrangements
-int record_encoders(RvContext* h, const Slab& sl) {
-  const RvConfig& c = h->cfg;
+int record_encoders(SlabCtx* cx, const Slab& sl) {
+  RvContext* const h = cx->h; const RvConfig& c = h->cfg;
   const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
   const int B = sl.call.B, T_r = sl.call.T_r, T_e = sl.call.T_e, Tm = sl.Tm;
   const float *xr = sl.call.raw, *xe = sl.call.ev;
   const void* const* ptab = sl.ptab;
   const RecWindow* win = sl.call.win_expand ? nullptr : sl.call.windows;      // (only the matrix-pipe layer 0 with the projection in the lane takes windows: enqueue)
-  hipStream_t s = h->stream;
+  hipStream_t s = cx->stream;
   // ---- _encode_input (basecaller.py:395-416)
   // The mask is first read by the memory set-up / the decode: it runs on a side stream beside the encoders instead of in front
   // of them (profiling modes keep it on the main stream so that its events pair up).
   // (with several slabs in flight the other slabs fill the chip: one stream per context then, no fork / join)
   // The matrix-pipe layer-0 kernels write it themselves (they read every input sample anyway): no launch at all then.
-  const bool mask_aside = !h->lwide && (h->opt.profile == 0 || h->opt.profile == 3) && h->inflight_hint <= 1 && !h->parent;
+  const bool wide = sl.plan.wide;
+  const bool mask_aside = !wide && (h->opt.profile == 0 || h->opt.profile == 3) && h->inflight_hint <= 1 && cx->own();
   if (mask_aside) {
-    hipStream_t sm = side_stream(h, 2);
-    HIPCHK(h, hipEventRecord(h->ev_fork, s));
-    HIPCHK(h, hipStreamWaitEvent(sm, h->ev_fork, 0));     // inputs (H2D copies on s) are in place
-    launch_input_mask(xr, xe, B, T_r, T_e, c.padding_value, h->mask, sm);
-    HIPCHK(h, hipEventRecord(h->ev_join[2], sm));
-  } else if (!h->lwide) {
-    Scope sc(h, "input_mask"); launch_input_mask(xr, xe, B, T_r, T_e, c.padding_value, h->mask, s);
+    hipStream_t sm = side_stream(cx, 2);
+    HIPCHK(h, hipEventRecord(cx->ev_fork, s));
+    HIPCHK(h, hipStreamWaitEvent(sm, cx->ev_fork, 0));     // inputs (H2D copies on s) are in place
+    launch_input_mask(xr, xe, B, T_r, T_e, c.padding_value, cx->mask, sm);
+    HIPCHK(h, hipEventRecord(cx->ev_join[2], sm));
+  } else if (!wide) {
+    Scope sc(cx, "input_mask"); launch_input_mask(xr, xe, B, T_r, T_e, c.padding_value, cx->mask, s);
   }
   // The two encoders are independent until the time-axis concat (basecaller.py:400-405).
   const bool side_ev = use_raw && use_ev && h->opt.side_ev && c.enc_depth > 1 && !h->opt.fuse;   // (nothing MFMA-bound to hide under once the projection is fused)
@@ -788,16 +835,16 @@ int record_encoders(RvContext* h, const Slab& sl) {
     // raw layer 0 alone (every recurrence workgroup needs a whole CU); then the short event chain on a side stream
     // UNDER the raw encoder's input-projection GEMM: a recurrence workgroup (2 x 168 VGPRs per SIMD, VALU-bound) and a
     // GEMM workgroup (144 registers, MFMA-bound) fit on one CU together.
-    hipStream_t sev = side_stream(h, 0);
-    run_encoder(h, 0, xr, 1, B, T_r, Tm, 0, s, 0, 1);
-    HIPCHK(h, hipEventRecord(h->ev_fork, s));
-    HIPCHK(h, hipStreamWaitEvent(sev, h->ev_fork, 0));
-    run_encoder(h, 1, xe, 5, B, T_e, Tm, T_r, sev);
-    run_encoder(h, 0, xr, 1, B, T_r, Tm, 0, s, 1);
-    HIPCHK(h, hipEventRecord(h->ev_join[0], sev));
-    HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[0], 0));
-  } else if (h->lwide && use_raw && use_ev && !ptab && h->opt.profile == 0 &&
-             ((h->inflight_hint <= 1 && h->opt.side_ev) || (h->g_cap > 0 && h->parent && group_side_ev(h->parent)))) {
+    hipStream_t sev = side_stream(cx, 0);
+    run_encoder(cx, sl.plan, 0, xr, 1, B, T_r, Tm, 0, s, 0, 1);
+    HIPCHK(h, hipEventRecord(cx->ev_fork, s));
+    HIPCHK(h, hipStreamWaitEvent(sev, cx->ev_fork, 0));
+    run_encoder(cx, sl.plan, 1, xe, 5, B, T_e, Tm, T_r, sev);
+    run_encoder(cx, sl.plan, 0, xr, 1, B, T_r, Tm, 0, s, 1);
+    HIPCHK(h, hipEventRecord(cx->ev_join[0], sev));
+    HIPCHK(h, hipStreamWaitEvent(s, cx->ev_join[0], 0));
+  } else if (wide && use_raw && use_ev && !ptab && h->opt.profile == 0 &&
+             ((h->inflight_hint <= 1 && h->opt.side_ev) || (cx->grp && group_side_ev(h)))) {
     // One isolated slab on the matrix-pipe form: every encoder launch is 2 x ceil(B / 16) workgroups (32 of the chip's 256 CUs at B = 256), so
     // the event encoder's chain (four launches, ~0.15 ms at the C3 shape) runs on a side stream BESIDE the raw encoder's instead of in front of
     // it: the synchronous call's latency drops by that much.  (With several slabs in flight the other slabs fill the chip: one stream per
@@ -806,107 +853,100 @@ int record_encoders(RvContext* h, const Slab& sl) {
     // A group of coalesced slabs forks the same way where the queues allow it (group_side_ev): with two groups in flight each one's next
     // launch waits for its whole chain, and the event launches (2 x ceil(B / 16) workgroups: 160 of 256 CUs for five C3 slabs) need not be
     // links of it.
-    hipStream_t sev = side_stream(h, 0);
-    HIPCHK(h, hipEventRecord(h->ev_fork, s));
-    HIPCHK(h, hipStreamWaitEvent(sev, h->ev_fork, 0));       // inputs (H2D copies on s) are in place
-    run_encoder(h, 1, xe, 5, B, T_e, Tm, T_r, sev, 0, 1 << 30, nullptr, win);
-    HIPCHK(h, hipEventRecord(h->ev_join[0], sev));
-    run_encoder(h, 0, xr, 1, B, T_r, Tm, 0, s, 0, 1 << 30, nullptr, win);
-    HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[0], 0));
+    hipStream_t sev = side_stream(cx, 0);
+    HIPCHK(h, hipEventRecord(cx->ev_fork, s));
+    HIPCHK(h, hipStreamWaitEvent(sev, cx->ev_fork, 0));       // inputs (H2D copies on s) are in place
+    run_encoder(cx, sl.plan, 1, xe, 5, B, T_e, Tm, T_r, sev, 0, 1 << 30, nullptr, win);
+    HIPCHK(h, hipEventRecord(cx->ev_join[0], sev));
+    run_encoder(cx, sl.plan, 0, xr, 1, B, T_r, Tm, 0, s, 0, 1 << 30, nullptr, win);
+    HIPCHK(h, hipStreamWaitEvent(s, cx->ev_join[0], 0));
   } else {
-    if (use_ev) run_encoder(h, 1, xe, 5, B, T_e, Tm, T_r, s, 0, 1 << 30, ptab, win);
-    if (use_raw) run_encoder(h, 0, xr, 1, B, T_r, Tm, 0, s, 0, 1 << 30, ptab, win);
+    if (use_ev) run_encoder(cx, sl.plan, 1, xe, 5, B, T_e, Tm, T_r, s, 0, 1 << 30, ptab, win);
+    if (use_raw) run_encoder(cx, sl.plan, 0, xr, 1, B, T_r, Tm, 0, s, 0, 1 << 30, ptab, win);
   }
 
-  if (mask_aside) HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[2], 0));
+  if (mask_aside) HIPCHK(h, hipStreamWaitEvent(s, cx->ev_join[2], 0));
   return RV_OK;
 }
 
-// Phase 3: which attend and which decode the call takes (lflash, persist_att), and the key GEMM where they need it
-int record_keys(RvContext* h, Slab& sl) {
-  const RvConfig& c = h->cfg;
-  const int B = sl.call.B, W = sl.call.W, Tm = sl.Tm;
-  const bool greedy = sl.call.greedy;
-  hipStream_t s = h->stream;
-  // ---- setup_memory (basecaller.py:303): keys = (enc_output * mask) . W_mem.  The single-pass Luong
-  //      attend never reads keys (score_t = values_t . (W_mem q)); they are built for the two-pass
-  //      kernel and for the "keys" debug tap only.
-  const int W_eff = greedy ? 1 : W;
-  h->fact.lflash = (c.attention == RV_ATT_LUONG && h->opt.flash && W_eff <= 5) ? 1 : 0;   // wider beams: register budget -> two-pass
-  // the persistent decode needs neither keys nor the per-step kernels
-  const int persist_att = sl.persist_att = persist_form(h, greedy, W, Tm, sl.res.labels != nullptr);
-  // (a moves call on the per-step kernels forms its alignments in the two-pass attend, beside the single-pass one where that runs the step)
-  h->fact.lkeys = ((!h->fact.lflash && persist_att < 0) || h->opt.taps || (sl.res.moves && persist_att < 0)) ? 1 : 0;
-  if (h->fact.lkeys) {
+// Phase 3: the key GEMM where the call's attend or a tap needs it (Plan::keys)
+int record_keys(SlabCtx* cx, const Slab& sl) {
+  RvContext* const h = cx->h;
+  const int B = sl.call.B, Tm = sl.Tm;
+  hipStream_t s = cx->stream;
+  cx->fact.lflash = sl.plan.flash ? 1 : 0;
+  cx->fact.lkeys = sl.plan.keys ? 1 : 0;
+  if (sl.plan.keys) {
     GemmArgs g{};
-    g.A = h->enc_out; g.lda = RV_E; g.Bm = h->W_mem; g.ldb = RV_U; g.C = h->keys; g.ldc = RV_U;
-    g.M = B * Tm; g.N = RV_U; g.K = RV_E; g.row_mask = h->mask;
-    Scope sc(h, "gemm_keys");
+    g.A = cx->enc_out; g.lda = RV_E; g.Bm = h->W_mem; g.ldb = RV_U; g.C = cx->keys; g.ldc = RV_U;
+    g.M = B * Tm; g.N = RV_U; g.K = RV_E; g.row_mask = cx->mask;
+    Scope sc(cx, "gemm_keys");
     launch_gemm_f32(g, false, s);
   }
   return RV_OK;
 }
 
 // A debug-tap buffer of at least `need` floats
-int grow_tap_buffer(RvContext* h, float** buf, size_t* cap, size_t need) {
+int grow_tap_buffer(SlabCtx* cx, float** buf, size_t* cap, size_t need) {
+  RvContext* const h = cx->h;
   if (need <= *cap) return RV_OK;
   if (*buf) hipFree(*buf);
   *buf = nullptr; *cap = 0;
-  for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // captured args hold the old pointer
-  h->graphs.clear();
+  for (auto& kv : cx->graphs) hipGraphExecDestroy(kv.second);   // captured args hold the old pointer
+  cx->graphs.clear();
   HIPCHK(h, hipMalloc((void**)buf, need * sizeof(float)));
   *cap = need;
   return RV_OK;
 }
 
 // Phase 4: the decode's arguments (sl.d) and the debug-tap buffers
-int fill_dec_state(RvContext* h, Slab& sl) {
-  const RvConfig& c = h->cfg;
+int fill_dec_state(SlabCtx* cx, Slab& sl) {
+  RvContext* const h = cx->h; const RvConfig& c = h->cfg;
   const int B = sl.call.B, W = sl.call.W, L = sl.call.L, Tm = sl.Tm, V = c.vocab, steps = sl.steps;
   const bool greedy = sl.call.greedy, calls = sl.call.lut != nullptr;
-  hipStream_t s = h->stream;
+  hipStream_t s = cx->stream;
   // ---- decode loop
   DecState& d = sl.d;
-  d = h->dec_st;
+  d = cx->dec_st;
   d.B = B; d.W = greedy ? 1 : W; d.Tm = Tm; d.V = V; d.L = L;
   d.greedy = greedy; d.attention = c.attention;
   d.forced = sl.res.labels;
   d.start_token = c.start_token; d.end_token = c.end_token; d.pad_token = c.pad_token;
   d.attend_threads = h->opt.att_nt;
-  d.keys = h->keys; d.values = h->enc_out; d.mask = h->mask;
+  d.keys = cx->keys; d.values = cx->enc_out; d.mask = cx->mask;
   d.W_att = h->W_att; d.W_fc = h->W_fc; d.b_fc = h->b_fc; d.W_q = h->W_q; d.v_att = h->v_att;
   d.call_bases = nullptr; d.call_probs = nullptr; d.call_len = nullptr;
   if (calls) {
-    d.call_bases = h->d_bases; d.call_probs = h->d_probs; d.call_len = h->d_clen;
+    d.call_bases = cx->d_bases; d.call_probs = cx->d_probs; d.call_len = cx->d_clen;
     for (int v = 0; v < RV_MAX_VOCAB; ++v) d.lut[v] = v < V ? sl.call.lut[v] : 0;
   }
   const size_t need = (size_t)steps * B * d.W * Tm;      // alignments of every step
-  if (h->opt.taps) {
-    TRY(grow_tap_buffer(h, &h->step_align, &h->step_align_cap, need));
-    d.step_align = h->step_align;
+  if (cx->taps()) {
+    TRY(grow_tap_buffer(cx, &cx->step_align, &cx->step_align_cap, need));
+    d.step_align = cx->step_align;
   } else {
     d.step_align = nullptr;
-    if (!greedy && !h->opt.ptaps) d.step_logits = nullptr;
+    if (!greedy && !cx->ptaps()) d.step_logits = nullptr;
   }
   d.persist_align = nullptr;
-  if (h->opt.ptaps) {
-    TRY(grow_tap_buffer(h, &h->palign, &h->palign_cap, need));
+  if (cx->ptaps()) {
+    TRY(grow_tap_buffer(cx, &cx->palign, &cx->palign_cap, need));
     // NaN everywhere first: a step the kernel does not record is never read as a stale value of an earlier call
-    if (need) HIPCHK(h, hipMemsetAsync(h->palign, 0xff, need * sizeof(float), s));
-    d.persist_align = h->palign;
+    if (need) HIPCHK(h, hipMemsetAsync(cx->palign, 0xff, need * sizeof(float), s));
+    d.persist_align = cx->palign;
   }
-  d.step_moves = sl.res.moves ? h->d_step_moves : nullptr;
+  d.step_moves = sl.res.moves ? cx->d_step_moves : nullptr;
   d.Tr = sl.call.T_r;      // (effective lengths: T_m in raw mode, 0 in event mode)
   d.moves_only = 0;
   return RV_OK;
 }
 
 // ... then which decode runs (lpersist), its sub-slabs (sl.part, sl.parts) and, for the per-step kernels, their initial state
-int split_decode(RvContext* h, Slab& sl) {
-  const RvConfig& c = h->cfg;
-  const int B = sl.call.B, Tm = sl.Tm, V = c.vocab, steps = sl.steps, persist_att = sl.persist_att;
+int split_decode(SlabCtx* cx, Slab& sl) {
+  RvContext* const h = cx->h; const RvConfig& c = h->cfg;
+  const int B = sl.call.B, Tm = sl.Tm, V = c.vocab, steps = sl.steps, persist_att = sl.plan.persist;
   const bool greedy = sl.call.greedy;
-  hipStream_t s = h->stream;
+  hipStream_t s = cx->stream;
   DecState& d = sl.d;
   DecState* part = sl.part;
   DecParts& parts = sl.parts;
@@ -917,16 +957,17 @@ int split_decode(RvContext* h, Slab& sl) {
   // output / beam phases.  Chunks never interact, and a sub-slab that finishes early is extended by
   // k_dec_finalize exactly as the reference's whole-slab loop would (beam search only; greedy rows
   // keep sampling after their end token, so greedy decodes as one piece).
-  nsplit = (greedy || h->opt.taps || B < 64) ? 1 : std::min(std::max(h->opt.split, 1), 4);
+  nsplit = (greedy || cx->taps() || B < 64) ? 1 : std::min(std::max(h->opt.split, 1), 4);
   d.chunk_steps = nullptr;
   d.persist_att = persist_att;
   d.Wc16 = h->img.Wc16; d.mx_cdescale = h->scales.cdescale; d.Wl16 = h->img.Wl16; d.mx_ldescale = h->scales.ldescale;
   d.Wq16 = h->img.Wq16; d.mx_qdescale = h->scales.qdescale; d.W1c16 = h->img.W1c16; d.mx_c1descale = h->scales.c1descale;
-  h->fact.lpersist = persist_att >= 0 ? 1 : 0;
-  h->fact.lmem2_stale = 0;
-  if (h->fact.lpersist) { nsplit = 1; d.chunk_steps = h->d_chunk_steps; }
-  h->fact.lsplit = nsplit;
-  if (!h->fact.lpersist) {
+  const bool persist = persist_att >= 0;
+  cx->fact.lpersist = persist ? 1 : 0;
+  cx->fact.lmem2_stale = 0;
+  if (persist) { nsplit = 1; d.chunk_steps = cx->d_chunk_steps; }
+  cx->fact.lsplit = nsplit;
+  if (!persist) {
     for (int k = 0; k < d.depth; ++k) {     // get_initial_state: all zeros (basecaller.py:305); the persistent kernel keeps state in LDS
       HIPCHK(h, hipMemsetAsync(d.xh + k * d.ls_xh, 0, sizeof(float) * N * RV_E, s));
       if (h->rnn == RV_RNN_BILSTM) HIPCHK(h, hipMemsetAsync(d.c + k * d.ls_c, 0, sizeof(float) * N * RV_U, s));      // (a GRU cell has no c)
@@ -952,16 +993,17 @@ int split_decode(RvContext* h, Slab& sl) {
     if (p.step_moves) p.step_moves += (size_t)steps * Wd * RV_MOVE_COLS * b0;
     p.nfin = d.nfin + g * (c.max_output_len + 1);
     parts.nfin[g] = p.nfin; parts.B[g] = p.B;
-    if (!h->fact.lpersist) launch_dec_init(p, s);
+    if (!persist) launch_dec_init(p, s);
   }
   return RV_OK;
 }
 
 // Phase 5: the persistent decode -- the whole loop in one launch, behind the projection of its attention memory where it does not project its own
-int decode_persist(RvContext* h, Slab& sl) {
-  const int B = sl.call.B, Tm = sl.Tm, V = h->cfg.vocab, persist_att = sl.persist_att;
+int decode_persist(SlabCtx* cx, Slab& sl) {
+  RvContext* const h = cx->h;
+  const int B = sl.call.B, Tm = sl.Tm, V = h->cfg.vocab, persist_att = sl.plan.persist;
   const bool greedy = sl.call.greedy;
-  hipStream_t s = h->stream;
+  hipStream_t s = cx->stream;
   DecState& d = sl.d;
   DecState* part = sl.part;
   DecParts& parts = sl.parts;
@@ -970,42 +1012,43 @@ int decode_persist(RvContext* h, Slab& sl) {
   // The default form (Luong, one cell, everything on the matrix pipe) takes enc_out and projects each chunk's rows in its own
   // prologue, with the split GEMM's arithmetic (decode.hip, persist_project_memory); every other form reads the GEMM's mem2
   const bool fused_mem = h->opt.fused_mem && h->opt.split_proj && persist_att == 3 && d.depth == 1;
-  h->fact.lmem2_stale = fused_mem && !h->opt.ptaps;
+  cx->fact.lmem2_stale = fused_mem && !cx->ptaps();
   d.enc_rows = nullptr; d.Wmp16 = h->img.Wmp16; d.Wkp16 = h->img.Wkp16; d.mem_tap = nullptr;
   if (fused_mem) {
-    d.enc_rows = h->enc_out; d.mem_tap = h->opt.ptaps ? h->mem2 : nullptr;
+    d.enc_rows = cx->enc_out; d.mem_tap = cx->ptaps() ? cx->mem2 : nullptr;
   } else {   // attention memory in the form the persistent decode keeps on chip: [keys | U'] = enc_out . [W_mem | A_c]
     GemmArgs g{};
-    g.A = h->enc_out; g.lda = RV_E; g.Bm = h->img.Wmp; g.ldb = RV_E; g.C = h->mem2; g.ldc = RV_E;
+    g.A = cx->enc_out; g.lda = RV_E; g.Bm = h->img.Wmp; g.ldb = RV_E; g.C = cx->mem2; g.ldc = RV_E;
     g.M = B * Tm; g.N = RV_E; g.K = RV_E;
     g.xcd_remap = 1;
-    Scope sc(h, "gemm_memory");
-    if (h->opt.split_proj) launch_gemm_mem_split(h->enc_out, B * Tm, h->img.Wmp16, h->mem2, s);
+    Scope sc(cx, "gemm_memory");
+    if (h->opt.split_proj) launch_gemm_mem_split(cx->enc_out, B * Tm, h->img.Wmp16, cx->mem2, s);
     else launch_gemm_f32(g, false, s);
   }
-  d.values = h->mem2; part[0].values = h->mem2;
+  d.values = cx->mem2; part[0].values = cx->mem2;
   d.mx_kscale = h->scales.kscale; d.mx_kdescale = std::ldexp(1.0f, -14) / h->scales.kscale;
   d.mx_uscale = h->scales.uscale; d.mx_udescale = std::ldexp(1.0f, -14) / h->scales.uscale;
   const bool p1 = h->opt.parts_loaded == 1 && h->opt.one_part && persist_att == 3 && d.depth == 1;
-  Scope sc(h, "dec_persist", nullptr, true);
+  Scope sc(cx, "dec_persist", nullptr, true);
   launch_dec_persist(d, d.depth > 1 ? h->dec[0].W + (size_t)V * RV_G : h->img.Wcat2, h->dec[0].W, h->dec[0].b,
-                     d.depth > 1 ? h->dec[1].W : nullptr, d.depth > 1 ? h->dec[1].b : nullptr, h->img.Nh, s, &h->lforms,
+                     d.depth > 1 ? h->dec[1].W : nullptr, d.depth > 1 ? h->dec[1].b : nullptr, h->img.Nh, s, &cx->lforms,
                      p1 ? h->img.Wc16p1 : nullptr, p1 ? h->img.Wl16p1 : nullptr);
   return RV_OK;
 }
 
 // The per-step launches of every sub-slab: part 0 on the context's stream, the others forked onto side streams and joined again
-int fork_decode_steps(RvContext* h, const Slab& sl, bool profiled, FormLog* log) {
+int fork_decode_steps(SlabCtx* cx, const Slab& sl, bool profiled, FormLog* log) {
+  RvContext* const h = cx->h;
   const int nsplit = sl.nsplit;
-  hipStream_t s = h->stream;
+  hipStream_t s = cx->stream;
   for (int g = 1; g < nsplit; ++g) {
-    HIPCHK(h, hipEventRecord(h->ev_fork, s));
-    HIPCHK(h, hipStreamWaitEvent(side_stream(h, g - 1), h->ev_fork, 0));
+    HIPCHK(h, hipEventRecord(cx->ev_fork, s));
+    HIPCHK(h, hipStreamWaitEvent(side_stream(cx, g - 1), cx->ev_fork, 0));
   }
-  for (int g = 0; g < nsplit; ++g) launch_decode_steps(h, sl.part[g], g == 0 ? s : side_stream(h, g - 1), profiled && nsplit == 1, log);
+  for (int g = 0; g < nsplit; ++g) launch_decode_steps(cx, sl.part[g], sl.plan.flash, g == 0 ? s : side_stream(cx, g - 1), profiled && nsplit == 1, log);
   for (int g = 1; g < nsplit; ++g) {
-    HIPCHK(h, hipEventRecord(h->ev_join[g - 1], side_stream(h, g - 1)));
-    HIPCHK(h, hipStreamWaitEvent(s, h->ev_join[g - 1], 0));
+    HIPCHK(h, hipEventRecord(cx->ev_join[g - 1], side_stream(cx, g - 1)));
+    HIPCHK(h, hipStreamWaitEvent(s, cx->ev_join[g - 1], 0));
   }
   return RV_OK;
 }
@@ -1015,62 +1058,63 @@ int fork_decode_steps(RvContext* h, const Slab& sl, bool profiled, FormLog* log)
 [[gnu::used]] void (FormLog::*const formlog_merge_out_of_line)(const FormLog&) = &FormLog::merge;
 
 // Phase 6: the per-step decode -- a replay of the decode graph of this shape (captured on its first use), or direct launches
-int decode_steps(RvContext* h, Slab& sl) {
+int decode_steps(SlabCtx* cx, Slab& sl) {
+  RvContext* const h = cx->h;
   const int B = sl.call.B, L = sl.call.L, Tm = sl.Tm;
   const bool greedy = sl.call.greedy;
-  hipStream_t s = h->stream;
+  hipStream_t s = cx->stream;
   DecState& d = sl.d;
   DecState* part = sl.part;
   DecParts& parts = sl.parts;
   int& nsplit = sl.nsplit;
   // (a forced decode and a moves call launch their steps without replay: the label and the records pointers are no part of the key)
   if (h->opt.graph && h->opt.profile != 2 && !d.forced && !d.step_moves) {
-    GraphKey key{B, d.W, Tm, L, greedy ? 1 : 0, h->opt.taps * 2 + h->fact.lflash + 4 * h->opt.att_nt + 4096 * (d.step_logits ? 1 : 0) + 8192 * (d.persist_align ? 1 : 0), nsplit};   // every captured pointer that can change is in the key
-    auto it = h->graphs.find(key);
-    if (it == h->graphs.end()) {
-      if (h->graphs.size() >= 32) {      // bound the cache (callers with ever-changing slab shapes)
-        for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
-        h->graphs.clear();
-        h->graph_forms.clear();
+    GraphKey key{B, d.W, Tm, L, greedy ? 1 : 0, cx->taps() * 2 + (sl.plan.flash ? 1 : 0) + 4 * h->opt.att_nt + 4096 * (d.step_logits ? 1 : 0) + 8192 * (d.persist_align ? 1 : 0), nsplit};   // every captured pointer that can change is in the key
+    auto it = cx->graphs.find(key);
+    if (it == cx->graphs.end()) {
+      if (cx->graphs.size() >= 32) {      // bound the cache (callers with ever-changing slab shapes)
+        for (auto& kv : cx->graphs) hipGraphExecDestroy(kv.second);
+        cx->graphs.clear();
+        cx->graph_forms.clear();
       }
-      FormLog& gforms = h->graph_forms[key];
+      FormLog& gforms = cx->graph_forms[key];
       gforms.n = 0; gforms.full = false;
       hipGraph_t graph = nullptr;
       HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      const int rc = fork_decode_steps(h, sl, false, &gforms);
+      const int rc = fork_decode_steps(cx, sl, false, &gforms);
       hipError_t ce = hipStreamEndCapture(s, &graph);
       if (rc != RV_OK) return rc;
       HIPCHK(h, ce);
       hipGraphExec_t exec = nullptr;
       HIPCHK(h, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
       hipGraphDestroy(graph);
-      it = h->graphs.emplace(key, exec).first;
+      it = cx->graphs.emplace(key, exec).first;
     }
-    h->lforms.merge(h->graph_forms[key]);      // the launches of the graph's capture: it replays those
-    Scope sc(h, "decode_graph", nullptr, true);
+    cx->lforms.merge(cx->graph_forms[key]);      // the launches of the graph's capture: it replays those
+    Scope sc(cx, "decode_graph", nullptr, true);
     HIPCHK(h, hipGraphLaunch(it->second, s));
   } else {
     if (h->opt.profile == 2) nsplit = 1, parts.n = 1;     // per-kernel events need one stream
     if (nsplit == 1) { part[0] = d; part[0].part = 0; part[0].nfin = d.nfin; parts.nfin[0] = d.nfin; parts.B[0] = B; launch_dec_init(part[0], s); }
-    TRY(fork_decode_steps(h, sl, h->opt.profile == 2, &h->lforms));
+    TRY(fork_decode_steps(cx, sl, h->opt.profile == 2, &cx->lforms));
   }
   return RV_OK;
 }
 
 // Phase 7: the outputs of every sub-slab from its beam records (k_dec_finalize, or k_dec_finalize_beams for the whole beam: never a
 // group, never captured), then the scores of a forced decode
-int finalize_and_score(RvContext* h, const Slab& sl) {
-  const RvConfig& c = h->cfg;
+int finalize_and_score(SlabCtx* cx, const Slab& sl) {
+  RvContext* const h = cx->h; const RvConfig& c = h->cfg;
   const int B = sl.call.B, L = sl.call.L, V = c.vocab, steps = sl.steps, Wd = sl.d.W;
   const bool greedy = sl.call.greedy;
   int32_t* tk = sl.call.tokens;
   float* o2 = sl.call.out2;
-  hipStream_t s = h->stream;
+  hipStream_t s = cx->stream;
   const DecState& d = sl.d;
   const DecParts& parts = sl.parts;
   {
-    Scope sc(h, sl.res.whole_beam ? "dec_finalize_beams" : "dec_finalize");
-    if (!h->fact.lpersist) launch_dec_reduce_steps(parts, s);
+    Scope sc(cx, sl.res.whole_beam ? "dec_finalize_beams" : "dec_finalize");
+    if (sl.plan.persist < 0) launch_dec_reduce_steps(parts, s);
     for (int g = 0; g < parts.n; ++g) {
       const size_t b0 = parts.n == 1 ? 0 : (size_t)B * g / parts.n;      // the sub-slab's first chunk
       if (sl.res.whole_beam) {
@@ -1082,12 +1126,12 @@ int finalize_and_score(RvContext* h, const Slab& sl) {
         launch_dec_finalize_beams(sl.part[g], o, s);
       } else {
         launch_dec_finalize(sl.part[g], tk + b0 * steps, o2 + b0 * steps * (greedy ? V : 1), s, sl.ptab,      // (ptab: persistent decode only, one part)
-                            h->fact.lpersist ? sl.res.members : nullptr);
+                            sl.plan.persist >= 0 ? sl.res.members : nullptr);
       }
     }
   }
   if (sl.res.moves) {      // behind k_dec_finalize_beams, which left S for every part
-    Scope sc(h, "dec_finalize_moves");
+    Scope sc(cx, "dec_finalize_moves");
     for (int g = 0; g < parts.n; ++g) {
       const size_t off = (parts.n == 1 ? 0 : (size_t)B * g / parts.n) * steps * Wd;
       MovesOut o = sl.res.moves_out;
@@ -1103,20 +1147,21 @@ int finalize_and_score(RvContext* h, const Slab& sl) {
   if (d.forced) {      // the forced decode's labels target[:, 1:] against the logits the finalize kernel just wrote
     ScoreArgs a = sl.res.score;
     a.logits = o2; a.labels = d.forced + 1; a.label_stride = L; a.B = B; a.S = steps; a.V = V; a.pad_token = c.pad_token; a.pred = nullptr;
-    Scope sc(h, "score_tokens");
+    Scope sc(cx, "score_tokens");
     launch_score_tokens(a, s);
   }
   return RV_OK;
 }
 
 // Phase 8: the results of a host caller, device -> pinned staging
-int stage_outputs(RvContext* h, const Slab& sl) {
+int stage_outputs(SlabCtx* cx, const Slab& sl) {
+  RvContext* const h = cx->h;
   const int B = sl.call.B, V = h->cfg.vocab, steps = sl.steps, Wd = sl.d.W;
   const bool greedy = sl.call.greedy, dev_out = sl.call.dev_out, calls = sl.call.lut != nullptr;
-  hipStream_t s = h->stream;
+  hipStream_t s = cx->stream;
   // (S reaches the host through d.S_host: the finalize / reduce kernel stores it straight into the mapped pinned word)
   if (sl.res.whole_beam && !dev_out) {
-    const BeamsOut &o = sl.res.beams, &p = h->pin_beams;
+    const BeamsOut &o = sl.res.beams, &p = cx->pin_beams;
     const size_t n = (size_t)B * steps * Wd, nb = (size_t)B * Wd;
     HIPCHK(h, hipMemcpyAsync(p.tokens, o.tokens, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(p.scores, o.scores, sizeof(float) * n, hipMemcpyDeviceToHost, s));
@@ -1124,45 +1169,46 @@ int stage_outputs(RvContext* h, const Slab& sl) {
     if (o.log_probs) HIPCHK(h, hipMemcpyAsync(p.log_probs, o.log_probs, sizeof(float) * nb, hipMemcpyDeviceToHost, s));
     if (o.lengths) HIPCHK(h, hipMemcpyAsync(p.lengths, o.lengths, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, s));
     if (sl.res.moves) {
-      const MovesOut &m = sl.res.moves_out, &q = h->pin_moves;
+      const MovesOut &m = sl.res.moves_out, &q = cx->pin_moves;
       const void* src[6] = {m.raw_pos, m.raw_mass, m.event_pos, m.event_mass, m.peak, m.peak_weight};
       void* dst[6] = {q.raw_pos, q.raw_mass, q.event_pos, q.event_mass, q.peak, q.peak_weight};
       for (int i = 0; i < 6; ++i) if (src[i]) HIPCHK(h, hipMemcpyAsync(dst[i], src[i], 4 * n, hipMemcpyDeviceToHost, s));
     }
   } else if (!dev_out && !calls) {
-    HIPCHK(h, hipMemcpyAsync(h->pin_tok, sl.call.tokens, sizeof(int32_t) * B * steps, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(h->pin_out2, sl.call.out2, sizeof(float) * B * steps * (greedy ? V : 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(cx->pin_tok, sl.call.tokens, sizeof(int32_t) * B * steps, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(cx->pin_out2, sl.call.out2, sizeof(float) * B * steps * (greedy ? V : 1), hipMemcpyDeviceToHost, s));
   }
   if (calls) {
-    HIPCHK(h, hipMemcpyAsync(h->pin_bases, h->d_bases, (size_t)B * steps, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(h->pin_probs, h->d_probs, sizeof(float) * B * steps, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(h->pin_clen, h->d_clen, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(cx->pin_bases, cx->d_bases, (size_t)B * steps, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(cx->pin_probs, cx->d_probs, sizeof(float) * B * steps, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(cx->pin_clen, cx->d_clen, sizeof(int) * B, hipMemcpyDeviceToHost, s));
   }
   return RV_OK;
 }
 
 // The stream work of one slab, in order: input copies, encoders, memory set-up, decode, finalize, output copies.  `ptab` non-null =
 // the call is being captured into a slab graph: kernels that touch caller memory read its address from the table.
-int record_slab(RvContext* h, const Call& call, const CallParts& res, const void* const* ptab) {
-  Slab sl{call, res, ptab, call.T_r + call.T_e, call.L - 1};
-  TRY(stage_inputs(h, sl));
-  TRY(record_encoders(h, sl));
-  TRY(record_keys(h, sl));
-  TRY(fill_dec_state(h, sl));
-  TRY(split_decode(h, sl));
-  TRY(h->fact.lpersist ? decode_persist(h, sl) : decode_steps(h, sl));
-  TRY(finalize_and_score(h, sl));
-  TRY(stage_outputs(h, sl));
-  h->fact.lW = sl.d.W;
+int record_slab(SlabCtx* cx, const Call& call, const CallParts& res, const Plan& plan, const void* const* ptab) {
+  Slab sl{call, res, plan, ptab, call.T_r + call.T_e, call.L - 1};
+  TRY(stage_inputs(cx, sl));
+  TRY(record_encoders(cx, sl));
+  TRY(record_keys(cx, sl));
+  TRY(fill_dec_state(cx, sl));
+  TRY(split_decode(cx, sl));
+  TRY(plan.persist >= 0 ? decode_persist(cx, sl) : decode_steps(cx, sl));
+  TRY(finalize_and_score(cx, sl));
+  TRY(stage_outputs(cx, sl));
+  cx->fact.lW = sl.d.W;
   return RV_OK;
 }
 
 // The rest of a call: wait for the context's stream, hand the staged results to the caller's host buffers.
-int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr,
+int finish(SlabCtx* cx, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr,
            const RvMoves* moves = nullptr) {
-  if (!h || !S_out) return RV_EINVAL;
-  if (!h->pend.busy) return fail(h, RV_ESTATE, "no call to collect on this context");
-  const RvContext::PendingCall p = h->pend;
+  RvContext* const h = cx->h;
+  if (!S_out) return RV_EINVAL;
+  if (!cx->pend.busy) return fail(h, RV_ESTATE, "no call to collect on this context");
+  const SlabCtx::PendingCall p = cx->pend;
   *S_out = 0;
   if (p.all != (beams != nullptr) && !(p.all && p.dev_out))      // (the ticket stays in flight)
     return fail(h, RV_EINVAL, p.all ? "this call hands out the whole beam: collect it with rv_beam_search_collect_all"
@@ -1172,7 +1218,7 @@ int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, in
                                       : "rv_beam_search_collect_moves takes the tickets of rv_beam_search_submit_moves");
   if (p.moves && !p.dev_out && !p.trivial && !moves->raw_pos && !moves->raw_mass && !moves->event_pos && !moves->event_mass && !moves->peak && !moves->peak_weight)
     return fail(h, RV_EINVAL, "null output pointer");
-  h->pend.busy = false;
+  cx->pend.busy = false;
   if (p.trivial) {
     if (p.all && !p.dev_out && beams) {      // the initial state
       for (size_t i = 0; i < (size_t)p.B * p.Wd; ++i) {
@@ -1186,12 +1232,12 @@ int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, in
   if (!p.all && !p.dev_out && !p.calls && (!tokens || !out2)) return fail(h, RV_EINVAL, "null output pointer");
   if (p.calls && (!calls || !calls->bases || !calls->lengths || !calls->probs)) return fail(h, RV_EINVAL, "null calls output pointer");
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipStreamSynchronize(cx->stream));
   HIPCHK(h, hipGetLastError());
-  const int S = *h->pin_S;
+  const int S = *cx->pin_S;
   const size_t B = p.B, steps = p.steps;
   if (p.all && !p.dev_out) {
-    const BeamsOut& q = h->pin_beams;
+    const BeamsOut& q = cx->pin_beams;
     const size_t n = B * steps * p.Wd, nb = B * p.Wd;
     memcpy(beams->tokens, q.tokens, sizeof(int32_t) * n);
     memcpy(beams->scores, q.scores, sizeof(float) * n);
@@ -1199,40 +1245,40 @@ int finish(RvContext* h, int32_t* tokens, float* out2, const CallsOut* calls, in
     if (beams->log_probs) memcpy(beams->log_probs, q.log_probs, sizeof(float) * nb);
     if (beams->lengths) memcpy(beams->lengths, q.lengths, sizeof(int32_t) * nb);
     if (p.moves) {
-      const MovesOut& m = h->pin_moves;
+      const MovesOut& m = cx->pin_moves;
       const void* src[6] = {m.raw_pos, m.raw_mass, m.event_pos, m.event_mass, m.peak, m.peak_weight};
       void* dst[6] = {moves->raw_pos, moves->raw_mass, moves->event_pos, moves->event_mass, moves->peak, moves->peak_weight};
       for (int i = 0; i < 6; ++i) if (dst[i]) memcpy(dst[i], src[i], 4 * n);
     }
   } else if (!p.dev_out && !p.calls) {
-    memcpy(tokens, h->pin_tok, sizeof(int32_t) * B * steps);
-    memcpy(out2, h->pin_out2, sizeof(float) * B * steps * (p.greedy ? p.V : 1));
+    memcpy(tokens, cx->pin_tok, sizeof(int32_t) * B * steps);
+    memcpy(out2, cx->pin_out2, sizeof(float) * B * steps * (p.greedy ? p.V : 1));
   }
   if (p.calls) {
-    memcpy(calls->bases, h->pin_bases, B * steps);
-    memcpy(calls->probs, h->pin_probs, sizeof(float) * B * steps);
-    memcpy(calls->lengths, h->pin_clen, sizeof(int) * B);
+    memcpy(calls->bases, cx->pin_bases, B * steps);
+    memcpy(calls->probs, cx->pin_probs, sizeof(float) * B * steps);
+    memcpy(calls->lengths, cx->pin_clen, sizeof(int) * B);
   }
-  drain_profile(h);
+  drain_profile(cx);
   *S_out = S;
-  h->lS = S;
+  if (cx->own()) h->lS = S;
   return RV_OK;
 }
 
-void sync_child(RvContext* k, const RvContext* p);
 int flush_open_group(RvContext* h);
 int uncollected(const RvContext* h);
 
 // The whole beam's device buffers and pinned staging of a context, for the host variants of rv_beam_search_all*
-int ensure_beam_buffers(RvContext* h) {
-  if (h->pin_beams.tokens) return RV_OK;
+int ensure_beam_buffers(SlabCtx* cx) {
+  RvContext* const h = cx->h;
+  if (cx->pin_beams.tokens) return RV_OK;
   const RvConfig& c = h->cfg;
-  const size_t n = (size_t)c.max_batch * c.max_output_len * c.max_beam, nb = (size_t)c.max_batch * c.max_beam;
+  const size_t n = (size_t)cx->cap * c.max_output_len * c.max_beam, nb = (size_t)cx->cap * c.max_beam;
   HIPCHK(h, hipSetDevice(c.device));
-  BeamsOut& d = h->d_beams;
-  BeamsOut& p = h->pin_beams;
-  TRY(dalloc(h, &d.tokens, n)); TRY(dalloc(h, &d.scores, n)); TRY(dalloc(h, &d.path_scores, n));
-  TRY(dalloc(h, &d.log_probs, nb)); TRY(dalloc(h, &d.lengths, nb));
+  BeamsOut& d = cx->d_beams;
+  BeamsOut& p = cx->pin_beams;
+  TRY(dalloc(cx, &d.tokens, n)); TRY(dalloc(cx, &d.scores, n)); TRY(dalloc(cx, &d.path_scores, n));
+  TRY(dalloc(cx, &d.log_probs, nb)); TRY(dalloc(cx, &d.lengths, nb));
   HIPCHK(h, hipHostMalloc((void**)&p.scores, n * sizeof(float), hipHostMallocDefault));
   HIPCHK(h, hipHostMalloc((void**)&p.path_scores, n * sizeof(float), hipHostMallocDefault));
   HIPCHK(h, hipHostMalloc((void**)&p.log_probs, nb * sizeof(float), hipHostMallocDefault));
@@ -1243,7 +1289,7 @@ int ensure_beam_buffers(RvContext* h) {
 
 // Before enqueue() of an all-beams call on `ctx`: where its finalize kernel writes.  call.beams null = every output, to the context's
 // own buffers (an asynchronous call with host outputs: what is asked for is known at its collect); dev_out = the caller's addresses
-int begin_all_beams(RvContext* ctx, const Call& call, CallParts& res) {
+int begin_all_beams(SlabCtx* ctx, const Call& call, CallParts& res) {
   const RvBeams* ab = call.beams;
   if (call.dev_out) {
     res.beams = BeamsOut{ab->tokens, ab->scores, ab->path_scores, ab->log_probs, ab->lengths};
@@ -1259,21 +1305,21 @@ int begin_all_beams(RvContext* ctx, const Call& call, CallParts& res) {
 }
 
 // The records of a moves call and, for the host variants, its six device outputs and their pinned staging
-int ensure_moves_buffers(RvContext* h, bool host_outputs) {
-  const RvConfig& c = h->cfg;
+int ensure_moves_buffers(SlabCtx* cx, bool host_outputs) {
+  RvContext* const h = cx->h; const RvConfig& c = h->cfg;
   HIPCHK(h, hipSetDevice(c.device));
-  if (!h->d_step_moves) TRY(dalloc(h, &h->d_step_moves, (size_t)std::max(c.max_output_len - 1, 1) * c.max_batch * c.max_beam * RV_MOVE_COLS));
+  if (!cx->d_step_moves) TRY(dalloc(cx, &cx->d_step_moves, (size_t)std::max(c.max_output_len - 1, 1) * cx->cap * c.max_beam * RV_MOVE_COLS));
   if (!host_outputs) return RV_OK;
-  const size_t n = (size_t)c.max_batch * c.max_output_len * c.max_beam;
-  MovesOut& d = h->d_moves;
-  MovesOut& p = h->pin_moves;
+  const size_t n = (size_t)cx->cap * c.max_output_len * c.max_beam;
+  MovesOut& d = cx->d_moves;
+  MovesOut& p = cx->pin_moves;
   // each buffer on its own test: a call that failed part-way leaves what it got, and the next one allocates only the rest
-  if (!d.raw_pos) TRY(dalloc(h, &d.raw_pos, n));
-  if (!d.raw_mass) TRY(dalloc(h, &d.raw_mass, n));
-  if (!d.event_pos) TRY(dalloc(h, &d.event_pos, n));
-  if (!d.event_mass) TRY(dalloc(h, &d.event_mass, n));
-  if (!d.peak) TRY(dalloc(h, &d.peak, n));
-  if (!d.peak_weight) TRY(dalloc(h, &d.peak_weight, n));
+  if (!d.raw_pos) TRY(dalloc(cx, &d.raw_pos, n));
+  if (!d.raw_mass) TRY(dalloc(cx, &d.raw_mass, n));
+  if (!d.event_pos) TRY(dalloc(cx, &d.event_pos, n));
+  if (!d.event_mass) TRY(dalloc(cx, &d.event_mass, n));
+  if (!d.peak) TRY(dalloc(cx, &d.peak, n));
+  if (!d.peak_weight) TRY(dalloc(cx, &d.peak_weight, n));
   void** pins[6] = {(void**)&p.raw_pos, (void**)&p.raw_mass, (void**)&p.event_pos, (void**)&p.event_mass, (void**)&p.peak, (void**)&p.peak_weight};
   for (void** q : pins)
     if (!*q) HIPCHK(h, hipHostMalloc(q, n * 4, hipHostMallocDefault));
@@ -1282,7 +1328,7 @@ int ensure_moves_buffers(RvContext* h, bool host_outputs) {
 
 // Before enqueue() of a moves call on `ctx` (after begin_all_beams): its records, and where k_dec_finalize_moves writes.  call.moves
 // null = every output, to the context's own buffers (an asynchronous call: what is asked for is known at its collect)
-int begin_moves(RvContext* ctx, const Call& call, CallParts& res) {
+int begin_moves(SlabCtx* ctx, const Call& call, CallParts& res) {
   const RvMoves* mv = call.moves;
   TRY(ensure_moves_buffers(ctx, !call.dev_out));
   if (call.dev_out) {
@@ -1301,21 +1347,22 @@ int begin_moves(RvContext* ctx, const Call& call, CallParts& res) {
 }
 
 // Labels and score outputs of a context on the device, for the host variants of rv_teacher_forced and for rv_score_logits
-int ensure_score_buffers(RvContext* h) {
-  if (h->d_sc_cnt) return RV_OK;
+int ensure_score_buffers(SlabCtx* cx) {
+  RvContext* const h = cx->h;
+  if (cx->d_sc_cnt) return RV_OK;
   const RvConfig& c = h->cfg;
-  const size_t n = (size_t)c.max_batch * c.max_output_len, nb = (size_t)c.max_batch;
+  const size_t n = (size_t)cx->cap * c.max_output_len, nb = (size_t)cx->cap;
   HIPCHK(h, hipSetDevice(c.device));
-  TRY(dalloc(h, &h->d_forced, n)); TRY(dalloc(h, &h->d_sc_nll, n)); TRY(dalloc(h, &h->d_sc_sum, nb));
-  TRY(dalloc(h, &h->d_sc_cnt, 3 * nb));      // (last: its address says the set is complete)
+  TRY(dalloc(cx, &cx->d_forced, n)); TRY(dalloc(cx, &cx->d_sc_nll, n)); TRY(dalloc(cx, &cx->d_sc_sum, nb));
+  TRY(dalloc(cx, &cx->d_sc_cnt, 3 * nb));      // (last: its address says the set is complete)
   return RV_OK;
 }
 
 // Where a call's k_score_tokens writes: the caller's device addresses, or the context's buffers for the outputs a host caller asked for
-ScoreArgs score_outputs(const RvContext* ctx, const ForcedCall* fc, bool dev_out) {
+ScoreArgs score_outputs(const SlabCtx* ctx, const ForcedCall* fc, bool dev_out) {
   const RvScore none{};
   const RvScore& o = fc->out ? *fc->out : none;
-  const size_t nb = (size_t)ctx->cfg.max_batch;
+  const size_t nb = (size_t)ctx->cap;
   ScoreArgs a{};
   a.omit_mask = fc->omit_mask;
   a.nll = dev_out ? o.nll : (o.nll ? ctx->d_sc_nll : nullptr);
@@ -1336,35 +1383,35 @@ int check_token_ids(RvContext* h, const int32_t* ids, size_t n, int row_len, con
 }
 
 // Before enqueue() of a forced decode on the idle context `ctx`: the call's own checks, then its labels and score outputs
-int begin_forced(RvContext* ctx, const Call& call, CallParts& res) {
+int begin_forced(SlabCtx* ctx, const Call& call, CallParts& res) {
   const ForcedCall* fc = call.forced;
   const int B = call.B, L = call.L;
   const bool dev = call.dev_in;      // (a forced decode's buffers are all the host's or all the device's)
   Call one = call, ok;
   one.W = 1;
   TRY(validate_call(ctx, one, ok));
-  if (B > 0 && !fc->targets) return fail(ctx, RV_EINVAL, "null target pointer");
+  if (B > 0 && !fc->targets) return fail(ctx->h, RV_EINVAL, "null target pointer");
   if (dev) {
     res.labels = fc->targets;
   } else {
-    TRY(check_token_ids(ctx, fc->targets, (size_t)B * L, L, "target"));
+    TRY(check_token_ids(ctx->h, fc->targets, (size_t)B * L, L, "target"));
     TRY(ensure_score_buffers(ctx));
-    if (B > 0) HIPCHK(ctx, hipMemcpy(ctx->d_forced, fc->targets, sizeof(int32_t) * (size_t)B * L, hipMemcpyHostToDevice));
+    if (B > 0) HIPCHK(ctx->h, hipMemcpy(ctx->d_forced, fc->targets, sizeof(int32_t) * (size_t)B * L, hipMemcpyHostToDevice));
     res.labels = ctx->d_forced;
   }
   res.score = score_outputs(ctx, fc, dev);
   return RV_OK;
 }
 
-// After the stream of `ctx` has drained: the scores of B chunks x S positions (k_score_tokens wrote them through `a`) to a host
+// After the stream of the call's context has drained: the scores of B chunks x S positions (k_score_tokens wrote them through `a`) to a host
 // caller's buffers (zeros when nothing was launched)
-int fetch_scores(RvContext* ctx, const ScoreArgs& a, const RvScore* out, bool dev_out, int B, int S) {
+int fetch_scores(RvContext* h, const ScoreArgs& a, const RvScore* out, bool dev_out, int B, int S) {
   if (!out || B <= 0) return RV_OK;
   const size_t nb = (size_t)B, n = nb * (size_t)std::max(S, 0);
   if (S <= 0) {      // nothing ran: every per-chunk sum is zero
     if (dev_out) {
-      if (out->nll_sum) HIPCHK(ctx, hipMemset(out->nll_sum, 0, sizeof(float) * nb));
-      for (int32_t* p : {out->n_labels, out->n_match, out->n_counted}) if (p) HIPCHK(ctx, hipMemset(p, 0, sizeof(int32_t) * nb));
+      if (out->nll_sum) HIPCHK(h, hipMemset(out->nll_sum, 0, sizeof(float) * nb));
+      for (int32_t* p : {out->n_labels, out->n_match, out->n_counted}) if (p) HIPCHK(h, hipMemset(p, 0, sizeof(int32_t) * nb));
     } else {
       if (out->nll_sum) memset(out->nll_sum, 0, sizeof(float) * nb);
       for (int32_t* p : {out->n_labels, out->n_match, out->n_counted}) if (p) memset(p, 0, sizeof(int32_t) * nb);
@@ -1372,37 +1419,33 @@ int fetch_scores(RvContext* ctx, const ScoreArgs& a, const RvScore* out, bool de
     return RV_OK;
   }
   if (dev_out) return RV_OK;
-  if (out->nll) HIPCHK(ctx, hipMemcpy(out->nll, a.nll, sizeof(float) * n, hipMemcpyDeviceToHost));
-  if (out->nll_sum) HIPCHK(ctx, hipMemcpy(out->nll_sum, a.nll_sum, sizeof(float) * nb, hipMemcpyDeviceToHost));
-  if (out->n_labels) HIPCHK(ctx, hipMemcpy(out->n_labels, a.n_labels, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
-  if (out->n_match) HIPCHK(ctx, hipMemcpy(out->n_match, a.n_match, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
-  if (out->n_counted) HIPCHK(ctx, hipMemcpy(out->n_counted, a.n_counted, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+  if (out->nll) HIPCHK(h, hipMemcpy(out->nll, a.nll, sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (out->nll_sum) HIPCHK(h, hipMemcpy(out->nll_sum, a.nll_sum, sizeof(float) * nb, hipMemcpyDeviceToHost));
+  if (out->n_labels) HIPCHK(h, hipMemcpy(out->n_labels, a.n_labels, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+  if (out->n_match) HIPCHK(h, hipMemcpy(out->n_match, a.n_match, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+  if (out->n_counted) HIPCHK(h, hipMemcpy(out->n_counted, a.n_counted, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
   return RV_OK;
 }
 
 // The slab context a synchronous call runs on.  A group of coalesced slabs that is still filling is launched first.
-int sync_context(RvContext* h, RvContext** out) {
+int sync_context(RvContext* h, SlabCtx** out) {
   {   // coalesced tickets hold the handle's slots as the slab contexts' tickets do: with async_depth of them uncollected a synchronous
-      // call is refused, touching nothing (the handle's own context is idle then, but the contract does not depend on the path)
+      // call is refused, touching nothing (slot 0 is idle then, but the contract does not depend on the path)
     bool ticks_out = false;
     for (const auto& t : h->ticks) ticks_out = ticks_out || t.busy;
     if (ticks_out && uncollected(h) >= async_depth(h))
       return fail(h, RV_ESTATE, "every slab context of this handle holds an uncollected asynchronous call: collect one before a synchronous call");
   }
   flush_open_group(h);      // (a group still filling goes first; a failure there is its tickets')
-  // A synchronous call between asynchronous ones: it runs on the handle's own context when that one is idle, else on any idle
-  // context of the handle -- never on one that still holds an uncollected ticket (its stream work and output pointers are live).
-  // Debug taps and rv_get_tensor belong to the handle's own context, so with taps on that context must be the idle one.
-  RvContext* ctx = h;
-  if (h->pend.busy) {
-    if (h->opt.taps || h->opt.ptaps)
-      return fail(h, RV_ESTATE, "debug taps need the handle's own context, which holds an uncollected asynchronous call: collect ticket %d first", h->pend.ticket);
-    ctx = nullptr;
-    for (RvContext* k : h->kids) if (!k->pend.busy) { ctx = k; break; }
-    if (!ctx) return fail(h, RV_ESTATE, "every slab context of this handle holds an uncollected asynchronous call: collect one before a synchronous call");
-  }
+  // A synchronous call between asynchronous ones: it runs on slot 0 when that one is idle, else on any idle context of the handle --
+  // never on one that still holds an uncollected ticket (its stream work and output pointers are live).  Debug taps and rv_get_tensor
+  // belong to slot 0 (SlabCtx::own), so with taps on that context must be the idle one.
+  SlabCtx* ctx = nullptr;
+  for (SlabCtx* k : h->slabs) if (!k->pend.busy) { ctx = k; break; }      // (slot 0 first)
+  if (h->slabs[0]->pend.busy && (h->opt.taps || h->opt.ptaps))
+    return fail(h, RV_ESTATE, "debug taps need the handle's own context, which holds an uncollected asynchronous call: collect ticket %d first", h->slabs[0]->pend.ticket);
+  if (!ctx) return fail(h, RV_ESTATE, "every slab context of this handle holds an uncollected asynchronous call: collect one before a synchronous call");
   h->inflight_hint = 1;
-  if (ctx != h) sync_child(ctx, h);
   *out = ctx;
   return RV_OK;
 }
@@ -1414,124 +1457,135 @@ int run(RvContext* h, const Call& call, int32_t* S_out) {
   if (!S_out || (call.B > 0 && call.L > 1 && !calls && (!call.tokens || !call.out2))) return fail(h, RV_EINVAL, "null output pointer");
   if (calls && (!calls->lut || !calls->bases || !calls->lengths || !calls->probs)) return fail(h, RV_EINVAL, "null calls output pointer");
   *S_out = 0;
-  RvContext* ctx = nullptr;
+  SlabCtx* ctx = nullptr;
   TRY(sync_context(h, &ctx));
   CallParts res;
-  if (call.whole_beam) { const int rb = begin_all_beams(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
-  if (call.want_moves) { const int rb = begin_moves(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
-  if (call.forced) { const int rb = begin_forced(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
+  if (call.whole_beam) TRY(begin_all_beams(ctx, call, res));
+  if (call.want_moves) TRY(begin_moves(ctx, call, res));
+  if (call.forced) TRY(begin_forced(ctx, call, res));
   const int rc = enqueue(ctx, call, res);
-  if (rc != RV_OK) { ctx->pend.busy = false; return relay(h, ctx, rc); }   // (ctx was idle on entry: the flag is this call's)
+  if (rc != RV_OK) { ctx->pend.busy = false; return rc; }   // (ctx was idle on entry: the flag is this call's)
   int rf = finish(ctx, call.tokens, call.out2, calls, S_out, call.beams, call.moves);
-  if (call.forced && rf == RV_OK) rf = fetch_scores(ctx, res.score, call.forced->out, call.dev_out, call.B, call.L - 1);
-  if (ctx != h) h->lS = ctx->lS;
-  return relay(h, ctx, rf);
+  if (call.forced && rf == RV_OK) rf = fetch_scores(h, res.score, call.forced->out, call.dev_out, call.B, call.L - 1);
+  h->lS = *S_out;      // (whichever slot it ran on: finish() leaves the two equal on slot 0)
+  return rf;
 }
 
-
-// Per-slab working set of a context: inputs, activations, decoder state, outputs, staging, side streams.  Weights are not part of it
-// (child contexts of the asynchronous calls share their parent's).
-int alloc_slab_buffers(RvContext* h) {
-  const RvConfig& c = h->cfg;
+// Per-slab working set of a context, for cx->cap chunks: inputs, activations, decoder state, outputs, staging, side streams
+int alloc_slab_buffers(SlabCtx* cx) {
+  RvContext* const h = cx->h; const RvConfig& c = h->cfg;
   const bool use_raw = c.mode != RV_MODE_EVENT, use_ev = c.mode != RV_MODE_RAW;
-  const size_t B = c.max_batch, Tr = use_raw ? c.max_raw_len : 0, Te = use_ev ? c.max_event_len : 0;
+  const size_t B = cx->cap, Tr = use_raw ? c.max_raw_len : 0, Te = use_ev ? c.max_event_len : 0;
   const size_t Tm = Tr + Te, L = c.max_output_len, N = B * c.max_beam, V = c.vocab;
-  TRY(dalloc(h, &h->d_raw, B * Tr));
-  TRY(dalloc(h, &h->d_ev, B * Te * 5));
-  TRY(dalloc(h, &h->mask, B * Tm));
+  TRY(dalloc(cx, &cx->d_raw, B * Tr));
+  TRY(dalloc(cx, &cx->d_ev, B * Te * 5));
+  TRY(dalloc(cx, &cx->mask, B * Tm));
   const int npp = c.enc_depth > 2 ? 2 : (c.enc_depth > 1 ? 1 : 0);
   for (int p = 0; p < npp; ++p) {
-    if (use_raw) TRY(dalloc(h, &h->act[0][p], B * Tr * RV_E));
-    if (use_ev) TRY(dalloc(h, &h->act[1][p], B * Te * RV_E));
+    if (use_raw) TRY(dalloc(cx, &cx->act[0][p], B * Tr * RV_E));
+    if (use_ev) TRY(dalloc(cx, &cx->act[1][p], B * Te * RV_E));
   }
   // The pre-projected tensors xw [max_batch, T_max, 2, 512] (4 KB per chunk-timestep) of the matrix-pipe recurrence (the default) and of the
   // unfused packed-FMA path: allocated HERE, with the context -- not on a context's first call.  (Round 4 found the first-use hipMalloc of a
   // fresh context inside bench.py's timed region: the driver's 5 warm-up steps touch 5 of the 10 contexts, the other five allocated 2 x ~300 MB
   // each while the GPU drained -- 1.5 to 10 ms of host stall per context, which rounds 3 and 4 had read as the pipeline's fill time.)
-  if (use_raw && c.enc_depth > 1) TRY(dalloc(h, &h->xw[0], B * Tr * 2 * RV_G));
-  if (use_ev) TRY(dalloc(h, &h->xw[1], B * Te * 2 * RV_G));
+  if (use_raw && c.enc_depth > 1) TRY(dalloc(cx, &cx->xw[0], B * Tr * 2 * RV_G));
+  if (use_ev) TRY(dalloc(cx, &cx->xw[1], B * Te * 2 * RV_G));
   for (int e = 0; e < 2; ++e)
     for (int st = 0; st < 2; ++st)
-      for (int k = 0; k < 4; k += h->rnn == RV_RNN_BIGRU ? 2 : 1) TRY(dalloc(h, &h->st[e][st][k], B * RV_U));      // (a GRU's sets hold h only)
-  TRY(dalloc(h, &h->enc_out, B * Tm * RV_E));
-  TRY(dalloc(h, &h->keys, B * Tm * RV_U));
-  if (h->rnn == RV_RNN_BILSTM) TRY(dalloc(h, &h->mem2, B * Tm * RV_E));      // (the persistent decode's projected memory)
-  DecState& d = h->dec_st;
+      for (int k = 0; k < 4; k += h->rnn == RV_RNN_BIGRU ? 2 : 1) TRY(dalloc(cx, &cx->st[e][st][k], B * RV_U));      // (a GRU's sets hold h only)
+  TRY(dalloc(cx, &cx->enc_out, B * Tm * RV_E));
+  TRY(dalloc(cx, &cx->keys, B * Tm * RV_U));
+  if (h->rnn == RV_RNN_BILSTM) TRY(dalloc(cx, &cx->mem2, B * Tm * RV_E));      // (the persistent decode's projected memory)
+  DecState& d = cx->dec_st;
 #ifdef RV_DIAG   // timing ablations that INVALIDATE results: only in `make diag` builds (libravvent_hip_diag.so), never in the product library
   if (const char* e = getenv("RV_ATT_STOP")) d.dbg_stop = atoi(e);
 #endif
-  if (getenv("RV_REC_STAMPS")) { TRY(dalloc(h, &h->rec_ts, 24)); h->rec_ts_layer = atoi(getenv("RV_REC_STAMPS")) == 2 ? 1 : 0; }
-  if (getenv("RV_DBG_STAMPS")) TRY(dalloc(h, &d.dbg_ts, 16));   // diagnostic builds: in-kernel phase stamps   // timing ablation only; results are invalid when set
+  if (getenv("RV_REC_STAMPS")) { TRY(dalloc(cx, &cx->rec_ts, 24)); cx->rec_ts_layer = atoi(getenv("RV_REC_STAMPS")) == 2 ? 1 : 0; }
+  if (getenv("RV_DBG_STAMPS")) TRY(dalloc(cx, &d.dbg_ts, 16));   // diagnostic builds: in-kernel phase stamps   // timing ablation only; results are invalid when set
   d.depth = c.dec_depth; d.ls_xh = N * RV_E; d.ls_c = N * RV_U;
-  TRY(dalloc(h, &d.xh, c.dec_depth * N * RV_E));
-  TRY(dalloc(h, &d.z, N * RV_G));
-  TRY(dalloc(h, &d.c, c.dec_depth * N * RV_U));
-  TRY(dalloc(h, &d.c_new, c.dec_depth * N * RV_U));
-  TRY(dalloc(h, &d.h_new, c.dec_depth * N * RV_U));
-  TRY(dalloc(h, &d.tok, N));
-  TRY(dalloc(h, &d.log_probs, N));
-  TRY(dalloc(h, &d.finished, N));
-  TRY(dalloc(h, &d.lengths, N));
-  TRY(dalloc(h, &d.step_ids, L * N));
-  TRY(dalloc(h, &d.parent_ids, L * N));
-  TRY(dalloc(h, &d.step_scores, L * N));
-  TRY(dalloc(h, &d.step_logits, L * N * V));
-  TRY(dalloc(h, &d.nfin, 4 * (L + 1)));
-  TRY(dalloc(h, &d.S_dev, 8));
-  TRY(dalloc(h, &h->d_chunk_steps, (size_t)c.max_batch));
+  TRY(dalloc(cx, &d.xh, c.dec_depth * N * RV_E));
+  TRY(dalloc(cx, &d.z, N * RV_G));
+  TRY(dalloc(cx, &d.c, c.dec_depth * N * RV_U));
+  TRY(dalloc(cx, &d.c_new, c.dec_depth * N * RV_U));
+  TRY(dalloc(cx, &d.h_new, c.dec_depth * N * RV_U));
+  TRY(dalloc(cx, &d.tok, N));
+  TRY(dalloc(cx, &d.log_probs, N));
+  TRY(dalloc(cx, &d.finished, N));
+  TRY(dalloc(cx, &d.lengths, N));
+  TRY(dalloc(cx, &d.step_ids, L * N));
+  TRY(dalloc(cx, &d.parent_ids, L * N));
+  TRY(dalloc(cx, &d.step_scores, L * N));
+  TRY(dalloc(cx, &d.step_logits, L * N * V));
+  TRY(dalloc(cx, &d.nfin, 4 * (L + 1)));
+  TRY(dalloc(cx, &d.S_dev, 8));
+  TRY(dalloc(cx, &cx->d_chunk_steps, B));
   // (side streams are created on first use -- side_stream(): the contexts of the asynchronous calls never need them, and every
   //  stream of the process competes for the same few hardware queues)
-  for (int g = 0; g < 3; ++g) HIPTRY(hipEventCreateWithFlags(&h->ev_join[g], hipEventDisableTiming));
-  HIPTRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-  if (const char* e = getenv("RV_DECODE_SPLIT")) h->opt.split = atoi(e);
-  TRY(dalloc(h, &h->out_tokens, B * L));
-  TRY(dalloc(h, &h->out2, B * L * V));
-  HIPTRY(hipHostMalloc((void**)&h->pin_raw, std::max<size_t>(B * Tr, 1) * sizeof(float), hipHostMallocDefault));
-  HIPTRY(hipHostMalloc((void**)&h->pin_ev, std::max<size_t>(B * Te * 5, 1) * sizeof(float), hipHostMallocDefault));
-  HIPTRY(hipHostMalloc((void**)&h->pin_tok, B * L * sizeof(int32_t), hipHostMallocDefault));
-  HIPTRY(hipHostMalloc((void**)&h->pin_out2, B * L * V * sizeof(float), hipHostMallocDefault));
-  HIPTRY(hipHostMalloc((void**)&h->pin_S, sizeof(int) * RV_MAX_MEMBERS, hipHostMallocMapped));
-  HIPTRY(hipHostGetDevicePointer((void**)&d.S_host, h->pin_S, 0));
-  TRY(dalloc(h, &h->d_bases, B * L));
-  TRY(dalloc(h, &h->d_probs, B * L));
-  TRY(dalloc(h, &h->d_clen, B));
-  HIPTRY(hipHostMalloc((void**)&h->pin_bases, B * L, hipHostMallocDefault));
-  HIPTRY(hipHostMalloc((void**)&h->pin_probs, B * L * sizeof(float), hipHostMallocDefault));
-  HIPTRY(hipHostMalloc((void**)&h->pin_clen, B * sizeof(int), hipHostMallocDefault));
+  for (int g = 0; g < 3; ++g) HIPTRY(hipEventCreateWithFlags(&cx->ev_join[g], hipEventDisableTiming));
+  HIPTRY(hipEventCreateWithFlags(&cx->ev_fork, hipEventDisableTiming));
+  TRY(dalloc(cx, &cx->out_tokens, B * L));
+  TRY(dalloc(cx, &cx->out2, B * L * V));
+  HIPTRY(hipHostMalloc((void**)&cx->pin_raw, std::max<size_t>(B * Tr, 1) * sizeof(float), hipHostMallocDefault));
+  HIPTRY(hipHostMalloc((void**)&cx->pin_ev, std::max<size_t>(B * Te * 5, 1) * sizeof(float), hipHostMallocDefault));
+  HIPTRY(hipHostMalloc((void**)&cx->pin_tok, B * L * sizeof(int32_t), hipHostMallocDefault));
+  HIPTRY(hipHostMalloc((void**)&cx->pin_out2, B * L * V * sizeof(float), hipHostMallocDefault));
+  HIPTRY(hipHostMalloc((void**)&cx->pin_S, sizeof(int) * RV_MAX_MEMBERS, hipHostMallocMapped));
+  HIPTRY(hipHostGetDevicePointer((void**)&d.S_host, cx->pin_S, 0));
+  TRY(dalloc(cx, &cx->d_bases, B * L));
+  TRY(dalloc(cx, &cx->d_probs, B * L));
+  TRY(dalloc(cx, &cx->d_clen, B));
+  HIPTRY(hipHostMalloc((void**)&cx->pin_bases, B * L, hipHostMallocDefault));
+  HIPTRY(hipHostMalloc((void**)&cx->pin_probs, B * L * sizeof(float), hipHostMallocDefault));
+  HIPTRY(hipHostMalloc((void**)&cx->pin_clen, B * sizeof(int), hipHostMallocDefault));
   // the table lives in mapped pinned memory: the three kernels that need a caller address read it over the host link once per workgroup
   // (a device copy refreshed by a memcpy node in front of the graph measured the same, and is one node more)
-  TRY(dalloc(h, &h->d_win, B));
-  HIPTRY(hipHostMalloc((void**)&h->pin_win, std::max<size_t>(B, 1) * sizeof(RecWindow), hipHostMallocDefault));
-  HIPTRY(hipHostMalloc((void**)&h->pin_ptab, sizeof(void*) * RV_PTAB_N, hipHostMallocMapped));
-  HIPTRY(hipHostGetDevicePointer((void**)&h->d_ptab, h->pin_ptab, 0));
+  TRY(dalloc(cx, &cx->d_win, B));
+  HIPTRY(hipHostMalloc((void**)&cx->pin_win, std::max<size_t>(B, 1) * sizeof(RecWindow), hipHostMallocDefault));
+  HIPTRY(hipHostMalloc((void**)&cx->pin_ptab, sizeof(void*) * RV_PTAB_N, hipHostMallocMapped));
+  HIPTRY(hipHostGetDevicePointer((void**)&cx->d_ptab, cx->pin_ptab, 0));
   return RV_OK;
 }
 
-// A further slab context of handle p for the asynchronous calls: own stream and buffers, p's weights.
-int create_child(RvContext* p, RvContext** out, int slabs = 1) {
-  RvContext* h = new RvContext();
-  h->cfg = p->cfg;
-  h->cfg.max_batch *= slabs;                // (a group context of the coalesced calls: room for `slabs` slabs back to back)
-  h->parent = p;
-  h->rnn = p->rnn;
+// Everything a slab context owns; its stream drains first
+void destroy_slab(SlabCtx* cx) {
+  if (!cx) return;
+  if (cx->stream) hipStreamSynchronize(cx->stream);
+  for (auto& kv : cx->graphs) hipGraphExecDestroy(kv.second);
+  for (auto& kv : cx->slab_graphs) hipGraphExecDestroy(kv.second.exec);
+  for (auto& p : cx->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
+  for (auto e : cx->ev_pool) hipEventDestroy(e);
+  for (int g = 0; g < 3; ++g) { if (cx->side[g]) hipStreamDestroy(cx->side[g]); if (cx->ev_join[g]) hipEventDestroy(cx->ev_join[g]); }
+  if (cx->ev_fork) hipEventDestroy(cx->ev_fork);
+  if (cx->step_align) hipFree(cx->step_align);
+  if (cx->palign) hipFree(cx->palign);
+  for (void* p : {(void*)cx->pin_raw, (void*)cx->pin_ev, (void*)cx->pin_tok, (void*)cx->pin_out2, (void*)cx->pin_S, (void*)cx->pin_bases, (void*)cx->pin_probs, (void*)cx->pin_clen, (void*)cx->pin_ptab, (void*)cx->pin_win,
+                  (void*)cx->pin_beams.tokens, (void*)cx->pin_beams.scores, (void*)cx->pin_beams.path_scores, (void*)cx->pin_beams.log_probs, (void*)cx->pin_beams.lengths,
+                  (void*)cx->pin_moves.raw_pos, (void*)cx->pin_moves.raw_mass, (void*)cx->pin_moves.event_pos, (void*)cx->pin_moves.event_mass, (void*)cx->pin_moves.peak, (void*)cx->pin_moves.peak_weight}) if (p) hipHostFree(p);
+  for (void* p : cx->allocs) hipFree(p);
+  if (cx->stream) hipStreamDestroy(cx->stream);
+  delete cx;
+}
+
+// A slab context of handle h for `cap` chunks: own stream and buffers.  slot: its place in h->slabs, -1 for a group's context
+int create_slab(RvContext* h, SlabCtx** out, int cap, int slot) {
+  SlabCtx* cx = new SlabCtx();
+  cx->h = h; cx->cap = cap; cx->slot = slot;
   // (stream priorities -- the contexts at the runtime's three levels in turn, so that slabs submitted together leave lockstep -- measured
   //  no gain at the driver's 20 steps and 4 % less once the stream has settled: tools/stream_ab.py, round 4)
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return fail(p, RV_EHIP, "hipStreamCreate failed for an asynchronous context"); }
-  h->d_w = p->d_w; h->n_w = p->n_w;
-  h->img = p->img;
-  bind_weights(h);
-  const int rc = alloc_slab_buffers(h);
-  if (rc != RV_OK) { p->err = h->err; rv_destroy(h); return rc; }
-  *out = h;
+  if (hipStreamCreateWithFlags(&cx->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete cx;
+    return fail(h, RV_EHIP, slot == 0 ? "hipStreamCreate failed" : "hipStreamCreate failed for an asynchronous context");
+  }
+  const int rc = alloc_slab_buffers(cx);
+  if (rc != RV_OK) { destroy_slab(cx); return rc; }
+  *out = cx;
   return RV_OK;
 }
 
-// options and weight-derived scalars of the parent, as of now
-void sync_child(RvContext* k, const RvContext* p) {
-  k->loaded = p->loaded; k->scales = p->scales;
-  k->opt = p->opt;
-  k->opt.taps = 0; k->opt.ptaps = 0;      // debug taps belong to the synchronous calls
-  k->inflight_hint = p->inflight_hint;
+void destroy_group(Group* g) {      // (launched or still filling: its stream drains in there)
+  destroy_slab(g->ctx);
+  delete g;
 }
 
 // ---- coalesced asynchronous calls
@@ -1555,27 +1609,29 @@ int coalesce_n(const RvContext* h, int depth) {
 // Does a group run its event encoder on a side stream beside its raw encoder (record_encoders)?  By default where every group context in
 // flight, ceil(depth / n) of them, gets a hardware queue for its own stream and one for its side stream (C3 at the defaults on 4 queues:
 // two groups of five; profiles/group_chain.md).
-bool group_side_ev(const RvContext* root) {
-  if (root->opt.group_side_ev >= 0) return root->opt.group_side_ev != 0;
-  const int depth = async_depth(root), n = coalesce_n(root, depth);
+bool group_side_ev(const RvContext* h) {
+  if (h->opt.group_side_ev >= 0) return h->opt.group_side_ev != 0;
+  const int depth = async_depth(h), n = coalesce_n(h, depth);
   return 2 * ((depth + n - 1) / n) <= hw_queues();
 }
 
 int uncollected(const RvContext* h) {
-  int n = h->pend.busy ? 1 : 0;
-  for (const RvContext* k : h->kids) n += k->pend.busy ? 1 : 0;
+  int n = 0;
+  for (const SlabCtx* k : h->slabs) n += k->pend.busy ? 1 : 0;
   for (const auto& t : h->ticks) n += t.busy ? 1 : 0;
   return n;
 }
 
 // Does this (validated) slab take the default streamed path, the only one that is coalesced?
 bool coalescible(const RvContext* h, const Call& call) {
-  if (h->opt.profile != 0 || h->opt.taps || h->opt.ptaps || h->rec_ts || h->dec_st.dbg_ts || h->opt.slab_graph || call.L <= 1) return false;
-  return wide_recurrence(h, call.B, call.T_r) && persist_form(h, false, call.W, call.T_r + call.T_e, false) >= 0;
+  const SlabCtx* cx = h->slabs[0];      // (the plan of a plain beam search is the same on every slot once the taps are off)
+  if (h->opt.profile != 0 || h->opt.taps || h->opt.ptaps || cx->rec_ts || cx->dec_st.dbg_ts || h->opt.slab_graph || call.L <= 1) return false;
+  const Plan p = plan_call(cx, call, CallParts{});
+  return p.wide && p.persist >= 0;
 }
 
-void reset_group(RvContext* g) {
-  g->g_n = 0; g->g_rows = 0; g->g_staged = 0; g->g_launched = false; g->g_synced = false; g->g_failed = RV_OK;
+void reset_group(Group* g) {
+  g->n = 0; g->rows = 0; g->staged = 0; g->launched = false; g->synced = false; g->failed = RV_OK;
 }
 
 // Can the layer-0 kernels of a group of this shape read their members' device inputs in place?  Only the matrix-pipe layer 0 with its
@@ -1585,36 +1641,35 @@ bool inplace_serves(const RvContext* h, int T_e) {
 }
 
 // Queue a group's internal call: its members' inputs are in d_raw / d_ev already, back to back, or stay where the callers hold them (submit_group).
-int launch_group(RvContext* root, RvContext* g) {
-  if (root->open_grp == g) root->open_grp = nullptr;
-  if (g->g_launched) return g->g_failed;
-  g->g_launched = true;
-  root->co_groups += 1; root->co_slabs += g->g_n; root->co_largest = std::max<long long>(root->co_largest, g->g_n);
-  if (g->g_rows == 0) return RV_OK;          // empty slabs only: nothing to run, S = 0
-  sync_child(g, root);
-  const size_t steps = (size_t)g->g_L - 1;
-  DecMembers& m = g->g_members;
-  m.n = g->g_n;
-  for (int i = 0; i < g->g_n; ++i) {
-    const RvContext::Tick& t = root->ticks[g->g_tslot[i]];
+int launch_group(RvContext* h, Group* g) {
+  if (h->open_grp == g) h->open_grp = nullptr;
+  if (g->launched) return g->failed;
+  g->launched = true;
+  h->co_groups += 1; h->co_slabs += g->n; h->co_largest = std::max<long long>(h->co_largest, g->n);
+  if (g->rows == 0) return RV_OK;          // empty slabs only: nothing to run, S = 0
+  const size_t steps = (size_t)g->L - 1;
+  DecMembers& m = g->members;
+  m.n = g->n;
+  for (int i = 0; i < g->n; ++i) {
+    const Tick& t = h->ticks[g->tslot[i]];
     m.row0[i] = t.row0; m.rows[i] = t.B;
-    for (RecMembers& in : g->g_in) { in.n = g->g_n; in.row0[i] = t.row0; in.rows[i] = t.B; }
-    if (!g->g_dev_out) { m.tokens[i] = g->out_tokens + (size_t)t.row0 * steps; m.out2[i] = g->out2 + (size_t)t.row0 * steps; }
+    for (RecMembers& in : g->in) { in.n = g->n; in.row0[i] = t.row0; in.rows[i] = t.B; }
+    if (!g->dev_out) { m.tokens[i] = g->ctx->out_tokens + (size_t)t.row0 * steps; m.out2[i] = g->ctx->out2 + (size_t)t.row0 * steps; }
   }
   Call call;
-  call.raw = g->d_raw; call.ev = g->d_ev; call.dev_in = true;
-  call.B = g->g_rows; call.T_r = g->g_Tr; call.T_e = g->g_Te; call.W = g->g_W; call.L = g->g_L;
-  call.tokens = g->out_tokens; call.out2 = g->out2; call.dev_out = g->g_dev_out;
-  call.lut = g->g_calls ? g->g_lut : nullptr;
-  if (g->g_win) { call.raw = call.ev = nullptr; call.windows = g->pin_win; }
+  call.raw = g->ctx->d_raw; call.ev = g->ctx->d_ev; call.dev_in = true;
+  call.B = g->rows; call.T_r = g->Tr; call.T_e = g->Te; call.W = g->W; call.L = g->L;
+  call.tokens = g->ctx->out_tokens; call.out2 = g->ctx->out2; call.dev_out = g->dev_out;
+  call.lut = g->calls ? g->lut : nullptr;
+  if (g->win) { call.raw = call.ev = nullptr; call.windows = g->ctx->pin_win; }
   CallParts res;
   res.members = &m;
-  res.form_B = g->g_B0;
-  const int rc = enqueue(g, call, res);
-  root->gforms = g->lforms;
-  g->pend.busy = false;                      // (the tickets live in the root's table)
-  if (rc != RV_OK) g->g_failed = rc;
-  return relay(root, g, rc);
+  res.form_B = g->B0;
+  const int rc = enqueue(g->ctx, call, res);
+  h->gforms = g->ctx->lforms;
+  g->ctx->pend.busy = false;                 // (the tickets live in the handle's table)
+  if (rc != RV_OK) g->failed = rc;
+  return rc;
 }
 
 int flush_open_group(RvContext* h) { return h->open_grp ? launch_group(h, h->open_grp) : RV_OK; }
@@ -1629,114 +1684,116 @@ int submit_group(RvContext* h, int n, const Call& call, int32_t* ticket) {
   const bool calls = lut != nullptr;
   const bool win = call.windows != nullptr;
   HIPCHK(h, hipSetDevice(c.device));
-  RvContext* g = h->open_grp;
-  if (g && (g->g_cap != n || g->g_win != win || g->g_Tr != T_r || g->g_Te != T_e || g->g_W != W || g->g_L != L || g->g_dev_in != dev_in || g->g_dev_out != dev_out ||
-            g->g_calls != calls || (calls && memcmp(g->g_lut, lut, (size_t)c.vocab)))) {
+  Group* g = h->open_grp;
+  if (g && (g->cap != n || g->win != win || g->Tr != T_r || g->Te != T_e || g->W != W || g->L != L || g->dev_in != dev_in || g->dev_out != dev_out ||
+            g->calls != calls || (calls && memcmp(g->lut, lut, (size_t)c.vocab)))) {
     launch_group(h, g);                      // another shape or kind: the group goes as it is (a failure is its members' to collect)
     g = nullptr;
   }
   if (!g) {
     for (size_t i = 0; i < h->groups.size() && !g; ++i) {
-      RvContext* cand = h->groups[i];
-      if (cand->g_n != 0) continue;
-      if (cand->g_cap == n) { g = cand; break; }
-      rv_destroy(cand);                      // idle, sized for another group size (the option changed)
+      Group* cand = h->groups[i];
+      if (cand->n != 0) continue;
+      if (cand->cap == n) { g = cand; break; }
+      destroy_group(cand);                     // idle, sized for another group size (the option changed)
       h->groups.erase(h->groups.begin() + i); --i;
     }
     // the group contexts an in-order stream needs, ceil(depth / n), exist from the first coalesced submit on, as the slab contexts do from the
     // first submit: none is allocated (gigabytes of hipMalloc at C3 sizes) in the middle of a stream.  One more only when none is idle
     const int depth = async_depth(h);
     while (!g || (int)h->groups.size() < (depth + n - 1) / n) {
-      RvContext* k = nullptr;
-      TRY(create_child(h, &k, n));
-      k->g_cap = n;
-      if (group_side_ev(h)) side_stream(k, 0);      // (created with the context, as its buffers are: not at a group's first launch in mid-stream)
+      SlabCtx* cx = nullptr;
+      TRY(create_slab(h, &cx, n * h->cfg.max_batch, -1));      // (room for n slabs back to back)
+      Group* k = new Group();
+      k->ctx = cx; k->cap = n;
+      cx->grp = k;
+      if (group_side_ev(h)) side_stream(cx, 0);     // (created with the context, as its buffers are: not at a group's first launch in mid-stream)
       reset_group(k);
       h->groups.push_back(k);
       if (!g) g = k;
     }
     reset_group(g);
-    g->g_Tr = T_r; g->g_Te = T_e; g->g_W = W; g->g_L = L; g->g_dev_in = dev_in; g->g_dev_out = dev_out; g->g_calls = calls; g->g_B0 = B;
-    g->g_win = win;
-    g->g_inplace = dev_in && !win && inplace_serves(h, T_e);      // (the options cannot change under an open group: rv_set_option launches it)
-    memset(g->g_lut, 0, sizeof g->g_lut);
-    if (calls) memcpy(g->g_lut, lut, (size_t)c.vocab);
+    g->Tr = T_r; g->Te = T_e; g->W = W; g->L = L; g->dev_in = dev_in; g->dev_out = dev_out; g->calls = calls; g->B0 = B;
+    g->win = win;
+    g->inplace = dev_in && !win && inplace_serves(h, T_e);      // (the options cannot change under an open group: rv_set_option launches it)
+    memset(g->lut, 0, sizeof g->lut);
+    if (calls) memcpy(g->lut, lut, (size_t)c.vocab);
     h->open_grp = g;
   }
   int slot = -1;
   for (int i = 0; i < RV_MAX_ASYNC && slot < 0; ++i) if (!h->ticks[i].busy) slot = i;
   if (slot < 0) return fail(h, RV_ESTATE, "no free ticket");      // (unreachable: at most async_depth <= RV_MAX_ASYNC are uncollected)
-  const size_t row0 = (size_t)g->g_rows;
+  const size_t row0 = (size_t)g->rows;
   if (win) {            // the member's rows behind those of the members before it: the group's table needs no member lookup
-    if (B > 0) memcpy(g->pin_win + row0, call.windows, sizeof(RecWindow) * (size_t)B);
-  } else if (g->g_inplace) {   // device inputs stay valid and untouched until the ticket is collected (ravvent_hip.h): the layer-0 kernels read them there
-    g->g_in[0].x[g->g_n] = raw; g->g_in[1].x[g->g_n] = ev;
+    if (B > 0) memcpy(g->ctx->pin_win + row0, call.windows, sizeof(RecWindow) * (size_t)B);
+  } else if (g->inplace) {   // device inputs stay valid and untouched until the ticket is collected (ravvent_hip.h): the layer-0 kernels read them there
+    g->in[0].x[g->n] = raw; g->in[1].x[g->n] = ev;
   } else if (B > 0) {   // the member's inputs go to its rows of the group's input buffers now: the caller's host buffers are free on return
     const size_t nr = (size_t)B * T_r, ne = (size_t)B * T_e * 5;
     if (!dev_in) {
-      if (nr) { memcpy(g->pin_raw + row0 * T_r, raw, sizeof(float) * nr); HIPCHK(h, hipMemcpyAsync(g->d_raw + row0 * T_r, g->pin_raw + row0 * T_r, sizeof(float) * nr, hipMemcpyHostToDevice, g->stream)); }
-      if (ne) { memcpy(g->pin_ev + row0 * T_e * 5, ev, sizeof(float) * ne); HIPCHK(h, hipMemcpyAsync(g->d_ev + row0 * T_e * 5, g->pin_ev + row0 * T_e * 5, sizeof(float) * ne, hipMemcpyHostToDevice, g->stream)); }
+      if (nr) { memcpy(g->ctx->pin_raw + row0 * T_r, raw, sizeof(float) * nr); HIPCHK(h, hipMemcpyAsync(g->ctx->d_raw + row0 * T_r, g->ctx->pin_raw + row0 * T_r, sizeof(float) * nr, hipMemcpyHostToDevice, g->ctx->stream)); }
+      if (ne) { memcpy(g->ctx->pin_ev + row0 * T_e * 5, ev, sizeof(float) * ne); HIPCHK(h, hipMemcpyAsync(g->ctx->d_ev + row0 * T_e * 5, g->ctx->pin_ev + row0 * T_e * 5, sizeof(float) * ne, hipMemcpyHostToDevice, g->ctx->stream)); }
     } else {
-      if (nr) HIPCHK(h, hipMemcpyAsync(g->d_raw + row0 * T_r, raw, sizeof(float) * nr, hipMemcpyDeviceToDevice, g->stream));
-      if (ne) HIPCHK(h, hipMemcpyAsync(g->d_ev + row0 * T_e * 5, ev, sizeof(float) * ne, hipMemcpyDeviceToDevice, g->stream));
+      if (nr) HIPCHK(h, hipMemcpyAsync(g->ctx->d_raw + row0 * T_r, raw, sizeof(float) * nr, hipMemcpyDeviceToDevice, g->ctx->stream));
+      if (ne) HIPCHK(h, hipMemcpyAsync(g->ctx->d_ev + row0 * T_e * 5, ev, sizeof(float) * ne, hipMemcpyDeviceToDevice, g->ctx->stream));
     }
   }
-  const int i = g->g_n++;
-  g->g_rows += B;
-  g->g_tslot[i] = slot;
-  if (dev_out) { g->g_members.tokens[i] = call.tokens; g->g_members.out2[i] = call.out2; } else g->g_staged += 1;
-  RvContext::Tick& t = h->ticks[slot];
-  t = RvContext::Tick{};
+  const int i = g->n++;
+  g->rows += B;
+  g->tslot[i] = slot;
+  if (dev_out) { g->members.tokens[i] = call.tokens; g->members.out2[i] = call.out2; } else g->staged += 1;
+  Tick& t = h->ticks[slot];
+  t = Tick{};
   t.busy = true; t.dev_out = dev_out; t.calls = calls; t.member = i; t.B = B; t.row0 = (int)row0; t.steps = L - 1; t.grp = g;
   t.ticket = issue_ticket(h, slot);
   *ticket = t.ticket;
-  if (g->g_n == g->g_cap) launch_group(h, g);      // (a failed launch is reported when its tickets are collected)
+  if (g->n == g->cap) launch_group(h, g);      // (a failed launch is reported when its tickets are collected)
   return RV_OK;
 }
 
 int collect_group(RvContext* h, int slot, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out) {
-  RvContext::Tick& t = h->ticks[slot];
+  Tick& t = h->ticks[slot];
   *S_out = 0;
   if (!t.done) {          // the first collect of a group's ticket launches it if need be, waits for it and settles every member's S
-    RvContext* g = t.grp;
+    Group* g = t.grp;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int rc = launch_group(h, g);
-    if (rc == RV_OK && g->g_rows > 0) {
-      hipError_t e = hipStreamSynchronize(g->stream);
+    if (rc == RV_OK && g->rows > 0) {
+      hipError_t e = hipStreamSynchronize(g->ctx->stream);
       if (e == hipSuccess) e = hipGetLastError();
       if (e != hipSuccess) rc = fail(h, RV_EHIP, "a coalesced call failed: %s", hipGetErrorString(e));
     }
-    g->g_synced = true;
-    for (int i = 0; i < g->g_n; ++i) {
-      RvContext::Tick& u = h->ticks[g->g_tslot[i]];
-      u.done = true; u.S = (rc == RV_OK && u.B > 0) ? g->pin_S[i] : 0;
+    g->synced = true;
+    for (int i = 0; i < g->n; ++i) {
+      Tick& u = h->ticks[g->tslot[i]];
+      u.done = true; u.S = (rc == RV_OK && u.B > 0) ? g->ctx->pin_S[i] : 0;
       if (rc != RV_OK) u.S = -1;
     }
-    if (rc != RV_OK || g->g_staged == 0) {   // results in the callers' device memory: the context takes the next group now
-      for (int i = 0; i < g->g_n; ++i) h->ticks[g->g_tslot[i]].grp = nullptr;
+    if (rc != RV_OK || g->staged == 0) {   // results in the callers' device memory: the context takes the next group now
+      for (int i = 0; i < g->n; ++i) h->ticks[g->tslot[i]].grp = nullptr;
       reset_group(g);
     }
   }
-  const RvContext::Tick u = t;
+  const Tick u = t;
   t.busy = false;
   if (u.S < 0) return fail(h, RV_EHIP, "ticket %d: its coalesced call failed", u.ticket);
   if (u.B > 0 && !u.dev_out) {
-    RvContext* g = u.grp;
+    Group* g = u.grp;
     const size_t B = u.B, steps = u.steps, r0 = u.row0;
     int rc = RV_OK;
     if (!u.calls && (!tokens || !out2)) rc = fail(h, RV_EINVAL, "null output pointer");
     else if (u.calls && (!calls || !calls->bases || !calls->lengths || !calls->probs)) rc = fail(h, RV_EINVAL, "null calls output pointer");
     else if (!u.calls) {
-      memcpy(tokens, g->pin_tok + r0 * steps, sizeof(int32_t) * B * steps);
-      memcpy(out2, g->pin_out2 + r0 * steps, sizeof(float) * B * steps);
+      memcpy(tokens, g->ctx->pin_tok + r0 * steps, sizeof(int32_t) * B * steps);
+      memcpy(out2, g->ctx->pin_out2 + r0 * steps, sizeof(float) * B * steps);
     } else {
-      memcpy(calls->bases, g->pin_bases + r0 * steps, B * steps);
-      memcpy(calls->probs, g->pin_probs + r0 * steps, sizeof(float) * B * steps);
-      memcpy(calls->lengths, g->pin_clen + r0, sizeof(int) * B);
+      memcpy(calls->bases, g->ctx->pin_bases + r0 * steps, B * steps);
+      memcpy(calls->probs, g->ctx->pin_probs + r0 * steps, sizeof(float) * B * steps);
+      memcpy(calls->lengths, g->ctx->pin_clen + r0, sizeof(int) * B);
     }
-    if (rc != RV_OK) { if (--g->g_staged == 0) reset_group(g); return rc; }
+    if (rc != RV_OK) { if (--g->staged == 0) reset_group(g); return rc; }
   }
-  if (!u.dev_out && u.grp && --u.grp->g_staged == 0) reset_group(u.grp);
+  if (!u.dev_out && u.grp && --u.grp->staged == 0) reset_group(u.grp);
   *S_out = u.S;
   h->lS = u.S;
   return RV_OK;
@@ -1954,7 +2011,6 @@ int rv_create_rnn(const RvConfig* cfg, int32_t rnn, rv_handle* out) {
   h->rnn = rnn;
   auto init = [&]() -> int {
   HIPTRY(hipSetDevice(c.device));
-  HIPTRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   HIPTRY(configure_decode_kernels());    // a refused LDS opt-in would otherwise surface as an opaque launch error later
   if (!gru) {                            // (a GRU handle launches neither LSTM recurrence)
     HIPTRY(configure_rec_kernels());
@@ -1971,8 +2027,11 @@ int rv_create_rnn(const RvConfig* cfg, int32_t rnn, rv_handle* out) {
 #ifdef RV_DIAG
   if (const char* e = getenv("RV_DBG_ROLE")) h->dbg_role = atoi(e);
 #endif
+  if (const char* e = getenv("RV_DECODE_SPLIT")) h->opt.split = atoi(e);
   bind_weights(h);
-  TRY(alloc_slab_buffers(h));
+  SlabCtx* own = nullptr;
+  TRY(create_slab(h, &own, c.max_batch, 0));
+  h->slabs.push_back(own);
   return RV_OK;
   };
   const int rc = init();
@@ -1983,29 +2042,14 @@ int rv_create_rnn(const RvConfig* cfg, int32_t rnn, rv_handle* out) {
 
 void rv_destroy(rv_handle h) {
   if (!h) return;
-  for (RvContext* k : h->kids) rv_destroy(k);
-  h->kids.clear();
-  for (RvContext* g : h->groups) rv_destroy(g);      // (launched or still filling: their streams drain in there)
-  h->groups.clear();
-  h->open_grp = nullptr;
   hipSetDevice(h->cfg.device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
-  for (auto& kv : h->slab_graphs) hipGraphExecDestroy(kv.second.exec);
-  for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
-  for (auto e : h->ev_pool) hipEventDestroy(e);
-  for (int g = 0; g < 3; ++g) { if (h->side[g]) hipStreamDestroy(h->side[g]); if (h->ev_join[g]) hipEventDestroy(h->ev_join[g]); }
-  if (h->ev_fork) hipEventDestroy(h->ev_fork);
-  if (h->step_align) hipFree(h->step_align);
-  if (h->palign) hipFree(h->palign);
-  for (void* p : {(void*)h->pin_raw, (void*)h->pin_ev, (void*)h->pin_tok, (void*)h->pin_out2, (void*)h->pin_S, (void*)h->pin_bases, (void*)h->pin_probs, (void*)h->pin_clen, (void*)h->pin_ptab, (void*)h->pin_win,
-                  (void*)h->pin_beams.tokens, (void*)h->pin_beams.scores, (void*)h->pin_beams.path_scores, (void*)h->pin_beams.log_probs, (void*)h->pin_beams.lengths,
-                  (void*)h->pin_moves.raw_pos, (void*)h->pin_moves.raw_mass, (void*)h->pin_moves.event_pos, (void*)h->pin_moves.event_mass, (void*)h->pin_moves.peak, (void*)h->pin_moves.peak_weight}) if (p) hipHostFree(p);
-  for (void* p : h->allocs) hipFree(p);
+  for (size_t i = 1; i < h->slabs.size(); ++i) destroy_slab(h->slabs[i]);
+  for (Group* g : h->groups) destroy_group(g);
+  if (!h->slabs.empty()) destroy_slab(h->slabs[0]);
+  for (void* p : h->allocs) hipFree(p);      // (behind every stream that read the weights)
   for (Read& r : h->reads) { if (r.owned) { if (r.d_raw) hipFree(r.d_raw); if (r.d_ev) hipFree(r.d_ev); } if (r.pin) hipHostFree(r.pin); }
   if (h->copy_stream) { hipStreamSynchronize(h->copy_stream); hipStreamDestroy(h->copy_stream); }
   if (h->ev_put) hipEventDestroy(h->ev_put);
-  if (h->stream) hipStreamDestroy(h->stream);
   delete h;
 }
 
@@ -2027,7 +2071,6 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
   if (n_floats != h->n_w) return fail(h, RV_EINVAL, "weight blob has %zu floats, config needs %zu", n_floats, h->n_w);
   flush_open_group(h);
   if (uncollected(h)) return fail(h, RV_ESTATE, "collect the calls in flight before loading weights");
-  for (RvContext* k : h->kids) if (k->pend.busy) return fail(h, RV_ESTATE, "collect the calls in flight before loading weights");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   h->opt.gen++;                      // (weight-derived scalars travel by value in the decode's kernel arguments)
   // weight_parts 1: every image -- and the device copy of the blob -- is built from the blob with its blob-level tensors rounded
@@ -2038,13 +2081,14 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
     blob = rounded.data();
   }
   h->opt.parts_loaded = h->opt.weight_parts;
-  HIPCHK(h, hipMemcpyAsync(h->d_w, blob, n_floats * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  hipStream_t s = h->slabs[0]->stream;
+  HIPCHK(h, hipMemcpyAsync(h->d_w, blob, n_floats * sizeof(float), hipMemcpyHostToDevice, s));
   const wimg::HostImages im = wimg::build_weight_images(h->cfg, h->rnn, h->opt.weight_parts, blob);
   h->scales = im.scales;
 #define X(T, name, count) TRY(upload_image(h, h->img.name, im.name.data(), im.name.size() * sizeof(T)));
   RV_WEIGHT_IMAGES(X)
 #undef X
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipStreamSynchronize(s));
   h->loaded = true;
   return RV_OK;
 }
@@ -2110,25 +2154,22 @@ int rv_score_logits(rv_handle h, const float* logits, const int32_t* labels, int
   if (B > 0 && S > 0 && (!logits || !labels)) return fail(h, RV_EINVAL, "null input pointer");
   const size_t n = (size_t)B * S;
   TRY(check_token_ids(h, labels, n, std::max(S, 1), "label"));
-  RvContext* ctx = nullptr;
+  SlabCtx* ctx = nullptr;
   TRY(sync_context(h, &ctx));
-  auto body = [&]() -> int {
-    if (n == 0) return fetch_scores(ctx, ScoreArgs{}, out, false, B, 0);
-    HIPCHK(ctx, hipSetDevice(c.device));
-    TRY(ensure_score_buffers(ctx));
-    const ForcedCall fc{labels, omit_mask, out};
-    HIPCHK(ctx, hipMemcpy(ctx->out2, logits, sizeof(float) * n * c.vocab, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->d_forced, labels, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    ScoreArgs a = score_outputs(ctx, &fc, false);
-    a.logits = ctx->out2; a.labels = ctx->d_forced; a.label_stride = S; a.B = B; a.S = S; a.V = c.vocab; a.pad_token = c.pad_token;
-    a.pred = pred ? ctx->out_tokens : nullptr;
-    launch_score_tokens(a, ctx->stream);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipGetLastError());
-    if (pred) HIPCHK(ctx, hipMemcpy(pred, ctx->out_tokens, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    return fetch_scores(ctx, a, out, false, B, S);
-  };
-  return relay(h, ctx, body());
+  if (n == 0) return fetch_scores(h, ScoreArgs{}, out, false, B, 0);
+  HIPCHK(h, hipSetDevice(c.device));
+  TRY(ensure_score_buffers(ctx));
+  const ForcedCall fc{labels, omit_mask, out};
+  HIPCHK(h, hipMemcpy(ctx->out2, logits, sizeof(float) * n * c.vocab, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(ctx->d_forced, labels, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+  ScoreArgs a = score_outputs(ctx, &fc, false);
+  a.logits = ctx->out2; a.labels = ctx->d_forced; a.label_stride = S; a.B = B; a.S = S; a.V = c.vocab; a.pad_token = c.pad_token;
+  a.pred = pred ? ctx->out_tokens : nullptr;
+  launch_score_tokens(a, ctx->stream);
+  HIPCHK(h, hipStreamSynchronize(ctx->stream));
+  HIPCHK(h, hipGetLastError());
+  if (pred) HIPCHK(h, hipMemcpy(pred, ctx->out_tokens, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  return fetch_scores(h, a, out, false, B, S);
 }
 
 // ---- asynchronous calls: submit returns once the slab's work is queued on one of the handle's contexts; collect waits for it.
@@ -2141,7 +2182,7 @@ static int submit(rv_handle h, const Call& call, int32_t* ticket) {
   for (const auto& t : h->ticks) ticks_out = ticks_out || t.busy;
   if (n_co >= 2 || ticks_out) {            // (neither: the path below, one context per slab, as it always was)
     Call ok;
-    TRY(validate_call(h, call, ok));
+    TRY(validate_call(h->slabs[0], call, ok));      // (against the handle's max_batch and options as set)
     if (uncollected(h) >= depth)
       return fail(h, RV_ESTATE, "all %d asynchronous slots hold uncollected calls (option async_depth): collect one first", depth);
     h->inflight_hint = depth;
@@ -2149,25 +2190,23 @@ static int submit(rv_handle h, const Call& call, int32_t* ticket) {
       return submit_group(h, n_co, ok, ticket);
     flush_open_group(h);      // a slab of another path: the group goes as it is, this slab on a context of its own
   }
-  while ((int)h->kids.size() < depth - 1) {
-    RvContext* k = nullptr;
-    TRY(create_child(h, &k));
-    h->kids.push_back(k);
+  while ((int)h->slabs.size() < depth) {
+    SlabCtx* k = nullptr;
+    TRY(create_slab(h, &k, h->cfg.max_batch, (int)h->slabs.size()));
+    h->slabs.push_back(k);
   }
-  RvContext* ctx = nullptr; int slot = -1;
+  SlabCtx* ctx = nullptr; int slot = -1;
   for (int i = 0; i < depth && !ctx; ++i) {          // round robin over the idle contexts
     const int sidx = (h->next_slot + i) % depth;
-    RvContext* cand = sidx == 0 ? h : h->kids[sidx - 1];
-    if (!cand->pend.busy) { ctx = cand; slot = sidx; }
+    if (!h->slabs[sidx]->pend.busy) { ctx = h->slabs[sidx]; slot = sidx; }
   }
   if (!ctx) return fail(h, RV_ESTATE, "all %d asynchronous contexts hold uncollected calls (option async_depth): collect one first", depth);
   h->inflight_hint = depth;
-  if (ctx != h) sync_child(ctx, h);
   CallParts res;
-  if (call.whole_beam) { const int rb = begin_all_beams(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
-  if (call.want_moves) { const int rb = begin_moves(ctx, call, res); if (rb != RV_OK) return relay(h, ctx, rb); }
+  if (call.whole_beam) TRY(begin_all_beams(ctx, call, res));
+  if (call.want_moves) TRY(begin_moves(ctx, call, res));
   const int rc = enqueue(ctx, call, res);
-  if (rc != RV_OK) { ctx->pend.busy = false; return relay(h, ctx, rc); }
+  if (rc != RV_OK) { ctx->pend.busy = false; return rc; }
   h->next_slot = (slot + 1) % depth;
   ctx->pend.ticket = issue_ticket(h, slot);
   *ticket = ctx->pend.ticket;
@@ -2184,10 +2223,10 @@ static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, co
     if (!(h->ticks[slot].busy && h->ticks[slot].ticket == ticket)) release_reads(h, ticket);      // (the ticket is gone: its reads may be dropped)
     return rc;
   }
-  if (ticket < 0 || slot > (int)h->kids.size()) return fail(h, RV_EINVAL, "unknown ticket %d", ticket);
-  RvContext* ctx = slot == 0 ? h : h->kids[slot - 1];
+  if (ticket < 0 || slot >= (int)h->slabs.size()) return fail(h, RV_EINVAL, "unknown ticket %d", ticket);
+  SlabCtx* ctx = h->slabs[slot];
   if (!ctx->pend.busy || ctx->pend.ticket != ticket) return fail(h, RV_ESTATE, "ticket %d is not in flight (collected already?)", ticket);
-  const int rc = relay(h, ctx, finish(ctx, tokens, out2, calls, S_out, beams, moves));
+  const int rc = finish(ctx, tokens, out2, calls, S_out, beams, moves);
   if (!(ctx->pend.busy && ctx->pend.ticket == ticket)) release_reads(h, ticket);
   return rc;
 }
@@ -2360,7 +2399,6 @@ int rv_set_option(rv_handle h, const char* key, int32_t value) {
   if (!strcmp(key, "weight_parts")) {
     if (value != 1 && value != 2) return fail(h, RV_EINVAL, "weight_parts must be 2 (each weight as two f16 parts) or 1 (rounded to its first part)");
     if (uncollected(h)) return fail(h, RV_ESTATE, "collect the calls in flight before setting weight_parts");
-    for (RvContext* k : h->kids) if (k->pend.busy) return fail(h, RV_ESTATE, "collect the calls in flight before setting weight_parts");
   }
   if (!strcmp(key, "one_part_kernels") && value != 0 && value != 1) return fail(h, RV_EINVAL, "one_part_kernels must be 0 or 1");
   h->opt.gen++;                      // slab graphs captured under the old options are rebuilt on their next use
@@ -2410,24 +2448,25 @@ int rv_set_option(rv_handle h, const char* key, int32_t value) {
 
 int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, size_t* n_written) {
   if (!h || !name || !n_written) return RV_EINVAL;
-  const size_t B = h->lB, W = h->fact.lW, Tm = h->lTm, S = h->lS, V = h->cfg.vocab;
+  SlabCtx* cx = h->slabs[0];            // slot 0's last call, and the handle's S
+  const size_t B = cx->lB, W = cx->fact.lW, Tm = cx->lTm, S = h->lS, V = h->cfg.vocab;
   const void* src = nullptr; size_t n = 0; int kind = 0;   // 0 f32, 1 i32, 2 u8
-  const DecState& d = h->dec_st;
-  if (!strcmp(name, "enc_output")) { src = h->enc_out; n = B * Tm * RV_E; }
-  else if (!strcmp(name, "mask")) { src = h->mask; n = B * Tm; kind = 2; }
+  const DecState& d = cx->dec_st;
+  if (!strcmp(name, "enc_output")) { src = cx->enc_out; n = B * Tm * RV_E; }
+  else if (!strcmp(name, "mask")) { src = cx->mask; n = B * Tm; kind = 2; }
   else if (!strcmp(name, "keys")) {
-    if (!h->fact.lkeys) return fail(h, RV_ESTATE, "keys were not built by the last call (single-pass attend); set debug_taps=1");
-    src = h->keys; n = B * Tm * RV_U;
+    if (!cx->fact.lkeys) return fail(h, RV_ESTATE, "keys were not built by the last call (single-pass attend); set debug_taps=1");
+    src = cx->keys; n = B * Tm * RV_U;
   }
   else if (!strcmp(name, "projected_memory")) {
-    if (!h->fact.lpersist) return fail(h, RV_ESTATE, "the projected memory is built for the persistent decode only (the last call ran the per-step kernels)");
-    if (h->fact.lmem2_stale) {   // the decode projected its chunks itself and stored nothing: the same product of that call's enc_out, now
+    if (!cx->fact.lpersist) return fail(h, RV_ESTATE, "the projected memory is built for the persistent decode only (the last call ran the per-step kernels)");
+    if (cx->fact.lmem2_stale) {   // the decode projected its chunks itself and stored nothing: the same product of that call's enc_out, now
       HIPCHK(h, hipSetDevice(h->cfg.device));
-      launch_gemm_mem_split(h->enc_out, (int)(B * Tm), h->img.Wmp16, h->mem2, h->stream);
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      h->fact.lmem2_stale = 0;
+      launch_gemm_mem_split(cx->enc_out, (int)(B * Tm), h->img.Wmp16, cx->mem2, cx->stream);
+      HIPCHK(h, hipStreamSynchronize(cx->stream));
+      cx->fact.lmem2_stale = 0;
     }
-    src = h->mem2; n = B * Tm * RV_E;
+    src = cx->mem2; n = B * Tm * RV_E;
   }
   else if (!strcmp(name, "coalesce_stats")) {   // groups launched, slabs they held, members of the largest, slabs per group in force
     *n_written = 4;
@@ -2445,9 +2484,9 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     return RV_OK;
   }
   else if (!strcmp(name, "rec_stamps")) {
-    if (!h->rec_ts) return fail(h, RV_ESTATE, "set RV_REC_STAMPS=1 before rv_create (and load a -DRV_REC_STAMPS build)");
+    if (!cx->rec_ts) return fail(h, RV_ESTATE, "set RV_REC_STAMPS=1 before rv_create (and load a -DRV_REC_STAMPS build)");
     long long ts[24];
-    HIPCHK(h, hipMemcpy(ts, h->rec_ts, sizeof ts, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(ts, cx->rec_ts, sizeof ts, hipMemcpyDeviceToHost));
     *n_written = 24;
     if (!dst || dst_floats < 24) return fail(h, RV_EINVAL, "rec_stamps needs 24 floats");
     for (int i = 0; i < 24; ++i) dst[i] = (float)ts[i];
@@ -2455,7 +2494,7 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
   }
   else if (!strcmp(name, "kernel_forms") || !strcmp(name, "kernel_form_list") || !strcmp(name, "kernel_form_list_1p") || !strcmp(name, "group_kernel_forms")) {
     FormLog all;
-    const FormLog* f = &h->lforms;
+    const FormLog* f = &cx->lforms;
     if (!strcmp(name, "kernel_form_list") && h->rnn == RV_RNN_BIGRU) {      // the list answers for the handle's family
       FormLog dec;
       list_gru_forms(all); list_decode_forms(dec);
@@ -2470,7 +2509,7 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
       f = &all;
     } else if (!strcmp(name, "group_kernel_forms")) {
       f = &h->gforms;
-    } else if (!h->lforms_ok) {
+    } else if (!cx->lforms_ok) {
       return fail(h, RV_ESTATE, "kernel_forms: the last call replayed a slab graph (option slab_graph), which launches nothing on the host");
     }
     if (f->full) return fail(h, RV_EUNSUPPORTED, "%s: more than %d forms (raise RV_FORM_ROWS)", name, RV_FORM_ROWS);
@@ -2489,25 +2528,25 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     for (int i = 0; i < 16; ++i) dst[i] = (float)(ts[i] - ts[0]);
     return RV_OK;
   }
-  else if ((!strncmp(name, "step_", 5) || !strcmp(name, "parent_ids")) && h->fact.lsplit > 1)
+  else if ((!strncmp(name, "step_", 5) || !strcmp(name, "parent_ids")) && cx->fact.lsplit > 1)
     return fail(h, RV_ESTATE, "per-step records are laid out per sub-slab when decode_split > 1; read them with decode_split=1 or debug_taps=1");
   else if (!strcmp(name, "chunk_steps")) {
-    if (!h->fact.lpersist) return fail(h, RV_ESTATE, "chunk_steps exist only after a persistent decode");
-    src = h->d_chunk_steps; n = B; kind = 1;
+    if (!cx->fact.lpersist) return fail(h, RV_ESTATE, "chunk_steps exist only after a persistent decode");
+    src = cx->d_chunk_steps; n = B; kind = 1;
   }
   else if (!strcmp(name, "step_moves")) {
-    if (!h->lmoves || !h->d_step_moves) return fail(h, RV_ESTATE, "step_moves are the records of a moves call (rv_beam_search_moves*): the last call on this context was none");
-    src = h->d_step_moves; n = S * B * W * RV_MOVE_COLS;
+    if (!cx->lmoves || !cx->d_step_moves) return fail(h, RV_ESTATE, "step_moves are the records of a moves call (rv_beam_search_moves*): the last call on this context was none");
+    src = cx->d_step_moves; n = S * B * W * RV_MOVE_COLS;
   }
   else if (!strcmp(name, "step_ids")) { src = d.step_ids; n = S * B * W; kind = 1; }
   else if (!strcmp(name, "parent_ids")) { src = d.parent_ids; n = S * B * W; kind = 1; }
   else if (!strcmp(name, "step_scores")) { src = d.step_scores; n = S * B * W; }
   else if (!strcmp(name, "step_logits")) {
-    if (!h->ltaps && !h->lgreedy && !h->lptaps) return fail(h, RV_ESTATE, "step_logits needs option debug_taps=1 or persist_taps=1");
+    if (!cx->ltaps && !cx->lgreedy && !cx->lptaps) return fail(h, RV_ESTATE, "step_logits needs option debug_taps=1 or persist_taps=1");
     src = d.step_logits; n = S * B * W * V;
   } else if (!strcmp(name, "step_alignments")) {
-    if (h->ltaps) src = h->step_align;
-    else if (h->lptaps && h->fact.lpersist) src = h->palign;   // [S][B][W][T_m] as the per-step tap
+    if (cx->ltaps) src = cx->step_align;
+    else if (cx->lptaps && cx->fact.lpersist) src = cx->palign;   // [S][B][W][T_m] as the per-step tap
     else return fail(h, RV_ESTATE, "step_alignments needs option debug_taps=1, or persist_taps=1 on the persistent decode");
     n = S * B * W * Tm;
   } else return fail(h, RV_EINVAL, "unknown tensor '%s'", name);
@@ -2517,7 +2556,7 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (kind == 0) {
     HIPCHK(h, hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (src == h->step_align && h->fact.lflash && !h->lmoves) {      // (a moves call's tap is the two-pass launch's: alignments already)
+    if (src == cx->step_align && cx->fact.lflash && !cx->lmoves) {      // (a moves call's tap is the two-pass launch's: alignments already)
       // the single-pass kernel taps raw log2-domain masked scores; normalise here (debug path only)
       for (size_t r = 0; r < n / Tm; ++r) {
         float* a = dst + r * Tm;
