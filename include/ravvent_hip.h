@@ -86,7 +86,8 @@ int rv_create(const RvConfig* cfg, rv_handle* out);
  * existing entry point or RvConfig: RV_ABI_VERSION stays at 1.  A GRU handle serves every mode, both attentions, enc_depth 1..8,
  * dec_depth 1..4, beam 1..8 and greedy search, the whole beam, teacher-forced scoring, moves, the asynchronous calls (never
  * coalesced), window calls (behind k_expand_windows) and the debug taps.  Its encoders run k_gru_rec_mx (matrix pipe, sixteen
- * chunks per workgroup) and its decode the per-step kernels with k_dec_cell_gru as the cell; there is no persistent GRU decode.
+ * chunks per workgroup) and its decode the per-step kernels with k_dec_cell_gru as the cell; with one decoder cell, option
+ * "gru_persistent" 1 moves the decode into one launch, k_dec_persist_gru (rv_set_option).
  * rv_set_option on such a handle fails with RV_EUNSUPPORTED for "weight_parts" 1, "wide_recurrence" other than 1,
  * "lane_projection" 0 and "slab_graph" 1 (no GRU kernel stands behind them); options that only pick LSTM forms or configure the
  * persistent decode are accepted and do nothing.  Any other value of `rnn` fails with RV_EUNSUPPORTED. */
@@ -432,6 +433,17 @@ int rv_score_logits(rv_handle h, const float* logits, const int32_t* labels, int
  *                       launch only -- the persistent decode kernel or the decode graph). */
 int rv_set_option(rv_handle h, const char* key, int32_t value);
 
+/* An option of a GRU handle alone (rv_create_rnn with RV_RNN_BIGRU), set through rv_set_option like the ones above:
+ *   "gru_persistent": 0 or 1, default 0; one decoder cell only.  A BiLSTM handle and a GRU handle with decoder_depth != 1 answer
+ *       RV_EUNSUPPORTED by name, calls in flight RV_ESTATE, any other value RV_EINVAL.  1: the decode of every call a form serves --
+ *       beam 1..8 and greedy search, both attentions, the whole beam, forced decodes, moves, "persist_taps", the asynchronous calls
+ *       and window calls, while "persistent_decode", "flash_attend", "matrix_attention" and "matrix_cell" are on and "debug_taps" is
+ *       off -- is ONE launch of k_dec_persist_gru, the persistent decode's body with a GRU gate phase, in place of a k_dec_cell_gru
+ *       and an attend launch per step.  Setting it builds the folded GRU images at once from the weights in force (else at the next
+ *       rv_load_weights) and allocates them and the projected-memory buffers on first use.  0 returns to the per-step decode and its
+ *       bytes; nothing is freed.  The slabs of such a handle are still never coalesced, its window calls still run behind
+ *       k_expand_windows and "slab_graph" 1 stays refused. */
+
 /* Debug taps of the LAST call, copied to host as fp32 (bool/int tensors are converted):
  *   "enc_output" [B,T_m,2u]   _encode_input's output              basecaller.py:405
  *   "mask"       [B,T_m]      input_mask (1.0 / 0.0)              basecaller.py:406
@@ -449,12 +461,13 @@ int rv_set_option(rv_handle h, const char* key, int32_t value);
  *                                 (kernel, p1, p2, p3, p4), unused parameters 0: kernel 0 k_dec_persist (W, NIT, D, ATT), 1 k_dec_attend_flash
  *                                 (W, NT), 2 k_dec_attend (W, TB), 3 k_lstm_rec (BT, F), 4 k_lstm_rec_tw (BT, F), 5 k_lstm_rec_proj (BT, SB),
  *                                 6 k_lstm_rec_mx (F, CH), 7 k_inproj_small (F), 8 k_dec_persist_1p (below), 9 k_gru_rec_mx (F, CH),
- *                                 10 k_dec_cell_gru (no parameters), the last two on a GRU handle only.  Noted by the walk of each kernel's form list that launches
+ *                                 10 k_dec_cell_gru (no parameters), 11 k_dec_persist_gru (W, NIT, 1, ATT), the last three on a GRU handle only.  Noted by the walk of each kernel's form list that launches
  *                                 it; a per-step decode replayed from its captured hipGraph reports the forms of the capture.  After a call
  *                                 that ran as a slab graph (option "slab_graph") it fails with RV_ESTATE
  *   "kernel_form_list" [n,5]      every instantiation the form lists hold, in the same rows, whatever the last call was.  It answers for
  *                                 the handle's family: a BiLSTM handle lists what it always did; a GRU handle (rv_create_rnn) lists the
- *                                 k_gru_rec_mx forms and k_dec_cell_gru in place of the LSTM recurrences and the persistent decode
+ *                                 k_gru_rec_mx forms, k_dec_cell_gru and the k_dec_persist_gru forms (id 11, whatever "gru_persistent" says)
+ *                                 in place of the LSTM recurrences and the persistent decode
  *   "kernel_form_list_1p" [n,5]   the one-part forms of the persistent decode (option "weight_parts" 1), a list of their own: rows
  *                                 (8, W, NIT, 1, ATT) for k_dec_persist_1p<W, NIT, ATT>.  "kernel_forms" reports a launched one under
  *                                 the same kernel id 8

@@ -195,6 +195,8 @@ class Basecaller:
                          "rv_load_weights")
         if self.weight_parts != (loaded if getattr(self, "_blob", None) is not None else 2):
             other._check(self._lib.rv_set_option(other._h, b"weight_parts", self.weight_parts), "rv_set_option(weight_parts)")
+        if self.gru_persistent:
+            other._check(self._lib.rv_set_option(other._h, b"gru_persistent", 1), "rv_set_option(gru_persistent)")
         return other
 
     @property
@@ -218,6 +220,21 @@ class Basecaller:
             self._check(self._lib.rv_load_weights(self._h, self._blob.ctypes.data_as(ctypes.c_void_p), self._blob.size),
                         "rv_load_weights")
             self._parts_loaded = int(n)          # (only once the reload has succeeded)
+        return self
+
+    @property
+    def gru_persistent(self) -> bool:
+        """Whether option ``gru_persistent`` is on (``set_gru_persistent``)."""
+        return bool(getattr(self, "_gru_persistent", False))
+
+    def set_gru_persistent(self, on: bool = True):
+        """A ``rnn_type='bigru'`` model of one decoder cell: decode every call in ONE launch of the persistent GRU kernel
+        (``k_dec_persist_gru``) instead of two launches per output step (include/ravvent_hip.h, option ``gru_persistent``; DESIGN.md
+        section 15).  Off by default.  The folded GRU images are built from the weights in force when this returns (else at the next
+        load); turning it off returns to the per-step decode and frees nothing.  Fails on a BiLSTM model, with more than one decoder
+        cell, and while asynchronous calls are in flight."""
+        self._check(self._lib.rv_set_option(self._h, b"gru_persistent", int(bool(on))), "rv_set_option(gru_persistent)")
+        self._gru_persistent = bool(on)
         return self
 
     def load_weights(self, path):
@@ -246,6 +263,8 @@ class Basecaller:
         self._check(rc, f"rv_set_option({key})")
         if key == "weight_parts":
             self._weight_parts = int(value)
+        if key == "gru_persistent":
+            self._gru_persistent = bool(value)
 
     # ------------------------------------------------------------------ input plumbing
     def _split_inputs(self, input_data):

@@ -27,6 +27,7 @@ enum {
   RV_K_DEC_PERSIST_1P = 8,     // k_dec_persist_1p<W, NIT, ATT>: (W, NIT, 1, ATT); launched under option weight_parts 1 only
   RV_K_GRU_REC_MX = 9,         // k_gru_rec_mx<F, CH> (a GRU handle only: rv_create_rnn)
   RV_K_DEC_CELL_GRU = 10,      // k_dec_cell_gru: no parameters
+  RV_K_DEC_PERSIST_GRU = 11,   // k_dec_persist_gru<W, NIT, ATT>: (W, NIT, 1, ATT); a GRU handle under option gru_persistent 1 only
 };
 #define RV_FORM_ROWS 512
 struct FormLog {
@@ -50,6 +51,7 @@ void list_rec_forms(FormLog& log);
 void list_mx_forms(FormLog& log);
 void list_decode_forms(FormLog& log);
 void list_decode_forms_1p(FormLog& log);   // the one-part forms of the persistent decode: a list of their own ("kernel_form_list_1p")
+void list_decode_forms_gru(FormLog& log);  // the persistent decode of a GRU cell: listed on a GRU handle's "kernel_form_list" only
 
 // ---------------------------------------------------------------- K1: BiLSTM recurrence
 // Members of a coalesced call whose inputs are read where their callers left them (matrix-pipe layer 0 only): chunk b of the group with
@@ -306,6 +308,12 @@ void launch_dec_persist(const DecState& d, const float* Wcat /*[256,512]*/, cons
 // Wc16p1 / Wl16p1 (option weight_parts 1; both or neither): the first f16 parts of the Wc16 / Wl16 images on their own.  Where the
 // one-part list holds a form for the call, k_dec_persist_1p runs on them in k_dec_persist's place; elsewhere k_dec_persist runs on
 // d's two-part images, whose second parts are zero then -- the same results bit for bit, but for the sign of a zero
+// The persistent decode of ONE Keras GRU cell (reset_after), k_dec_persist_gru: the same body and arguments with d.Wc16 / d.Wl16 /
+// d.Wq16 naming the folded GRU images (weight_images.h: GruPersistImages), Wtok [V,512] / bdec [512] its token table and bias in the
+// cell product's four tiles z, r, candidate-input, candidate-recurrent.  att: 3 Luong, 4 Bahdanau.  dec_persist_form_gru: att when the
+// GRU list holds a form for (W, T_m) and its LDS fits, else -1
+int dec_persist_form_gru(int attention, int W, int Tm, bool greedy);
+void launch_dec_persist_gru(const DecState& d, const float* Wtok, const float* bdec, hipStream_t s, FormLog* log = nullptr);
 // ptab != null: the two output addresses are read from ptab[RV_PTAB_TOKENS] / ptab[RV_PTAB_OUT2] on the device instead
 // Members (persistent beam-search decode only): the slab is n slabs of the asynchronous calls decoded as one, back to back.  Member m
 // owns rows row0[m] .. row0[m] + rows[m] - 1: its S is the maximum of chunk_steps over those rows alone, goes to S_host[m], and its rows

@@ -1269,9 +1269,11 @@ __device__ __forceinline__ int persist_forced_tok(const DecState& d, int b, int 
 }
 
 // The compile-time facts of one form k_dec_persist<W, NIT, D, ATT>
-template <int W_, int NIT_, int D_, int ATT_, int PARTS_ = 2>
+template <int W_, int NIT_, int D_, int ATT_, int PARTS_ = 2, bool GRU_ = false>
 struct PersistTraits {
   static constexpr int W = W_, NIT = NIT_, D = D_, ATT = ATT_;
+  static constexpr bool GRU = GRU_;               // k_dec_persist_gru: the one cell is a Keras GRU (reset_after), its four gate tiles z, r, candidate-input, candidate-recurrent
+  static_assert(!GRU || (PARTS_ == 2 && D == 1 && (ATT == 3 || ATT == 4)), "a GRU cell: one cell, two-part fragments, the cell product on the matrix pipe");
   static constexpr int PARTS = PARTS_;            // f16 parts per weight of the Wc16 / Wl16 fragments: 2, or 1 in k_dec_persist_1p (the beams' A image keeps both of its parts)
   static constexpr bool P1 = PARTS == 1;
   static constexpr int FR = P1 ? 64 : 128;        // uint4 per (k-step, gate) pair of a wave: 64 lanes x PARTS fragments
@@ -1699,6 +1701,7 @@ void launch_dec_attend(const DecState& d, const float* WmemT, bool flash, int st
 // Kernels that use more than the default dynamic-LDS limit opt in once per device (called by rv_create after hipSetDevice): sized
 // for the largest shapes the library accepts (T_m <= 352), up to what the kernel's static LDS leaves of the 160 KB (the attend
 // kernels' static part, like k_dec_persist's with packed-FMA cells, is under 10 KB)
+static hipError_t configure_dec_persist_gru();      // (the GRU forms: defined with their kernel at the end of the file)
 hipError_t configure_decode_kernels() {
   hipError_t first = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dec_cell), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)(sizeof(float) * CELL_LDS_FLOATS));
@@ -1725,7 +1728,8 @@ hipError_t configure_decode_kernels() {
     return opt(reinterpret_cast<const void*>(&k_dec_persist_1p<F::W, F::NIT, F::ATT>), sizeof(float) * PersistLds(F::W, 1, F::ATT, 1).total,
                persist_static_lds(F::ATT));
   });
-  return first;
+  const hipError_t eg = configure_dec_persist_gru();
+  return first != hipSuccess ? first : eg;
 }
 
 void launch_dec_finalize(const DecState& d, int32_t* tokens, float* out2, hipStream_t s, const void* const* ptab, const DecMembers* members) {
@@ -1747,4 +1751,57 @@ static bool launch_dec_persist_1p(const DecState& d, const float* Wcat, const fl
     if (log) log->add(RV_K_DEC_PERSIST_1P, F::W, F::NIT, F::D, F::ATT);
     return true;
   });
+}
+
+// ---- the persistent decode of a GRU cell (a GRU handle under option gru_persistent 1).  A third kernel over the body of k_dec_persist:
+// one cell, two-part fragments, the cell product on the matrix pipe; T::GRU switches the gate phase, nothing else.  d.Wc16 / d.Wl16 /
+// d.Wq16 name the folded GRU images, whose four column tiles are z, r and the candidate's input and recurrent halves; Wcat, Wcat1, bdec1
+// and Nh are unused (the arguments stay those of the body).  Kernel, form list and launchers stand behind every kernel that was in this
+// file before them: see the note above the form lists
+namespace {
+template <int W, int NIT, int ATT>
+__global__ __launch_bounds__(512) void k_dec_persist_gru(DecState d, const float* __restrict__ Wcat, const float* __restrict__ Wtok, const float* __restrict__ bdec,
+                                                          const float* __restrict__ Wcat1, const float* __restrict__ bdec1, const float* __restrict__ Nh) {
+  constexpr int NT = 512, D = 1;
+  using T = PersistTraits<W, NIT, D, ATT, 2, true>;
+#include "decode_persist_body.inc"
+}
+// k_dec_persist_gru<W, NIT, ATT>: Luong (3) and Bahdanau (4) for every beam width at the NIT bands of the LSTM list
+template <int W, typename Fn> bool persist_gru_w(Fn& fn) { return persist_nit<W, 1, 3>(fn) || persist_nit<W, 1, 4>(fn); }
+template <typename Fn> bool for_each_persist_form_gru(Fn&& fn) {
+  return persist_gru_w<1>(fn) || persist_gru_w<2>(fn) || persist_gru_w<3>(fn) || persist_gru_w<4>(fn) || persist_gru_w<5>(fn) ||
+         persist_gru_w<6>(fn) || persist_gru_w<7>(fn) || persist_gru_w<8>(fn);
+}
+}  // namespace
+
+void list_decode_forms_gru(FormLog& log) {
+  for_each_persist_form_gru([&](auto f) { using F = decltype(f); log.add(RV_K_DEC_PERSIST_GRU, F::W, F::NIT, F::D, F::ATT); return false; });
+}
+int dec_persist_form_gru(int attention, int W, int Tm, bool greedy) {
+  const int att = attention == 1 ? 4 : attention == 0 ? 3 : -1;
+  if (greedy && W != 1) return -1;
+  if (!for_each_persist_form_gru([&](auto f) { return persist_serves<decltype(f)>(W, 1, att, Tm); })) return -1;
+  return sizeof(float) * PersistLds(W, 1, att).total + persist_static_lds(att) <= 160 * 1024 ? att : -1;
+}
+void launch_dec_persist_gru(const DecState& d, const float* Wtok, const float* bdec, hipStream_t s, FormLog* log) {
+  for_each_persist_form_gru([&](auto f) {
+    using F = decltype(f);
+    if (!persist_serves<F>(d.W, d.depth, d.persist_att, d.Tm)) return false;
+    hipLaunchKernelGGL((k_dec_persist_gru<F::W, F::NIT, F::ATT>), dim3(d.B), dim3(512), sizeof(float) * PersistLds(F::W, 1, F::ATT).total, s,
+                       d, nullptr, Wtok, bdec, nullptr, nullptr, nullptr);
+    if (log) log->add(RV_K_DEC_PERSIST_GRU, F::W, F::NIT, F::D, F::ATT);
+    return true;
+  });
+}
+static hipError_t configure_dec_persist_gru() {
+  hipError_t first = hipSuccess;
+  for_each_persist_form_gru([&](auto f) {
+    using F = decltype(f);
+    const size_t bytes = sizeof(float) * PersistLds(F::W, 1, F::ATT).total, cap = 160 * 1024 - persist_static_lds(F::ATT);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dec_persist_gru<F::W, F::NIT, F::ATT>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes < cap ? bytes : cap));
+    if (e != hipSuccess && first == hipSuccess) first = e;
+    return false;
+  });
+  return first;
 }

@@ -1,6 +1,8 @@
-// The body of the persistent decode's kernels (decode.hip: k_dec_persist, k_dec_persist_1p), included inside each of them.  In scope at
-// the point of inclusion: the kernel's arguments (d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh) and the compile-time W, NIT, D, ATT, NT and
-// T = PersistTraits<...>, whose PARTS says how many f16 parts a weight of the Wc16 / Wl16 fragments has.
+// The body of the persistent decode's kernels (decode.hip: k_dec_persist, k_dec_persist_1p, k_dec_persist_gru), included inside each of
+// them.  In scope at the point of inclusion: the kernel's arguments (d, Wcat, Wtok, bdec, Wcat1, bdec1, Nh) and the compile-time W, NIT,
+// D, ATT, NT and T = PersistTraits<...>, whose PARTS says how many f16 parts a weight of the Wc16 / Wl16 fragments has and whose GRU
+// says that the one cell is a GRU (the gate phase alone differs: the four gate tiles of the cell product are then z, r and the two
+// halves of the candidate, and `cS` holds h).
   extern __shared__ __align__(16) float dsm[];
   const PersistLds L(W, D, ATT, T::PARTS);
   _Float16* xim = reinterpret_cast<_Float16*>(dsm + L.xim);   // MXC only
@@ -199,17 +201,39 @@
           const int w = ok[it] ? idx >> 7 : 0, u = idx & 127, pb = s_parent[w], tk = s_tok[w];
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
+            if constexpr (T::GRU && NITEM == 1) continue;      // (a GRU thread with one item reads each operand where the gate math uses it)
             if constexpr (CELL == 0) z4[it][g] = part[pb * T::ZS + g * RV_U + u] + zb[tk * RV_G + g * RV_U + u];
             else z4[it][g] = (part[w * T::ZS + g * RV_U + u] + partU[pb * T::ZS + g * RV_U + u]) + b1s[g * RV_U + u];
           }
-          cp[it] = cst[cb * W * RV_U + pb * RV_U + u];
+          if constexpr (!T::GRU || W > 5) cp[it] = cst[cb * W * RV_U + pb * RV_U + u];
         }
 #pragma unroll
         for (int it = 0; it < NITEM; ++it) {
           if (!ok[it]) continue;
           const int idx = tid + it * NT, w = idx >> 7, u = idx & 127;
-          const float c2 = fmaf(rv_sigmoid(z4[it][1]), cp[it], rv_sigmoid(z4[it][0]) * rv_tanh(z4[it][2]));
-          const float hh = rv_sigmoid(z4[it][3]) * rv_tanh(c2);
+          float c2, hh;
+          if constexpr (T::GRU) {
+            // Keras GRU cell, reset_after: the tiles are z, r, candidate-input, candidate-recurrent (the last with b[1]_h from its token-table
+            // row, so that the reset gate multiplies h . U_h + b[1]_h whole); hp = the parent's h, the cell's one state, kept in fp32 in `cS`.
+            // The candidate first, then z and hp.  Up to W = 5 (at most waves 0-1 carry a second item) hp is read here, as late as its use,
+            // and a thread with one item reads its tiles here too: the Bahdanau forms hold W_q's fragments across this phase, and with
+            // the LSTM's order of reads k_dec_persist_gru<4,8,4> and <5,8,4> spill more than their LSTM forms; wider beams keep that
+            // order, under which <7,8,4> spills no more than its LSTM form (tests/test_gru_persist_build.py holds every form to it)
+            const int pb = s_parent[w];
+            auto zt = [&](int g) {
+              if constexpr (NITEM == 1) return part[pb * T::ZS + g * RV_U + u] + zb[s_tok[w] * RV_G + g * RV_U + u];
+              else return z4[it][g];
+            };
+            const float cand = rv_tanh(fmaf(rv_sigmoid(zt(1)), zt(3), zt(2)));
+            const float zg = rv_sigmoid(zt(0));
+            float hp;
+            if constexpr (W > 5) hp = cp[it]; else hp = cst[cb * W * RV_U + pb * RV_U + u];
+            hh = fmaf(zg, hp - cand, cand);                    // z h + (1 - z) hh
+            c2 = hh;
+          } else {
+            c2 = fmaf(rv_sigmoid(z4[it][1]), cp[it], rv_sigmoid(z4[it][0]) * rv_tanh(z4[it][2]));
+            hh = rv_sigmoid(z4[it][3]) * rv_tanh(c2);
+          }
           cst[(cb ^ 1) * W * RV_U + idx] = c2;
           {   // h as A fragments: h 2^14 in two f16 parts, k = 128 + u (top cell), 256 + u (cell 0 of two)
             const float sv = hh * 16384.f;

@@ -72,6 +72,7 @@ struct Options {
   int weight_parts = 2;                     // option "weight_parts": f16 parts a weight image keeps of each weight, as of the next rv_load_weights (round_blob_weights)
   int parts_loaded = 2;                     // ... and what the images in force were built with
   int one_part = 1;                         // option "one_part_kernels": weight_parts 1 decodes with k_dec_persist_1p where a form exists (0: the two-part kernels on the zero-lo images)
+  int gru_persist = 0;                      // option "gru_persistent" (a GRU handle of one decoder cell): the one-launch persistent decode, k_dec_persist_gru, where a form serves the call
 };
 
 // Device images derived from the weights (weight_images.h lists them; rv_load_weights uploads what build_weight_images returns).  The
@@ -82,6 +83,14 @@ struct WeightImages {
 #undef X
 };
 static_assert(wimg::U == RV_U && wimg::E == RV_E && wimg::MAX_VOCAB == RV_MAX_VOCAB, "weight_images.h restates common.h");
+// ... and those of a GRU handle's persistent decode (wimg::GruPersistImages): allocated when option "gru_persistent" is first set to 1
+struct GruPersistDev {
+#define X(T, name, count) T* name = nullptr;
+  RV_GRU_PERSIST_IMAGES(X)
+#undef X
+  bool allocated = false, built = false;    // built: they hold the images of the weights in force
+  wimg::ImageScales scales;
+};
 
 // What a recording leaves behind for rv_get_tensor beside lB .. lptaps; a slab graph stores them at its capture and puts them back at every replay
 struct SlabFacts {
@@ -177,6 +186,7 @@ struct RvContext {
   WeightImages img;                         // derived from the weights
   const float *W_mem = nullptr, *W_q = nullptr, *v_att = nullptr, *W_att = nullptr, *W_fc = nullptr, *b_fc = nullptr;
   wimg::ImageScales scales;                 // the weight-derived scalars of the decode (set by rv_load_weights)
+  GruPersistDev gimg;                       // a GRU handle under option "gru_persistent"
 
   Options opt;
   int dbg_role = 0;                         // timing probe (RV_DBG_ROLE): 1 = no projection math, 2 = no recurrence math
@@ -616,10 +626,13 @@ void launch_decode_steps(SlabCtx* cx, const DecState& d, bool flash, hipStream_t
 // The form of the one-launch persistent decode this call takes (dec_persist_form), or -1: the per-step kernels
 int persist_form(const SlabCtx* cx, bool greedy, int W, int Tm, bool forced) {
   const RvContext* const h = cx->h;
-  if (h->rnn != RV_RNN_BILSTM) return -1;                // (a GRU handle decodes per step: no persistent GRU kernel)
+  const bool gru = h->rnn == RV_RNN_BIGRU;
+  if (gru && !(h->opt.gru_persist && h->gimg.built && cx->mem2)) return -1;      // (a GRU handle decodes per step unless option gru_persistent is on)
   if (!h->opt.persist || !h->opt.flash || cx->taps()) return -1;
   const RvConfig& c = h->cfg;
   if (forced && c.vocab >= RV_MAX_VOCAB) return -1;      // (a forced decode keeps a bias-only row behind the vocabulary's in the resident token table)
+  // k_dec_persist_gru: one cell, everything but Bahdanau's scores on the matrix pipe -- no other GRU form exists to fall to
+  if (gru) return c.dec_depth == 1 && h->opt.mx_att && h->opt.mx_cell ? dec_persist_form_gru(c.attention, greedy ? 1 : W, Tm, greedy) : -1;
   return dec_persist_form(c.attention, c.dec_depth, greedy ? 1 : W, Tm, greedy, h->opt.mx_att, h->opt.mx_cell);
 }
 
@@ -642,10 +655,10 @@ Plan plan_call(const SlabCtx* cx, const Call& call, const CallParts& res) {
   // A window call: the default path gathers each chunk in the lane of its layer-0 recurrence; every other form -- the packed-FMA
   // recurrence, "lane_projection" 0, the per-step decode, taps, profiling, a group with "group_inplace" 0 -- runs unchanged behind
   // k_expand_windows, which writes the padded chunk tensors into the context's input buffers
-  p.win_lane = call.windows && p.wide && (h->cfg.mode == RV_MODE_RAW || lane_layer0(h, 5, call.T_e)) && quiet && p.persist >= 0 &&
-               !(cx->grp && !o.group_inplace);
+  p.win_lane = call.windows && !gru && p.wide && (h->cfg.mode == RV_MODE_RAW || lane_layer0(h, 5, call.T_e)) && quiet && p.persist >= 0 &&
+               !(cx->grp && !o.group_inplace);      // (k_gru_rec_mx gathers no windows: a GRU handle's window call runs behind k_expand_windows)
   // A slab graph: the default path only -- matrix-pipe recurrences + persistent decode, no profiling, no taps
-  p.graphable = o.slab_graph && !call.windows && p.wide && !p.rows8 && p.persist >= 0 && quiet && !res.whole_beam && !res.labels &&
+  p.graphable = o.slab_graph && !gru && !call.windows && p.wide && !p.rows8 && p.persist >= 0 && quiet && !res.whole_beam && !res.labels &&
                 !cx->ptaps() && !cx->rec_ts && !cx->dec_st.dbg_ts && cx->d_ptab;
   return p;
 }
@@ -963,6 +976,11 @@ int split_decode(SlabCtx* cx, Slab& sl) {
   d.Wc16 = h->img.Wc16; d.mx_cdescale = h->scales.cdescale; d.Wl16 = h->img.Wl16; d.mx_ldescale = h->scales.ldescale;
   d.Wq16 = h->img.Wq16; d.mx_qdescale = h->scales.qdescale; d.W1c16 = h->img.W1c16; d.mx_c1descale = h->scales.c1descale;
   const bool persist = persist_att >= 0;
+  if (persist && h->rnn == RV_RNN_BIGRU) {      // k_dec_persist_gru: the folded GRU images under the LSTM forms' names
+    const GruPersistDev& gi = h->gimg;
+    d.Wc16 = gi.gWc16; d.mx_cdescale = gi.scales.cdescale; d.Wl16 = gi.gWl16; d.mx_ldescale = gi.scales.ldescale;
+    d.Wq16 = gi.gWq16; d.mx_qdescale = gi.scales.qdescale;
+  }
   cx->fact.lpersist = persist ? 1 : 0;
   cx->fact.lmem2_stale = 0;
   if (persist) { nsplit = 1; d.chunk_steps = cx->d_chunk_steps; }
@@ -1013,21 +1031,30 @@ int decode_persist(SlabCtx* cx, Slab& sl) {
   // prologue, with the split GEMM's arithmetic (decode.hip, persist_project_memory); every other form reads the GEMM's mem2
   const bool fused_mem = h->opt.fused_mem && h->opt.split_proj && persist_att == 3 && d.depth == 1;
   cx->fact.lmem2_stale = fused_mem && !cx->ptaps();
-  d.enc_rows = nullptr; d.Wmp16 = h->img.Wmp16; d.Wkp16 = h->img.Wkp16; d.mem_tap = nullptr;
+  const bool gru = h->rnn == RV_RNN_BIGRU;
+  const wimg::ImageScales& scales = gru ? h->gimg.scales : h->scales;
+  const float* Wmp = gru ? h->gimg.gWmp : h->img.Wmp;
+  const uint16_t* Wmp16 = gru ? h->gimg.gWmp16 : h->img.Wmp16;
+  d.enc_rows = nullptr; d.Wmp16 = Wmp16; d.Wkp16 = gru ? h->gimg.gWkp16 : h->img.Wkp16; d.mem_tap = nullptr;
   if (fused_mem) {
     d.enc_rows = cx->enc_out; d.mem_tap = cx->ptaps() ? cx->mem2 : nullptr;
   } else {   // attention memory in the form the persistent decode keeps on chip: [keys | U'] = enc_out . [W_mem | A_c]
     GemmArgs g{};
-    g.A = cx->enc_out; g.lda = RV_E; g.Bm = h->img.Wmp; g.ldb = RV_E; g.C = cx->mem2; g.ldc = RV_E;
+    g.A = cx->enc_out; g.lda = RV_E; g.Bm = Wmp; g.ldb = RV_E; g.C = cx->mem2; g.ldc = RV_E;
     g.M = B * Tm; g.N = RV_E; g.K = RV_E;
     g.xcd_remap = 1;
     Scope sc(cx, "gemm_memory");
-    if (h->opt.split_proj) launch_gemm_mem_split(cx->enc_out, B * Tm, h->img.Wmp16, cx->mem2, s);
+    if (h->opt.split_proj) launch_gemm_mem_split(cx->enc_out, B * Tm, Wmp16, cx->mem2, s);
     else launch_gemm_f32(g, false, s);
   }
   d.values = cx->mem2; part[0].values = cx->mem2;
-  d.mx_kscale = h->scales.kscale; d.mx_kdescale = std::ldexp(1.0f, -14) / h->scales.kscale;
-  d.mx_uscale = h->scales.uscale; d.mx_udescale = std::ldexp(1.0f, -14) / h->scales.uscale;
+  d.mx_kscale = scales.kscale; d.mx_kdescale = std::ldexp(1.0f, -14) / scales.kscale;
+  d.mx_uscale = scales.uscale; d.mx_udescale = std::ldexp(1.0f, -14) / scales.uscale;
+  if (gru) {
+    Scope sc(cx, "dec_persist_gru", nullptr, true);
+    launch_dec_persist_gru(d, h->gimg.gWtok, h->gimg.gbdec, s, &cx->lforms);
+    return RV_OK;
+  }
   const bool p1 = h->opt.parts_loaded == 1 && h->opt.one_part && persist_att == 3 && d.depth == 1;
   Scope sc(cx, "dec_persist", nullptr, true);
   launch_dec_persist(d, d.depth > 1 ? h->dec[0].W + (size_t)V * RV_G : h->img.Wcat2, h->dec[0].W, h->dec[0].b,
@@ -1496,7 +1523,7 @@ int alloc_slab_buffers(SlabCtx* cx) {
       for (int k = 0; k < 4; k += h->rnn == RV_RNN_BIGRU ? 2 : 1) TRY(dalloc(cx, &cx->st[e][st][k], B * RV_U));      // (a GRU's sets hold h only)
   TRY(dalloc(cx, &cx->enc_out, B * Tm * RV_E));
   TRY(dalloc(cx, &cx->keys, B * Tm * RV_U));
-  if (h->rnn == RV_RNN_BILSTM) TRY(dalloc(cx, &cx->mem2, B * Tm * RV_E));      // (the persistent decode's projected memory)
+  if (h->rnn == RV_RNN_BILSTM || h->gimg.allocated) TRY(dalloc(cx, &cx->mem2, B * Tm * RV_E));      // (the persistent decode's projected memory; a GRU handle: under option gru_persistent)
   DecState& d = cx->dec_st;
 #ifdef RV_DIAG   // timing ablations that INVALIDATE results: only in `make diag` builds (libravvent_hip_diag.so), never in the product library
   if (const char* e = getenv("RV_ATT_STOP")) d.dbg_stop = atoi(e);
@@ -1626,6 +1653,7 @@ int uncollected(const RvContext* h) {
 bool coalescible(const RvContext* h, const Call& call) {
   const SlabCtx* cx = h->slabs[0];      // (the plan of a plain beam search is the same on every slot once the taps are off)
   if (h->opt.profile != 0 || h->opt.taps || h->opt.ptaps || cx->rec_ts || cx->dec_st.dbg_ts || h->opt.slab_graph || call.L <= 1) return false;
+  if (h->rnn != RV_RNN_BILSTM) return false;      // (the group kernels are the BiLSTM's: a GRU handle's slabs run one by one, persistent decode or not)
   const Plan p = plan_call(cx, call, CallParts{});
   return p.wide && p.persist >= 0;
 }
@@ -1952,6 +1980,39 @@ int refuse_gru_option(RvContext* h, const char* key, int value) {
               "layer-0 projection in the lane, its weights keep two f16 parts, and its decode runs per step outside a slab graph", key, value);
 }
 
+// Option "gru_persistent" 1 on a GRU handle: the images of k_dec_persist_gru and every context's projected-memory buffer, allocated
+// on first use; the images built from `blob` (host; null: the device copy of the weights in force, copied back)
+int build_gru_persist(RvContext* h, const float* blob) {
+  GruPersistDev& gi = h->gimg;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (!gi.allocated) {
+#define X(T, name, count) if (!gi.name) TRY(dalloc(h, &gi.name, (count)));      /* (a retry after a failed allocation keeps what it has) */
+    using wimg::E; using wimg::U; using wimg::MAX_VOCAB;
+    RV_GRU_PERSIST_IMAGES(X)
+#undef X
+    gi.allocated = true;
+  }
+  for (SlabCtx* cx : h->slabs)      // (contexts created from here on allocate theirs: alloc_slab_buffers)
+    if (!cx->mem2) {
+      const RvConfig& c = h->cfg;
+      const size_t Tm = (c.mode != RV_MODE_EVENT ? c.max_raw_len : 0) + (c.mode != RV_MODE_RAW ? c.max_event_len : 0);
+      TRY(dalloc(cx, &cx->mem2, (size_t)cx->cap * Tm * RV_E));
+    }
+  std::vector<float> back;
+  if (!blob) {
+    back.resize(h->n_w);
+    HIPCHK(h, hipMemcpy(back.data(), h->d_w, h->n_w * sizeof(float), hipMemcpyDeviceToHost));
+    blob = back.data();
+  }
+  const wimg::GruPersistImages im = wimg::build_gru_persist_images(h->cfg, blob);
+  gi.scales = im.scales;
+#define X(T, name, count) TRY(upload_image(h, gi.name, im.name.data(), im.name.size() * sizeof(T)));
+  RV_GRU_PERSIST_IMAGES(X)
+#undef X
+  gi.built = true;
+  return RV_OK;
+}
+
 }  // namespace
 
 // Loading the library is the earliest point a C caller reaches: ask the HIP runtime for 16 hardware queues (the asynchronous calls keep up
@@ -2089,6 +2150,8 @@ int rv_load_weights(rv_handle h, const float* blob, size_t n_floats) {
   RV_WEIGHT_IMAGES(X)
 #undef X
   HIPCHK(h, hipStreamSynchronize(s));
+  h->gimg.built = false;
+  if (h->opt.gru_persist) TRY(build_gru_persist(h, blob));
   h->loaded = true;
   return RV_OK;
 }
@@ -2401,9 +2464,20 @@ int rv_set_option(rv_handle h, const char* key, int32_t value) {
     if (uncollected(h)) return fail(h, RV_ESTATE, "collect the calls in flight before setting weight_parts");
   }
   if (!strcmp(key, "one_part_kernels") && value != 0 && value != 1) return fail(h, RV_EINVAL, "one_part_kernels must be 0 or 1");
+  if (!strcmp(key, "gru_persistent")) {
+    if (value != 0 && value != 1) return fail(h, RV_EINVAL, "gru_persistent must be 0 or 1");
+    if (h->rnn != RV_RNN_BIGRU)
+      return fail(h, RV_EUNSUPPORTED, "gru_persistent is an option of a bigru handle: this one is bilstm, whose decode is persistent by default (option persistent_decode)");
+    if (h->cfg.dec_depth != 1)
+      return fail(h, RV_EUNSUPPORTED, "gru_persistent serves a bigru handle of one decoder cell: this one has decoder_depth %d, whose cells decode per step", h->cfg.dec_depth);
+    if (uncollected(h)) return fail(h, RV_ESTATE, "collect the calls in flight before setting gru_persistent");
+    // on: the images now, from the weights in force if there are any (else the next rv_load_weights builds them); off: nothing is freed
+    if (value == 1 && h->loaded && !h->gimg.built) TRY(build_gru_persist(h, nullptr));
+  }
   h->opt.gen++;                      // slab graphs captured under the old options are rebuilt on their next use
   if (!strcmp(key, "weight_parts")) h->opt.weight_parts = value;      // (in force from the next rv_load_weights)
   else if (!strcmp(key, "one_part_kernels")) h->opt.one_part = value;
+  else if (!strcmp(key, "gru_persistent")) h->opt.gru_persist = value;
   else if (!strcmp(key, "debug_taps")) h->opt.taps = value != 0;
   else if (!strcmp(key, "slab_graph")) h->opt.slab_graph = value != 0;
   else if (!strcmp(key, "coalesce")) {
@@ -2462,7 +2536,7 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     if (!cx->fact.lpersist) return fail(h, RV_ESTATE, "the projected memory is built for the persistent decode only (the last call ran the per-step kernels)");
     if (cx->fact.lmem2_stale) {   // the decode projected its chunks itself and stored nothing: the same product of that call's enc_out, now
       HIPCHK(h, hipSetDevice(h->cfg.device));
-      launch_gemm_mem_split(cx->enc_out, (int)(B * Tm), h->img.Wmp16, cx->mem2, cx->stream);
+      launch_gemm_mem_split(cx->enc_out, (int)(B * Tm), h->rnn == RV_RNN_BIGRU ? h->gimg.gWmp16 : h->img.Wmp16, cx->mem2, cx->stream);
       HIPCHK(h, hipStreamSynchronize(cx->stream));
       cx->fact.lmem2_stale = 0;
     }
@@ -2497,8 +2571,8 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     const FormLog* f = &cx->lforms;
     if (!strcmp(name, "kernel_form_list") && h->rnn == RV_RNN_BIGRU) {      // the list answers for the handle's family
       FormLog dec;
-      list_gru_forms(all); list_decode_forms(dec);
-      for (int i = 0; i < dec.n; ++i)      // (the attend kernels; no persistent GRU decode)
+      list_gru_forms(all); list_decode_forms(dec); list_decode_forms_gru(all);
+      for (int i = 0; i < dec.n; ++i)      // (the attend kernels; the persistent decode is k_dec_persist_gru's list)
         if (dec.row[i][0] != RV_K_DEC_PERSIST) all.add(dec.row[i][0], dec.row[i][1], dec.row[i][2], dec.row[i][3], dec.row[i][4]);
       f = &all;
     } else if (!strcmp(name, "kernel_form_list")) {

@@ -217,9 +217,9 @@ void build_lstm_encoder_extras(const RvConfig& c, const BlobLayout& lay, const f
 
 // [W_mem | A_c] [256][256]: column block 0 = W_mem (keys), column block 1 = rows 128..383 of the attention layer (its context part), so
 // that enc_out . Wmp = [keys | image of the values under the attention layer]; its split image; and the scales of both products
-void build_memory_images(const BlobLayout& lay, const float* blob, HostImages& im) {
+void build_memory_images(const BlobLayout& lay, const float* blob, std::vector<float>& wmp, std::vector<uint16_t>& wmp16,
+                         std::vector<uint16_t>& wkp16, ImageScales& sc) {
   const float *Wmem = blob + lay.W_mem, *Ac = blob + lay.W_att + (size_t)U * U;
-  std::vector<float>& wmp = im.Wmp;
   for (int k = 0; k < E; ++k)
     for (int n = 0; n < U; ++n) {
       wmp[(size_t)k * E + n] = Wmem[(size_t)k * U + n];
@@ -232,8 +232,8 @@ void build_memory_images(const BlobLayout& lay, const float* blob, HostImages& i
     for (int k = 0; k < E; ++k) cs += std::fabs((double)wmp[(size_t)k * E + n]);
     if (n < U) bk = std::max(bk, cs); else bu = std::max(bu, cs);
   }
-  im.scales.kscale = bound_scale(bk); im.scales.uscale = bound_scale(bu);
-  rv_pack_split_image(wmp.data(), E, 1, [](int cc) { return (size_t)cc; }, im.Wmp16.data());
+  sc.kscale = bound_scale(bk); sc.uscale = bound_scale(bu);
+  rv_pack_split_image(wmp.data(), E, 1, [](int cc) { return (size_t)cc; }, wmp16.data());
   // the same f16 parts of the W_mem half, for the decode's own projection (DecState::Wkp16): lane (i, kq) of key tile 2 ks + y takes
   // what lane (c % 16, kq) of column tile c / 16 holds, c = 32 ks + 8 (i / 4) + 4 y + i % 4 -- a permutation, no second rounding
   for (int st = 0; st < 8; ++st)
@@ -241,10 +241,41 @@ void build_memory_images(const BlobLayout& lay, const float* blob, HostImages& i
       for (int part = 0; part < 2; ++part)
         for (int ln = 0; ln < 64; ++ln) {
           const int i = ln & 15, q = ln >> 4, cc = 32 * (t8 >> 1) + 8 * (i >> 2) + 4 * (t8 & 1) + (i & 3);
-          memcpy(&im.Wkp16[((((size_t)st * 8 + t8) * 2 + part) * 64 + ln) * 8],
-                 &im.Wmp16[((((size_t)st * 16 + cc / 16) * 2 + part) * 64 + 16 * q + cc % 16) * 8], 8 * sizeof(uint16_t));
+          memcpy(&wkp16[((((size_t)st * 8 + t8) * 2 + part) * 64 + ln) * 8],
+                 &wmp16[((((size_t)st * 16 + cc / 16) * 2 + part) * 64 + 16 * q + cc % 16) * 8], 8 * sizeof(uint16_t));
         }
 }
+
+// A_h W_fc [128][V] (products in double): the h half of the folded output layer
+void fold_output_h(const float* Ah, const float* Wfc, int V, float* nh) {
+  for (int i = 0; i < U; ++i)
+    for (int v = 0; v < V; ++v) {
+      double acc = 0.0;
+      for (int j = 0; j < U; ++j) acc += (double)Ah[(size_t)i * U + j] * (double)Wfc[(size_t)j * V + v];
+      nh[(size_t)i * V + v] = (float)acc;
+    }
+}
+
+// The factor the f16 image of row k of [ctx' | h (| h_0)] carries: ctx' the scale of U', every h 2^14
+inline float input_factor(int k, float uscale) { return k < U ? uscale : 16384.f; }
+
+// The folded output layer [W_fc ; A_h W_fc] on the [ctx' | h] image (DecState::Wl16): rows divided by their input's factor (exact:
+// powers of two), columns >= V zero, one power-of-two scale for the tensor, k-step ks, part p
+struct OutputLayer {
+  const float *fcw, *nh;                    // W_fc [128][V], A_h W_fc [128][V]
+  int V;
+  float uscale;
+  float at(int k, int v) const { return v >= V ? 0.f : (k < U ? fcw[(size_t)k * V + v] : nh[(size_t)(k - U) * V + v]) / input_factor(k, uscale); }
+  float scale() const {
+    float ml = 0.f;
+    for (int k = 0; k < E; ++k)
+      for (int v = 0; v < V; ++v) ml = std::max(ml, std::fabs(at(k, v)));
+    return rv_column_scale(ml);
+  }
+  void pack(float Tl, uint16_t* img) const {
+    for (int ks = 0; ks < 8; ++ks) rv_write_fragment(img + ((size_t)ks * 2) * 512, 512, [&](int k, int n) { return at(32 * ks + k, n) * Tl; });
+  }
+};
 
 // One or two decoder cells: attention = h . A_h + ctx' (h = the top cell's output); its h part is folded into what consumes the attention
 // vector (products in double):
@@ -265,34 +296,23 @@ void build_folded_decoder(const RvConfig& c, const BlobLayout& lay, const ImageC
       w2[(size_t)(U + i) * G + n] = (float)acc;
       if (two) w2[(size_t)(2 * U + i) * G + n] = U0[(size_t)i * G + n];
     }
-  for (int i = 0; i < U; ++i)
-    for (int v = 0; v < V; ++v) {
-      double acc = 0.0;
-      for (int j = 0; j < U; ++j) acc += (double)Ah[(size_t)i * U + j] * (double)Wfc[(size_t)j * V + v];
-      nh[(size_t)i * V + v] = (float)acc;
-    }
+  fold_output_h(Ah, Wfc, V, nh.data());
   // the scales of the matrix-pipe images of both folded tensors (Wc16, Wl16): rows divided by the factor their input's f16 image
   // carries (exact: powers of two), then one power-of-two scale for the tensor
-  auto xs = [&](int k) { return k < U ? sc.uscale : 16384.f; };
+  auto xs = [&](int k) { return input_factor(k, sc.uscale); };
   float mx = 0.f;
   for (int k = 0; k < KR; ++k)
     for (int n = 0; n < G; ++n) mx = std::max(mx, std::fabs(w2[(size_t)k * G + n] / xs(k)));
   const float T = rv_column_scale(mx);
   std::vector<float> fcw(Wfc, Wfc + (size_t)U * V);      // W_fc, the output layer's upper half
-  auto wl = [&](int k, int v) -> float {                    // [W_fc ; A_h W_fc]; columns >= V are zero
-    if (v >= V) return 0.f;
-    return (k < U ? fcw[(size_t)k * V + v] : nh[(size_t)(k - U) * V + v]) / xs(k);
-  };
-  float ml = 0.f;
-  for (int k = 0; k < E; ++k)
-    for (int v = 0; v < V; ++v) ml = std::max(ml, std::fabs(wl(k, v)));
-  const float Tl = rv_column_scale(ml);
+  const OutputLayer out{fcw.data(), nh.data(), V, sc.uscale};
+  const float Tl = out.scale();
   if (one_part) {   // weight_parts 1: both folded tensors rounded to the first f16 part of those images, under the scales just taken
                     // (kept for the packing below), so that their fp32 images (Wcat2, Nh) carry the same numbers
     for (int k = 0; k < KR; ++k)
       for (int n = 0; n < G; ++n) w2[(size_t)k * G + n] = rv_round_to_first_part(w2[(size_t)k * G + n] / xs(k), T) * xs(k);
     for (int k = 0; k < E; ++k)
-      for (int v = 0; v < V; ++v) (k < U ? fcw[(size_t)k * V + v] : nh[(size_t)(k - U) * V + v]) = rv_round_to_first_part(wl(k, v), Tl) * xs(k);
+      for (int v = 0; v < V; ++v) (k < U ? fcw[(size_t)k * V + v] : nh[(size_t)(k - U) * V + v]) = rv_round_to_first_part(out.at(k, v), Tl) * xs(k);
   }
   if (!two) im.Wcat2 = w2;                                  // (the packed-FMA form of one cell)
   im.Nh = nh;
@@ -315,7 +335,7 @@ void build_folded_decoder(const RvConfig& c, const BlobLayout& lay, const ImageC
   // the output layer on the same [ctx' | h] image: logits = ctx' . W_fc + h . (A_h W_fc) + b_fc, k-step ks, part p
   sc.ldescale = 1.0f / Tl;
   im.Wl16.assign(cnt.Wl16, 0);
-  for (int ks = 0; ks < 8; ++ks) rv_write_fragment(im.Wl16.data() + ((size_t)ks * 2) * 512, 512, [&](int k, int n) { return wl(32 * ks + k, n) * Tl; });
+  out.pack(Tl, im.Wl16.data());
   if (one_part) { im.Wl16p1.assign(cnt.Wl16p1, 0); first_parts(im.Wl16.data(), 8, im.Wl16p1); }
   if (!two) {
     im.Wq16.assign(cnt.Wq16, 0);
@@ -324,6 +344,59 @@ void build_folded_decoder(const RvConfig& c, const BlobLayout& lay, const ImageC
 }
 
 }  // namespace
+
+// One GRU decoder cell (Keras, reset_after) for the persistent decode.  As build_folded_decoder, attention = h . A_h + ctx' is folded
+// into what consumes it, tile by tile: z and r take [ctx' | h] . [W_a ; U + A_h W_a]; the candidate's input half takes [ctx' | h] .
+// [W_a,h ; A_h W_a,h] and its recurrent half [0 ; U_h] alone, so that the reset gate multiplies h . U_h + b[1]_h and nothing else
+// (products in double).  The cell-independent images are build_memory_images' and the LSTM forms' output layer on the GRU blob.
+GruPersistImages build_gru_persist_images(const RvConfig& c, const float* blob) {
+  const BlobLayout lay(c, RV_RNN_BIGRU);
+  const int V = c.vocab, N = 3 * U;
+  GruPersistImages g;
+#define X(T, name, count) g.name.assign((count), 0);
+  RV_GRU_PERSIST_IMAGES(X)
+#undef X
+  ImageScales& sc = g.scales;
+  build_memory_images(lay, blob, g.gWmp, g.gWmp16, g.gWkp16, sc);
+  const float *W0 = blob + lay.dec[0].W, *Wa = W0 + (size_t)V * N, *Uk = blob + lay.dec[0].U, *b = blob + lay.dec[0].b;
+  const float *Ah = blob + lay.W_att, *Wfc = blob + lay.W_fc;
+  std::vector<float> w2((size_t)E * G, 0.f), nh((size_t)U * V, 0.f);
+  for (int i = 0; i < U; ++i)
+    for (int tile = 0; tile < 4; ++tile)
+      for (int n = 0; n < U; ++n) {
+        const int col = tile * U + n, src = std::min(tile, 2) * U + n;      // (the blob's gate columns: z, r, h)
+        w2[(size_t)i * G + col] = tile < 3 ? Wa[(size_t)i * N + src] : 0.f;
+        double acc = tile != 2 ? (double)Uk[(size_t)i * N + src] : 0.0;
+        if (tile < 3)
+          for (int j = 0; j < U; ++j) acc += (double)Ah[(size_t)i * U + j] * (double)Wa[(size_t)j * N + src];
+        w2[(size_t)(U + i) * G + col] = (float)acc;
+      }
+  fold_output_h(Ah, Wfc, V, nh.data());
+  // scales and fragments as build_folded_decoder takes them: rows divided by the factor their input's f16 image carries, one
+  // power-of-two scale per tensor
+  auto xs = [&](int k) { return input_factor(k, sc.uscale); };
+  float mx = 0.f;
+  for (int k = 0; k < E; ++k)
+    for (int n = 0; n < G; ++n) mx = std::max(mx, std::fabs(w2[(size_t)k * G + n] / xs(k)));
+  const float T = rv_column_scale(mx);
+  sc.cdescale = 1.0f / T;
+  pack_gate_pairs(E / 8, g.gWc16.data(), [&](int pr, int k, int n) { const int row = 32 * (pr >> 2) + k; return (w2[(size_t)row * G + n] / xs(row)) * T; });
+  const OutputLayer out{Wfc, nh.data(), V, sc.uscale};
+  const float Tl = out.scale();
+  sc.ldescale = 1.0f / Tl;
+  out.pack(Tl, g.gWl16.data());
+  sc.qdescale = std::ldexp(1.0f, -14) / pack_wq16(blob + lay.W_q, g.gWq16.data());
+  // the token table and the bias in the same four tiles: b[1]_h rides in the fourth tile's row, inside the reset product
+  for (int v = 0; v < V; ++v)
+    for (int n = 0; n < N; ++n) g.gWtok[(size_t)v * G + n] = W0[(size_t)v * N + n];
+  for (int n = 0; n < U; ++n) {
+    g.gbdec[n] = b[n] + b[N + n];
+    g.gbdec[U + n] = b[U + n] + b[N + U + n];
+    g.gbdec[2 * U + n] = b[2 * U + n];
+    g.gbdec[3 * U + n] = b[N + 2 * U + n];
+  }
+  return g;
+}
 
 HostImages build_weight_images(const RvConfig& c, int rnn, int weight_parts, const float* blob) {
   const BlobLayout lay(c, rnn);
@@ -368,7 +441,7 @@ HostImages build_weight_images(const RvConfig& c, int rnn, int weight_parts, con
       for (int n = 0; n < G; ++n) t[(size_t)n * E + k] = W[(size_t)k * G + n];
   }
   build_lstm_encoder_extras(c, lay, blob, im);
-  build_memory_images(lay, blob, im);
+  build_memory_images(lay, blob, im.Wmp, im.Wmp16, im.Wkp16, im.scales);
   if (c.dec_depth <= 2) build_folded_decoder(c, lay, cnt, weight_parts == 1, blob, im);
   return im;
 }

@@ -94,6 +94,29 @@ struct HostImages {
 // blob: BlobLayout(c, rnn).total floats, already rounded (round_blob_weights) where weight_parts is 1
 HostImages build_weight_images(const RvConfig& c, int rnn, int weight_parts, const float* blob);
 
+// The images of the persistent decode of a GRU handle (option gru_persistent; decode.hip: k_dec_persist_gru), apart from the table
+// above: a handle allocates and builds them only once that option is set.  One decoder cell.  The cell product's four column tiles of
+// 128 are z, r and the candidate's input and recurrent halves; with W_a = rows V.. of the cell's W [V + u, 3 u], U its recurrent kernel
+// and A_h, A_c the attention layer's h and context rows:
+//   X(type, name, elements)
+#define RV_GRU_PERSIST_IMAGES(X)                                                                                                        \
+  X(float, gWmp, (size_t)E * E)                       /* [W_mem | A_c] [256][256], as Wmp */                                            \
+  X(uint16_t, gWmp16, (size_t)2 * E * E + 2 * E)      /* ... as Wmp16 */                                                                \
+  X(uint16_t, gWkp16, (size_t)2 * E * U)              /* ... as Wkp16 */                                                                \
+  X(uint16_t, gWc16, (size_t)2 * E * 4 * U)           /* rows ctx': W_a,z | W_a,r | W_a,h | 0; rows h: U_z + A_h W_a,z | U_r + A_h W_a,r | A_h W_a,h | U_h; in Wc16's B-fragment order */ \
+  X(uint16_t, gWl16, (size_t)2 * E * 16)              /* [W_fc ; A_h W_fc], as Wl16 */                                                  \
+  X(uint16_t, gWq16, (size_t)2 * U * U)               /* Bahdanau's W_q, as Wq16 */                                                     \
+  X(float, gWtok, (size_t)MAX_VOCAB * 4 * U)          /* the token's W row in tiles z, r, candidate-input; zeros in the fourth: [V][512] */ \
+  X(float, gbdec, (size_t)4 * U)                      /* b[0] + b[1] for z and r, b[0]_h, b[1]_h: [512] */
+struct GruPersistImages {
+#define X(T, name, count) std::vector<T> name;
+  RV_GRU_PERSIST_IMAGES(X)
+#undef X
+  ImageScales scales;                       // all but c1descale
+};
+// blob: BlobLayout(c, RV_RNN_BIGRU).total floats; c.dec_depth == 1
+GruPersistImages build_gru_persist_images(const RvConfig& c, const float* blob);
+
 // The builders of the image families that share the fragment writer of split_image.h, one slot each (tests/kernels/wimg_dump.cpp)
 void pack_recurrent(const float* Uk, int g, uint16_t* img);        // Uk [128][128 g] -> [8 waves][g gates][4 k-steps][2 parts][64 lanes][8] + 128 g factors
 void pack_wh(const float* W, uint16_t* img);                       // W [256][512] -> [32 tiles][2 parts][8 k-steps][64 lanes][8] (low part x 2048) + 512 factors
