@@ -285,6 +285,40 @@ int rv_beam_search_submit_windows(rv_handle h, const int32_t* win, int32_t B, in
 int rv_beam_search_submit_windows_calls(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
                                         const uint8_t* lut, int32_t* ticket);
 
+/* Reads from raw signal: the events, both scaled tables and the window table of each read are made on the device from its int16 ADC
+ * samples -- what data_loader.prepare_windows makes on the host for an unlabelled read, with the event arrays bit
+ * for bit those of rv_detect_events on the same samples, the window table equal, and the scaled tables equal up to the summation order of
+ * the two fits (an f32 element may land on the neighbouring value; a zero stays zero).  Added without changing an existing entry point:
+ * RV_ABI_VERSION stays at 1.
+ *
+ *   rv_read_put_signals  signal[r]: n[r] samples of read r (NULL allowed where n[r] == 0), r < n_reads.  Uploads the batch, runs the
+ *                        kernels for all its reads on the handle's copy stream and returns when they are done: read_id[r], n_events[r],
+ *                        n_windows[r] (the last two may be NULL).  The reads are ordinary reads: the window calls and rv_read_drop work
+ *                        on them unchanged, and like rv_read_put the call is allowed while tickets are in flight.  Both scaled tables and
+ *                        the window table are made in every mode (the windows come from the events); a call reads those of its mode.
+ *                        n[r] == 0 gives a read without events and windows.  Refused, making no read: n[r] > 2^22 (RV_EUNSUPPORTED: the
+ *                        exactness of the running sums in fp64 is argued up to there), window lengths outside 1 <= w1 <= w2, stride,
+ *                        max_raw_len or max_event_len < 1 (RV_EINVAL), more reads than the 1,024 slots have room for (RV_ESTATE).
+ *                        Scan and t-statistic scratch is the handle's, reused from batch to batch and grown like the read buffers
+ *                        ("read_stats" counts its allocations too).
+ *   rv_read_fetch        copies one table of a read to the host: dst holds `cap` BYTES, RV_EINVAL (with the size needed in the message,
+ *                        nothing copied) when the table is larger.  RV_FETCH_WINDOWS i32 [n_windows,4] = (raw_start,
+ *                        raw_len, event_start, event_len), the columns a window call takes behind the read_id; RV_FETCH_RAW_SC f32
+ *                        [n]; RV_FETCH_EVENTS_SC f32 [n_events,5]; RV_FETCH_EVENT_START / _LENGTH i64 [n_events]; RV_FETCH_EVENT_MEAN /
+ *                        _STDV f64 [n_events].  The two scaled tables can be fetched from any read the handle owns; the others only
+ *                        from a read put by rv_read_put_signals (else RV_ESTATE). */
+typedef struct RvSignalPrep {
+  int32_t window_length1, window_length2;   /* the detector's short and long window (data_loader: 6, 9) */
+  double threshold1, threshold2, peak_height;
+  int32_t stride;                           /* events between the starts of two chunks */
+  int32_t max_raw_len, max_event_len;       /* a chunk's windows: at most this many samples / events */
+} RvSignalPrep;
+enum { RV_FETCH_WINDOWS = 0, RV_FETCH_RAW_SC = 1, RV_FETCH_EVENTS_SC = 2, RV_FETCH_EVENT_START = 3, RV_FETCH_EVENT_LENGTH = 4,
+       RV_FETCH_EVENT_MEAN = 5, RV_FETCH_EVENT_STDV = 6 };
+int rv_read_put_signals(rv_handle h, int32_t n_reads, const int16_t* const* signal, const size_t* n, const RvSignalPrep* prep,
+                        int32_t* read_id, int32_t* n_events, int32_t* n_windows);
+int rv_read_fetch(rv_handle h, int32_t read_id, int32_t what, void* dst, size_t cap);
+
 /* Basecaller.greedy_search_prediction (basecaller.py:317-330): tokens = sample_id [B, L-1],
  * logits = rnn_output [B, L-1, vocab]; columns >= S are pad_token / 0. */
 int rv_greedy_search(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r,

@@ -32,6 +32,17 @@ class CRvScore(ctypes.Structure):
     _fields_ = [("nll", c_void_p), ("nll_sum", c_void_p), ("n_labels", c_void_p), ("n_match", c_void_p), ("n_counted", c_void_p)]
 
 
+class CRvSignalPrep(ctypes.Structure):
+    """RvSignalPrep (include/ravvent_hip.h): the detector's and the chunker's parameters of rv_read_put_signals."""
+    _fields_ = [("window_length1", c_int32), ("window_length2", c_int32), ("threshold1", c_double), ("threshold2", c_double),
+                ("peak_height", c_double), ("stride", c_int32), ("max_raw_len", c_int32), ("max_event_len", c_int32)]
+
+
+# rv_read_fetch: which table
+RV_FETCH_WINDOWS, RV_FETCH_RAW_SC, RV_FETCH_EVENTS_SC, RV_FETCH_EVENT_START, RV_FETCH_EVENT_LENGTH, RV_FETCH_EVENT_MEAN, \
+    RV_FETCH_EVENT_STDV = range(7)
+
+
 # every symbol include/ravvent_hip.h declares: (name, restype, argtypes)
 _F, _I = POINTER(c_float), POINTER(c_int32)
 _B = POINTER(CRvBeams)
@@ -67,6 +78,8 @@ SYMBOLS = [
     ("rv_read_put", c_int32, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, _I]),
     ("rv_read_put_dev", c_int32, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, _I]),
     ("rv_read_drop", c_int32, [c_void_p, c_int32]),
+    ("rv_read_put_signals", c_int32, [c_void_p, c_int32, c_void_p, c_void_p, POINTER(CRvSignalPrep), c_void_p, c_void_p, c_void_p]),
+    ("rv_read_fetch", c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_size_t]),
     ("rv_beam_search_windows", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
     ("rv_beam_search_windows_dev", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
     ("rv_beam_search_windows_calls", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, _I]),

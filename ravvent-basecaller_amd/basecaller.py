@@ -62,8 +62,24 @@ class BasecallResult:
 class ReadHandle:
     """A read on the device (Basecaller.put_read): `read_id` for the first column of a window table, `drop()` when done."""
 
-    def __init__(self, basecaller, read_id, n_raw, n_event, keep=None):
+    def __init__(self, basecaller, read_id, n_raw, n_event, keep=None, windows=None):
         self._bc, self.read_id, self.n_raw, self.n_event, self._keep = basecaller, int(read_id), n_raw, n_event, keep
+        self.windows = windows      # i32 [n,4], the read's own window table: set by Basecaller.put_signal(s), else None
+
+    def fetch(self, what: str) -> np.ndarray:
+        """A table of the read, copied back (rv_read_fetch): 'windows' i32 [n,4], 'raw_sc' f32 [N], 'events_sc' f32 [E,5], and of a
+        read put from its signal 'start' / 'length' i64 [E], 'mean' / 'stdv' f64 [E]."""
+        code, dtype, shape = {"windows": (_capi.RV_FETCH_WINDOWS, np.int32, (len(self.windows) if self.windows is not None else 0, 4)),
+                              "raw_sc": (_capi.RV_FETCH_RAW_SC, np.float32, (self.n_raw,)),
+                              "events_sc": (_capi.RV_FETCH_EVENTS_SC, np.float32, (self.n_event, 5)),
+                              "start": (_capi.RV_FETCH_EVENT_START, np.int64, (self.n_event,)),
+                              "length": (_capi.RV_FETCH_EVENT_LENGTH, np.int64, (self.n_event,)),
+                              "mean": (_capi.RV_FETCH_EVENT_MEAN, np.float64, (self.n_event,)),
+                              "stdv": (_capi.RV_FETCH_EVENT_STDV, np.float64, (self.n_event,))}[what]
+        out = np.empty(shape, dtype)
+        self._bc._check(self._bc._lib.rv_read_fetch(self._bc._h, self.read_id, code, out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
+                        "rv_read_fetch")
+        return out
 
     def table(self, windows) -> np.ndarray:
         """windows i32 [n,4] (data_loader.prepare_windows) -> the [n,5] table of the window calls, this read's id in column 0."""
@@ -657,6 +673,59 @@ class Basecaller:
             self._check(self._lib.rv_read_put(self._h, ptr(r), n_raw, ptr(e), n_ev, ctypes.byref(rid)), "rv_read_put")
         return ReadHandle(self, rid.value, n_raw, n_ev, (r, e) if on_dev else None)
 
+    @staticmethod
+    def _signal_int16(signal) -> np.ndarray:
+        """A signal as the device path takes it: integer ADC counts that fit int16.  Anything else is refused, never rounded."""
+        x = np.asarray(signal)
+        if x.ndim != 1:
+            x = x.reshape(-1)
+        if x.dtype == np.int16:
+            return np.ascontiguousarray(x)
+        if x.dtype.kind not in "iuf" or (x.dtype.kind == "f" and not (np.isfinite(x).all() and (x == np.rint(x)).all())):
+            raise ValueError("device preparation takes integer ADC samples; this signal is not integer-valued: use the host path "
+                             "(basecall(..., device_prep=False), data_loader.prepare_windows)")
+        if x.size and (x.min() < -32768 or x.max() > 32767):
+            raise ValueError("device preparation takes samples that fit int16; this signal does not: use the host path "
+                             "(basecall(..., device_prep=False), data_loader.prepare_windows)")
+        return np.ascontiguousarray(x.astype(np.int16))
+
+    def put_signals(self, signals, stride=6, max_raw_len=None, max_event_len=None, detector=None):
+        """Reads from their raw signals, prepared on the device (rv_read_put_signals): one upload of the int16 samples, then the
+        events, both scaled tables and the window table of every read are made by kernels -> list of ReadHandle, each with
+        `.windows` (i32 [n,4], what `data_loader.prepare_windows` gives for the unlabelled read) ready for `.table()`.
+        detector: an `EventDetector` for other parameters than the chunker's (windows 6 / 9).  ValueError for a signal that is not
+        integer-valued or does not fit int16."""
+        from .event_detection import EventDetector
+        xs = [self._signal_int16(sig) for sig in signals]
+        R = len(xs)
+        if R == 0:
+            return []
+        dp = (detector or EventDetector(window_length1=_dl.ED_WINDOW_LENGTH_1, window_length2=_dl.ED_WINDOW_LENGTH_2)).params
+        T_r = min(_dl.MAX_RAW_LEN, self.cfg.max_raw_len) if max_raw_len is None else int(max_raw_len)
+        T_e = min(_dl.MAX_EVENT_LEN, self.cfg.max_event_len) if max_event_len is None else int(max_event_len)
+        prep = _capi.CRvSignalPrep(int(dp["window_length1"]), int(dp["window_length2"]), float(dp["threshold1"]), float(dp["threshold2"]),
+                                   float(dp["peak_height"]), int(stride), T_r, T_e)
+        ptrs = (ctypes.c_void_p * R)(*[x.ctypes.data if x.size else None for x in xs])
+        lens = (ctypes.c_size_t * R)(*[int(x.size) for x in xs])
+        ids, nev, nwin = np.full(R, -1, np.int32), np.zeros(R, np.int32), np.zeros(R, np.int32)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self._lib.rv_read_put_signals(self._h, R, ptrs, lens, ctypes.byref(prep), p(ids), p(nev), p(nwin)), "rv_read_put_signals")
+        handles = [ReadHandle(self, int(ids[r]), int(xs[r].size), int(nev[r])) for r in range(R)]
+        try:
+            for r, h in enumerate(handles):
+                h.windows = np.empty((int(nwin[r]), 4), np.int32)
+                if nwin[r]:
+                    h.windows = h.fetch("windows")
+        except Exception:
+            for h in handles:
+                h.drop()
+            raise
+        return handles
+
+    def put_signal(self, signal, **kwargs):
+        """`put_signals` of one read -> ReadHandle."""
+        return self.put_signals([signal], **kwargs)[0]
+
     def _window_table(self, windows, T_r, T_e):
         w = np.ascontiguousarray(np.asarray(windows, np.int32))
         if w.ndim != 2 or w.shape[1] != 5:
@@ -746,34 +815,40 @@ class Basecaller:
             bases[a:b] = bs; probs[a:b] = pr; lens[a:b] = ln
         return bases, probs, lens
 
-    def basecall(self, signal, stride=6, beam_width=5, max_output_len=None, chunk_size=1024):
+    def basecall(self, signal, stride=6, beam_width=5, max_output_len=None, chunk_size=1024, device_prep=False):
         """An unlabelled read's signal -> BasecallResult (seq, probs, qualities, chunks_num, to_fastq): `prepare_windows` without
         labels, `put_read`, window slabs of `chunk_size` chunks streamed with the fused post-processing, the C++ merger, drop.
-        max_output_len None: the handle's."""
-        return self.basecall_many([signal], stride, beam_width, max_output_len, chunk_size)[0]
+        max_output_len None: the handle's.  device_prep: see `basecall_many`."""
+        return self.basecall_many([signal], stride, beam_width, max_output_len, chunk_size, device_prep)[0]
 
-    def basecall_many(self, signals, stride=6, beam_width=5, max_output_len=None, chunk_size=1024):
+    def basecall_many(self, signals, stride=6, beam_width=5, max_output_len=None, chunk_size=1024, device_prep=False):
         """`basecall` of several reads through shared slabs: the windows of all reads are queued into full slabs (a slab's rows may
-        name different reads) and each read is stitched from its own rows -> list of BasecallResult, equal to one `basecall` each."""
+        name different reads) and each read is stitched from its own rows -> list of BasecallResult, equal to one `basecall` each.
+        device_prep True: events, scaling and windows are made on the device from the int16 samples of all reads at once
+        (`put_signals`) instead of read by read on the host; integer signals only (ValueError otherwise)."""
         from . import merger as _merger
         L = self.cfg.max_output_len if max_output_len is None else _as_int(max_output_len)
         T_r, T_e = min(_dl.MAX_RAW_LEN, self.cfg.max_raw_len), min(_dl.MAX_EVENT_LEN, self.cfg.max_event_len)
-        reads, handles = [], []
+        windows, handles = [], []
         try:
-            for sig in signals:
-                rw = _dl.prepare_windows(sig, stride=stride, max_raw_len=T_r, max_event_len=T_e)
-                reads.append(rw)
-                handles.append(self.put_read(rw.raw_sc, rw.events_sc))
-            n = [len(rw) for rw in reads]
+            if device_prep:
+                handles = self.put_signals(list(signals), stride=stride, max_raw_len=T_r, max_event_len=T_e)
+                windows = [h.windows for h in handles]
+            else:
+                for sig in signals:
+                    rw = _dl.prepare_windows(sig, stride=stride, max_raw_len=T_r, max_event_len=T_e)
+                    windows.append(rw.windows)
+                    handles.append(self.put_read(rw.raw_sc, rw.events_sc))
+            n = [int(w.shape[0]) for w in windows]
             off = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
-            table = (np.concatenate([h.table(rw.windows) for h, rw in zip(handles, reads)]) if reads else np.zeros((0, 5), np.int32))
+            table = (np.concatenate([h.table(w) for h, w in zip(handles, windows)]) if windows else np.zeros((0, 5), np.int32))
             bases, probs, lens = self._stream_window_calls(table, beam_width, L, int(chunk_size), T_r, T_e)
         finally:
             for h in handles:
                 h.drop()
         mg = _merger.Merger()
         out = []
-        for i in range(len(reads)):
+        for i in range(len(windows)):
             a, b = int(off[i]), int(off[i + 1])
             seq, pr = mg.merge_arrays(bases[a:b], probs[a:b], lens[a:b]) if b > a else ("", np.zeros(0, np.float32))
             out.append(BasecallResult(seq, pr, n[i]))

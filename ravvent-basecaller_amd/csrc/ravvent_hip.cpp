@@ -5,6 +5,7 @@
 #include "../../include/ravvent_hip.h"
 #include "common.h"
 #include "weight_images.h"
+#include "signal_prep.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -136,6 +137,25 @@ struct Read {
   float* pin = nullptr; size_t pin_cap = 0;                 // pinned staging of the upload: the caller's buffers are free when the put returns
   bool live = false, owned = false, used = false;
   int users = 0, id = -1;
+  // a read made from its signal (rv_read_put_signals) also keeps its event arrays [n_ev] and its window table [n_win,4] for rv_read_fetch
+  bool prepped = false;
+  int64_t *d_est = nullptr, *d_eln = nullptr;
+  double *d_emu = nullptr, *d_esd = nullptr;
+  int32_t* d_win = nullptr;
+  size_t cap_evd = 0, cap_win = 0, n_win = 0;               // cap_evd: events the four arrays hold; cap_win: window rows
+};
+
+// The handle's scratch of rv_read_put_signals, reused from batch to batch: per sample (cap_x), per tile (cap_tiles), per read (cap_reads)
+struct SignalScratch {
+  int16_t *d_x = nullptr, *pin_x = nullptr;
+  double *ps = nullptr, *pq = nullptr, *t1 = nullptr, *t2 = nullptr;
+  uint2* bounds = nullptr;
+  long long* tile_sums = nullptr;
+  double* var_part = nullptr;
+  SpRead *d_reads = nullptr, *pin_reads = nullptr;
+  int *d_cnt = nullptr, *pin_cnt = nullptr;                 // [2][cap_reads]: events, windows
+  double* fit = nullptr;
+  size_t cap_x = 0, cap_tiles = 0, cap_reads = 0;
 };
 
 // What a recording needs beyond the call, resolved once before enqueue() (begin_all_beams, begin_forced, launch_group)
@@ -217,6 +237,7 @@ struct RvContext {
   long long win_expands = 0;                // ... and launches of k_expand_windows
   int read_gen = 0;
   std::map<int, std::vector<int>> ticket_reads;
+  SignalScratch sp;                         // rv_read_put_signals
 };
 
 namespace {
@@ -1954,11 +1975,229 @@ int put_read(RvContext* h, const float* raw, size_t n_raw, const float* event, s
     HIPCHK(h, hipEventRecord(h->ev_put, h->copy_stream));
     r.used = true;
   }
-  r.n_raw = n_raw; r.n_ev = n_event; r.live = true; r.users = 0;
+  r.n_raw = n_raw; r.n_ev = n_event; r.live = true; r.users = 0; r.prepped = false; r.n_win = 0;
   h->read_gen = (h->read_gen + 1) & 0xFFFFF;
   r.id = (h->read_gen << 10) | slot;
   h->read_puts += 1;
   *read_id = r.id;
+  return RV_OK;
+}
+
+// ---- reads from raw signal (rv_read_put_signals; kernels: signal_prep.hip)
+// A device or pinned buffer of the signal path that only grows; device allocations count as the reads' do ("read_stats")
+template <class T>
+int sp_grow(RvContext* h, T** p, size_t* cap, size_t need, bool pinned = false) {
+  if (need <= *cap && *p) return RV_OK;
+  if (*p) { if (pinned) hipHostFree(*p); else hipFree(*p); *p = nullptr; *cap = 0; }
+  const size_t bytes = std::max<size_t>(need, 1) * sizeof(T);
+  const hipError_t e = pinned ? hipHostMalloc((void**)p, bytes, hipHostMallocDefault) : hipMalloc((void**)p, bytes);
+  if (e != hipSuccess) { *p = nullptr; return fail(h, RV_ENOMEM, "%s(%zu bytes) failed for signal preparation", pinned ? "hipHostMalloc" : "hipMalloc", bytes); }
+  *cap = need;
+  if (!pinned) h->read_allocs += 1;
+  return RV_OK;
+}
+
+int put_signals(RvContext* h, int n_reads, const int16_t* const* signal, const size_t* n, const RvSignalPrep* prep, int32_t* read_id,
+                int32_t* n_events, int32_t* n_windows) {
+  if (!h) return RV_EINVAL;
+  if (!prep || !read_id || n_reads < 0 || (n_reads > 0 && (!signal || !n))) return fail(h, RV_EINVAL, "rv_read_put_signals: null argument or negative n_reads");
+  for (int r = 0; r < n_reads; ++r) { read_id[r] = -1; if (n_events) n_events[r] = 0; if (n_windows) n_windows[r] = 0; }
+  const RvSignalPrep& q = *prep;
+  if (q.window_length1 < 1 || q.window_length2 < q.window_length1 || q.window_length2 > (1 << 20))
+    return fail(h, RV_EINVAL, "window lengths (%d, %d): 1 <= window_length1 <= window_length2 is needed", q.window_length1, q.window_length2);
+  if (q.stride < 1) return fail(h, RV_EINVAL, "stride %d < 1", q.stride);
+  if (q.max_raw_len < 1 || q.max_event_len < 1) return fail(h, RV_EINVAL, "max_raw_len %d / max_event_len %d < 1", q.max_raw_len, q.max_event_len);
+  for (int r = 0; r < n_reads; ++r) {
+    if (n[r] > (size_t)SP_MAX_SAMPLES)
+      return fail(h, RV_EUNSUPPORTED, "read %d has %zu samples; device preparation takes up to %d (2^22): beyond that the running sums of x^2 are "
+                  "no longer exact in fp64, which its bit equality with the host detector rests on -- use the host path (rv_read_put)", r, n[r], SP_MAX_SAMPLES);
+    if (n[r] > 0 && !signal[r]) return fail(h, RV_EINVAL, "read %d: null signal with %zu samples", r, n[r]);
+  }
+  int alive = 0;
+  for (const Read& r : h->reads) alive += r.live ? 1 : 0;
+  if (alive + n_reads > RV_READ_SLOTS)
+    return fail(h, RV_ESTATE, "%d reads are alive and %d more were put: at most %d at once, drop some first", alive, n_reads, RV_READ_SLOTS);
+  if (n_reads == 0) return RV_OK;
+
+  const RvConfig& c = h->cfg;
+  HIPCHK(h, hipSetDevice(c.device));
+  if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+  if (!h->ev_put) HIPCHK(h, hipEventCreateWithFlags(&h->ev_put, hipEventDisableTiming));
+  hipStream_t s = h->copy_stream;
+  SignalScratch& sp = h->sp;
+
+  // the batch's layout: a read takes n + 1 entries of the per-sample arrays (rounded up to 8) and ceil(n / SP_TILE) tiles
+  std::vector<SpRead> rd((size_t)n_reads, SpRead{});
+  size_t total = 0; int tiles = 0, max_tiles = 0;
+  for (int r = 0; r < n_reads; ++r) {
+    rd[r].off = (long long)total; rd[r].n = (int)n[r]; rd[r].tile0 = tiles; rd[r].ntile = (int)((n[r] + SP_TILE - 1) / SP_TILE);
+    total += (n[r] + 1 + 7) / 8 * 8; tiles += rd[r].ntile; max_tiles = std::max(max_tiles, rd[r].ntile);
+  }
+  if (total > sp.cap_x) {      // (a group of buffers grows together; a failure leaves its capacity at 0, so that the next call starts over)
+    const size_t old = sp.cap_x;
+    size_t cap;
+    sp.cap_x = 0;
+    cap = old; TRY(sp_grow(h, &sp.d_x, &cap, total));
+    cap = old; TRY(sp_grow(h, &sp.pin_x, &cap, total, true));
+    cap = old; TRY(sp_grow(h, &sp.ps, &cap, total));
+    cap = old; TRY(sp_grow(h, &sp.pq, &cap, total));
+    cap = old; TRY(sp_grow(h, &sp.t1, &cap, total));
+    cap = old; TRY(sp_grow(h, &sp.t2, &cap, total));
+    cap = old; TRY(sp_grow(h, &sp.bounds, &cap, total));
+    sp.cap_x = total;
+  }
+  if ((size_t)tiles > sp.cap_tiles || !sp.tile_sums) {
+    const size_t old = sp.cap_tiles;
+    size_t cap;
+    sp.cap_tiles = 0;
+    cap = old; TRY(sp_grow(h, &sp.tile_sums, &cap, 2 * (size_t)tiles));
+    cap = old; TRY(sp_grow(h, &sp.var_part, &cap, (size_t)tiles));
+    sp.cap_tiles = (size_t)tiles;
+  }
+  if ((size_t)n_reads > sp.cap_reads) {
+    const size_t old = sp.cap_reads;
+    size_t cap;
+    sp.cap_reads = 0;
+    cap = old; TRY(sp_grow(h, &sp.d_reads, &cap, (size_t)n_reads));
+    cap = old; TRY(sp_grow(h, &sp.pin_reads, &cap, (size_t)n_reads, true));
+    cap = old; TRY(sp_grow(h, &sp.d_cnt, &cap, 2 * (size_t)n_reads));
+    cap = old; TRY(sp_grow(h, &sp.pin_cnt, &cap, 2 * (size_t)n_reads, true));
+    cap = old; TRY(sp_grow(h, &sp.fit, &cap, (size_t)SP_FIT * n_reads));
+    sp.cap_reads = (size_t)n_reads;
+  }
+  const SpScratch sc{sp.d_x, sp.ps, sp.pq, sp.t1, sp.t2, sp.bounds, sp.tile_sums, sp.var_part, sp.d_cnt, sp.d_cnt + n_reads, sp.fit};
+  const SpParams pr{q.window_length1, q.window_length2, q.threshold1, q.threshold2, q.peak_height, q.stride, q.max_raw_len, q.max_event_len};
+
+  // per-stage device times under option "profile" (scopes "sp_*")
+  struct Stage { const char* name; hipEvent_t a, b; };
+  std::vector<Stage> stages;
+  const bool prof = h->opt.profile != 0;
+  auto stage = [&](const char* name, auto&& body) {
+    hipEvent_t a = nullptr, b = nullptr;
+    if (prof) { hipEventCreate(&a); hipEventCreate(&b); hipEventRecord(a, s); }
+    body();
+    if (prof) { hipEventRecord(b, s); stages.push_back({name, a, b}); }
+  };
+  auto drain = [&]() {
+    for (Stage& g : stages) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, g.a, g.b) == hipSuccess) { ProfEntry& e = h->prof[g.name]; e.ms += ms; e.n += 1; }
+      hipEventDestroy(g.a); hipEventDestroy(g.b);
+    }
+    stages.clear();
+  };
+
+  // the slots: a dropped read whose sample buffer holds this one (the smallest such), else any dropped one, else a new one.  Taken now,
+  // given back if anything below fails: the call makes all its reads or none
+  std::vector<int> slots;
+  auto give_back = [&](int code) { for (int sl : slots) h->reads[sl].live = false; drain(); return code; };
+#define SPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return give_back(fail(h, RV_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__)); } while (0)
+#define SPTRY(x) do { int r_ = (x); if (r_ != RV_OK) return give_back(r_); } while (0)
+  for (int r = 0; r < n_reads; ++r) {
+    int slot = -1;
+    for (size_t i = 0; i < h->reads.size(); ++i) {
+      const Read& x = h->reads[i];
+      if (x.live || !x.owned || x.cap_raw < n[r]) continue;
+      if (slot < 0 || x.cap_raw < h->reads[slot].cap_raw) slot = (int)i;
+    }
+    for (size_t i = 0; i < h->reads.size() && slot < 0; ++i) if (!h->reads[i].live && !h->reads[i].owned) slot = (int)i;
+    for (size_t i = 0; i < h->reads.size() && slot < 0; ++i) if (!h->reads[i].live) slot = (int)i;
+    if (slot < 0) { h->reads.emplace_back(); slot = (int)h->reads.size() - 1; }      // (room for it: checked above)
+    Read& x = h->reads[slot];
+    if (!x.owned) { x.d_raw = x.d_ev = nullptr; x.cap_raw = x.cap_ev = 0; x.owned = true; }
+    x.live = true; x.users = 0;
+    slots.push_back(slot);
+  }
+
+  for (int r = 0; r < n_reads; ++r) if (n[r]) memcpy(sp.pin_x + rd[r].off, signal[r], n[r] * sizeof(int16_t));
+  memcpy(sp.pin_reads, rd.data(), (size_t)n_reads * sizeof(SpRead));
+  hipError_t up = hipSuccess;
+  stage("sp_upload", [&]() {
+    up = hipMemcpyAsync(sp.d_x, sp.pin_x, total * sizeof(int16_t), hipMemcpyHostToDevice, s);
+    if (up == hipSuccess) up = hipMemcpyAsync(sp.d_reads, sp.pin_reads, (size_t)n_reads * sizeof(SpRead), hipMemcpyHostToDevice, s);
+    if (up == hipSuccess) up = hipMemsetAsync(sp.d_cnt, 0, 2 * (size_t)n_reads * sizeof(int), s);
+  });
+  SPCHK(up);
+  stage("sp_scan", [&]() { sp_launch_scan(sp.d_reads, n_reads, max_tiles, sc, s); });
+  stage("sp_tstat", [&]() { sp_launch_tstat(sp.d_reads, n_reads, max_tiles, sc, pr, s); });
+  stage("sp_peaks", [&]() { sp_launch_peaks(sp.d_reads, n_reads, sc, pr, s); });
+  SPCHK(hipGetLastError());
+  SPCHK(hipMemcpyAsync(sp.pin_cnt, sp.d_cnt, (size_t)n_reads * sizeof(int), hipMemcpyDeviceToHost, s));
+  SPCHK(hipStreamSynchronize(s));
+
+  // the event counts are known: the reads' own tables
+  int max_ev = 0, max_win = 0;
+  for (int r = 0; r < n_reads; ++r) {
+    Read& x = h->reads[slots[r]];
+    const size_t E = (size_t)sp.pin_cnt[r], K = (E + (size_t)q.stride - 1) / (size_t)q.stride;
+    SPTRY(sp_grow(h, &x.d_raw, &x.cap_raw, n[r]));
+    SPTRY(sp_grow(h, &x.d_ev, &x.cap_ev, E * 5));
+    if (E > x.cap_evd || !x.d_est) {
+      const size_t old = x.cap_evd;
+      size_t cap;
+      x.cap_evd = 0;
+      cap = old; SPTRY(sp_grow(h, &x.d_est, &cap, E));
+      cap = old; SPTRY(sp_grow(h, &x.d_eln, &cap, E));
+      cap = old; SPTRY(sp_grow(h, &x.d_emu, &cap, E));
+      cap = old; SPTRY(sp_grow(h, &x.d_esd, &cap, E));
+      x.cap_evd = E;
+    }
+    SPTRY(sp_grow(h, &x.d_win, &x.cap_win, K * 4));
+    SpRead& g = sp.pin_reads[r];
+    g.n_ev = (int)E; g.ev_start = x.d_est; g.ev_len = x.d_eln; g.ev_mean = x.d_emu; g.ev_stdv = x.d_esd;
+    g.raw_sc = x.d_raw; g.ev_sc = x.d_ev; g.win = x.d_win;
+    max_ev = std::max(max_ev, (int)E); max_win = std::max(max_win, (int)K);
+  }
+  SPCHK(hipMemcpyAsync(sp.d_reads, sp.pin_reads, (size_t)n_reads * sizeof(SpRead), hipMemcpyHostToDevice, s));
+  stage("sp_events", [&]() { sp_launch_events(sp.d_reads, n_reads, max_ev, sc, pr, s); });
+  stage("sp_fit", [&]() { sp_launch_fit(sp.d_reads, n_reads, sc, s); });
+  stage("sp_raw_scale", [&]() { sp_launch_raw_scale(sp.d_reads, n_reads, max_tiles, sc, s); });
+  stage("sp_windows", [&]() { sp_launch_windows(sp.d_reads, n_reads, max_win, sc, pr, s); });
+  SPCHK(hipGetLastError());
+  SPCHK(hipMemcpyAsync(sp.pin_cnt + n_reads, sp.d_cnt + n_reads, (size_t)n_reads * sizeof(int), hipMemcpyDeviceToHost, s));
+  SPCHK(hipEventRecord(h->ev_put, s));
+  SPCHK(hipStreamSynchronize(s));
+#undef SPCHK
+#undef SPTRY
+  drain();
+
+  for (int r = 0; r < n_reads; ++r) {
+    Read& x = h->reads[slots[r]];
+    x.n_raw = n[r]; x.n_ev = (size_t)sp.pin_cnt[r]; x.n_win = (size_t)sp.pin_cnt[n_reads + r]; x.prepped = true; x.used = true;
+    h->read_gen = (h->read_gen + 1) & 0xFFFFF;
+    x.id = (h->read_gen << 10) | slots[r];
+    h->read_puts += 1;
+    read_id[r] = x.id;
+    if (n_events) n_events[r] = (int32_t)x.n_ev;
+    if (n_windows) n_windows[r] = (int32_t)x.n_win;
+  }
+  return RV_OK;
+}
+
+int fetch_read(RvContext* h, int read_id, int what, void* dst, size_t cap) {
+  if (!h) return RV_EINVAL;
+  const Read* r = find_read(h, read_id);
+  if (!r) return fail(h, RV_EINVAL, "unknown read_id %d", read_id);
+  if (!r->owned) return fail(h, RV_ESTATE, "read %d lives in the caller's device buffers (rv_read_put_dev): nothing to fetch", read_id);
+  const void* src = nullptr; size_t bytes = 0;
+  switch (what) {
+    case RV_FETCH_RAW_SC: src = r->d_raw; bytes = r->n_raw * sizeof(float); break;
+    case RV_FETCH_EVENTS_SC: src = r->d_ev; bytes = r->n_ev * 5 * sizeof(float); break;
+    case RV_FETCH_WINDOWS: src = r->d_win; bytes = r->n_win * 4 * sizeof(int32_t); break;
+    case RV_FETCH_EVENT_START: src = r->d_est; bytes = r->n_ev * sizeof(int64_t); break;
+    case RV_FETCH_EVENT_LENGTH: src = r->d_eln; bytes = r->n_ev * sizeof(int64_t); break;
+    case RV_FETCH_EVENT_MEAN: src = r->d_emu; bytes = r->n_ev * sizeof(double); break;
+    case RV_FETCH_EVENT_STDV: src = r->d_esd; bytes = r->n_ev * sizeof(double); break;
+    default: return fail(h, RV_EINVAL, "rv_read_fetch: unknown table %d", what);
+  }
+  if (what != RV_FETCH_RAW_SC && what != RV_FETCH_EVENTS_SC && !r->prepped)
+    return fail(h, RV_ESTATE, "read %d was not made by rv_read_put_signals: it has no window table and no event arrays", read_id);
+  if (bytes > cap) return fail(h, RV_EINVAL, "rv_read_fetch: the table takes %zu bytes, dst holds %zu", bytes, cap);
+  if (bytes == 0) return RV_OK;
+  if (!dst) return fail(h, RV_EINVAL, "rv_read_fetch: null dst");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (h->copy_stream) HIPCHK(h, hipStreamSynchronize(h->copy_stream));      // (a read put by rv_read_put: its upload is behind this)
+  HIPCHK(h, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
   return RV_OK;
 }
 
@@ -2108,7 +2347,17 @@ void rv_destroy(rv_handle h) {
   for (Group* g : h->groups) destroy_group(g);
   if (!h->slabs.empty()) destroy_slab(h->slabs[0]);
   for (void* p : h->allocs) hipFree(p);      // (behind every stream that read the weights)
-  for (Read& r : h->reads) { if (r.owned) { if (r.d_raw) hipFree(r.d_raw); if (r.d_ev) hipFree(r.d_ev); } if (r.pin) hipHostFree(r.pin); }
+  for (Read& r : h->reads) {
+    if (r.owned) { if (r.d_raw) hipFree(r.d_raw); if (r.d_ev) hipFree(r.d_ev); }
+    if (r.pin) hipHostFree(r.pin);
+    for (void* q : {(void*)r.d_est, (void*)r.d_eln, (void*)r.d_emu, (void*)r.d_esd, (void*)r.d_win}) if (q) hipFree(q);
+  }
+  {
+    SignalScratch& sp = h->sp;
+    for (void* q : {(void*)sp.d_x, (void*)sp.ps, (void*)sp.pq, (void*)sp.t1, (void*)sp.t2, (void*)sp.bounds, (void*)sp.tile_sums, (void*)sp.var_part,
+                    (void*)sp.d_reads, (void*)sp.d_cnt, (void*)sp.fit}) if (q) hipFree(q);
+    for (void* q : {(void*)sp.pin_x, (void*)sp.pin_reads, (void*)sp.pin_cnt}) if (q) hipHostFree(q);
+  }
   if (h->copy_stream) { hipStreamSynchronize(h->copy_stream); hipStreamDestroy(h->copy_stream); }
   if (h->ev_put) hipEventDestroy(h->ev_put);
   delete h;
@@ -2328,6 +2577,11 @@ int rv_read_put(rv_handle h, const float* raw, size_t n_raw, const float* event,
 int rv_read_put_dev(rv_handle h, const float* d_raw, size_t n_raw, const float* d_event, size_t n_event, int32_t* read_id) {
   return put_read(h, d_raw, n_raw, d_event, n_event, true, read_id);
 }
+int rv_read_put_signals(rv_handle h, int32_t n_reads, const int16_t* const* signal, const size_t* n, const RvSignalPrep* prep,
+                        int32_t* read_id, int32_t* n_events, int32_t* n_windows) {
+  return put_signals(h, n_reads, signal, n, prep, read_id, n_events, n_windows);
+}
+int rv_read_fetch(rv_handle h, int32_t read_id, int32_t what, void* dst, size_t cap) { return fetch_read(h, read_id, what, dst, cap); }
 int rv_read_drop(rv_handle h, int32_t read_id) {
   if (!h) return RV_EINVAL;
   Read* r = find_read(h, read_id);

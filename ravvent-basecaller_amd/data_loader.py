@@ -109,6 +109,25 @@ def compute_fitting_event_ranges(events_lens, stride, raw_max_len=200):
     return np.array(out)
 
 
+def fitting_event_ranges_closed_form(events_lens, stride, raw_max_len=200):
+    """`compute_fitting_event_ranges` without its loop, as the device states it (csrc/signal_prep.hip, k_sp_windows): with C the prefix
+    sums of the lengths, chunk k starts at event i = k * stride, base = C[i - 1] (0 for i = 0) and ends at the first j with
+    C[j] > base + raw_max_len; the table stops at the first k whose end does not exist or is 0.  For positive lengths C grows, so the
+    end is a binary search, and the chunks that have one are a prefix of all chunks.  -> the same [n,2] array (or the empty one)."""
+    lens = np.asarray(events_lens)
+    E = int(lens.shape[0])
+    if E == 0:
+        return np.array([])
+    C = np.cumsum(lens, axis=0, dtype=np.int64)
+    if C[0] > raw_max_len:                  # an oversized first event: end is 0 at once
+        return np.array([])
+    i = np.arange(0, E, int(stride), dtype=np.int64)
+    base = np.where(i > 0, C[np.maximum(i - 1, 0)], 0)
+    end = np.searchsorted(C, base + raw_max_len, side="right")      # the first j with C[j] > base + raw_max_len
+    n = int(np.argmax(end >= E)) if (end >= E).any() else len(i)    # the first chunk whose tail fits ends the table
+    return np.column_stack((i[:n], end[:n])) if n else np.array([])
+
+
 def prepare_snippets(raw, nuc_raw_ranges, nuc_reference_symbols, stride, max_raw_len=MAX_RAW_LEN):
     """data_loader.py:70-108 -- events -> 5 scaled features, raw standard-scaled per read, windows of
     <= max_raw_len samples every `stride` events, target strings '$...^' per window."""
