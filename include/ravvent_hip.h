@@ -12,9 +12,9 @@
  * ravvent_performance_evaluator.py:51-55); use one handle per GPU / per process.
  *
  * Synchronous calls -- rv_beam_search, rv_beam_search_dev, rv_beam_search_calls, rv_beam_search_windows, _windows_dev, _windows_calls, rv_beam_search_all, rv_beam_search_all_dev,
- * rv_greedy_search, rv_greedy_search_dev, rv_teacher_forced, rv_teacher_forced_dev, rv_score_logits, rv_load_weights, rv_get_tensor: results are complete when the call
+ * rv_beam_search_calls_moves, rv_beam_search_windows_calls_moves, rv_greedy_search, rv_greedy_search_dev, rv_teacher_forced, rv_teacher_forced_dev, rv_teacher_forced_moves, _moves_dev, rv_score_logits, rv_load_weights, rv_get_tensor: results are complete when the call
  * returns, so a caller's wall-clock timers mean what they mean around the reference's methods.
- * Asynchronous calls -- rv_beam_search_submit, _submit_dev, _submit_calls, _submit_windows, _submit_windows_calls, _submit_all, _submit_all_dev: they return once the
+ * Asynchronous calls -- rv_beam_search_submit, _submit_dev, _submit_calls, _submit_windows, _submit_windows_calls, _submit_windows_calls_moves, _submit_all, _submit_all_dev: they return once the
  * slab is queued, or held for its group until one of the events listed at rv_beam_search_flush
  * (option "coalesce"); the matching rv_beam_search_collect* waits for it.  A synchronous call may be
  * made while tickets are in flight: it runs on an idle slab context of the handle (its own when
@@ -219,6 +219,35 @@ int rv_beam_search_submit_moves(rv_handle h, const float* raw, const float* even
                                 int32_t L, int32_t* ticket);
 int rv_beam_search_collect_moves(rv_handle h, int32_t ticket, const RvBeams* out, const RvMoves* moves, int32_t* S_out);
 
+/* Calls with positions: the fused post-processing of rv_beam_search_calls together with the moves of the best hypothesis, one value per
+ * LETTER of each chunk's string.  The decode leaves the step records of a moves call; behind the call's finalize,
+ * k_dec_finalize_calls_moves back-traces hypothesis 0 exactly as the moves finalize does for w = 0 and compacts the six values with the
+ * rule that compacts the letters (lut[token] != 0).  `moves` holds six outputs [B, L-1], row stride L-1, each of which may be NULL, but not
+ * all of them.  Element i < lengths[b] belongs to letter i of chunk b's string and equals, bit for bit, what rv_beam_search_moves returns
+ * at [b, t_i, 0] for the column t_i of that letter (same records, same IEEE division, same NaN rule for a chunk that is padding from end
+ * to end); elements i >= lengths[b] hold the fill values: positions -1, masses and peak_weight 0, peak -1.  bases, lengths, probs and
+ * S_out are byte-identical to the corresponding *_calls call.  Limits, RV_ESTATE rules and messages are those of the call each one
+ * mirrors; scheduling is a moves slab's: a slab context of its own, never coalesced (it launches the group that is filling), never
+ * replayed as a "slab_graph", records and staging allocated on a context's first such call, the per-step decode's steps launched directly
+ * with the two-pass attend aside where the single-pass kernel runs the step.  A window call still gathers in the lane where a calls
+ * window call does.  Every handle kind that serves rv_beam_search_moves serves these.  B == 0 or L == 1 launches nothing and writes
+ * nothing.  Profile scope "dec_finalize_calls_moves" (behind "dec_finalize").  Added without changing an existing entry point:
+ * RV_ABI_VERSION stays at 1.
+ *   rv_beam_search_calls_moves                 chunk tensors, synchronous, host buffers: rv_beam_search_calls
+ *   rv_beam_search_windows_calls_moves         window table, synchronous: rv_beam_search_windows_calls
+ *   rv_beam_search_submit_windows_calls_moves  asynchronous: the ticket is collected by ...
+ *   rv_beam_search_collect_calls_moves         ... which takes the calls' outputs and the struct (no other collect takes such a ticket) */
+typedef struct RvCallMoves { float* raw_pos; float* raw_mass; float* event_pos; float* event_mass; int32_t* peak; float* peak_weight; } RvCallMoves;
+int rv_beam_search_calls_moves(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                               const uint8_t* lut, uint8_t* bases, int32_t* lengths, float* probs, const RvCallMoves* moves, int32_t* S_out);
+int rv_beam_search_windows_calls_moves(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                       const uint8_t* lut, uint8_t* bases, int32_t* lengths, float* probs, const RvCallMoves* moves,
+                                       int32_t* S_out);
+int rv_beam_search_submit_windows_calls_moves(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                              const uint8_t* lut, int32_t* ticket);
+int rv_beam_search_collect_calls_moves(rv_handle h, int32_t ticket, uint8_t* bases, int32_t* lengths, float* probs, const RvCallMoves* moves,
+                                       int32_t* S_out);
+
 /* Coalesced slabs (option "coalesce" = n >= 2, or its default when it chooses so): up to n consecutively submitted slabs of the default
  * streamed path -- beam search, persistent decode, matrix-pipe recurrences, "profile" 0, no taps, "slab_graph" 0 -- are decoded as ONE
  * internal call of sum(B) chunks on a group context (buffers for n x max_batch chunks; ceil(async_depth / n) of them in ordinary use, one
@@ -359,6 +388,21 @@ int rv_teacher_forced_dev(rv_handle h, const float* d_raw, const float* d_event,
                           const int32_t* d_targets, uint32_t omit_mask, int32_t* d_sample_id, float* d_logits, const RvScore* d_out);
 int rv_score_logits(rv_handle h, const float* logits, const int32_t* labels, int32_t B, int32_t S, uint32_t omit_mask, int32_t* pred,
                     const RvScore* out);
+
+/* Forced alignment: where in a chunk's signal the labels of a KNOWN sequence lie.  rv_teacher_forced* with the decode's step records
+ * kept (DecState::step_moves, as in a moves call) and k_forced_moves behind the finalize: the arguments of rv_teacher_forced / _dev plus
+ * `moves`, whose six members are [B, L-1] (one row per chunk, no beam axis), each may be NULL, not all (RV_EINVAL).  Column t holds the
+ * record of step t -- the step that was fed targets[b, t] and scored targets[b, t+1], so the column belongs to label targets[b, t+1], as
+ * nll[b, t] does; quotients and NaN rule as for rv_beam_search_moves; the fill values (positions -1, masses and peak_weight 0, peak -1)
+ * where that label is pad_token.  sample_id, logits and `out` are byte-identical to rv_teacher_forced on the same inputs; every other
+ * refusal is rv_teacher_forced's.  B == 0 or L == 1 launches nothing.  On the per-step decode, where the single-pass attend runs the
+ * steps, the records come from the two-pass launch beside it, as in a moves call.  Profile scope "forced_moves". */
+int rv_teacher_forced_moves(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t L,
+                            const int32_t* targets, uint32_t omit_mask, int32_t* sample_id, float* logits, const RvScore* out,
+                            const RvMoves* moves);
+int rv_teacher_forced_moves_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e, int32_t L,
+                                const int32_t* d_targets, uint32_t omit_mask, int32_t* d_sample_id, float* d_logits, const RvScore* d_out,
+                                const RvMoves* d_moves);
 
 /* Options.  The DEFAULT path is: matrix-pipe recurrences ("wide_recurrence" 1) + split-f16 GEMMs + the one-launch persistent decode with
  * attention and cell product on the matrix pipe ("persistent_decode", "matrix_attention", "matrix_cell" 1).  Options marked [fma form] only

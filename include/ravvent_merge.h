@@ -37,6 +37,14 @@ int rv_merger_append(rv_merger m, const uint8_t* bases, const float* probs, cons
                      int32_t n_chunks);
 int rv_merger_result(rv_merger m, uint8_t* out_seq, float* out_probs, int64_t out_cap, int64_t* out_len);
 void rv_merger_destroy(rv_merger m);
+/* Provenance of the merged read: for base i of rv_merger_result's sequence, chunk[i] is the chunk it was called in, counted from 0
+ * over all appends of the handle, and index[i] its place in that chunk's call -- bases[chunk[i]][index[i]] is the letter and
+ * probs[chunk[i]][index[i]] the value the merged read holds at i.  The pair travels through exactly what the letters and values go
+ * through: the per-column picks, the splice, the replacement of the read while nothing has merged yet, and the early stop.  Inside a
+ * run of bases from one chunk the indices rise strictly.  The merger knows nothing of what else a caller keeps per called base
+ * (positions in the signal, say): any such payload of the merged read is a gather by these pairs.
+ * *out_len is always set; RV_MERGE_ESPACE (nothing written) when cap is too small. */
+int rv_merger_sources(rv_merger m, int32_t* chunk, int32_t* index, int64_t cap, int64_t* out_len);
 
 /* pairwise2.align.localms / localds (a, b, <scores_id tables>)[0]: the two gapped, equal-length strings (both
  * sequences in full, '-' for gaps), score, begin, end.  Returns 1 with *out_len columns written, 0 when the

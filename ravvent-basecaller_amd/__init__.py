@@ -19,6 +19,6 @@ if not _os.environ.get("RAVVENT_KEEP_ENV"):
 
 from .config import RvConfig  # noqa: F401
 from . import data_loader, utils, weights, synthetic, dist, evaluator, event_detection, checkpoint  # noqa: F401
-from .basecaller import Basecaller, BeamHypotheses, Moves  # noqa: F401
+from .basecaller import Basecaller, BeamHypotheses, Moves, CallMoves  # noqa: F401
 
-__all__ = ["RvConfig", "Basecaller", "BeamHypotheses", "Moves", "data_loader", "utils", "weights", "synthetic", "dist", "evaluator", "event_detection", "checkpoint"]
+__all__ = ["RvConfig", "Basecaller", "BeamHypotheses", "Moves", "CallMoves", "data_loader", "utils", "weights", "synthetic", "dist", "evaluator", "event_detection", "checkpoint"]

@@ -27,6 +27,11 @@ class CRvMoves(ctypes.Structure):
                 ("peak_weight", c_void_p)]
 
 
+class CRvCallMoves(ctypes.Structure):
+    """RvCallMoves (include/ravvent_hip.h): the six outputs [B, L-1] of the rv_beam_search_*calls_moves calls; each may be None, not all."""
+    _fields_ = CRvMoves._fields_
+
+
 class CRvScore(ctypes.Structure):
     """RvScore (include/ravvent_hip.h): the outputs of rv_teacher_forced* / rv_score_logits; each may be None."""
     _fields_ = [("nll", c_void_p), ("nll_sum", c_void_p), ("n_labels", c_void_p), ("n_match", c_void_p), ("n_counted", c_void_p)]
@@ -48,6 +53,7 @@ _F, _I = POINTER(c_float), POINTER(c_int32)
 _B = POINTER(CRvBeams)
 _S = POINTER(CRvScore)
 _M = POINTER(CRvMoves)
+_CM = POINTER(CRvCallMoves)
 SYMBOLS = [
     ("rv_abi_version", c_int32, []),
     ("rv_create", c_int32, [POINTER(CRvConfig), POINTER(c_void_p)]),
@@ -74,6 +80,10 @@ SYMBOLS = [
     ("rv_beam_search_moves_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _B, _M, _I]),
     ("rv_beam_search_submit_moves", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _I]),
     ("rv_beam_search_collect_moves", c_int32, [c_void_p, c_int32, _B, _M, _I]),
+    ("rv_beam_search_calls_moves", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, _CM, _I]),
+    ("rv_beam_search_windows_calls_moves", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, _CM, _I]),
+    ("rv_beam_search_submit_windows_calls_moves", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, _I]),
+    ("rv_beam_search_collect_calls_moves", c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, _CM, _I]),
     ("rv_beam_search_flush", c_int32, [c_void_p]),
     ("rv_read_put", c_int32, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, _I]),
     ("rv_read_put_dev", c_int32, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, _I]),
@@ -89,6 +99,8 @@ SYMBOLS = [
     ("rv_greedy_search_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
     ("rv_teacher_forced", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, _S]),
     ("rv_teacher_forced_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, _S]),
+    ("rv_teacher_forced_moves", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, _S, _M]),
+    ("rv_teacher_forced_moves_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, _S, _M]),
     ("rv_score_logits", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_uint32, c_void_p, _S]),
     ("rv_set_option", c_int32, [c_void_p, c_char_p, c_int32]),
     ("rv_get_tensor", c_int32, [c_void_p, c_char_p, c_void_p, c_size_t, POINTER(c_size_t)]),
@@ -105,6 +117,7 @@ SYMBOLS = [
     ("rv_merger_append", c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32]),
     ("rv_merger_result", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
     ("rv_merger_destroy", None, [c_void_p]),
+    ("rv_merger_sources", c_int32, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
     ("rv_local_align", c_int32, [c_char_p, c_int32, c_char_p, c_int32, c_int32, c_char_p, c_char_p, c_int32, _I,
                                  POINTER(c_double), _I, _I]),
 ]

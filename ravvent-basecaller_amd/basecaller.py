@@ -36,6 +36,47 @@ Moves = collections.namedtuple("Moves", "raw_pos raw_mass event_pos event_mass p
 ForcedScores = collections.namedtuple("ForcedScores", "sample_id logits nll nll_sum n_labels n_match n_counted")
 
 
+# The same six values per LETTER of each chunk's call (rv_beam_search_*calls_moves, include/ravvent_hip.h: RvCallMoves): numpy arrays
+# [B, L-1] beside the call arrays; element i < lengths[b] belongs to letter i of chunk b, the tail holds -1 / 0
+CallMoves = collections.namedtuple("CallMoves", "raw_pos raw_mass event_pos event_mass peak peak_weight")
+
+
+def raw_position_estimate(raw_start, raw_pos, offset=0):
+    """Position of a base in samples of the signal from the raw segment of its chunk: raw_start + raw_pos (+ the sample of the signal
+    at which the scaled raw table starts); NaN stays NaN.  f64."""
+    return np.asarray(raw_start, np.float64) + np.asarray(raw_pos, np.float64) + float(offset)
+
+
+def event_position_estimate(event_start, event_pos, ev_starts, ev_lengths):
+    """... from the event segment: e = event_start + event_pos in events of the read, i = floor(e) clipped to the read's events,
+    c_j = start_j + length_j / 2 the centre of event j, estimate = c_i + (e - i) (c_min(i+1, E-1) - c_i): linear between the centres
+    of neighbouring events, the last event's centre at and beyond it.  NaN stays NaN (and a read without events gives NaN).  f64."""
+    e = np.asarray(event_start, np.float64) + np.asarray(event_pos, np.float64)
+    c = np.asarray(ev_starts, np.float64) + np.asarray(ev_lengths, np.float64) / 2.0
+    out = np.full(e.shape, np.nan, np.float64)
+    E = int(c.shape[0])
+    ok = ~np.isnan(e)
+    if E == 0 or not ok.any():
+        return out
+    i = np.clip(np.floor(e[ok]), 0, E - 1).astype(np.int64)
+    j = np.minimum(i + 1, E - 1)
+    out[ok] = c[i] + (e[ok] - i) * (c[j] - c[i])
+    return out
+
+
+def signal_positions(mode, raw_start, event_start, raw_pos, raw_mass, event_pos, event_mass, ev_starts, ev_lengths, offset=0):
+    """The position of each base in samples of the signal as passed in: raw mode takes the raw estimate,
+    event mode the event estimate, joint mode the raw estimate where raw_mass >= event_mass and the event estimate elsewhere.
+    Reported as computed: nothing forces the positions of consecutive bases to rise."""
+    if mode == "raw":
+        return raw_position_estimate(raw_start, raw_pos, offset)
+    ev = event_position_estimate(event_start, event_pos, ev_starts, ev_lengths)
+    if mode == "event":
+        return ev
+    take_raw = np.asarray(raw_mass, np.float32) >= np.asarray(event_mass, np.float32)
+    return np.where(take_raw, raw_position_estimate(raw_start, raw_pos, offset), ev)
+
+
 def phred_qualities(probs) -> np.ndarray:
     """Per-base probabilities -> Phred values u8: p clipped to [0, 1], round(-10 log10(max(1 - p, 1e-4))), clipped to [0, 40]."""
     p = np.clip(np.asarray(probs, np.float64), 0.0, 1.0)
@@ -45,14 +86,26 @@ def phred_qualities(probs) -> np.ndarray:
 
 class BasecallResult:
     """What `Basecaller.basecall` returns for a read: seq, probs (the merger's per-base probabilities, f32), qualities (their
-    Phred values, u8), chunks_num."""
-    __slots__ = ("seq", "probs", "qualities", "chunks_num")
+    Phred values, u8), chunks_num.  With moves=True also, one per base of seq: positions (f64, samples of the signal as passed in;
+    `signal_positions`), raw_mass / event_mass (f32, the attention weight on each segment of the base's chunk), source_chunk /
+    source_index (int32: the chunk of the read the merger took the base from and its index in that chunk's call); None otherwise."""
+    __slots__ = ("seq", "probs", "qualities", "chunks_num", "positions", "raw_mass", "event_mass", "source_chunk", "source_index")
 
-    def __init__(self, seq, probs, chunks_num):
+    def __init__(self, seq, probs, chunks_num, positions=None, raw_mass=None, event_mass=None, source_chunk=None, source_index=None):
         self.seq = seq
         self.probs = np.asarray(probs, np.float32)
         self.qualities = phred_qualities(self.probs)
         self.chunks_num = int(chunks_num)
+        self.positions, self.raw_mass, self.event_mass = positions, raw_mass, event_mass
+        self.source_chunk, self.source_index = source_chunk, source_index
+
+    def positions_tsv(self, name) -> str:
+        """A '# name' line, then one line per base: index, letter, position (three decimals, 'nan' where unknown), Phred value;
+        tab-separated.  Needs a result of basecall(..., moves=True)."""
+        if self.positions is None:
+            raise ValueError("positions_tsv needs basecall(..., moves=True)")
+        rows = [f"{i}\t{c}\t{p:.3f}\t{int(q)}" for i, (c, p, q) in enumerate(zip(self.seq, self.positions, self.qualities))]
+        return "\n".join([f"# {name}"] + rows) + "\n"
 
     def to_fastq(self, name) -> str:
         """Four lines: @name, the sequence, +, the qualities as chr(33 + Q)."""
@@ -459,6 +512,13 @@ class Basecaller:
         kept = table[np.clip(tokens, 0, 255).astype(np.uint8)] != 0
         return [positions[b][kept[b]] for b in range(tokens.shape[0])]
 
+    def label_positions(self, target_tokens, positions):
+        """`base_positions` for a forced decode (`align`): `target_tokens` [B,L] and `positions` [B,L-1] (a Moves member of `align`) ->
+        per chunk the positions at the columns whose label target_tokens[b, t+1] is a letter; element i belongs to letter i of the
+        chunk's label string."""
+        as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        return self.base_positions(as_np(target_tokens)[:, 1:], positions)
+
     # ------------------------------------------------------------------ the hot path, several slabs in flight
     def set_async_depth(self, depth: int):
         """Slab contexts the submit_* calls rotate through (1..16; default 2).  With several slabs in flight the GPU never idles
@@ -769,13 +829,84 @@ class Basecaller:
         self.last_steps = S.value
         return bases, probs, lens
 
-    def submit_windows(self, windows, beam_width, max_output_len, calls=False, *, T_r=None, T_e=None):
+    @staticmethod
+    def _call_moves_bufs(B, steps):
+        f = lambda: np.zeros((B, steps), np.float32)
+        return CallMoves(f(), f(), f(), f(), np.zeros((B, steps), np.int32), f())
+
+    @staticmethod
+    def _call_moves_struct(bufs):
+        return _capi.CRvCallMoves(*[ctypes.c_void_p(a.ctypes.data) for a in bufs])
+
+    def beam_search_calls_moves(self, input_data, beam_width, max_output_len):
+        """`beam_search_call_arrays` with the position of every called letter (rv_beam_search_calls_moves) -> (bases u8 [B,L-1],
+        probs f32 [B,L-1], lengths i32 [B], CallMoves of six [B,L-1] arrays).  The first three are `beam_search_call_arrays`'s byte
+        for byte; element i < lengths[b] of a CallMoves member is what `base_positions` cuts from `beam_search_moves` for letter i of
+        hypothesis 0, the tail holds -1 (positions, peak) / 0.  Host buffers: device inputs are brought down."""
+        keep, pr, pe, B, Tr, Te, on_dev = self._gather_inputs(input_data)
+        if on_dev:
+            host = tuple(None if k is None else k.cpu().numpy() for k in keep)
+            return self.beam_search_calls_moves(host if self.input_data_type == "joint" else (host[0] if host[0] is not None else host[1]),
+                                                beam_width, max_output_len)
+        L = _as_int(max_output_len)
+        steps = max(L - 1, 0)
+        lut = self._call_lut()
+        bases = np.zeros((B, steps), np.uint8); lens = np.zeros(B, np.int32); probs = np.zeros((B, steps), np.float32)
+        mv = self._call_moves_bufs(B, steps)
+        sm = self._call_moves_struct(mv)
+        S = ctypes.c_int32(0)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self._lib.rv_beam_search_calls_moves(self._h, pr, pe, B, Tr, Te, int(beam_width), L, p(lut), p(bases), p(lens),
+                                                         p(probs), ctypes.byref(sm), ctypes.byref(S)), "rv_beam_search_calls_moves")
+        self.last_steps = S.value
+        return bases, probs, lens, mv
+
+    def beam_search_windows_calls_moves(self, windows, beam_width, max_output_len, *, T_r=None, T_e=None):
+        """`beam_search_calls_moves` on windows (rv_beam_search_windows_calls_moves): positions in samples / events of each CHUNK."""
+        w, pw, B, T_r, T_e = self._window_table(windows, T_r, T_e)
+        L = _as_int(max_output_len)
+        steps = max(L - 1, 0)
+        lut = self._call_lut()
+        bases = np.zeros((B, steps), np.uint8); lens = np.zeros(B, np.int32); probs = np.zeros((B, steps), np.float32)
+        mv = self._call_moves_bufs(B, steps)
+        sm = self._call_moves_struct(mv)
+        S = ctypes.c_int32(0)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self._lib.rv_beam_search_windows_calls_moves(self._h, pw, B, T_r, T_e, int(beam_width), L, p(lut), p(bases), p(lens),
+                                                                 p(probs), ctypes.byref(sm), ctypes.byref(S)),
+                    "rv_beam_search_windows_calls_moves")
+        self.last_steps = S.value
+        return bases, probs, lens, mv
+
+    def collect_calls_moves(self, call):
+        """-> (bases, probs, lengths, CallMoves) of a `submit_windows(..., calls=True, moves=True)` ticket."""
+        B, steps = call["B"], call["steps"]
+        bases = np.zeros((B, steps), np.uint8); lens = np.zeros(B, np.int32); probs = np.zeros((B, steps), np.float32)
+        mv = self._call_moves_bufs(B, steps)
+        sm = self._call_moves_struct(mv)
+        S = ctypes.c_int32(0)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self._lib.rv_beam_search_collect_calls_moves(self._h, call["ticket"], p(bases), p(lens), p(probs), ctypes.byref(sm),
+                                                                 ctypes.byref(S)), "rv_beam_search_collect_calls_moves")
+        self.last_steps = S.value
+        return bases, probs, lens, mv
+
+    def submit_windows(self, windows, beam_width, max_output_len, calls=False, *, T_r=None, T_e=None, moves=False):
         """Queue `beam_search_windows` (calls=True: with the fused post-processing) without waiting for the GPU
         (rv_beam_search_submit_windows / _windows_calls); the ticket goes to `collect` / `collect_calls`.  The reads the table
-        names cannot be dropped until the ticket is collected."""
+        names cannot be dropped until the ticket is collected.  moves=True (with calls): `beam_search_windows_calls_moves`
+        (rv_beam_search_submit_windows_calls_moves); the ticket goes to `collect_calls_moves`."""
         w, pw, B, T_r, T_e = self._window_table(windows, T_r, T_e)
         L = _as_int(max_output_len)
         t = ctypes.c_int32(-1)
+        if moves:
+            if not calls:
+                raise ValueError("moves=True goes with calls=True")
+            lut = self._call_lut()
+            self._check(self._lib.rv_beam_search_submit_windows_calls_moves(self._h, pw, B, T_r, T_e, int(beam_width), L,
+                                                                            lut.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t)),
+                        "rv_beam_search_submit_windows_calls_moves")
+            return {"kind": "calls_moves", "ticket": t.value, "B": B, "steps": max(L - 1, 0)}
         if calls:
             lut = self._call_lut()
             self._check(self._lib.rv_beam_search_submit_windows_calls(self._h, pw, B, T_r, T_e, int(beam_width), L,
@@ -786,16 +917,19 @@ class Basecaller:
                     "rv_beam_search_submit_windows")
         return {"kind": "host", "keep": None, "ticket": t.value, "B": B, "steps": max(L - 1, 0)}
 
-    def beam_search_stream_windows(self, tables, beam_width, max_output_len, calls: bool = False, *, T_r=None, T_e=None):
+    def beam_search_stream_windows(self, tables, beam_width, max_output_len, calls: bool = False, *, T_r=None, T_e=None, moves=False):
         """`beam_search_stream` over window tables: `async_depth` slabs in flight, each table's result in order."""
         depth = getattr(self, "async_depth", 2)
-        col = self.collect_calls if calls else self.collect
+        col = self.collect_calls_moves if moves else (self.collect_calls if calls else self.collect)
         queue = []
         try:
             for w in tables:
                 if len(queue) >= depth:
                     yield col(queue.pop(0))
-                queue.append(self.submit_windows(w, beam_width, max_output_len, calls=calls, T_r=T_r, T_e=T_e))
+                if moves:
+                    queue.append(self.submit_windows(w, beam_width, max_output_len, calls=True, T_r=T_r, T_e=T_e, moves=True))
+                else:
+                    queue.append(self.submit_windows(w, beam_width, max_output_len, calls=calls, T_r=T_r, T_e=T_e))
             while queue:
                 yield col(queue.pop(0))
         finally:                       # (as beam_search_stream: no ticket may stay uncollected on the handle)
@@ -805,44 +939,68 @@ class Basecaller:
                 except Exception:
                     pass
 
-    def _stream_window_calls(self, table, beam_width, L, chunk_size, T_r, T_e):
-        """The call arrays of a whole table, decoded in slabs of `chunk_size` rows with the handle's depth of them in flight."""
+    def _stream_window_calls(self, table, beam_width, L, chunk_size, T_r, T_e, moves=False):
+        """The call arrays of a whole table, decoded in slabs of `chunk_size` rows with the handle's depth of them in flight.
+        moves: through the calls-with-positions window call; a CallMoves over all rows comes fourth."""
         n, steps = int(table.shape[0]), max(L - 1, 0)
         bases = np.zeros((n, steps), np.uint8); probs = np.zeros((n, steps), np.float32); lens = np.zeros(n, np.int32)
         cuts = [(a, min(a + chunk_size, n)) for a in range(0, n, chunk_size)]
+        if moves:
+            mv = self._call_moves_bufs(n, steps)
+            results = self.beam_search_stream_windows((table[a:b] for a, b in cuts), beam_width, L, calls=True, T_r=T_r, T_e=T_e, moves=True)
+            for (a, b), (bs, pr, ln, m) in zip(cuts, results):
+                bases[a:b] = bs; probs[a:b] = pr; lens[a:b] = ln
+                for dst, src in zip(mv, m):
+                    dst[a:b] = src
+            return bases, probs, lens, mv
         results = self.beam_search_stream_windows((table[a:b] for a, b in cuts), beam_width, L, calls=True, T_r=T_r, T_e=T_e)
         for (a, b), (bs, pr, ln) in zip(cuts, results):
             bases[a:b] = bs; probs[a:b] = pr; lens[a:b] = ln
         return bases, probs, lens
 
-    def basecall(self, signal, stride=6, beam_width=5, max_output_len=None, chunk_size=1024, device_prep=False):
+    def basecall(self, signal, stride=6, beam_width=5, max_output_len=None, chunk_size=1024, device_prep=False, moves=False):
         """An unlabelled read's signal -> BasecallResult (seq, probs, qualities, chunks_num, to_fastq): `prepare_windows` without
         labels, `put_read`, window slabs of `chunk_size` chunks streamed with the fused post-processing, the C++ merger, drop.
-        max_output_len None: the handle's.  device_prep: see `basecall_many`."""
-        return self.basecall_many([signal], stride, beam_width, max_output_len, chunk_size, device_prep)[0]
+        max_output_len None: the handle's.  device_prep, moves: see `basecall_many`."""
+        return self.basecall_many([signal], stride, beam_width, max_output_len, chunk_size, device_prep, moves)[0]
 
-    def basecall_many(self, signals, stride=6, beam_width=5, max_output_len=None, chunk_size=1024, device_prep=False):
+    def basecall_many(self, signals, stride=6, beam_width=5, max_output_len=None, chunk_size=1024, device_prep=False, moves=False):
         """`basecall` of several reads through shared slabs: the windows of all reads are queued into full slabs (a slab's rows may
         name different reads) and each read is stitched from its own rows -> list of BasecallResult, equal to one `basecall` each.
         device_prep True: events, scaling and windows are made on the device from the int16 samples of all reads at once
-        (`put_signals`) instead of read by read on the host; integer signals only (ValueError otherwise)."""
+        (`put_signals`) instead of read by read on the host; integer signals only (ValueError otherwise).
+        moves True: the slabs stream through the calls-with-positions window call and the merger reports where each merged base
+        came from; every result then carries positions / raw_mass / event_mass / source_chunk / source_index (BasecallResult,
+        `signal_positions`).  seq and probs are what moves=False gives, byte for byte."""
         from . import merger as _merger
+        from .event_detection import EventDetector
         L = self.cfg.max_output_len if max_output_len is None else _as_int(max_output_len)
         T_r, T_e = min(_dl.MAX_RAW_LEN, self.cfg.max_raw_len), min(_dl.MAX_EVENT_LEN, self.cfg.max_event_len)
-        windows, handles = [], []
+        windows, handles, ev_tabs = [], [], []
+        mv = None
         try:
             if device_prep:
                 handles = self.put_signals(list(signals), stride=stride, max_raw_len=T_r, max_event_len=T_e)
                 windows = [h.windows for h in handles]
+                if moves:      # the read's events, as the device made them
+                    ev_tabs = [(h.fetch("start"), h.fetch("length")) if h.n_event else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+                               for h in handles]
             else:
                 for sig in signals:
                     rw = _dl.prepare_windows(sig, stride=stride, max_raw_len=T_r, max_event_len=T_e)
                     windows.append(rw.windows)
                     handles.append(self.put_read(rw.raw_sc, rw.events_sc))
+                    if moves:      # ... as the host detector makes them: a second run of the detector prepare_windows ran, whose
+                        #     return type has no room for the event arrays
+                        st, ln, _, _ = EventDetector(window_length1=_dl.ED_WINDOW_LENGTH_1, window_length2=_dl.ED_WINDOW_LENGTH_2).run_arrays(np.asarray(sig))
+                        ev_tabs.append((np.asarray(st, np.int64), np.asarray(ln, np.int64)))
             n = [int(w.shape[0]) for w in windows]
             off = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
             table = (np.concatenate([h.table(w) for h, w in zip(handles, windows)]) if windows else np.zeros((0, 5), np.int32))
-            bases, probs, lens = self._stream_window_calls(table, beam_width, L, int(chunk_size), T_r, T_e)
+            if moves:
+                bases, probs, lens, mv = self._stream_window_calls(table, beam_width, L, int(chunk_size), T_r, T_e, moves=True)
+            else:
+                bases, probs, lens = self._stream_window_calls(table, beam_width, L, int(chunk_size), T_r, T_e)
         finally:
             for h in handles:
                 h.drop()
@@ -850,8 +1008,21 @@ class Basecaller:
         out = []
         for i in range(len(windows)):
             a, b = int(off[i]), int(off[i + 1])
-            seq, pr = mg.merge_arrays(bases[a:b], probs[a:b], lens[a:b]) if b > a else ("", np.zeros(0, np.float32))
-            out.append(BasecallResult(seq, pr, n[i]))
+            if not moves:
+                seq, pr = mg.merge_arrays(bases[a:b], probs[a:b], lens[a:b]) if b > a else ("", np.zeros(0, np.float32))
+                out.append(BasecallResult(seq, pr, n[i]))
+                continue
+            if b > a:
+                seq, pr, ck, ix = mg.merge_arrays(bases[a:b], probs[a:b], lens[a:b], sources=True)
+            else:
+                seq, pr, ck, ix = "", np.zeros(0, np.float32), np.zeros(0, np.int32), np.zeros(0, np.int32)
+            # every per-base payload is a gather by the merger's (chunk, index) pairs; the scaled raw table starts at sample 0 of the
+            # signal (prepare_windows scales the whole read), so no offset is added
+            w = windows[i]
+            g = lambda m: m[a:b][ck, ix]
+            pos = signal_positions(self.input_data_type, w[ck, 0], w[ck, 2], g(mv.raw_pos), g(mv.raw_mass), g(mv.event_pos),
+                                   g(mv.event_mass), ev_tabs[i][0], ev_tabs[i][1])
+            out.append(BasecallResult(seq, pr, n[i], pos, g(mv.raw_mass).copy(), g(mv.event_mass).copy(), ck, ix))
         return out
 
     def greedy_search_prediction(self, input_data, max_output_len):
@@ -902,10 +1073,11 @@ class Basecaller:
         acc = t(sc.n_match).sum().to(torch.float64) / t(sc.n_counted).sum().to(torch.float64)
         return {"loss": loss.cpu(), "acc": acc.cpu()}
 
-    def _teacher_forced(self, input_data, target_tokens, omit):
+    def _teacher_forced(self, input_data, target_tokens, omit, moves=False):
         """One rv_teacher_forced / _dev call -> ForcedScores over the L - 1 positions of every chunk.  Host inputs take host labels
         (checked by the library: an id outside the vocabulary is RV_EINVAL); device inputs take the labels to the device unchecked
-        (the kernels never index with such an id: it adds no input row, and as a label its nll is NaN)."""
+        (the kernels never index with such an id: it adds no input row, and as a label its nll is NaN).
+        moves: rv_teacher_forced_moves / _dev -> (ForcedScores, Moves of six [B,L-1] tensors)."""
         keep, pr, pe, B, Tr, Te, on_dev = self._gather_inputs(input_data)
         V = self.cfg.vocab
         if isinstance(target_tokens, torch.Tensor) and not on_dev:
@@ -929,9 +1101,30 @@ class Basecaller:
             ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
             fn, what = self._lib.rv_teacher_forced, "rv_teacher_forced"
         st = _capi.CRvScore(*[ptr(a) for a in bufs[2:]])
+        if moves:
+            if on_dev:
+                mk = lambda dt: torch.empty((B, steps), dtype=dt, device=self.device)
+                mv = Moves(*[mk(torch.int32 if k == 4 else torch.float32) for k in range(6)])
+            else:
+                mv = Moves(*[np.empty((B, steps), np.int32 if k == 4 else np.float32) for k in range(6)])
+            sm = self._moves_struct(mv)
+            fn = self._lib.rv_teacher_forced_moves_dev if on_dev else self._lib.rv_teacher_forced_moves
+            self._check(fn(self._h, pr, pe, B, Tr, Te, L, ptr(tg), self._omit_mask(omit), ptr(bufs[0]), ptr(bufs[1]), ctypes.byref(st),
+                           ctypes.byref(sm)), what.replace("forced", "forced_moves"))
+            self.last_steps = steps
+            as_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(a)
+            return ForcedScores(*[as_t(a) for a in bufs]), Moves(*[as_t(a) for a in mv])
         self._check(fn(self._h, pr, pe, B, Tr, Te, L, ptr(tg), self._omit_mask(omit), ptr(bufs[0]), ptr(bufs[1]), ctypes.byref(st)), what)
         self.last_steps = steps
         return ForcedScores(*[a if isinstance(a, torch.Tensor) else torch.from_numpy(a) for a in bufs])
+
+    def align(self, input_data, target_tokens):
+        """Forced alignment of known sequences: the forced decode of `teacher_forced_prediction` / `sequence_nll` with the moves of
+        its steps kept (rv_teacher_forced_moves / _dev) -> (ForcedScores, Moves).  Moves: six [B,L-1] tensors; column t is the step
+        that was fed target_tokens[b, t] and scored target_tokens[b, t+1], so it belongs to that label (as nll[b, t] does); -1 / 0
+        where the label is the padding token.  `label_positions` cuts a row to its letters.  Host or device tensors follow the
+        inputs; the ForcedScores is byte for byte that of the calls without moves."""
+        return self._teacher_forced(input_data, target_tokens, self._train_omit, moves=True)
 
     def teacher_forced_prediction(self, input_data, target_tokens):
         """Decoder.call as _train_step uses it (basecaller.py:142-152, :234-244): the decoder is fed target_tokens[:, :-1] instead of

@@ -333,6 +333,13 @@ void launch_dec_finalize_beams(const DecState& d, const BeamsOut& o, hipStream_t
 // RvMoves); the kernel skips a null output.
 struct MovesOut { float* raw_pos; float* raw_mass; float* event_pos; float* event_mass; int32_t* peak; float* peak_weight; };
 void launch_dec_finalize_moves(const DecState& d, const MovesOut& o, hipStream_t s);
+// The moves of a call with fused post-processing (rv_beam_search_calls_moves*): k_dec_finalize_calls_moves runs behind k_dec_finalize,
+// one launch per decode part, back-traces the best hypothesis' records and compacts them like call_bases.  `tokens` [B,L-1]: what
+// k_dec_finalize of that part wrote.  Six outputs [B,L-1] (include/ravvent_hip.h: RvCallMoves); the kernel skips a null output.
+void launch_dec_finalize_calls_moves(const DecState& d, const int32_t* tokens, const MovesOut& o, hipStream_t s);
+// The moves of a forced decode (rv_teacher_forced_moves*): k_forced_moves hands out step t's record in column t, [B,L-1]; needs
+// d.forced and d.step_moves.
+void launch_forced_moves(const DecState& d, const MovesOut& o, hipStream_t s);
 
 // ---------------------------------------------------------------- scoring (score.hip)
 // Masked sparse cross-entropy and masked token accuracy of label rows against logits (Basecaller.loss_function, basecaller.py:212-220;

@@ -432,14 +432,27 @@ struct RvMerger {
   std::vector<float> lg;
   std::string m_seq;
   std::vector<float> m_lg;
+  // provenance (rv_merger_sources): for every base of seq the chunk it was called in, counted from 0 over all appends of the handle,
+  // and its index within that chunk's call; carried through exactly what seq and lg go through
+  int32_t n_seen = 0;
+  std::vector<int32_t> sc_chunk, sc_index, m_chunk, m_index;
+
+  void assign_chunk(const char* sa, const float* la, int n, int32_t chunk) {
+    seq.assign(sa, n); lg.assign(la, la + n);
+    sc_chunk.assign(n, chunk); sc_index.resize(n);
+    for (int k = 0; k < n; ++k) sc_index[k] = k;
+  }
 
   int append(const uint8_t* bases, const float* probs, const int32_t* lengths, int64_t stride, int32_t n_chunks) {
     for (int i = 0; i < n_chunks; ++i) if (lengths[i] < 0 || lengths[i] > stride) return RV_MERGE_EINVAL;
+    const int32_t first = n_seen;
+    n_seen += n_chunks;
     for (int i = 0; i < n_chunks; ++i) {
       const char* sa = (const char*)bases + (size_t)i * stride;
       const float* la = probs + (size_t)i * stride;
       const int n = lengths[i];
-      if (!started) { seq.assign(sa, n); lg.assign(la, la + n); started = true; continue; }   // nuc_pred_snippets[0]
+      const int32_t chunk = first + i;
+      if (!started) { assign_chunk(sa, la, n, chunk); started = true; continue; }   // nuc_pred_snippets[0]
       if (stopped) break;
       const int n1 = (int)std::min<size_t>(seq.size(), overlap);      // seq_merged[-overlap:]
       const int n2 = std::min(n, overlap);                             // seq_appended[:overlap]
@@ -451,27 +464,34 @@ struct RvMerger {
       }
       Aligned r;
       if (!al.align(s1, n1, sa, n2, &r)) {                             // merger.py:181-200
-        if (!merge_flag) { seq.assign(sa, n); lg.assign(la, la + n); continue; }
+        if (!merge_flag) { assign_chunk(sa, la, n, chunk); continue; }
         stopped = true;
         break;
       }
       merge_flag = true;
       // align_logits + SingleMergerByLogits (merger.py:9-23, 88-119)
-      m_seq.clear(); m_lg.clear();
+      m_seq.clear(); m_lg.clear(); m_chunk.clear(); m_index.clear();
+      const int32_t* k1 = sc_chunk.data() + sc_chunk.size() - n1;
+      const int32_t* x1 = sc_index.data() + sc_index.size() - n1;
       int i1 = 0, i2 = 0;
       for (size_t c = 0; c < r.a.size(); ++c) {
         const char c1 = r.a[c], c2 = r.b[c];
-        const float v1 = c1 == '-' ? -1.f : l1[i1++];
-        const float v2 = c2 == '-' ? -1.f : la[i2++];
-        if (c1 == '-') { m_seq.push_back(c2); m_lg.push_back(v2); }
-        else if (c2 == '-') { m_seq.push_back(c1); m_lg.push_back(v1); }
-        else if (v2 > v1) { m_seq.push_back(c2); m_lg.push_back(v2); }
-        else { m_seq.push_back(c1); m_lg.push_back(v1); }
+        const int p1 = c1 == '-' ? -1 : i1++, p2 = c2 == '-' ? -1 : i2++;
+        const float v1 = p1 < 0 ? -1.f : l1[p1];
+        const float v2 = p2 < 0 ? -1.f : la[p2];
+        const bool second = c1 == '-' || (c2 != '-' && v2 > v1);      // the appended chunk's column is picked
+        if (second) { m_seq.push_back(c2); m_lg.push_back(v2); m_chunk.push_back(chunk); m_index.push_back(p2); }
+        else { m_seq.push_back(c1); m_lg.push_back(v1); m_chunk.push_back(k1[p1]); m_index.push_back(x1[p1]); }
       }
       // seq_merged[:-overlap] + merged + seq_appended[overlap:]   (merger.py:236-245)
       seq.resize(seq.size() - n1); lg.resize(lg.size() - n1);
+      sc_chunk.resize(sc_chunk.size() - n1); sc_index.resize(sc_index.size() - n1);
       seq.append(m_seq); lg.insert(lg.end(), m_lg.begin(), m_lg.end());
-      if (n > overlap) { seq.append(sa + overlap, n - overlap); lg.insert(lg.end(), la + overlap, la + n); }
+      sc_chunk.insert(sc_chunk.end(), m_chunk.begin(), m_chunk.end()); sc_index.insert(sc_index.end(), m_index.begin(), m_index.end());
+      if (n > overlap) {
+        seq.append(sa + overlap, n - overlap); lg.insert(lg.end(), la + overlap, la + n);
+        for (int k = overlap; k < n; ++k) { sc_chunk.push_back(chunk); sc_index.push_back(k); }
+      }
     }
     return 0;
   }
@@ -504,6 +524,18 @@ int rv_merger_result(rv_merger m, uint8_t* out_seq, float* out_probs, int64_t ou
     if (!out_seq || !out_probs) return RV_MERGE_ESPACE;
     memcpy(out_seq, m->seq.data(), m->seq.size());
     memcpy(out_probs, m->lg.data(), m->lg.size() * sizeof(float));
+  }
+  return 0;
+}
+
+int rv_merger_sources(rv_merger m, int32_t* chunk, int32_t* index, int64_t cap, int64_t* out_len) {
+  if (!m || !out_len) return RV_MERGE_EINVAL;
+  *out_len = (int64_t)m->sc_chunk.size();
+  if ((int64_t)m->sc_chunk.size() > cap) return RV_MERGE_ESPACE;
+  if (!m->sc_chunk.empty()) {
+    if (!chunk || !index) return RV_MERGE_ESPACE;
+    memcpy(chunk, m->sc_chunk.data(), m->sc_chunk.size() * sizeof(int32_t));
+    memcpy(index, m->sc_index.data(), m->sc_index.size() * sizeof(int32_t));
   }
   return 0;
 }

@@ -121,6 +121,9 @@ struct Call {
   const ForcedCall* forced = nullptr;       // rv_teacher_forced*
   bool want_moves = false;                  // rv_beam_search_moves* / rv_beam_search_submit_moves (always with whole_beam): the moves too, through ...
   const RvMoves* moves = nullptr;           // ... these outputs (null: an asynchronous call, named at its collect)
+  bool want_call_moves = false;             // rv_beam_search_*calls_moves (always with lut): a position per called letter, through ...
+  const RvCallMoves* call_moves = nullptr;  // ... these host outputs (null: an asynchronous call, named at its collect)
+  const RvMoves* forced_moves = nullptr;    // rv_teacher_forced_moves* (always with forced): the moves of the forced decode, [B,L-1]
   // rv_beam_search_windows*: the chunks are windows of reads on the device (raw / ev unset, dev_in set).  As the entry point states it: its
   // table's rows, resolved and checked against their reads (resolve_windows), in host memory; past enqueue()'s staging: the context's device
   // copy of them.  win_expand (set by enqueue): the call takes a path whose layer-0 kernels read chunk tensors, so k_expand_windows writes
@@ -164,6 +167,9 @@ struct CallParts {
   BeamsOut beams{};                         // ... these device addresses (the caller's, or the context's d_beams)
   bool moves = false;                       // the decode leaves step_moves records and k_dec_finalize_moves runs behind k_dec_finalize_beams, writing to ...
   MovesOut moves_out{};                     // ... these device addresses (the caller's, or the context's d_moves)
+  bool call_moves = false;                  // a calls slab whose decode leaves the records too: k_dec_finalize_calls_moves runs behind k_dec_finalize, ...
+  bool forced_moves = false;                // ... a forced decode's: k_forced_moves does; either writes through moves_out, [B,L-1]
+  bool records() const { return moves || call_moves || forced_moves; }      // the decode leaves step_moves records
   const int* labels = nullptr;              // a forced decode feeds these label rows [B,L] (device: the caller's, or d_forced) instead of its argmax
   ScoreArgs score{};                        // ... and scores them: omit_mask and the output addresses (device: the caller's, or the d_sc_* buffers; null = not asked for)
   const DecMembers* members = nullptr;      // the member table of a group's internal call
@@ -315,7 +321,7 @@ struct SlabCtx {
   FormLog lforms;                           // the kernel instantiations it launched ("kernel_forms"); lforms_ok = 0: it ran as a slab graph
   int lforms_ok = 1;
   std::map<GraphKey, FormLog> graph_forms;  // ... those a captured decode graph of `graphs` launches (recorded at its capture)
-  struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false, all = false, moves = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
+  struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false, all = false, moves = false, cmoves = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
 
   // window calls (rv_beam_search_windows*): the resolved table of the call this context runs, [cap] rows -- written by the host into
   // pinned staging when the call is queued (a group: as its members come), copied to the device in front of the call's first kernel
@@ -672,14 +678,14 @@ Plan plan_call(const SlabCtx* cx, const Call& call, const CallParts& res) {
   //      (score_t = values_t . (W_mem q)), and the persistent decode needs neither keys nor the per-step kernels; a moves call on the
   //      per-step kernels forms its alignments in the two-pass attend, beside the single-pass one where that runs the step
   p.flash = h->cfg.attention == RV_ATT_LUONG && o.flash && (call.greedy ? 1 : call.W) <= 5;      // wider beams: register budget -> two-pass
-  p.keys = (!p.flash && p.persist < 0) || cx->taps() || (res.moves && p.persist < 0);
+  p.keys = (!p.flash && p.persist < 0) || cx->taps() || (res.records() && p.persist < 0);
   // A window call: the default path gathers each chunk in the lane of its layer-0 recurrence; every other form -- the packed-FMA
   // recurrence, "lane_projection" 0, the per-step decode, taps, profiling, a group with "group_inplace" 0 -- runs unchanged behind
   // k_expand_windows, which writes the padded chunk tensors into the context's input buffers
   p.win_lane = call.windows && !gru && p.wide && (h->cfg.mode == RV_MODE_RAW || lane_layer0(h, 5, call.T_e)) && quiet && p.persist >= 0 &&
                !(cx->grp && !o.group_inplace);      // (k_gru_rec_mx gathers no windows: a GRU handle's window call runs behind k_expand_windows)
   // A slab graph: the default path only -- matrix-pipe recurrences + persistent decode, no profiling, no taps
-  p.graphable = o.slab_graph && !gru && !call.windows && p.wide && !p.rows8 && p.persist >= 0 && quiet && !res.whole_beam && !res.labels &&
+  p.graphable = o.slab_graph && !gru && !call.windows && p.wide && !p.rows8 && p.persist >= 0 && quiet && !res.whole_beam && !res.labels && !res.records() &&
                 !cx->ptaps() && !cx->rec_ts && !cx->dec_st.dbg_ts && cx->d_ptab;
   return p;
 }
@@ -727,11 +733,11 @@ int enqueue(SlabCtx* cx, const Call& stated, const CallParts& res) {
   const bool greedy = call.greedy, dev_out = call.dev_out, calls = call.lut != nullptr;
   HIPCHK(h, hipSetDevice(c.device));
   cx->lB = B; cx->fact.lW = W; cx->lL = L; cx->lgreedy = greedy; cx->lTm = T_r + T_e; cx->ltaps = cx->taps(); cx->lptaps = cx->ptaps();
-  cx->lmoves = res.moves ? 1 : 0;
+  cx->lmoves = res.records() ? 1 : 0;
   if (cx->own()) h->lS = 0;
   cx->lforms.n = 0; cx->lforms.full = false; cx->lforms_ok = 1;
   cx->pend = SlabCtx::PendingCall{};
-  cx->pend.busy = true; cx->pend.greedy = greedy; cx->pend.dev_out = dev_out; cx->pend.calls = calls; cx->pend.all = res.whole_beam; cx->pend.moves = res.moves;
+  cx->pend.busy = true; cx->pend.greedy = greedy; cx->pend.dev_out = dev_out; cx->pend.calls = calls; cx->pend.all = res.whole_beam; cx->pend.moves = res.moves; cx->pend.cmoves = res.call_moves;
   cx->pend.B = B; cx->pend.steps = std::max(L - 1, 0); cx->pend.V = c.vocab; cx->pend.Wd = greedy ? 1 : W;
   if (B == 0 || L <= 1) {
     cx->pend.trivial = true;
@@ -969,7 +975,7 @@ int fill_dec_state(SlabCtx* cx, Slab& sl) {
     if (need) HIPCHK(h, hipMemsetAsync(cx->palign, 0xff, need * sizeof(float), s));
     d.persist_align = cx->palign;
   }
-  d.step_moves = sl.res.moves ? cx->d_step_moves : nullptr;
+  d.step_moves = sl.res.records() ? cx->d_step_moves : nullptr;
   d.Tr = sl.call.T_r;      // (effective lengths: T_m in raw mode, 0 in event mode)
   d.moves_only = 0;
   return RV_OK;
@@ -1192,6 +1198,21 @@ int finalize_and_score(SlabCtx* cx, const Slab& sl) {
       launch_dec_finalize_moves(sl.part[g], o, s);
     }
   }
+  if (sl.res.call_moves || sl.res.forced_moves) {      // [B,L-1]: behind k_dec_finalize, which left the tokens and S of every part
+    Scope sc(cx, sl.res.call_moves ? "dec_finalize_calls_moves" : "forced_moves");
+    for (int g = 0; g < parts.n; ++g) {
+      const size_t off = (parts.n == 1 ? 0 : (size_t)B * g / parts.n) * steps;
+      MovesOut o = sl.res.moves_out;
+      if (o.raw_pos) o.raw_pos += off;
+      if (o.raw_mass) o.raw_mass += off;
+      if (o.event_pos) o.event_pos += off;
+      if (o.event_mass) o.event_mass += off;
+      if (o.peak) o.peak += off;
+      if (o.peak_weight) o.peak_weight += off;
+      if (sl.res.call_moves) launch_dec_finalize_calls_moves(sl.part[g], tk + off, o, s);
+      else launch_forced_moves(sl.part[g], o, s);
+    }
+  }
   if (d.forced) {      // the forced decode's labels target[:, 1:] against the logits the finalize kernel just wrote
     ScoreArgs a = sl.res.score;
     a.logits = o2; a.labels = d.forced + 1; a.label_stride = L; a.B = B; a.S = steps; a.V = V; a.pad_token = c.pad_token; a.pred = nullptr;
@@ -1226,6 +1247,12 @@ int stage_outputs(SlabCtx* cx, const Slab& sl) {
     HIPCHK(h, hipMemcpyAsync(cx->pin_tok, sl.call.tokens, sizeof(int32_t) * B * steps, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(cx->pin_out2, sl.call.out2, sizeof(float) * B * steps * (greedy ? V : 1), hipMemcpyDeviceToHost, s));
   }
+  if (sl.res.call_moves || (sl.res.forced_moves && !dev_out)) {
+    const MovesOut &m = sl.res.moves_out, &q = cx->pin_moves;
+    const void* src[6] = {m.raw_pos, m.raw_mass, m.event_pos, m.event_mass, m.peak, m.peak_weight};
+    void* dst[6] = {q.raw_pos, q.raw_mass, q.event_pos, q.event_mass, q.peak, q.peak_weight};
+    for (int i = 0; i < 6; ++i) if (src[i]) HIPCHK(h, hipMemcpyAsync(dst[i], src[i], 4 * (size_t)B * steps, hipMemcpyDeviceToHost, s));
+  }
   if (calls) {
     HIPCHK(h, hipMemcpyAsync(cx->pin_bases, cx->d_bases, (size_t)B * steps, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(cx->pin_probs, cx->d_probs, sizeof(float) * B * steps, hipMemcpyDeviceToHost, s));
@@ -1252,7 +1279,7 @@ int record_slab(SlabCtx* cx, const Call& call, const CallParts& res, const Plan&
 
 // The rest of a call: wait for the context's stream, hand the staged results to the caller's host buffers.
 int finish(SlabCtx* cx, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr,
-           const RvMoves* moves = nullptr) {
+           const RvMoves* moves = nullptr, const RvCallMoves* cmoves = nullptr) {
   RvContext* const h = cx->h;
   if (!S_out) return RV_EINVAL;
   if (!cx->pend.busy) return fail(h, RV_ESTATE, "no call to collect on this context");
@@ -1264,6 +1291,11 @@ int finish(SlabCtx* cx, int32_t* tokens, float* out2, const CallsOut* calls, int
   if (p.moves != (moves != nullptr) && !(p.moves && p.dev_out))      // (the ticket stays in flight)
     return fail(h, RV_EINVAL, p.moves ? "this call hands out the moves: collect it with rv_beam_search_collect_moves"
                                       : "rv_beam_search_collect_moves takes the tickets of rv_beam_search_submit_moves");
+  if (p.cmoves != (cmoves != nullptr))      // (the ticket stays in flight)
+    return fail(h, RV_EINVAL, p.cmoves ? "this call hands out the positions of its calls: collect it with rv_beam_search_collect_calls_moves"
+                                       : "rv_beam_search_collect_calls_moves takes the tickets of rv_beam_search_submit_windows_calls_moves");
+  if (p.cmoves && !p.trivial && !cmoves->raw_pos && !cmoves->raw_mass && !cmoves->event_pos && !cmoves->event_mass && !cmoves->peak && !cmoves->peak_weight)
+    return fail(h, RV_EINVAL, "null output pointer");
   if (p.moves && !p.dev_out && !p.trivial && !moves->raw_pos && !moves->raw_mass && !moves->event_pos && !moves->event_mass && !moves->peak && !moves->peak_weight)
     return fail(h, RV_EINVAL, "null output pointer");
   cx->pend.busy = false;
@@ -1306,6 +1338,12 @@ int finish(SlabCtx* cx, int32_t* tokens, float* out2, const CallsOut* calls, int
     memcpy(calls->bases, cx->pin_bases, B * steps);
     memcpy(calls->probs, cx->pin_probs, sizeof(float) * B * steps);
     memcpy(calls->lengths, cx->pin_clen, sizeof(int) * B);
+  }
+  if (p.cmoves) {
+    const MovesOut& m = cx->pin_moves;
+    const void* src[6] = {m.raw_pos, m.raw_mass, m.event_pos, m.event_mass, m.peak, m.peak_weight};
+    void* dst[6] = {cmoves->raw_pos, cmoves->raw_mass, cmoves->event_pos, cmoves->event_mass, cmoves->peak, cmoves->peak_weight};
+    for (int i = 0; i < 6; ++i) if (dst[i]) memcpy(dst[i], src[i], 4 * B * steps);
   }
   drain_profile(cx);
   *S_out = S;
@@ -1391,6 +1429,41 @@ int begin_moves(SlabCtx* ctx, const Call& call, CallParts& res) {
     if (mv && !mv->peak_weight) res.moves_out.peak_weight = nullptr;
   }
   res.moves = true;
+  return RV_OK;
+}
+
+// Before enqueue() of a calls-with-positions call on `ctx`: its records, and where k_dec_finalize_calls_moves writes -- always the
+// context's own buffers (host outputs).  call.call_moves null = every output (an asynchronous call: what is asked for is known at its collect)
+int begin_call_moves(SlabCtx* ctx, const Call& call, CallParts& res) {
+  const RvCallMoves* mv = call.call_moves;
+  TRY(ensure_moves_buffers(ctx, true));
+  res.moves_out = ctx->d_moves;
+  if (mv && !mv->raw_pos) res.moves_out.raw_pos = nullptr;
+  if (mv && !mv->raw_mass) res.moves_out.raw_mass = nullptr;
+  if (mv && !mv->event_pos) res.moves_out.event_pos = nullptr;
+  if (mv && !mv->event_mass) res.moves_out.event_mass = nullptr;
+  if (mv && !mv->peak) res.moves_out.peak = nullptr;
+  if (mv && !mv->peak_weight) res.moves_out.peak_weight = nullptr;
+  res.call_moves = true;
+  return RV_OK;
+}
+
+// Before enqueue() of a forced decode with moves (after begin_forced): its records, and where k_forced_moves writes
+int begin_forced_moves(SlabCtx* ctx, const Call& call, CallParts& res) {
+  const RvMoves* mv = call.forced_moves;
+  TRY(ensure_moves_buffers(ctx, !call.dev_out));
+  if (call.dev_out) {
+    res.moves_out = MovesOut{mv->raw_pos, mv->raw_mass, mv->event_pos, mv->event_mass, mv->peak, mv->peak_weight};
+  } else {
+    res.moves_out = ctx->d_moves;
+    if (!mv->raw_pos) res.moves_out.raw_pos = nullptr;
+    if (!mv->raw_mass) res.moves_out.raw_mass = nullptr;
+    if (!mv->event_pos) res.moves_out.event_pos = nullptr;
+    if (!mv->event_mass) res.moves_out.event_mass = nullptr;
+    if (!mv->peak) res.moves_out.peak = nullptr;
+    if (!mv->peak_weight) res.moves_out.peak_weight = nullptr;
+  }
+  res.forced_moves = true;
   return RV_OK;
 }
 
@@ -1510,11 +1583,20 @@ int run(RvContext* h, const Call& call, int32_t* S_out) {
   CallParts res;
   if (call.whole_beam) TRY(begin_all_beams(ctx, call, res));
   if (call.want_moves) TRY(begin_moves(ctx, call, res));
+  if (call.want_call_moves) TRY(begin_call_moves(ctx, call, res));
   if (call.forced) TRY(begin_forced(ctx, call, res));
+  if (call.forced_moves) TRY(begin_forced_moves(ctx, call, res));
   const int rc = enqueue(ctx, call, res);
   if (rc != RV_OK) { ctx->pend.busy = false; return rc; }   // (ctx was idle on entry: the flag is this call's)
-  int rf = finish(ctx, call.tokens, call.out2, calls, S_out, call.beams, call.moves);
+  int rf = finish(ctx, call.tokens, call.out2, calls, S_out, call.beams, call.moves, call.call_moves);
   if (call.forced && rf == RV_OK) rf = fetch_scores(h, res.score, call.forced->out, call.dev_out, call.B, call.L - 1);
+  if (call.forced_moves && rf == RV_OK && !call.dev_out && call.B > 0 && call.L > 1) {      // staged by stage_outputs; the stream has drained
+    const MovesOut& m = ctx->pin_moves;
+    const RvMoves* o = call.forced_moves;
+    const void* src[6] = {m.raw_pos, m.raw_mass, m.event_pos, m.event_mass, m.peak, m.peak_weight};
+    void* dst[6] = {o->raw_pos, o->raw_mass, o->event_pos, o->event_mass, o->peak, o->peak_weight};
+    for (int i = 0; i < 6; ++i) if (dst[i]) memcpy(dst[i], src[i], 4 * (size_t)call.B * (call.L - 1));
+  }
   h->lS = *S_out;      // (whichever slot it ran on: finish() leaves the two equal on slot 0)
   return rf;
 }
@@ -2498,7 +2580,7 @@ static int submit(rv_handle h, const Call& call, int32_t* ticket) {
     if (uncollected(h) >= depth)
       return fail(h, RV_ESTATE, "all %d asynchronous slots hold uncollected calls (option async_depth): collect one first", depth);
     h->inflight_hint = depth;
-    if (n_co >= 2 && !call.whole_beam && coalescible(h, ok))
+    if (n_co >= 2 && !call.whole_beam && !call.want_call_moves && coalescible(h, ok))
       return submit_group(h, n_co, ok, ticket);
     flush_open_group(h);      // a slab of another path: the group goes as it is, this slab on a context of its own
   }
@@ -2517,6 +2599,7 @@ static int submit(rv_handle h, const Call& call, int32_t* ticket) {
   CallParts res;
   if (call.whole_beam) TRY(begin_all_beams(ctx, call, res));
   if (call.want_moves) TRY(begin_moves(ctx, call, res));
+  if (call.want_call_moves) TRY(begin_call_moves(ctx, call, res));
   const int rc = enqueue(ctx, call, res);
   if (rc != RV_OK) { ctx->pend.busy = false; return rc; }
   h->next_slot = (slot + 1) % depth;
@@ -2525,11 +2608,12 @@ static int submit(rv_handle h, const Call& call, int32_t* ticket) {
   return RV_OK;
 }
 static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr,
-                   const RvMoves* moves = nullptr) {
+                   const RvMoves* moves = nullptr, const RvCallMoves* cmoves = nullptr) {
   if (!h || !S_out) return RV_EINVAL;
   const int slot = ticket & 15;
   if (ticket >= 0 && h->ticks[slot].busy && h->ticks[slot].ticket == ticket) {
     if (moves) return fail(h, RV_EINVAL, "rv_beam_search_collect_moves takes the tickets of rv_beam_search_submit_moves");
+    if (cmoves) return fail(h, RV_EINVAL, "rv_beam_search_collect_calls_moves takes the tickets of rv_beam_search_submit_windows_calls_moves");
     if (beams) return fail(h, RV_EINVAL, "rv_beam_search_collect_all takes the tickets of rv_beam_search_submit_all");      // (a group never holds one)
     const int rc = collect_group(h, slot, tokens, out2, calls, S_out);
     if (!(h->ticks[slot].busy && h->ticks[slot].ticket == ticket)) release_reads(h, ticket);      // (the ticket is gone: its reads may be dropped)
@@ -2538,7 +2622,7 @@ static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, co
   if (ticket < 0 || slot >= (int)h->slabs.size()) return fail(h, RV_EINVAL, "unknown ticket %d", ticket);
   SlabCtx* ctx = h->slabs[slot];
   if (!ctx->pend.busy || ctx->pend.ticket != ticket) return fail(h, RV_ESTATE, "ticket %d is not in flight (collected already?)", ticket);
-  const int rc = finish(ctx, tokens, out2, calls, S_out, beams, moves);
+  const int rc = finish(ctx, tokens, out2, calls, S_out, beams, moves, cmoves);
   if (!(ctx->pend.busy && ctx->pend.ticket == ticket)) release_reads(h, ticket);
   return rc;
 }
@@ -2700,6 +2784,73 @@ int rv_beam_search_collect_moves(rv_handle h, int32_t ticket, const RvBeams* out
   if (!h) return RV_EINVAL;
   if (!out || !moves) return fail(h, RV_EINVAL, "null output pointer");      // (all six null: refused at the ticket, which knows whether anything ran)
   return collect(h, ticket, nullptr, nullptr, nullptr, S_out, out, moves);
+}
+
+// ---- calls with positions (k_dec_finalize_calls_moves behind k_dec_finalize): the calls' outputs and lut as rv_beam_search_calls';
+// every member of `moves` may be null, not all
+static bool call_moves_missing(const RvCallMoves* m, int B, int L) {      // (an empty tensor has no address)
+  return !m || (B > 0 && L > 1 && !m->raw_pos && !m->raw_mass && !m->event_pos && !m->event_mass && !m->peak && !m->peak_weight);
+}
+int rv_beam_search_calls_moves(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                               const uint8_t* lut, uint8_t* bases, int32_t* lengths, float* probs, const RvCallMoves* moves, int32_t* S_out) {
+  if (!h) return RV_EINVAL;
+  if (call_moves_missing(moves, B, L)) return fail(h, RV_EINVAL, "null output pointer");
+  const CallsOut co{lut, bases, lengths, probs};
+  Call c = slab_call(raw, event, false, B, T_r, T_e, W, L);
+  c.lut = lut; c.calls = &co; c.want_call_moves = true; c.call_moves = moves;
+  return run(h, c, S_out);
+}
+int rv_beam_search_windows_calls_moves(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                       const uint8_t* lut, uint8_t* bases, int32_t* lengths, float* probs, const RvCallMoves* moves,
+                                       int32_t* S_out) {
+  if (!h) return RV_EINVAL;
+  if (call_moves_missing(moves, B, L)) return fail(h, RV_EINVAL, "null output pointer");
+  std::vector<RecWindow> rows; std::vector<int> ids; Call c;
+  TRY(windows_call(h, win, B, T_r, T_e, W, L, rows, ids, c));
+  const CallsOut co{lut, bases, lengths, probs};
+  c.lut = lut; c.calls = &co; c.want_call_moves = true; c.call_moves = moves;
+  return run(h, c, S_out);
+}
+int rv_beam_search_submit_windows_calls_moves(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                              const uint8_t* lut, int32_t* ticket) {
+  if (!lut) return h ? fail(h, RV_EINVAL, "null lut") : RV_EINVAL;
+  std::vector<RecWindow> rows; std::vector<int> ids; Call c;
+  TRY(windows_call(h, win, B, T_r, T_e, W, L, rows, ids, c));
+  c.lut = lut; c.want_call_moves = true;
+  TRY(submit(h, c, ticket));
+  hold_reads(h, *ticket, ids);
+  return RV_OK;
+}
+int rv_beam_search_collect_calls_moves(rv_handle h, int32_t ticket, uint8_t* bases, int32_t* lengths, float* probs, const RvCallMoves* moves,
+                                       int32_t* S_out) {
+  if (!h) return RV_EINVAL;
+  if (!moves) return fail(h, RV_EINVAL, "null output pointer");      // (all six null: refused at the ticket, which knows whether anything ran)
+  const CallsOut c{nullptr, bases, lengths, probs};
+  return collect(h, ticket, nullptr, nullptr, &c, S_out, nullptr, nullptr, moves);
+}
+
+// ---- forced alignment: the forced decode with its records kept, k_forced_moves behind the finalize
+int rv_teacher_forced_moves(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t L,
+                            const int32_t* targets, uint32_t omit_mask, int32_t* sample_id, float* logits, const RvScore* out,
+                            const RvMoves* moves) {
+  if (!h) return RV_EINVAL;
+  if (moves_missing(moves, B, L)) return fail(h, RV_EINVAL, "null output pointer");
+  const ForcedCall fc{targets, omit_mask, out};
+  Call c = slab_call(raw, event, false, B, T_r, T_e, 1, L);
+  c.greedy = true; c.tokens = sample_id; c.out2 = logits; c.forced = &fc; c.forced_moves = moves;
+  int32_t S = 0;
+  return run(h, c, &S);
+}
+int rv_teacher_forced_moves_dev(rv_handle h, const float* d_raw, const float* d_event, int32_t B, int32_t T_r, int32_t T_e, int32_t L,
+                                const int32_t* d_targets, uint32_t omit_mask, int32_t* d_sample_id, float* d_logits, const RvScore* d_out,
+                                const RvMoves* d_moves) {
+  if (!h) return RV_EINVAL;
+  if (moves_missing(d_moves, B, L)) return fail(h, RV_EINVAL, "null output pointer");
+  const ForcedCall fc{d_targets, omit_mask, d_out};
+  Call c = slab_call(d_raw, d_event, true, B, T_r, T_e, 1, L);
+  c.greedy = true; c.tokens = d_sample_id; c.out2 = d_logits; c.forced = &fc; c.forced_moves = d_moves;
+  int32_t S = 0;
+  return run(h, c, &S);
 }
 
 int rv_beam_search_flush(rv_handle h) {

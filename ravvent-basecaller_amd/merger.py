@@ -121,6 +121,18 @@ class StreamingMerger:
             raise ValueError(f"rv_merger_result: {_ERR.get(rc, rc)}")
         return out_s[:m.value].tobytes().decode("ascii"), out_p[:m.value].copy()
 
+    def sources(self):
+        """(chunk, index) int32 arrays, one pair per base of `result()`: the chunk the base was called in, counted from 0 over all
+        appends, and its index within that chunk's call (rv_merger_sources)."""
+        m = ctypes.c_int64(0)
+        self._lib.rv_merger_sources(self._h, None, None, 0, ctypes.byref(m))
+        chunk, index = np.empty(max(m.value, 1), np.int32), np.empty(max(m.value, 1), np.int32)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = self._lib.rv_merger_sources(self._h, p(chunk), p(index), chunk.size, ctypes.byref(m))
+        if rc != 0:
+            raise ValueError(f"rv_merger_sources: {_ERR.get(rc, rc)}")
+        return chunk[:m.value].copy(), index[:m.value].copy()
+
     def close(self):
         if self._h:
             self._lib.rv_merger_destroy(self._h)
@@ -140,14 +152,26 @@ class Merger():
         self.scores_id = scores_id
         self.overlap_seq_len = 25
 
-    def merge_arrays(self, bases: np.ndarray, probs: np.ndarray, lengths: Sequence[int]):
-        """bases u8 [n, stride], probs f32 [n, stride], lengths [n] -> (merged str, f32 array)."""
+    def merge_arrays(self, bases: np.ndarray, probs: np.ndarray, lengths: Sequence[int], sources: bool = False):
+        """bases u8 [n, stride], probs f32 [n, stride], lengths [n] -> (merged str, f32 array).  sources=True: the same two, then
+        the (chunk, index) int32 arrays of `StreamingMerger.sources` -- where each merged base was called."""
         lib = _capi.load_library()
         bases = np.ascontiguousarray(bases, np.uint8)
         probs = np.ascontiguousarray(probs, np.float32)
         lengths = np.ascontiguousarray(lengths, np.int32)
         n, stride = bases.shape
         assert probs.shape == bases.shape and lengths.shape == (n,)
+        if sources:
+            if n < 1:
+                raise ValueError(f"rv_merge_calls: {_ERR[-1]}")
+            sm = StreamingMerger(self.scores_id, self.overlap_seq_len)
+            try:
+                sm.append(bases, probs, lengths)
+                seq, out = sm.result()
+                chunk, index = sm.sources()
+            finally:
+                sm.close()
+            return seq, out, chunk, index
         cap = int(lengths.sum()) + 2 * self.overlap_seq_len * n + 1     # every merge adds at most `overlap` gap columns
         out_s, out_p = np.empty(cap, np.uint8), np.empty(cap, np.float32)
         m = ctypes.c_int64(0)
