@@ -463,7 +463,7 @@ int rv_teacher_forced_moves_dev(rv_handle h, const float* d_raw, const float* d_
  *                       per group: depth 10 in groups of five on 4 queues.  Results do not depend on it.  Other values fail with RV_EINVAL),
  *          "slab_graph" (0/1, default 0: a call on the default path -- matrix-pipe recurrences, persistent decode, no profiling, no taps --
  *                       replays as ONE hipGraphLaunch per slab (captured per slab context and call shape; the caller's input / output
- *                       addresses reach the kernels through a table in mapped pinned memory) instead of eight kernel launches (nine with "fused_memory" 0, one more with "lane_projection" 0): half the
+ *                       addresses reach the kernels through a table in mapped pinned memory) instead of eight kernel launches (six where "fused_inproj" takes the projecting form: a stream of slabs; nine with "fused_memory" 0, one more with "lane_projection" 0): half the
  *                       host time per call (24 us against 46), but the replayed slabs stream 1.5-3 % slower on ROCm 7.2, so it is off
  *                       unless a caller's host thread is the bottleneck; results are identical),
  *          "persistent_decode" (0/1, default 1: Luong beam search (beam <= 8; <= 5 with two decoder cells) and greedy search, no
@@ -487,6 +487,17 @@ int rv_teacher_forced_moves_dev(rv_handle h, const float* d_raw, const float* d_
  *                       prologue of its own workgroup, with the arithmetic of the split GEMM, straight into the resident fragments: no
  *                       `gemm_memory` launch and no [B,T_m,2u] tensor written and read back.  0 = the GEMM launch in front of the decode,
  *                       which every other form of the decode keeps in either case.  Results are identical bit for bit),
+ *          "fused_inproj" (1/0/-1, default -1: BiLSTM layers >= 1 of a call on the sixteen-chunk matrix-pipe recurrence ("wide_recurrence" 1, or -1
+ *                       where it picks that form; both encoders, any encoder depth) compute x . W + b on their own MFMAs from the previous
+ *                       layer's output (k_lstm_rec_mx_proj): no `gemm_inproj_*` launch and no [B,T,2,4u] tensor written and read back; the
+ *                       launch keeps the scope names `lstm_rec_raw_l1p` / `lstm_rec_event_l1p`.  1 = wherever the call runs the sixteen-chunk form (with "wide_recurrence" -1 a call that picks the eight-chunk form or the packed-FMA
+ *                       path keeps its projection, without notice), 0 = never (the GEMM launch in front
+ *                       of the layer), -1 = per call: the projecting form when the slabs in flight hold 1,280 chunks or more (chunks of the call
+ *                       x "async_depth"; a coalesced group: its first member's), the two launches below that -- one isolated slab is a latency
+ *                       chain that the GEMM plus the shorter steps win, a stream is bound by CU-time that the projecting form saves.  Results are
+ *                       identical bit for bit, whichever form runs.  The bigru family, the eight-chunk form ("wide_recurrence" 2) and the
+ *                       packed-FMA path ("wide_recurrence" 0) keep their projection: an explicit 1 on a bigru handle or with one of those
+ *                       values in force -- and one of those values with an explicit 1 in force -- fails with RV_EUNSUPPORTED and changes nothing),
  *          "weight_parts" (2/1, default 2; any other value fails with RV_EINVAL, and setting it with calls in flight with RV_ESTATE.
  *                       In force from the next rv_load_weights.  2: every dense weight enters the matrix pipe as two f16 parts, fp32
  *                       accuracy.  1: every weight tensor that rv_load_weights turns into a split-f16 image is first rounded to what
@@ -549,6 +560,8 @@ int rv_set_option(rv_handle h, const char* key, int32_t value);
  *   "kernel_form_list_1p" [n,5]   the one-part forms of the persistent decode (option "weight_parts" 1), a list of their own: rows
  *                                 (8, W, NIT, 1, ATT) for k_dec_persist_1p<W, NIT, ATT>.  "kernel_forms" reports a launched one under
  *                                 the same kernel id 8
+ *   "kernel_form_list_proj" [n,5] the projecting matrix-pipe recurrence (option "fused_inproj"), a list of its own: the row (12, 16, 0, 0, 0)
+ *                                 for k_lstm_rec_mx_proj.  "kernel_forms" / "group_kernel_forms" report a launched one under kernel id 12
  *   "group_kernel_forms" [n,5]    the instantiations the last coalesced group of asynchronous calls (option "coalesce") launched on its
  *                                 own context, in the same rows; empty before the first group
  *   "coalesce_stats"  [4]         of the handle since it was created: groups launched (option "coalesce"), slabs they held, members of the

@@ -28,6 +28,7 @@ enum {
   RV_K_GRU_REC_MX = 9,         // k_gru_rec_mx<F, CH> (a GRU handle only: rv_create_rnn)
   RV_K_DEC_CELL_GRU = 10,      // k_dec_cell_gru: no parameters
   RV_K_DEC_PERSIST_GRU = 11,   // k_dec_persist_gru<W, NIT, ATT>: (W, NIT, 1, ATT); a GRU handle under option gru_persistent 1 only
+  RV_K_LSTM_REC_MX_PROJ = 12,  // k_lstm_rec_mx_proj: (CH) = (16); launched under option fused_inproj only, a list of its own
 };
 #define RV_FORM_ROWS 512
 struct FormLog {
@@ -49,6 +50,7 @@ struct FormLog {
 // every instantiation the form lists hold, whatever a call would pick (the lists are walked; no kernel is named)
 void list_rec_forms(FormLog& log);
 void list_mx_forms(FormLog& log);
+void list_mx_proj_forms(FormLog& log);     // the projecting matrix-pipe recurrence (option fused_inproj): a list of its own ("kernel_form_list_proj")
 void list_decode_forms(FormLog& log);
 void list_decode_forms_1p(FormLog& log);   // the one-part forms of the persistent decode: a list of their own ("kernel_form_list_1p")
 void list_decode_forms_gru(FormLog& log);  // the persistent decode of a GRU cell: listed on a GRU handle's "kernel_form_list" only
@@ -105,6 +107,10 @@ void launch_lstm_rec_proj(const RecArgs& a, int rows_per_block, hipStream_t s, F
 #define RV_MX_ROWS 16
 #define RV_UA_SLOT ((size_t)2 * RV_U * RV_G + 2 * RV_G)
 void launch_lstm_rec_mx(const RecArgs& a, int F, hipStream_t s, bool rows8 = false, FormLog* log = nullptr);   // rows8: eight chunks per workgroup (latency form)
+// The projecting form for layers >= 1 (option fused_inproj; sixteen chunks per workgroup only): a.x = the previous layer's output
+// act [B*T,256], a.Wh[0] = the split GEMM's image of the layer's input kernels (Wx16: both directions, RV_WX16_SLOT), a.bias[0] = their
+// biases [b_fwd | b_bwd] (bx2).  No xw tensor: the results are those of launch_gemm_split_blocks + launch_lstm_rec_mx(F = 0), bit for bit.
+void launch_lstm_rec_mx_proj(const RecArgs& a, hipStream_t s, FormLog* log = nullptr);
 bool lstm_rec_mx_window_fits(int T, int F = 1);   // layer 0 with its input projection in the lane: do the input windows of a workgroup's chunks fit in LDS?
 hipError_t configure_mx_kernels();
 // The padded chunk tensors of a window table, written on the device (k_expand_windows): raw [B,T_r,1] from the rows' raw windows (null:

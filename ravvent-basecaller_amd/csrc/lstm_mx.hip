@@ -304,6 +304,221 @@ __global__ __launch_bounds__(512) void k_lstm_rec_mx_members(RecArgs a) { rec_mx
 template <int F, int CH>
 __global__ __launch_bounds__(512) void k_lstm_rec_mx_windows(RecArgs a) { rec_mx_body<F, CH, SRC_WINDOWS>(a); }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The PROJECTING form for layers >= 1 (option fused_inproj): the sixteen-chunk recurrence computes x_t . W + b itself, on its own MFMAs,
+// from the previous layer's output act [B*T, 256] -- no k_gemm_ws launch and no xw [B,T,2,512] round trip through HBM (315 MB written and
+// read back per C3 raw layer).  A body of its own, so that the six forms above keep their instruction streams.
+//   * The split GEMM issues mfma(weight fragment, activation fragment): lane (chunk n, q) of its transposed tile ends with gate columns
+//     16 nt + 4 q + 0..3 of row n -- with nt = w, column block cb = 2 dir + g / 2 and half hb = g & 1 that IS the recurrence's C/D map
+//     (units 16 w + 4 q + 0..3 of gate g).  Wave w's projection of a timestep leaves in every lane the 16 floats the lane adds to its
+//     gate sums: no LDS block, no exchange.  The (k-step, gate) fragment pair of wave w is 2 KB contiguous in the GEMM's own image Wx16,
+//     at cb 262144 + ks 32768 + hb 16384 + (2 w + part) 1024 + lane 16; the column factors follow the image, the biases are bx2.
+//   * TWO timesteps per pass (MXP_NT): in front of every pair of steps one pass projects the pair's two timesteps (in walking order) into
+//     32 registers, where the form <0, 16> keeps its ring of pre-projected inputs; each streamed weight fragment meets two activation
+//     fragments: 512 KB from L2 per pass and workgroup, 256 KB per step.  (Three per pass -- 48 accumulators, 171 KB per step -- do not fit
+//     beside U's 128 registers without scratch: 36 to 212 B per lane in every schedule tried, profiles/fused_inproj.md.)
+//   * The activations reach the pass as B fragments of two f16 parts (the GEMM's split: sv = 2^14 v, hi = f16(sv), lo = f16(sv - hi)) in
+//     LDS, [2 buffers][2 timesteps][2 parts][32 k-blocks of 8][16 chunks][8 f16] = 2 x 32 KB, converted once per workgroup: thread
+//     (chunk tid % 16, k-block tid / 16) moves eight floats per timestep.  Step s converts the row of walking position s + 2, requested
+//     one step earlier (eight registers in flight, across the pass too), into the next pass's buffer and requests position s + 3: every
+//     request has a whole step or more to come back from HBM, and a pass's two timesteps are in LDS behind the barrier of the step before it.
+//   * Every xin element keeps k_gemm_ws's chain -- k in eight steps of 32, per step w_lo a_hi, w_hi a_lo, w_hi a_hi into one f32
+//     accumulator, then fmaf(acc, column factor, bias) -- and the step is the one above: the results are those of the two launches bit
+//     for bit (tests/test_fused_inproj_gpu.py), which is what lets a call choose the form.
+// RecArgs: x = act [B*T, 256], Wh[0] = the layer's Wx16 image (both directions), bias[0] = its bx2 [1024]; Ua, h0 .. cT, out as above.
+constexpr int MXP_NT = 2;                                         // timesteps per projection pass
+constexpr int MXP_FRAG = MXP_NT * 2 * 32 * 16 * 16;               // one fragment buffer: 16 KB per timestep
+constexpr int MXP_LDS = 16384 + 3 * RV_G * (int)sizeof(float) + 2 * MXP_FRAG;
+constexpr int MXP_RING = 3;                                       // (k-step, gate) weight fragment pairs in flight per wave (four: 16 B of scratch)
+
+__global__ __launch_bounds__(512) void k_lstm_rec_mx_proj(RecArgs a) {
+  extern __shared__ __align__(16) char mxsm[];
+  char* hb = mxsm;                                               // the h image, as above
+  float* dss = reinterpret_cast<float*>(mxsm + 16384);           // [512] 2^-14 / s_r
+  float* css = dss + RV_G;                                       // [512] the projection's column factors of this direction
+  float* bss = css + RV_G;                                       // [512] ... and its biases
+  char* frag = mxsm + 16384 + 3 * RV_G * sizeof(float);          // the two fragment buffers
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = lane & 15, q = lane >> 4;
+  const int dir = blockIdx.y, b0 = blockIdx.x * 16, T = a.T;
+  const int bc = min(b0 + n, a.B - 1);                           // rows beyond the slab compute on a copy of its last chunk, never stored
+  const bool live = b0 + n < a.B;
+  const int u0 = 16 * w + 4 * q;
+
+  float4 ua[4][4][2];
+  {
+    const float4* src = reinterpret_cast<const float4*>(a.Ua[dir]) + (size_t)w * (4 * 4 * 2 * 64) + lane;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) ua[g][ks][p] = src[((g * 4 + ks) * 2 + p) * 64];
+  }
+  const char* img = reinterpret_cast<const char*>(a.Wh[0]);
+  {
+    const float* dsg = reinterpret_cast<const float*>(a.Ua[dir] + (size_t)2 * RV_U * RV_G);
+    dss[tid] = dsg[tid];
+    css[tid] = reinterpret_cast<const float*>(img + (size_t)4 * 262144)[dir * RV_G + tid];
+    bss[tid] = a.bias[0][dir * RV_G + tid];
+  }
+  float c[4];
+  {
+    float4 h0{0.f, 0.f, 0.f, 0.f}, c0{0.f, 0.f, 0.f, 0.f};
+    if (a.h0[dir]) { h0 = *reinterpret_cast<const float4*>(a.h0[dir] + (size_t)bc * RV_U + u0); c0 = *reinterpret_cast<const float4*>(a.c0[dir] + (size_t)bc * RV_U + u0); }
+    const float hv0[4] = {h0.x, h0.y, h0.z, h0.w}, cv0[4] = {c0.x, c0.y, c0.z, c0.w};
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    h4 hi, lo;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { c[i] = cv0[i]; const float sv = hv0[i] * 16384.f; hi[i] = (_Float16)sv; lo[i] = (_Float16)(sv - (float)hi[i]); }
+    char* dst = hb + ((2 * w + (q >> 1)) * 16 + n) * 16 + (q & 1) * 8;
+    *reinterpret_cast<h4*>(dst) = hi; *reinterpret_cast<h4*>(dst + 4096) = lo;
+  }
+  // ---- the staging role of this thread: eight floats (one lane's share of a B fragment) of chunk tid % 16, k-block tid / 16
+  // (addresses as a workgroup-uniform 64-bit base + a 32-bit lane offset: a register less each than a 64-bit lane pointer, which this kernel has not got)
+  const float* abase = a.x + (size_t)b0 * T * RV_E;
+  const unsigned aoff = (unsigned)(min(b0 + (tid & 15), a.B - 1) - b0) * (unsigned)T * RV_E + (tid >> 4) * 8;
+  float* obase = a.out + ((size_t)b0 * a.out_T + a.out_t0) * RV_E + dir * RV_U;
+  const unsigned ooff = (unsigned)n * (unsigned)a.out_T * RV_E + u0;
+  auto trow = [&](int s) { s = min(s, T - 1); return dir ? T - 1 - s : s; };      // the timestep of walking position s (past the end: the last one again)
+  auto split_store = [&](const float4& x0, const float4& x1, char* dst) {
+    const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+    h8 hi, lo;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float sv = v[j] * 16384.f; hi[j] = (_Float16)sv; lo[j] = (_Float16)(sv - (float)hi[j]); }
+    *reinterpret_cast<h8*>(dst) = hi; *reinterpret_cast<h8*>(dst + 8192) = lo;
+  };
+#pragma unroll
+  for (int j = 0; j < MXP_NT; ++j) {                             // the first pass: nothing was requested ahead
+    const float* ap = abase + (size_t)trow(j) * RV_E + aoff;
+    split_store(*reinterpret_cast<const float4*>(ap), *reinterpret_cast<const float4*>(ap + 4), frag + j * 16384 + tid * 16);
+  }
+  float4 pf[2];                                                  // the row in flight: walking position s + MXP_NT at the top of step s
+  { const float* ap = abase + (size_t)trow(MXP_NT) * RV_E + aoff; pf[0] = *reinterpret_cast<const float4*>(ap); pf[1] = *reinterpret_cast<const float4*>(ap + 4); }
+  __syncthreads();
+
+  // ---- one projection pass: xa[j][g] = x_{t_j} . W + b of this lane's four units of gate g, for the MXP_NT timesteps of fragment buffer `buf`
+  // (the wave's stream as a wave-uniform base + a 32-bit lane offset that the compiler must take as new in every pass: left to itself it
+  //  forms the 64 fragment addresses once, in front of the step loop, and spills them)
+  const char* wsrc = img + (size_t)dir * 524288 + __builtin_amdgcn_readfirstlane(w) * 2048;
+  auto pass = [&](int buf, f4v (&xa)[MXP_NT][4]) {
+    unsigned wo = lane * 16;
+    asm volatile("" : "+v"(wo));
+#pragma unroll
+    for (int j = 0; j < MXP_NT; ++j)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) xa[j][g] = f4v{0.f, 0.f, 0.f, 0.f};
+    const char* fb = frag + buf * MXP_FRAG + (q * 16 + n) * 16;
+    h8 wr[MXP_RING][2];                                          // [slot][high part, low part]
+    auto wload = [&](int p, int slot) {                          // pair p = 4 ks + g
+      const char* src = wsrc + (wo + (unsigned)(((p & 3) >> 1) * 262144 + (p >> 2) * 32768 + (p & 1) * 16384));
+      wr[slot][0] = *reinterpret_cast<const h8*>(src); wr[slot][1] = *reinterpret_cast<const h8*>(src + 1024);
+    };
+#pragma unroll
+    for (int p = 0; p < MXP_RING; ++p) wload(p, p);
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      h8 bh[MXP_NT], bl[MXP_NT];
+#pragma unroll
+      for (int j = 0; j < MXP_NT; ++j) { bh[j] = *reinterpret_cast<const h8*>(fb + j * 16384 + ks * 1024); bl[j] = *reinterpret_cast<const h8*>(fb + j * 16384 + 8192 + ks * 1024); }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int p = 4 * ks + g;
+        const h8 wh = wr[p % MXP_RING][0], wl = wr[p % MXP_RING][1];
+        // the MXP_NT timesteps in turns for each part product (per accumulator: w_lo a_hi, w_hi a_lo, w_hi a_hi -- k_gemm_ws's order)
+#pragma unroll
+        for (int j = 0; j < MXP_NT; ++j) xa[j][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, bh[j], xa[j][g], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < MXP_NT; ++j) xa[j][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bl[j], xa[j][g], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < MXP_NT; ++j) xa[j][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bh[j], xa[j][g], 0, 0, 0);
+        if (p + MXP_RING < 32) wload(p + MXP_RING, p % MXP_RING);
+        __builtin_amdgcn_sched_barrier(0);                       // (without the fences the scheduler hoists the k-step's fragment reads and the ring's loads, and spills)
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4 f = *reinterpret_cast<const float4*>(&css[g * RV_U + u0]), bb = *reinterpret_cast<const float4*>(&bss[g * RV_U + u0]);
+#pragma unroll
+      for (int j = 0; j < MXP_NT; ++j)
+        xa[j][g] = f4v{fmaf(xa[j][g][0], f.x, bb.x), fmaf(xa[j][g][1], f.y, bb.y), fmaf(xa[j][g][2], f.z, bb.z), fmaf(xa[j][g][3], f.w, bb.w)};
+    }
+  };
+
+  float hl[4] = {};
+  int cur = 0;
+  // a step of the form <0, 16> on the pass's xin.  PF = 0, 1: the step's place in its pair -- it converts the row in flight into timestep
+  // PF of the next pass's fragment buffer nbuf and requests the next row; MXP_NT: neither (the step behind the last whole pair)
+  auto step = [&](int s, const f4v (&xin)[4], auto pfc, int nbuf) {
+    constexpr int PF = decltype(pfc)::value;
+    const int t = dir ? T - 1 - s : s;
+    char* fdst = frag + nbuf * MXP_FRAG + tid * 16;
+    if constexpr (PF < MXP_NT) {                                 // position s + MXP_NT is timestep PF of the next pass; position s + MXP_NT + 1 goes out
+      split_store(pf[0], pf[1], fdst + PF * 16384);
+      const float* ap = abase + (size_t)trow(s + MXP_NT + 1) * RV_E + aoff;
+      pf[0] = *reinterpret_cast<const float4*>(ap); pf[1] = *reinterpret_cast<const float4*>(ap + 4);
+    }
+    f4v acc[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[g] = f4v{0.f, 0.f, 0.f, 0.f};
+    const char* hp = hb + cur * 8192 + (q * 16 + n) * 16;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const h8 bh = *reinterpret_cast<const h8*>(hp + ks * 1024), bl = *reinterpret_cast<const h8*>(hp + 4096 + ks * 1024);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, ua[g][ks][0]), bl, acc[g], 0, 0, 0);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, ua[g][ks][1]), bh, acc[g], 0, 0, 0);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, ua[g][ks][0]), bh, acc[g], 0, 0, 0);
+    }
+    float z[4][4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4 ds = *reinterpret_cast<const float4*>(&dss[g * RV_U + u0]);
+      const float dv[4] = {ds.x, ds.y, ds.z, ds.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) z[g][i] = fmaf(acc[g][i], dv[i], xin[g][i]);
+    }
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    h4 hi, lo;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float cc = fmaf(rv_sigmoid(z[1][i]), c[i], rv_sigmoid(z[0][i]) * rv_tanh(z[2][i]));
+      const float hh = rv_sigmoid(z[3][i]) * rv_tanh(cc);
+      c[i] = cc; hl[i] = hh;
+      const float sv = hh * 16384.f;
+      hi[i] = (_Float16)sv; lo[i] = (_Float16)(sv - (float)hi[i]);
+    }
+    {
+      char* dst = hb + (cur ^ 1) * 8192 + ((2 * w + (q >> 1)) * 16 + n) * 16 + (q & 1) * 8;
+      *reinterpret_cast<h4*>(dst) = hi; *reinterpret_cast<h4*>(dst + 4096) = lo;
+    }
+    if (live) *reinterpret_cast<float4*>(obase + (size_t)t * RV_E + ooff) = vec(hl);
+    cur ^= 1;
+    RV_MX_BARRIER();
+  };
+  // whole pairs in the loop (every one requests the rows of the next: past the end the last timestep again, which no step consumes),
+  // the one step that may be left behind it -- as in rec_mx_body, no conditional step inside the loop
+  f4v xa[MXP_NT][4];
+  int s = 0, buf = 0;
+  for (; s + 1 < T; s += 2) {
+    pass(buf, xa);
+    step(s, xa[0], std::integral_constant<int, 0>{}, buf ^ 1);
+    step(s + 1, xa[1], std::integral_constant<int, 1>{}, buf ^ 1);
+    buf ^= 1;
+  }
+  if (s < T) {
+    pass(buf, xa);
+    step(s, xa[0], std::integral_constant<int, MXP_NT>{}, 0);
+  }
+  if (live) {
+    *reinterpret_cast<float4*>(a.hT[dir] + (size_t)(b0 + n) * RV_U + u0) = vec(hl);
+    *reinterpret_cast<float4*>(a.cT[dir] + (size_t)(b0 + n) * RV_U + u0) = vec(c);
+  }
+}
+
 // The padded chunk tensors of a window table for every path that reads chunk tensors (the packed-FMA recurrence, k_inproj_small, the
 // tapped and profiled calls): workgroup (b, seg) writes chunk b's raw [T_r,1] (seg 0) or event [T_e,5] (seg 1) row.  The rows were
 // checked on the host, like the windows kind of the recurrence; a null output is a segment the mode does not use.
@@ -365,6 +580,8 @@ void list_mx_forms(FormLog& log) {
   for_each_inproj_form([&](auto form) { log.add(RV_K_INPROJ_SMALL, decltype(form)::F); return false; });
 }
 
+void list_mx_proj_forms(FormLog& log) { log.add(RV_K_LSTM_REC_MX_PROJ, RV_MX_ROWS); }
+
 bool lstm_rec_mx_window_fits(int T, int F) { return mx_lds_bytes(F, T) <= 160 * 1024; }
 
 hipError_t configure_mx_kernels() {
@@ -380,7 +597,14 @@ hipError_t configure_mx_kernels() {
       if (ew != hipSuccess && first == hipSuccess) first = ew;
     }
   });
+  const hipError_t ep = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lstm_rec_mx_proj), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (ep != hipSuccess && first == hipSuccess) first = ep;
   return first;
+}
+
+void launch_lstm_rec_mx_proj(const RecArgs& a, hipStream_t s, FormLog* log) {
+  hipLaunchKernelGGL(k_lstm_rec_mx_proj, dim3((a.B + RV_MX_ROWS - 1) / RV_MX_ROWS, 2), dim3(512), MXP_LDS, s, a);      // (its LDS does not depend on T)
+  if (log) log->add(RV_K_LSTM_REC_MX_PROJ, RV_MX_ROWS);
 }
 
 void launch_lstm_rec_mx(const RecArgs& a, int F, hipStream_t s, bool rows8, FormLog* log) {

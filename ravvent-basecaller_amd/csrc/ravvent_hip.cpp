@@ -37,7 +37,7 @@ struct GraphKey {
 
 // whole-slab graphs: everything of a call that ends up in a frozen kernel argument or decides which kernels run
 struct SlabKey {
-  int B, T_r, T_e, W, L, flags;             // flags: greedy | calls << 1 | host inputs << 2 | host outputs << 3
+  int B, T_r, T_e, W, L, flags;             // flags: greedy | calls << 1 | host inputs << 2 | host outputs << 3 | projecting layers >= 1 (Plan::fused_inproj) << 4
   uint64_t lut;                             // the fused post-processing's letter table travels by value in a kernel argument
   bool operator<(const SlabKey& o) const {
     return std::tie(B, T_r, T_e, W, L, flags, lut) < std::tie(o.B, o.T_r, o.T_e, o.W, o.L, o.flags, o.lut);
@@ -60,6 +60,8 @@ struct Options {
   int tail_wave = 1;                        // layer 0: cell update on a ninth wave, two row groups half a step apart
   int fuse = 1;                             // layers >= 1: input projection inside the recurrence kernel (MFMA waves)
   int fused_mem = 1;                        // option "fused_memory": the default decode form projects its own attention memory (no gemm_memory launch)
+  int fused_inproj = -1;                    // option "fused_inproj": BiLSTM layers >= 1 of a sixteen-chunk matrix-pipe call project their own inputs
+                                            // (k_lstm_rec_mx_proj: no k_gemm_ws launch, no xw round trip); 1 wherever the sixteen-chunk form runs, 0 never, -1 per call (fused_inproj_wanted)
   int taps = 0, graph = 1, profile = 0;
   int ptaps = 0;                            // persist_taps: per-step logits of the persistent decode (debug)
   int slab_graph = 0;                       // option "slab_graph": off by default -- measured (tools/graph_ab.py, C3, depth 10): a submit costs the host
@@ -180,6 +182,7 @@ struct CallParts {
 struct Plan {
   bool wide = false;                        // encoder recurrences on the matrix pipe (lstm_mx.hip; a GRU handle: always) ...
   bool rows8 = false;                       // ... with eight chunks per workgroup (the latency form)
+  bool fused_inproj = false;                // ... with layers >= 1 projecting their own inputs (sixteen chunks only: k_lstm_rec_mx_proj)
   int persist = -1;                         // the form of the one-launch persistent decode (dec_persist_form), or -1: the per-step kernels
   bool flash = false;                       // single-pass Luong attend (wider beams: register budget -> two-pass)
   bool keys = false;                        // the key GEMM runs: the two-pass attend, the "keys" debug tap, a moves call on the per-step kernels
@@ -471,6 +474,16 @@ bool rows8_wanted(const RvContext* h, int B) {
   return h->opt.wide < 0 && n >= 160 && n <= 512;
 }
 
+// Do layers >= 1 of a sixteen-chunk matrix-pipe call project their own inputs (k_lstm_rec_mx_proj) instead of reading xw from the split
+// GEMM?  Both forms give the same bits, so the choice is free per call.  fused_inproj = 1 always; = -1 by the chunks in flight: one
+// isolated slab is a latency chain, where the GEMM (0.12 ms at C3) plus the streaming layer beats the fused layer's longer steps; a
+// stream of slabs is bound by CU-time, where the fused layer takes less of it (profiles/fused_inproj.md has the sweep).
+constexpr long long FUSED_INPROJ_MIN_CHUNKS = 1280;
+bool fused_inproj_wanted(const RvContext* h, int B) {
+  if (h->opt.fused_inproj >= 0) return h->opt.fused_inproj == 1;
+  return (long long)B * std::max(h->inflight_hint, 1) >= FUSED_INPROJ_MIN_CHUNKS;
+}
+
 // Does layer 0 of this encoder take x . W + b in the lane of its matrix-pipe recurrence, from LDS windows of the chunks' inputs?
 bool lane_layer0(const RvContext* h, int F, int T) {
   return F == 1 || (F == 5 && h->opt.lane_inproj && lstm_rec_mx_window_fits(T, 5));
@@ -554,6 +567,16 @@ void run_encoder(SlabCtx* cx, const Plan& plan, int e, const float* x, int F, in
         Scope sc(cx, F == 1 ? "lstm_rec_raw_l0" : "lstm_rec_event_l0", s);
         launch_lstm_rec_mx(a, F, s, plan.rows8, &cx->lforms);
         a.dbg_ts = nullptr; a.ptab = nullptr; a.mask = nullptr; a.members.n = 0; a.windows = nullptr;
+        continue;
+      }
+      if (l > 0 && plan.fused_inproj) {
+        // the layer projects its own inputs from the previous layer's output: no projection launch, xw[e] untouched
+        const size_t slot = (size_t)(e * (depth - 1) + (l - 1));
+        a.x = cx->act[e][(l - 1) & 1];
+        a.Wh[0] = h->img.Wx16 + slot * RV_WX16_SLOT;
+        a.bias[0] = h->img.bx2 + slot * 2 * RV_G;
+        Scope sc(cx, e == 0 ? "lstm_rec_raw_l1p" : "lstm_rec_event_l1p", s);
+        launch_lstm_rec_mx_proj(a, s, &cx->lforms);
         continue;
       }
       if (l == 0) {
@@ -673,6 +696,7 @@ Plan plan_call(const SlabCtx* cx, const Call& call, const CallParts& res) {
   Plan p;
   p.wide = gru || wide_recurrence(h, form_B, call.T_r);
   p.rows8 = !gru && p.wide && rows8_wanted(h, form_B);
+  p.fused_inproj = !gru && p.wide && !p.rows8 && fused_inproj_wanted(h, form_B);
   p.persist = persist_form(cx, call.greedy, call.W, call.T_r + call.T_e, res.labels != nullptr);
   // ---- setup_memory (basecaller.py:303): keys = (enc_output * mask) . W_mem.  The single-pass Luong attend never reads keys
   //      (score_t = values_t . (W_mem q)), and the persistent decode needs neither keys nor the per-step kernels; a moves call on the
@@ -782,7 +806,7 @@ int enqueue(SlabCtx* cx, const Call& stated, const CallParts& res) {
   if (!plan.graphable) return record_slab(cx, call, res, plan, nullptr);
   cx->lforms_ok = 0;                             // (a slab graph replays without the host launchers: "kernel_forms" answers RV_ESTATE)
   cx->pin_ptab[RV_PTAB_RAW] = call.raw; cx->pin_ptab[RV_PTAB_EVENT] = call.ev; cx->pin_ptab[RV_PTAB_TOKENS] = call.tokens; cx->pin_ptab[RV_PTAB_OUT2] = call.out2;
-  SlabKey key{B, T_r, T_e, W, L, (greedy ? 1 : 0) | (calls ? 2 : 0) | (call.dev_in ? 0 : 4) | (dev_out ? 0 : 8), 0};
+  SlabKey key{B, T_r, T_e, W, L, (greedy ? 1 : 0) | (calls ? 2 : 0) | (call.dev_in ? 0 : 4) | (dev_out ? 0 : 8) | (plan.fused_inproj ? 16 : 0), 0};
   if (calls) memcpy(&key.lut, call.lut, std::min<size_t>(sizeof key.lut, (size_t)c.vocab));
   auto it = cx->slab_graphs.find(key);
   if (it == cx->slab_graphs.end()) {
@@ -2869,6 +2893,18 @@ int rv_set_option(rv_handle h, const char* key, int32_t value) {
     if (uncollected(h)) return fail(h, RV_ESTATE, "collect the calls in flight before setting weight_parts");
   }
   if (!strcmp(key, "one_part_kernels") && value != 0 && value != 1) return fail(h, RV_EINVAL, "one_part_kernels must be 0 or 1");
+  if (!strcmp(key, "fused_inproj")) {
+    if (value < -1 || value > 1) return fail(h, RV_EINVAL, "fused_inproj must be 1 (always), 0 (never) or -1 (per call)");
+    // an explicit 1 stands behind one kernel, the sixteen-chunk BiLSTM form: every other recurrence keeps its GEMM
+    if (value == 1 && h->rnn == RV_RNN_BIGRU)
+      return fail(h, RV_EUNSUPPORTED, "fused_inproj 1 is not served on a bigru handle: k_gru_rec_mx reads its layers' inputs from the split GEMM");
+    if (value == 1 && h->opt.wide != 1 && h->opt.wide != -1)
+      return fail(h, RV_EUNSUPPORTED, "fused_inproj 1 is not served with wide_recurrence %d: only the sixteen-chunk matrix-pipe recurrence projects its own "
+                  "inputs (the %s keeps its projection)", h->opt.wide, h->opt.wide == 2 ? "eight-chunk form" : "packed-FMA path");
+  }
+  if (!strcmp(key, "wide_recurrence") && h->opt.fused_inproj == 1 && (value == 0 || value == 2))
+    return fail(h, RV_EUNSUPPORTED, "wide_recurrence %d is not served with fused_inproj 1: only the sixteen-chunk matrix-pipe recurrence projects its own "
+                "inputs; set fused_inproj to 0 or -1 first", value);
   if (!strcmp(key, "gru_persistent")) {
     if (value != 0 && value != 1) return fail(h, RV_EINVAL, "gru_persistent must be 0 or 1");
     if (h->rnn != RV_RNN_BIGRU)
@@ -2893,6 +2929,7 @@ int rv_set_option(rv_handle h, const char* key, int32_t value) {
   else if (!strcmp(key, "group_side_ev")) h->opt.group_side_ev = value;
   else if (!strcmp(key, "persist_taps")) h->opt.ptaps = value != 0;
   else if (!strcmp(key, "fused_memory")) h->opt.fused_mem = value != 0;
+  else if (!strcmp(key, "fused_inproj")) h->opt.fused_inproj = value;
   else if (!strcmp(key, "use_graph")) h->opt.graph = value != 0;
   else if (!strcmp(key, "flash_attend")) h->opt.flash = value != 0;
   else if (!strcmp(key, "persistent_decode")) h->opt.persist = value != 0;
@@ -2971,7 +3008,8 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
     for (int i = 0; i < 24; ++i) dst[i] = (float)ts[i];
     return RV_OK;
   }
-  else if (!strcmp(name, "kernel_forms") || !strcmp(name, "kernel_form_list") || !strcmp(name, "kernel_form_list_1p") || !strcmp(name, "group_kernel_forms")) {
+  else if (!strcmp(name, "kernel_forms") || !strcmp(name, "kernel_form_list") || !strcmp(name, "kernel_form_list_1p") || !strcmp(name, "kernel_form_list_proj") ||
+           !strcmp(name, "group_kernel_forms")) {
     FormLog all;
     const FormLog* f = &cx->lforms;
     if (!strcmp(name, "kernel_form_list") && h->rnn == RV_RNN_BIGRU) {      // the list answers for the handle's family
@@ -2985,6 +3023,9 @@ int rv_get_tensor(rv_handle h, const char* name, float* dst, size_t dst_floats, 
       f = &all;
     } else if (!strcmp(name, "kernel_form_list_1p")) {
       list_decode_forms_1p(all);
+      f = &all;
+    } else if (!strcmp(name, "kernel_form_list_proj")) {
+      list_mx_proj_forms(all);
       f = &all;
     } else if (!strcmp(name, "group_kernel_forms")) {
       f = &h->gforms;
