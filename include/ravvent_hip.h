@@ -12,9 +12,9 @@
  * ravvent_performance_evaluator.py:51-55); use one handle per GPU / per process.
  *
  * Synchronous calls -- rv_beam_search, rv_beam_search_dev, rv_beam_search_calls, rv_beam_search_windows, _windows_dev, _windows_calls, rv_beam_search_all, rv_beam_search_all_dev,
- * rv_beam_search_calls_moves, rv_beam_search_windows_calls_moves, rv_greedy_search, rv_greedy_search_dev, rv_teacher_forced, rv_teacher_forced_dev, rv_teacher_forced_moves, _moves_dev, rv_score_logits, rv_load_weights, rv_get_tensor: results are complete when the call
+ * rv_beam_search_calls_moves, rv_beam_search_windows_calls_moves, rv_greedy_search, rv_greedy_search_dev, rv_teacher_forced, rv_teacher_forced_dev, rv_teacher_forced_moves, _moves_dev, rv_score_logits, rv_stitch_calls, rv_stitch_run, rv_load_weights, rv_get_tensor: results are complete when the call
  * returns, so a caller's wall-clock timers mean what they mean around the reference's methods.
- * Asynchronous calls -- rv_beam_search_submit, _submit_dev, _submit_calls, _submit_windows, _submit_windows_calls, _submit_windows_calls_moves, _submit_all, _submit_all_dev: they return once the
+ * Asynchronous calls -- rv_beam_search_submit, _submit_dev, _submit_calls, _submit_windows, _submit_windows_calls, _submit_windows_calls_moves, _submit_windows_stitch, _submit_all, _submit_all_dev: they return once the
  * slab is queued, or held for its group until one of the events listed at rv_beam_search_flush
  * (option "coalesce"); the matching rv_beam_search_collect* waits for it.  A synchronous call may be
  * made while tickets are in flight: it runs on an idle slab context of the handle (its own when
@@ -347,6 +347,72 @@ enum { RV_FETCH_WINDOWS = 0, RV_FETCH_RAW_SC = 1, RV_FETCH_EVENTS_SC = 2, RV_FET
 int rv_read_put_signals(rv_handle h, int32_t n_reads, const int16_t* const* signal, const size_t* n, const RvSignalPrep* prep,
                         int32_t* read_id, int32_t* n_events, int32_t* n_windows);
 int rv_read_fetch(rv_handle h, int32_t read_id, int32_t what, void* dst, size_t cap);
+
+/* Stitching a read by signal position (no counterpart in the reference, whose evaluator chains one local alignment
+ * per chunk pair on the host).  The calls-with-positions calls give every called base a place in the signal; every chunk owns the stretch
+ * of signal around its own centre; a base belongs to the chunk that owns the sample it lies on.  Parallel over chunks, on arrays that
+ * need not leave the device.  Added without changing an existing entry point: RV_ABI_VERSION stays at 1.
+ *
+ * The rule, for the chunks k = 0 .. n-1 of a read in the order of its window rows (raw_start a, raw_len la, event_start e, event_len le),
+ * all values f64 (tests/stitch_reference.py states it in numpy):
+ *   position   p[k,i], i < lengths[k] (clamped into [0, stride]): raw mode a + raw_pos; event mode, with x = e + event_pos, j = floor(x)
+ *              clipped to the read's events and c_j = start_j + length_j / 2: c_j + (x - j) (c_min(j+1, E-1) - c_j), NaN for a NaN x or a
+ *              read without events; joint mode the raw estimate where raw_mass >= event_mass, else the event estimate.  Bit for bit
+ *              ravvent-basecaller_amd/basecaller.py's signal_positions (the kernels are compiled without floating-point contraction)
+ *   ownership  m_k = a_k + la_k / 2; cut_k = (m_{k-1} + m_k) / 2; lo_0 = -inf, lo_k = cut_k; hi_{n-1} = +inf, hi_k = cut_{k+1}.  The raw
+ *              columns are read as sample coordinates in every mode (prepare_windows and rv_read_put_signals fill them in every mode)
+ *   inside     lo_k <= p[k,i] < hi_k; a NaN is never inside
+ *   kept       from the first to the last inside index of the chunk, whole (a base between two inside bases is kept whatever its own
+ *              position); a chunk with no inside base keeps nothing
+ *   read       the kept bases of chunk 0, then of chunk 1, ...; each with its letter, prob, position, raw_mass, event_mass,
+ *              source_chunk (k within the read) and source_index (i)
+ * Nothing is summed: the result is the rule's, bit for bit.  A base whose positions in two chunks lie on different sides of their cut can
+ * be kept twice or not at all; which of this merge and the alignment merge reads better is not measured (no trained weights here).
+ *
+ *   rv_read_put_events   the i64 event starts and lengths [n_event] of a read put by rv_read_put / _dev, which the event estimate needs
+ *                        (host arrays, copied before the call returns; in event and joint mode n_event must be the read's event count).
+ *                        A read put by rv_read_put_signals has them on the device already: RV_ESTATE.  A stitch of an event- or
+ *                        joint-mode row whose read has no event table on the device fails with RV_ESTATE, naming the read; raw mode
+ *                        needs none
+ *   rv_stitch_calls      host arrays: upload, the kernels (positions and keep ranges, one wave per chunk; an exclusive scan of the counts
+ *                        over all chunks; the scatter), download.  `in`: bases u8, probs f32 and the four position values f32 [n, stride]
+ *                        (stride = L - 1 of the calls, at most 64), lengths i32 [n], win i32 [n,5] as the window calls take it.
+ *                        read_rows [n_reads + 1], ascending inside [0, n]: read r is rows read_rows[r] .. read_rows[r+1] - 1 (rows outside
+ *                        [read_rows[0], read_rows[n_reads]) take no part).  `out`: seven arrays of `capacity` ELEMENTS each, any of which
+ *                        may be NULL, and read_offsets i64 [n_reads + 1], which is always written: read r's bases are elements
+ *                        read_offsets[r] .. read_offsets[r+1] - 1.  A total beyond `capacity`: RV_EINVAL with the size needed in the
+ *                        message; read_offsets is written and nothing else.  Checked on the host before anything is queued, RV_EINVAL
+ *                        naming the row: an unknown read_id, a row that names another read than the first row of the read it lies in
+ *   rv_stitch_open / rv_stitch_close   device tables of n_chunks rows for calls of L - 1 columns, and their release
+ *   rv_beam_search_submit_windows_stitch   a slab of rv_beam_search_submit_windows_calls_moves -- same scheduling, limits and refusals --
+ *                        whose results are copied device-to-device into rows row0 .. row0 + B - 1 of `sb` on the slab's stream instead of
+ *                        being staged for the host; L must be the buffer's, the rows inside it (RV_EINVAL)
+ *   rv_beam_search_collect_stitch   collects such a ticket (and no other; no other collect takes one): it waits and copies nothing
+ *   rv_stitch_run        rv_stitch_calls on the tables of `sb`, with the window rows its slabs stated.  A row no slab has written names
+ *                        read -1 (RV_EINVAL); tickets into `sb` that are uncollected at rv_stitch_run or rv_stitch_close: RV_ESTATE; the
+ *                        reads must be alive (not dropped) when it runs
+ * Every handle kind that serves the calls-with-positions calls serves these.  Profile scopes "stitch_keep", "stitch_scan",
+ * "stitch_scatter". */
+typedef struct RvStitchIn {
+  const uint8_t* bases; const float* probs; const int32_t* lengths;
+  const float *raw_pos, *raw_mass, *event_pos, *event_mass;
+  const int32_t* win;
+  int32_t n, stride;
+} RvStitchIn;
+typedef struct RvStitchOut {
+  uint8_t* bases; float* probs; double* positions; float *raw_mass, *event_mass; int32_t *source_chunk, *source_index;
+  size_t capacity;
+  int64_t* read_offsets;
+} RvStitchOut;
+typedef struct RvStitchBuf* rv_stitch;
+int rv_read_put_events(rv_handle h, int32_t read_id, const int64_t* start, const int64_t* length, size_t n_event);
+int rv_stitch_calls(rv_handle h, const RvStitchIn* in, int32_t n_reads, const int32_t* read_rows, const RvStitchOut* out);
+int rv_stitch_open(rv_handle h, int32_t n_chunks, int32_t L, rv_stitch* sb);
+int rv_stitch_close(rv_handle h, rv_stitch sb);
+int rv_beam_search_submit_windows_stitch(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                         const uint8_t* lut, rv_stitch sb, int32_t row0, int32_t* ticket);
+int rv_beam_search_collect_stitch(rv_handle h, int32_t ticket, int32_t* S_out);
+int rv_stitch_run(rv_handle h, rv_stitch sb, int32_t n_reads, const int32_t* read_rows, const RvStitchOut* out);
 
 /* Basecaller.greedy_search_prediction (basecaller.py:317-330): tokens = sample_id [B, L-1],
  * logits = rnn_output [B, L-1, vocab]; columns >= S are pad_token / 0. */

@@ -43,6 +43,19 @@ class CRvSignalPrep(ctypes.Structure):
                 ("peak_height", c_double), ("stride", c_int32), ("max_raw_len", c_int32), ("max_event_len", c_int32)]
 
 
+class CRvStitchIn(ctypes.Structure):
+    """RvStitchIn (include/ravvent_hip.h): the call tables [n, stride] / [n] and the window table [n,5] of rv_stitch_calls."""
+    _fields_ = [("bases", c_void_p), ("probs", c_void_p), ("lengths", c_void_p), ("raw_pos", c_void_p), ("raw_mass", c_void_p),
+                ("event_pos", c_void_p), ("event_mass", c_void_p), ("win", c_void_p), ("n", c_int32), ("stride", c_int32)]
+
+
+class CRvStitchOut(ctypes.Structure):
+    """RvStitchOut (include/ravvent_hip.h): the seven per-base outputs of a stitch (each may be None), their capacity in elements, and
+    read_offsets i64 [n_reads + 1]."""
+    _fields_ = [("bases", c_void_p), ("probs", c_void_p), ("positions", c_void_p), ("raw_mass", c_void_p), ("event_mass", c_void_p),
+                ("source_chunk", c_void_p), ("source_index", c_void_p), ("capacity", c_size_t), ("read_offsets", c_void_p)]
+
+
 # rv_read_fetch: which table
 RV_FETCH_WINDOWS, RV_FETCH_RAW_SC, RV_FETCH_EVENTS_SC, RV_FETCH_EVENT_START, RV_FETCH_EVENT_LENGTH, RV_FETCH_EVENT_MEAN, \
     RV_FETCH_EVENT_STDV = range(7)
@@ -95,6 +108,14 @@ SYMBOLS = [
     ("rv_beam_search_windows_calls", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, _I]),
     ("rv_beam_search_submit_windows", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, _I]),
     ("rv_beam_search_submit_windows_calls", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, _I]),
+    ("rv_read_put_events", c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_size_t]),
+    ("rv_stitch_calls", c_int32, [c_void_p, POINTER(CRvStitchIn), c_int32, c_void_p, POINTER(CRvStitchOut)]),
+    ("rv_stitch_open", c_int32, [c_void_p, c_int32, c_int32, POINTER(c_void_p)]),
+    ("rv_stitch_close", c_int32, [c_void_p, c_void_p]),
+    ("rv_beam_search_submit_windows_stitch", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                                       c_int32, _I]),
+    ("rv_beam_search_collect_stitch", c_int32, [c_void_p, c_int32, _I]),
+    ("rv_stitch_run", c_int32, [c_void_p, c_void_p, c_int32, c_void_p, POINTER(CRvStitchOut)]),
     ("rv_greedy_search", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
     ("rv_greedy_search_dev", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _I]),
     ("rv_teacher_forced", c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, _S]),

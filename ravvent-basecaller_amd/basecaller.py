@@ -41,6 +41,12 @@ ForcedScores = collections.namedtuple("ForcedScores", "sample_id logits nll nll_
 CallMoves = collections.namedtuple("CallMoves", "raw_pos raw_mass event_pos event_mass peak peak_weight")
 
 
+# What a stitch by signal position returns (rv_stitch_calls / rv_stitch_run, include/ravvent_hip.h: RvStitchOut): seven arrays with one
+# element per kept base -- bases u8, probs f32, positions f64, raw_mass / event_mass f32, source_chunk / source_index int32 -- and
+# read_offsets int64 [n_reads + 1]: read r is elements read_offsets[r] .. read_offsets[r+1] - 1
+StitchedCalls = collections.namedtuple("StitchedCalls", "bases probs positions raw_mass event_mass source_chunk source_index read_offsets")
+
+
 def raw_position_estimate(raw_start, raw_pos, offset=0):
     """Position of a base in samples of the signal from the raw segment of its chunk: raw_start + raw_pos (+ the sample of the signal
     at which the scaled raw table starts); NaN stays NaN.  f64."""
@@ -705,10 +711,12 @@ class Basecaller:
                     pass
 
     # ------------------------------------------------------------------ reads on the device, chunks as windows of them
-    def put_read(self, raw_sc, events_sc):
+    def put_read(self, raw_sc, events_sc, event_starts=None, event_lengths=None):
         """Upload a read's scaled tables once (rv_read_put; torch device tensors: rv_read_put_dev, no copy) -> ReadHandle.
         raw_sc f32 [N] (None in event mode), events_sc f32 [E,5] (None in raw mode): `data_loader.prepare_windows` makes both.
-        The handle's `table(windows)` turns that function's [n,4] windows into the [n,5] tables the window calls take."""
+        The handle's `table(windows)` turns that function's [n,4] windows into the [n,5] tables the window calls take.
+        event_starts / event_lengths (both or neither): the read's events as int64 [E], which a stitch by signal position needs in
+        event and joint mode (rv_read_put_events)."""
         use_raw, use_ev = self.input_data_type != "event", self.input_data_type != "raw"
         on_dev = any(isinstance(x, torch.Tensor) and x.is_cuda for x in (raw_sc, events_sc))
 
@@ -731,7 +739,21 @@ class Basecaller:
             self._check(self._lib.rv_read_put_dev(self._h, ptr(r), n_raw, ptr(e), n_ev, ctypes.byref(rid)), "rv_read_put_dev")
         else:
             self._check(self._lib.rv_read_put(self._h, ptr(r), n_raw, ptr(e), n_ev, ctypes.byref(rid)), "rv_read_put")
-        return ReadHandle(self, rid.value, n_raw, n_ev, (r, e) if on_dev else None)
+        handle = ReadHandle(self, rid.value, n_raw, n_ev, (r, e) if on_dev else None)
+        if event_starts is not None or event_lengths is not None:
+            try:
+                if event_starts is None or event_lengths is None:
+                    raise ValueError("event_starts and event_lengths go together")
+                st = np.ascontiguousarray(np.asarray(event_starts, np.int64).reshape(-1))
+                ln = np.ascontiguousarray(np.asarray(event_lengths, np.int64).reshape(-1))
+                if st.shape != ln.shape:
+                    raise ValueError(f"event_starts {st.shape} and event_lengths {ln.shape} differ in length")
+                self._check(self._lib.rv_read_put_events(self._h, handle.read_id, st.ctypes.data_as(ctypes.c_void_p),
+                                                         ln.ctypes.data_as(ctypes.c_void_p), int(st.shape[0])), "rv_read_put_events")
+            except Exception:
+                handle.drop()
+                raise
+        return handle
 
     @staticmethod
     def _signal_int16(signal) -> np.ndarray:
@@ -958,42 +980,164 @@ class Basecaller:
             bases[a:b] = bs; probs[a:b] = pr; lens[a:b] = ln
         return bases, probs, lens
 
-    def basecall(self, signal, stride=6, beam_width=5, max_output_len=None, chunk_size=1024, device_prep=False, moves=False):
+    # ------------------------------------------------------------------ stitching a read by signal position
+    @staticmethod
+    def _stitch_out(capacity, n_reads):
+        """Host arrays for the outputs of a stitch and the struct that names them."""
+        cap = max(int(capacity), 0)
+        arrs = [np.empty(cap, np.uint8), np.empty(cap, np.float32), np.empty(cap, np.float64), np.empty(cap, np.float32),
+                np.empty(cap, np.float32), np.empty(cap, np.int32), np.empty(cap, np.int32), np.zeros(n_reads + 1, np.int64)]
+        ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+        return arrs, _capi.CRvStitchOut(*[ptr(a) for a in arrs[:7]], cap, ptr(arrs[7]))
+
+    @staticmethod
+    def _stitch_cut(arrs):
+        total = int(arrs[7][-1])
+        return StitchedCalls(*[a[:total] for a in arrs[:7]], arrs[7])
+
+    def stitch_calls(self, bases, probs, lengths, moves, windows, read_rows, capacity=None):
+        """Stitch reads from their chunks' calls by signal position (rv_stitch_calls) -> StitchedCalls.
+        bases u8 / probs f32 [n, stride] and lengths i32 [n] as the call-array calls return them, moves: a CallMoves (or any object
+        with raw_pos / raw_mass / event_pos / event_mass [n, stride]), windows i32 [n,5] the table the calls ran on, read_rows
+        [n_reads + 1] the first row of every read.  Each chunk owns the signal up to half way to its neighbours' centres, and keeps
+        its bases from the first to the last one that lies there.  The reads of the table must be alive, and in event and joint mode
+        hold their events (`put_signals`, or `put_read(..., event_starts=, event_lengths=)`).  capacity: elements the outputs
+        hold (default: n x stride, which always suffices)."""
+        c = lambda a, dt: np.ascontiguousarray(np.asarray(a), dtype=dt)
+        bases, probs, lengths = c(bases, np.uint8), c(probs, np.float32), c(lengths, np.int32).reshape(-1)
+        n = int(lengths.shape[0])
+        if bases.ndim != 2 or bases.shape[0] != n or probs.shape != bases.shape:
+            raise ValueError(f"bases and probs: two [{n},stride] arrays, got {bases.shape} and {probs.shape}")
+        stride = int(bases.shape[1])
+        mv = [c(getattr(moves, k), np.float32) for k in ("raw_pos", "raw_mass", "event_pos", "event_mass")]
+        if any(m.shape != bases.shape for m in mv):
+            raise ValueError(f"moves: four arrays of shape {bases.shape}")
+        win = c(windows, np.int32)
+        if win.shape != (n, 5):
+            raise ValueError(f"windows: expected [{n},5] (read_id, raw_start, raw_len, event_start, event_len), got {win.shape}")
+        rows = c(read_rows, np.int32).reshape(-1)
+        if rows.shape[0] < 1:
+            raise ValueError("read_rows: n_reads + 1 entries")
+        ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+        cin = _capi.CRvStitchIn(ptr(bases), ptr(probs), ptr(lengths), *[ptr(m) for m in mv], ptr(win), n, stride)
+        arrs, cout = self._stitch_out(n * stride if capacity is None else capacity, int(rows.shape[0]) - 1)
+        self._check(self._lib.rv_stitch_calls(self._h, ctypes.byref(cin), int(rows.shape[0]) - 1, ptr(rows), ctypes.byref(cout)), "rv_stitch_calls")
+        return self._stitch_cut(arrs)
+
+    def _put_signals_for_calls(self, signals, stride, T_r, T_e, device_prep, events, handles, windows, ev_tabs):
+        """The preparation `basecall_many` starts with, for either merge: every read on the device and its window table [n,4], by
+        `put_signals` (device_prep) or read by read through `prepare_windows` and `put_read`.  The handles, windows and event
+        tables (starts, lengths) are appended to the caller's lists as they come, so that its `finally` drops whatever was put.
+        events None: no event tables; "host": in ev_tabs (fetched from a device-made read); "device": the reads hold them on the
+        device -- those of `put_signals` do, a host-made read is given the host detector's arrays (rv_read_put_events)."""
+        from .event_detection import EventDetector
+        if device_prep:
+            handles.extend(self.put_signals(list(signals), stride=stride, max_raw_len=T_r, max_event_len=T_e))
+            windows.extend(h.windows for h in handles)
+            if events == "host":      # the read's events, as the device made them
+                ev_tabs.extend((h.fetch("start"), h.fetch("length")) if h.n_event else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+                               for h in handles)
+            return
+        for sig in signals:
+            rw = _dl.prepare_windows(sig, stride=stride, max_raw_len=T_r, max_event_len=T_e)
+            windows.append(rw.windows)
+            if events is None:
+                handles.append(self.put_read(rw.raw_sc, rw.events_sc))
+                continue
+            # ... as the host detector makes them: a second run of the detector prepare_windows ran, whose return type has no room
+            # for the event arrays
+            st, ln, _, _ = EventDetector(window_length1=_dl.ED_WINDOW_LENGTH_1, window_length2=_dl.ED_WINDOW_LENGTH_2).run_arrays(np.asarray(sig))
+            st, ln = np.asarray(st, np.int64), np.asarray(ln, np.int64)
+            if events == "host":
+                handles.append(self.put_read(rw.raw_sc, rw.events_sc))
+                ev_tabs.append((st, ln))
+            else:
+                handles.append(self.put_read(rw.raw_sc, rw.events_sc, event_starts=st, event_lengths=ln))
+
+    def _basecall_many_position(self, signals, stride, beam_width, max_output_len, chunk_size, device_prep):
+        """`basecall_many(..., merge="position")`: the slabs stream through the stitch submit into one device buffer, one
+        rv_stitch_run follows, and the reads come back stitched -- no slab result is copied to the host, no alignment runs."""
+        L = self.cfg.max_output_len if max_output_len is None else _as_int(max_output_len)
+        T_r, T_e = min(_dl.MAX_RAW_LEN, self.cfg.max_raw_len), min(_dl.MAX_EVENT_LEN, self.cfg.max_event_len)
+        windows, handles = [], []
+        sb = ctypes.c_void_p()
+        queue = []
+        S = ctypes.c_int32(0)
+        try:
+            # (raw mode: the positions are the raw estimate, which reads no event table)
+            self._put_signals_for_calls(signals, stride, T_r, T_e, device_prep, None if self.input_data_type == "raw" else "device",
+                                        handles, windows, [])
+            n = [int(w.shape[0]) for w in windows]
+            rows = np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
+            table = (np.concatenate([h.table(w) for h, w in zip(handles, windows)]) if windows else np.zeros((0, 5), np.int32))
+            total, steps = int(table.shape[0]), max(L - 1, 0)
+            self._check(self._lib.rv_stitch_open(self._h, total, L, ctypes.byref(sb)), "rv_stitch_open")
+            lut = self._call_lut()
+            depth = getattr(self, "async_depth", 2)
+            collect = lambda t: self._check(self._lib.rv_beam_search_collect_stitch(self._h, t, ctypes.byref(S)), "rv_beam_search_collect_stitch")
+            for a in range(0, total, int(chunk_size)):
+                if len(queue) >= depth:
+                    collect(queue.pop(0))
+                w = np.ascontiguousarray(table[a:a + int(chunk_size)])
+                t = ctypes.c_int32(-1)
+                self._check(self._lib.rv_beam_search_submit_windows_stitch(self._h, w.ctypes.data_as(ctypes.c_void_p), int(w.shape[0]), T_r, T_e,
+                                                                           int(beam_width), L, lut.ctypes.data_as(ctypes.c_void_p), sb, a,
+                                                                           ctypes.byref(t)), "rv_beam_search_submit_windows_stitch")
+                queue.append(t.value)
+            while queue:
+                collect(queue.pop(0))
+            self.last_steps = S.value
+            arrs, cout = self._stitch_out(total * steps, len(windows))
+            self._check(self._lib.rv_stitch_run(self._h, sb, len(windows), rows.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cout)), "rv_stitch_run")
+        finally:
+            while queue:                   # (an error: no ticket may stay uncollected on the handle)
+                try:
+                    collect(queue.pop(0))
+                except Exception:
+                    pass
+            if sb:
+                self._lib.rv_stitch_close(self._h, sb)
+            for h in handles:
+                h.drop()
+        r = self._stitch_cut(arrs)
+        flat = r.bases.tobytes()
+        out = []
+        for i in range(len(windows)):
+            a, b = int(r.read_offsets[i]), int(r.read_offsets[i + 1])
+            out.append(BasecallResult(flat[a:b].decode("ascii"), r.probs[a:b].copy(), n[i], r.positions[a:b].copy(), r.raw_mass[a:b].copy(),
+                                      r.event_mass[a:b].copy(), r.source_chunk[a:b].copy(), r.source_index[a:b].copy()))
+        return out
+
+    def basecall(self, signal, stride=6, beam_width=5, max_output_len=None, chunk_size=1024, device_prep=False, moves=False, merge="align"):
         """An unlabelled read's signal -> BasecallResult (seq, probs, qualities, chunks_num, to_fastq): `prepare_windows` without
         labels, `put_read`, window slabs of `chunk_size` chunks streamed with the fused post-processing, the C++ merger, drop.
-        max_output_len None: the handle's.  device_prep, moves: see `basecall_many`."""
-        return self.basecall_many([signal], stride, beam_width, max_output_len, chunk_size, device_prep, moves)[0]
+        max_output_len None: the handle's.  device_prep, moves, merge: see `basecall_many`."""
+        return self.basecall_many([signal], stride, beam_width, max_output_len, chunk_size, device_prep, moves, merge)[0]
 
-    def basecall_many(self, signals, stride=6, beam_width=5, max_output_len=None, chunk_size=1024, device_prep=False, moves=False):
+    def basecall_many(self, signals, stride=6, beam_width=5, max_output_len=None, chunk_size=1024, device_prep=False, moves=False,
+                      merge="align"):
         """`basecall` of several reads through shared slabs: the windows of all reads are queued into full slabs (a slab's rows may
         name different reads) and each read is stitched from its own rows -> list of BasecallResult, equal to one `basecall` each.
         device_prep True: events, scaling and windows are made on the device from the int16 samples of all reads at once
         (`put_signals`) instead of read by read on the host; integer signals only (ValueError otherwise).
         moves True: the slabs stream through the calls-with-positions window call and the merger reports where each merged base
         came from; every result then carries positions / raw_mass / event_mass / source_chunk / source_index (BasecallResult,
-        `signal_positions`).  seq and probs are what moves=False gives, byte for byte."""
+        `signal_positions`).  seq and probs are what moves=False gives, byte for byte.
+        merge "align" (default): the chunks' calls come to the host and the C++ merger chains one local alignment per chunk pair.
+        "position": the reads are stitched on the device by signal position instead (every chunk keeps the
+        bases that lie on its own stretch of signal; `stitch_calls` states the rule) -- another read than "align" gives, with every
+        position field set whatever `moves` says; which of the two is the more accurate is not measured."""
+        if merge != "align":
+            if merge != "position":
+                raise ValueError(f"merge {merge!r}: 'align' or 'position'")
+            return self._basecall_many_position(signals, stride, beam_width, max_output_len, chunk_size, device_prep)
         from . import merger as _merger
-        from .event_detection import EventDetector
         L = self.cfg.max_output_len if max_output_len is None else _as_int(max_output_len)
         T_r, T_e = min(_dl.MAX_RAW_LEN, self.cfg.max_raw_len), min(_dl.MAX_EVENT_LEN, self.cfg.max_event_len)
         windows, handles, ev_tabs = [], [], []
         mv = None
         try:
-            if device_prep:
-                handles = self.put_signals(list(signals), stride=stride, max_raw_len=T_r, max_event_len=T_e)
-                windows = [h.windows for h in handles]
-                if moves:      # the read's events, as the device made them
-                    ev_tabs = [(h.fetch("start"), h.fetch("length")) if h.n_event else (np.zeros(0, np.int64), np.zeros(0, np.int64))
-                               for h in handles]
-            else:
-                for sig in signals:
-                    rw = _dl.prepare_windows(sig, stride=stride, max_raw_len=T_r, max_event_len=T_e)
-                    windows.append(rw.windows)
-                    handles.append(self.put_read(rw.raw_sc, rw.events_sc))
-                    if moves:      # ... as the host detector makes them: a second run of the detector prepare_windows ran, whose
-                        #     return type has no room for the event arrays
-                        st, ln, _, _ = EventDetector(window_length1=_dl.ED_WINDOW_LENGTH_1, window_length2=_dl.ED_WINDOW_LENGTH_2).run_arrays(np.asarray(sig))
-                        ev_tabs.append((np.asarray(st, np.int64), np.asarray(ln, np.int64)))
+            self._put_signals_for_calls(signals, stride, T_r, T_e, device_prep, "host" if moves else None, handles, windows, ev_tabs)
             n = [int(w.shape[0]) for w in windows]
             off = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
             table = (np.concatenate([h.table(w) for h, w in zip(handles, windows)]) if windows else np.zeros((0, 5), np.int32))

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "weight_images.h"
 #include "signal_prep.h"
+#include "stitch.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -17,6 +18,18 @@
 #include <string>
 #include <tuple>
 #include <vector>
+
+// A stitch buffer (rv_stitch_open): device tables of n chunk rows that stitch slabs write and rv_stitch_run reads -- the calls' bases,
+// probs [n, steps] and lengths [n], the four position values [n, steps] -- and on the host the window rows as the slabs stated them
+struct RvStitchBuf {
+  int n = 0, L = 0, steps = 0;
+  uint8_t* bases = nullptr;
+  float* probs = nullptr;
+  int32_t* lens = nullptr;
+  float* mv[4] = {nullptr, nullptr, nullptr, nullptr};      // raw_pos, raw_mass, event_pos, event_mass
+  std::vector<int32_t> win;                                 // [n,5]; read_id -1: a row no slab has written
+  int tickets = 0;                                          // uncollected tickets that write into it
+};
 
 namespace {
 
@@ -132,6 +145,10 @@ struct Call {
   // them into the context's input buffers first and raw / ev name those
   const RecWindow* windows = nullptr;
   bool win_expand = false;
+  // rv_beam_search_submit_windows_stitch (always with want_call_moves): the slab's results go device-to-device into rows stitch_row0 .. of
+  // this buffer on the slab's stream instead of into the staging of a host caller
+  RvStitchBuf* stitch = nullptr;
+  int stitch_row0 = 0;
 };
 
 // A read on the device (rv_read_put*): its scaled samples [n_raw] and scaled events [n_ev,5].  owned: the buffers are the handle's (a
@@ -148,6 +165,30 @@ struct Read {
   double *d_emu = nullptr, *d_esd = nullptr;
   int32_t* d_win = nullptr;
   size_t cap_evd = 0, cap_win = 0, n_win = 0;               // cap_evd: events the four arrays hold; cap_win: window rows
+  // the event starts and lengths [n_xev] a caller gave for a read put by rv_read_put / _dev (rv_read_put_events), for the stitch; they
+  // belong to the read whose id is ev_id (a slot taken again keeps the buffers, not the table)
+  int64_t *d_xst = nullptr, *d_xln = nullptr;
+  size_t cap_xev = 0, n_xev = 0;
+  int ev_id = -2;
+};
+
+// The handle's scratch of a stitch (rv_stitch_calls, rv_stitch_run), reused and grown: per chunk, per read, per base of the outputs
+struct StitchScratch {
+  StChunk* chunks = nullptr; size_t cap_chunks = 0;
+  int2* keep = nullptr; size_t cap_keep = 0;
+  long long* off = nullptr; size_t cap_off = 0;
+  long long* tiles = nullptr; size_t cap_tiles = 0;
+  StRead* reads = nullptr; size_t cap_reads = 0;
+  int32_t* rows = nullptr; size_t cap_rows = 0;
+  long long *read_off = nullptr, *pin_read_off = nullptr; size_t cap_read_off = 0, cap_pin = 0;
+  uint8_t* o_bases = nullptr; size_t cap_o_bases = 0;
+  float* o_f[3] = {nullptr, nullptr, nullptr}; size_t cap_o_f[3] = {0, 0, 0};      // probs, raw_mass, event_mass
+  double* o_pos = nullptr; size_t cap_o_pos = 0;
+  int32_t* o_i[2] = {nullptr, nullptr}; size_t cap_o_i[2] = {0, 0};              // source_chunk, source_index
+  // the tables of rv_stitch_calls, which brings them from the host (rv_stitch_run reads those of its stitch buffer)
+  uint8_t* in_bases = nullptr; size_t cap_in_bases = 0;
+  float* in_f[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t cap_in_f[5] = {0, 0, 0, 0, 0};      // probs and the four position values
+  int32_t* in_len = nullptr; size_t cap_in_len = 0;
 };
 
 // The handle's scratch of rv_read_put_signals, reused from batch to batch: per sample (cap_x), per tile (cap_tiles), per read (cap_reads)
@@ -247,6 +288,10 @@ struct RvContext {
   int read_gen = 0;
   std::map<int, std::vector<int>> ticket_reads;
   SignalScratch sp;                         // rv_read_put_signals
+  // stitching by signal position (rv_stitch_*): the buffers that are open, which uncollected ticket writes into which, the scratch
+  std::vector<RvStitchBuf*> stitch_bufs;
+  std::map<int, RvStitchBuf*> stitch_tickets;
+  StitchScratch st;
 };
 
 namespace {
@@ -324,7 +369,7 @@ struct SlabCtx {
   FormLog lforms;                           // the kernel instantiations it launched ("kernel_forms"); lforms_ok = 0: it ran as a slab graph
   int lforms_ok = 1;
   std::map<GraphKey, FormLog> graph_forms;  // ... those a captured decode graph of `graphs` launches (recorded at its capture)
-  struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false, all = false, moves = false, cmoves = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
+  struct PendingCall { bool busy = false, trivial = false, greedy = false, dev_out = false, calls = false, all = false, moves = false, cmoves = false, stitch = false; int B = 0, steps = 0, V = 0, Wd = 0, ticket = -1; } pend;
 
   // window calls (rv_beam_search_windows*): the resolved table of the call this context runs, [cap] rows -- written by the host into
   // pinned staging when the call is queued (a group: as its members come), copied to the device in front of the call's first kernel
@@ -762,6 +807,7 @@ int enqueue(SlabCtx* cx, const Call& stated, const CallParts& res) {
   cx->lforms.n = 0; cx->lforms.full = false; cx->lforms_ok = 1;
   cx->pend = SlabCtx::PendingCall{};
   cx->pend.busy = true; cx->pend.greedy = greedy; cx->pend.dev_out = dev_out; cx->pend.calls = calls; cx->pend.all = res.whole_beam; cx->pend.moves = res.moves; cx->pend.cmoves = res.call_moves;
+  cx->pend.stitch = stated.stitch != nullptr;
   cx->pend.B = B; cx->pend.steps = std::max(L - 1, 0); cx->pend.V = c.vocab; cx->pend.Wd = greedy ? 1 : W;
   if (B == 0 || L <= 1) {
     cx->pend.trivial = true;
@@ -1271,6 +1317,17 @@ int stage_outputs(SlabCtx* cx, const Slab& sl) {
     HIPCHK(h, hipMemcpyAsync(cx->pin_tok, sl.call.tokens, sizeof(int32_t) * B * steps, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(cx->pin_out2, sl.call.out2, sizeof(float) * B * steps * (greedy ? V : 1), hipMemcpyDeviceToHost, s));
   }
+  if (sl.call.stitch) {      // a stitch slab: the calls and their positions stay on the device, in the rows of the caller's stitch buffer
+    const RvStitchBuf* sb = sl.call.stitch;
+    const size_t r0 = (size_t)sl.call.stitch_row0, at = r0 * steps, n = (size_t)B * steps;
+    const MovesOut& m = sl.res.moves_out;
+    const float* src[4] = {m.raw_pos, m.raw_mass, m.event_pos, m.event_mass};
+    for (int i = 0; i < 4; ++i) HIPCHK(h, hipMemcpyAsync(sb->mv[i] + at, src[i], sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(sb->bases + at, cx->d_bases, n, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(sb->probs + at, cx->d_probs, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(sb->lens + r0, cx->d_clen, sizeof(int) * B, hipMemcpyDeviceToDevice, s));
+    return RV_OK;
+  }
   if (sl.res.call_moves || (sl.res.forced_moves && !dev_out)) {
     const MovesOut &m = sl.res.moves_out, &q = cx->pin_moves;
     const void* src[6] = {m.raw_pos, m.raw_mass, m.event_pos, m.event_mass, m.peak, m.peak_weight};
@@ -1303,12 +1360,26 @@ int record_slab(SlabCtx* cx, const Call& call, const CallParts& res, const Plan&
 
 // The rest of a call: wait for the context's stream, hand the staged results to the caller's host buffers.
 int finish(SlabCtx* cx, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr,
-           const RvMoves* moves = nullptr, const RvCallMoves* cmoves = nullptr) {
+           const RvMoves* moves = nullptr, const RvCallMoves* cmoves = nullptr, bool stitch = false) {
   RvContext* const h = cx->h;
   if (!S_out) return RV_EINVAL;
   if (!cx->pend.busy) return fail(h, RV_ESTATE, "no call to collect on this context");
   const SlabCtx::PendingCall p = cx->pend;
   *S_out = 0;
+  if (p.stitch != stitch)      // (the ticket stays in flight)
+    return fail(h, RV_EINVAL, p.stitch ? "this call's results went to a stitch buffer: collect it with rv_beam_search_collect_stitch"
+                                       : "rv_beam_search_collect_stitch takes the tickets of rv_beam_search_submit_windows_stitch");
+  if (p.stitch) {              // nothing to hand out: the slab's copies into the stitch buffer are behind its stream
+    cx->pend.busy = false;
+    if (p.trivial) return RV_OK;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(cx->stream));
+    HIPCHK(h, hipGetLastError());
+    drain_profile(cx);
+    *S_out = *cx->pin_S;
+    if (cx->own()) h->lS = *S_out;
+    return RV_OK;
+  }
   if (p.all != (beams != nullptr) && !(p.all && p.dev_out))      // (the ticket stays in flight)
     return fail(h, RV_EINVAL, p.all ? "this call hands out the whole beam: collect it with rv_beam_search_collect_all"
                                     : "rv_beam_search_collect_all takes the tickets of rv_beam_search_submit_all");
@@ -2082,6 +2153,7 @@ int put_read(RvContext* h, const float* raw, size_t n_raw, const float* event, s
     r.used = true;
   }
   r.n_raw = n_raw; r.n_ev = n_event; r.live = true; r.users = 0; r.prepped = false; r.n_win = 0;
+  r.ev_id = -2; r.n_xev = 0;      // (a slot taken again: the event table a caller gave its last read is not this read's)
   h->read_gen = (h->read_gen + 1) & 0xFFFFF;
   r.id = (h->read_gen << 10) | slot;
   h->read_puts += 1;
@@ -2211,7 +2283,7 @@ int put_signals(RvContext* h, int n_reads, const int16_t* const* signal, const s
     if (slot < 0) { h->reads.emplace_back(); slot = (int)h->reads.size() - 1; }      // (room for it: checked above)
     Read& x = h->reads[slot];
     if (!x.owned) { x.d_raw = x.d_ev = nullptr; x.cap_raw = x.cap_ev = 0; x.owned = true; }
-    x.live = true; x.users = 0;
+    x.live = true; x.users = 0; x.ev_id = -2; x.n_xev = 0;
     slots.push_back(slot);
   }
 
@@ -2305,6 +2377,174 @@ int fetch_read(RvContext* h, int read_id, int what, void* dst, size_t cap) {
   if (h->copy_stream) HIPCHK(h, hipStreamSynchronize(h->copy_stream));      // (a read put by rv_read_put: its upload is behind this)
   HIPCHK(h, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
   return RV_OK;
+}
+
+// ---- stitching by signal position (rv_stitch_*, rv_read_put_events; kernels: stitch.hip)
+// A device or pinned buffer of the stitch that only grows (sp_grow without the count: "read_stats" counts allocations made for reads)
+template <class T>
+int st_grow(RvContext* h, T** p, size_t* cap, size_t need, bool pinned = false) {
+  if (need <= *cap && *p) return RV_OK;
+  if (*p) { if (pinned) hipHostFree(*p); else hipFree(*p); *p = nullptr; *cap = 0; }
+  const size_t bytes = std::max<size_t>(need, 1) * sizeof(T);
+  const hipError_t e = pinned ? hipHostMalloc((void**)p, bytes, hipHostMallocDefault) : hipMalloc((void**)p, bytes);
+  if (e != hipSuccess) { *p = nullptr; return fail(h, RV_ENOMEM, "%s(%zu bytes) failed for a stitch", pinned ? "hipHostMalloc" : "hipMalloc", bytes); }
+  *cap = need;
+  return RV_OK;
+}
+
+void free_stitch_buf(RvStitchBuf* sb) {
+  for (void* q : {(void*)sb->bases, (void*)sb->probs, (void*)sb->lens, (void*)sb->mv[0], (void*)sb->mv[1], (void*)sb->mv[2], (void*)sb->mv[3]})
+    if (q) hipFree(q);
+  delete sb;
+}
+
+void free_stitch_scratch(RvContext* h) {
+  StitchScratch& t = h->st;
+  for (void* q : {(void*)t.chunks, (void*)t.keep, (void*)t.off, (void*)t.tiles, (void*)t.reads, (void*)t.rows, (void*)t.read_off, (void*)t.o_bases,
+                  (void*)t.o_f[0], (void*)t.o_f[1], (void*)t.o_f[2], (void*)t.o_pos, (void*)t.o_i[0], (void*)t.o_i[1], (void*)t.in_bases,
+                  (void*)t.in_f[0], (void*)t.in_f[1], (void*)t.in_f[2], (void*)t.in_f[3], (void*)t.in_f[4], (void*)t.in_len}) if (q) hipFree(q);
+  if (t.pin_read_off) hipHostFree(t.pin_read_off);
+  t = StitchScratch{};
+}
+
+RvStitchBuf* find_stitch_buf(RvContext* h, const RvStitchBuf* sb) {
+  for (RvStitchBuf* k : h->stitch_bufs) if (k == sb) return k;
+  return nullptr;
+}
+
+// The event table of a read on the device: its own (rv_read_put_signals) or the caller's (rv_read_put_events)
+bool read_events(const Read& r, StRead* out) {
+  if (r.prepped) { *out = StRead{r.d_est, r.d_eln, (int)r.n_ev}; return true; }
+  if (r.ev_id == r.id) { *out = StRead{r.d_xst, r.d_xln, (int)r.n_xev}; return true; }
+  return false;
+}
+
+int put_events(RvContext* h, int read_id, const int64_t* start, const int64_t* length, size_t n_event) {
+  if (!h) return RV_EINVAL;
+  Read* r = find_read(h, read_id);
+  if (!r) return fail(h, RV_EINVAL, "unknown read_id %d", read_id);
+  if (r->prepped) return fail(h, RV_ESTATE, "read %d was made by rv_read_put_signals: its event table is on the device already", read_id);
+  if (n_event > 0 && (!start || !length)) return fail(h, RV_EINVAL, "rv_read_put_events: null array");
+  if (n_event > (size_t)INT32_MAX) return fail(h, RV_EINVAL, "rv_read_put_events: %zu events exceed 32-bit event indices", n_event);
+  if (h->cfg.mode != RV_MODE_RAW && n_event != r->n_ev)
+    return fail(h, RV_EINVAL, "rv_read_put_events: %zu events for read %d, whose event table holds %zu", n_event, read_id, r->n_ev);
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (n_event > r->cap_xev || !r->d_xst) {
+    const size_t old = r->cap_xev;
+    size_t cap;
+    r->cap_xev = 0;
+    cap = old; TRY(st_grow(h, &r->d_xst, &cap, n_event));
+    cap = old; TRY(st_grow(h, &r->d_xln, &cap, n_event));
+    r->cap_xev = n_event;
+  }
+  if (n_event) {      // (synchronous copies: the arrays are the caller's again on return, and every later stream sees them)
+    HIPCHK(h, hipMemcpy(r->d_xst, start, n_event * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(r->d_xln, length, n_event * sizeof(int64_t), hipMemcpyHostToDevice));
+  }
+  r->n_xev = n_event; r->ev_id = r->id;
+  return RV_OK;
+}
+
+// The stitch of rows read_rows[0] .. read_rows[n_reads] of the device tables `din` (n rows in all), whose window rows `win` [n,5] are on
+// the host: checked there before anything is queued, then the three stages on the handle's copy stream (behind every upload of a read or
+// of its events), the read offsets, and -- when they fit `out` -- the outputs
+int stitch_core(RvContext* h, StIn din, const int32_t* win, int n_reads, const int32_t* read_rows, const RvStitchOut* out, const char* what) {
+  if (!out || !out->read_offsets) return fail(h, RV_EINVAL, "%s: null read_offsets", what);
+  if (n_reads < 0 || !read_rows) return fail(h, RV_EINVAL, "%s: null read_rows or negative n_reads", what);
+  for (int r = 0; r <= n_reads; ++r)
+    if (read_rows[r] < 0 || read_rows[r] > din.n || (r > 0 && read_rows[r] < read_rows[r - 1]))
+      return fail(h, RV_EINVAL, "%s: read_rows[%d] = %d lies outside the table's %d rows or below the entry before it", what, r, read_rows[r], din.n);
+  const int r0 = read_rows[0], n = read_rows[n_reads] - r0;
+  const bool use_ev = h->cfg.mode != RV_MODE_RAW;
+  std::vector<StChunk> chunks((size_t)n);
+  std::vector<StRead> reads((size_t)std::max(n_reads, 1), StRead{nullptr, nullptr, 0});
+  std::vector<int32_t> rows((size_t)n_reads + 1);
+  for (int r = 0; r <= n_reads; ++r) rows[r] = read_rows[r] - r0;
+  for (int r = 0; r < n_reads; ++r) {
+    const int a = read_rows[r], b = read_rows[r + 1];
+    for (int row = a; row < b; ++row) {
+      const int32_t* w = win + (size_t)row * 5;
+      const Read* rd = find_read(h, w[0]);
+      if (!rd) return fail(h, RV_EINVAL, "%s: row %d: unknown read_id %d", what, row, w[0]);
+      if (w[0] != win[(size_t)a * 5]) return fail(h, RV_EINVAL, "%s: row %d names read %d, but lies in the rows [%d,%d) of read %d", what, row, w[0], a, b, win[(size_t)a * 5]);
+      if (row == a && use_ev && !read_events(*rd, &reads[r]))
+        return fail(h, RV_ESTATE, "%s: read %d has no event table on the device, which the positions of this mode need: give it with rv_read_put_events", what, w[0]);
+      chunks[(size_t)(row - r0)] = StChunk{w[1], w[2], w[3], w[4], r, row - a, b - a};
+    }
+  }
+
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+  hipStream_t s = h->copy_stream;
+  StitchScratch& t = h->st;
+  const int ntile = n / ST_THREADS + 1;
+  TRY(st_grow(h, &t.chunks, &t.cap_chunks, (size_t)n));
+  TRY(st_grow(h, &t.keep, &t.cap_keep, (size_t)n));
+  TRY(st_grow(h, &t.off, &t.cap_off, (size_t)n + 1));
+  TRY(st_grow(h, &t.tiles, &t.cap_tiles, (size_t)ntile));
+  TRY(st_grow(h, &t.reads, &t.cap_reads, reads.size()));
+  TRY(st_grow(h, &t.rows, &t.cap_rows, rows.size()));
+  TRY(st_grow(h, &t.read_off, &t.cap_read_off, rows.size()));
+  TRY(st_grow(h, &t.pin_read_off, &t.cap_pin, rows.size(), true));
+
+  // per-stage device times under option "profile" (scopes "stitch_*")
+  struct Stage { const char* name; hipEvent_t a, b; };
+  std::vector<Stage> stages;
+  const bool prof = h->opt.profile != 0;
+  auto stage = [&](const char* name, auto&& body) {
+    hipEvent_t a = nullptr, b = nullptr;
+    if (prof) { hipEventCreate(&a); hipEventCreate(&b); hipEventRecord(a, s); }
+    body();
+    if (prof) { hipEventRecord(b, s); stages.push_back({name, a, b}); }
+  };
+  auto drain = [&](int code) {      // (behind a synchronise of the stream, or on the way out of a failure)
+    for (Stage& g : stages) {
+      float ms = 0.f;
+      if (code == RV_OK && hipEventElapsedTime(&ms, g.a, g.b) == hipSuccess) { ProfEntry& e = h->prof[g.name]; e.ms += ms; e.n += 1; }
+      hipEventDestroy(g.a); hipEventDestroy(g.b);
+    }
+    stages.clear();
+    return code;
+  };
+#define STCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return drain(fail(h, RV_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__)); } while (0)
+
+  const size_t at = (size_t)r0 * din.stride;
+  din.bases += at; din.probs += at; din.raw_pos += at; din.raw_mass += at; din.event_pos += at; din.event_mass += at; din.lengths += r0;
+  din.n = n; din.mode = h->cfg.mode;
+  // (synchronous copies from these vectors, which go when the call returns: the stream's kernels are queued behind them)
+  if (n) STCHK(hipMemcpy(t.chunks, chunks.data(), sizeof(StChunk) * (size_t)n, hipMemcpyHostToDevice));
+  STCHK(hipMemcpy(t.reads, reads.data(), sizeof(StRead) * reads.size(), hipMemcpyHostToDevice));
+  STCHK(hipMemcpy(t.rows, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice));
+  stage("stitch_keep", [&]() { st_launch_keep(din, t.chunks, t.reads, t.keep, s); });
+  stage("stitch_scan", [&]() { st_launch_scan(t.keep, n, t.tiles, t.off, t.rows, n_reads, t.read_off, s); });
+  STCHK(hipGetLastError());
+  STCHK(hipMemcpyAsync(t.pin_read_off, t.read_off, sizeof(long long) * rows.size(), hipMemcpyDeviceToHost, s));
+  STCHK(hipStreamSynchronize(s));
+  const long long total = t.pin_read_off[n_reads];
+  for (int r = 0; r <= n_reads; ++r) out->read_offsets[r] = (int64_t)t.pin_read_off[r];
+  if (total < 0 || (size_t)total > out->capacity)
+    return drain(fail(h, RV_EINVAL, "%s: the reads hold %lld bases, the outputs have room for %zu", what, total, out->capacity));
+  if (total > 0) {
+    const size_t m = (size_t)total;
+    StOut o{};
+    if (out->bases) { if (int rc = st_grow(h, &t.o_bases, &t.cap_o_bases, m)) return drain(rc); o.bases = t.o_bases; }
+    float** of[3] = {&o.probs, &o.raw_mass, &o.event_mass};
+    float* const hf[3] = {out->probs, out->raw_mass, out->event_mass};
+    for (int i = 0; i < 3; ++i) if (hf[i]) { if (int rc = st_grow(h, &t.o_f[i], &t.cap_o_f[i], m)) return drain(rc); *of[i] = t.o_f[i]; }
+    if (out->positions) { if (int rc = st_grow(h, &t.o_pos, &t.cap_o_pos, m)) return drain(rc); o.positions = t.o_pos; }
+    int32_t** oi[2] = {&o.source_chunk, &o.source_index};
+    int32_t* const hi[2] = {out->source_chunk, out->source_index};
+    for (int i = 0; i < 2; ++i) if (hi[i]) { if (int rc = st_grow(h, &t.o_i[i], &t.cap_o_i[i], m)) return drain(rc); *oi[i] = t.o_i[i]; }
+    stage("stitch_scatter", [&]() { st_launch_scatter(din, t.chunks, t.reads, t.keep, t.off, o, s); });
+    STCHK(hipGetLastError());
+    if (o.bases) STCHK(hipMemcpyAsync(out->bases, o.bases, m, hipMemcpyDeviceToHost, s));
+    for (int i = 0; i < 3; ++i) if (hf[i]) STCHK(hipMemcpyAsync(hf[i], *of[i], sizeof(float) * m, hipMemcpyDeviceToHost, s));
+    if (o.positions) STCHK(hipMemcpyAsync(out->positions, o.positions, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    for (int i = 0; i < 2; ++i) if (hi[i]) STCHK(hipMemcpyAsync(hi[i], *oi[i], sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
+    STCHK(hipStreamSynchronize(s));
+  }
+#undef STCHK
+  return drain(RV_OK);
 }
 
 // One host image to the device (rv_load_weights), in pieces of 1 MiB: the runtime stages a copy from pageable memory of up to a few MiB
@@ -2456,8 +2696,10 @@ void rv_destroy(rv_handle h) {
   for (Read& r : h->reads) {
     if (r.owned) { if (r.d_raw) hipFree(r.d_raw); if (r.d_ev) hipFree(r.d_ev); }
     if (r.pin) hipHostFree(r.pin);
-    for (void* q : {(void*)r.d_est, (void*)r.d_eln, (void*)r.d_emu, (void*)r.d_esd, (void*)r.d_win}) if (q) hipFree(q);
+    for (void* q : {(void*)r.d_est, (void*)r.d_eln, (void*)r.d_emu, (void*)r.d_esd, (void*)r.d_win, (void*)r.d_xst, (void*)r.d_xln}) if (q) hipFree(q);
   }
+  for (RvStitchBuf* sb : h->stitch_bufs) free_stitch_buf(sb);
+  free_stitch_scratch(h);
   {
     SignalScratch& sp = h->sp;
     for (void* q : {(void*)sp.d_x, (void*)sp.ps, (void*)sp.pq, (void*)sp.t1, (void*)sp.t2, (void*)sp.bounds, (void*)sp.tile_sums, (void*)sp.var_part,
@@ -2631,14 +2873,21 @@ static int submit(rv_handle h, const Call& call, int32_t* ticket) {
   *ticket = ctx->pend.ticket;
   return RV_OK;
 }
+static void release_stitch(RvContext* h, int ticket) {
+  auto it = h->stitch_tickets.find(ticket);
+  if (it == h->stitch_tickets.end()) return;
+  it->second->tickets -= 1;
+  h->stitch_tickets.erase(it);
+}
 static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, const CallsOut* calls, int32_t* S_out, const RvBeams* beams = nullptr,
-                   const RvMoves* moves = nullptr, const RvCallMoves* cmoves = nullptr) {
+                   const RvMoves* moves = nullptr, const RvCallMoves* cmoves = nullptr, bool stitch = false) {
   if (!h || !S_out) return RV_EINVAL;
   const int slot = ticket & 15;
   if (ticket >= 0 && h->ticks[slot].busy && h->ticks[slot].ticket == ticket) {
     if (moves) return fail(h, RV_EINVAL, "rv_beam_search_collect_moves takes the tickets of rv_beam_search_submit_moves");
     if (cmoves) return fail(h, RV_EINVAL, "rv_beam_search_collect_calls_moves takes the tickets of rv_beam_search_submit_windows_calls_moves");
     if (beams) return fail(h, RV_EINVAL, "rv_beam_search_collect_all takes the tickets of rv_beam_search_submit_all");      // (a group never holds one)
+    if (stitch) return fail(h, RV_EINVAL, "rv_beam_search_collect_stitch takes the tickets of rv_beam_search_submit_windows_stitch");
     const int rc = collect_group(h, slot, tokens, out2, calls, S_out);
     if (!(h->ticks[slot].busy && h->ticks[slot].ticket == ticket)) release_reads(h, ticket);      // (the ticket is gone: its reads may be dropped)
     return rc;
@@ -2646,8 +2895,8 @@ static int collect(rv_handle h, int32_t ticket, int32_t* tokens, float* out2, co
   if (ticket < 0 || slot >= (int)h->slabs.size()) return fail(h, RV_EINVAL, "unknown ticket %d", ticket);
   SlabCtx* ctx = h->slabs[slot];
   if (!ctx->pend.busy || ctx->pend.ticket != ticket) return fail(h, RV_ESTATE, "ticket %d is not in flight (collected already?)", ticket);
-  const int rc = finish(ctx, tokens, out2, calls, S_out, beams, moves, cmoves);
-  if (!(ctx->pend.busy && ctx->pend.ticket == ticket)) release_reads(h, ticket);
+  const int rc = finish(ctx, tokens, out2, calls, S_out, beams, moves, cmoves, stitch);
+  if (!(ctx->pend.busy && ctx->pend.ticket == ticket)) { release_reads(h, ticket); release_stitch(h, ticket); }
   return rc;
 }
 int rv_beam_search_submit(rv_handle h, const float* raw, const float* event, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
@@ -2851,6 +3100,96 @@ int rv_beam_search_collect_calls_moves(rv_handle h, int32_t ticket, uint8_t* bas
   if (!moves) return fail(h, RV_EINVAL, "null output pointer");      // (all six null: refused at the ticket, which knows whether anything ran)
   const CallsOut c{nullptr, bases, lengths, probs};
   return collect(h, ticket, nullptr, nullptr, &c, S_out, nullptr, nullptr, moves);
+}
+
+// ---- stitching by signal position (stitch.hip)
+int rv_read_put_events(rv_handle h, int32_t read_id, const int64_t* start, const int64_t* length, size_t n_event) {
+  return put_events(h, read_id, start, length, n_event);
+}
+int rv_stitch_calls(rv_handle h, const RvStitchIn* in, int32_t n_reads, const int32_t* read_rows, const RvStitchOut* out) {
+  if (!h) return RV_EINVAL;
+  if (!in || in->n < 0) return fail(h, RV_EINVAL, "rv_stitch_calls: null input or negative n");
+  if (in->stride < 0 || in->stride > ST_LANES) return fail(h, RV_EINVAL, "rv_stitch_calls: row stride %d outside [0,%d]", in->stride, ST_LANES);
+  const size_t n = (size_t)in->n, cells = n * (size_t)in->stride;
+  if (n > 0 && (!in->lengths || !in->win)) return fail(h, RV_EINVAL, "rv_stitch_calls: null lengths or window table");
+  if (cells > 0 && (!in->bases || !in->probs || !in->raw_pos || !in->raw_mass || !in->event_pos || !in->event_mass))
+    return fail(h, RV_EINVAL, "rv_stitch_calls: null input array");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  // the tables go up into the handle's stitch scratch (synchronous copies: the caller's arrays are free on return)
+  StitchScratch& t = h->st;
+  TRY(st_grow(h, &t.in_bases, &t.cap_in_bases, cells));
+  TRY(st_grow(h, &t.in_len, &t.cap_in_len, n));
+  const float* const src[5] = {in->probs, in->raw_pos, in->raw_mass, in->event_pos, in->event_mass};
+  for (int i = 0; i < 5; ++i) TRY(st_grow(h, &t.in_f[i], &t.cap_in_f[i], cells));
+  if (cells) {
+    HIPCHK(h, hipMemcpy(t.in_bases, in->bases, cells, hipMemcpyHostToDevice));
+    for (int i = 0; i < 5; ++i) HIPCHK(h, hipMemcpy(t.in_f[i], src[i], cells * sizeof(float), hipMemcpyHostToDevice));
+  }
+  if (n) HIPCHK(h, hipMemcpy(t.in_len, in->lengths, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  StIn d{t.in_bases, t.in_f[0], t.in_len, t.in_f[1], t.in_f[2], t.in_f[3], t.in_f[4], 0, 0, 0};
+  d.n = in->n; d.stride = in->stride;
+  return stitch_core(h, d, in->win, n_reads, read_rows, out, "rv_stitch_calls");
+}
+int rv_stitch_open(rv_handle h, int32_t n_chunks, int32_t L, rv_stitch* sb_out) {
+  if (!h || !sb_out) return RV_EINVAL;
+  *sb_out = nullptr;
+  if (n_chunks < 0) return fail(h, RV_EINVAL, "rv_stitch_open: n_chunks=%d is negative", n_chunks);
+  if (L < 1 || L > h->cfg.max_output_len) return fail(h, RV_EINVAL, "max_output_len=%d outside [1,%d]", L, h->cfg.max_output_len);
+  if (L - 1 > ST_LANES) return fail(h, RV_EUNSUPPORTED, "max_output_len %d exceeds %d", L, ST_LANES + 1);
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  RvStitchBuf* sb = new RvStitchBuf();
+  sb->n = n_chunks; sb->L = L; sb->steps = L - 1;
+  sb->win.assign((size_t)n_chunks * 5, -1);
+  const size_t cells = std::max<size_t>((size_t)n_chunks * sb->steps, 1), rows = std::max<size_t>((size_t)n_chunks, 1);
+  bool ok = hipMalloc((void**)&sb->bases, cells) == hipSuccess && hipMalloc((void**)&sb->probs, cells * 4) == hipSuccess &&
+            hipMalloc((void**)&sb->lens, rows * 4) == hipSuccess;
+  for (int i = 0; i < 4 && ok; ++i) ok = hipMalloc((void**)&sb->mv[i], cells * 4) == hipSuccess;
+  // (rows that only a slab without steps, L == 1, writes: no letters)
+  ok = ok && hipMemset(sb->lens, 0, rows * 4) == hipSuccess;
+  if (!ok) { free_stitch_buf(sb); return fail(h, RV_ENOMEM, "rv_stitch_open: device tables of %d rows: %s", n_chunks, hipGetErrorString(hipGetLastError())); }
+  h->stitch_bufs.push_back(sb);
+  *sb_out = sb;
+  return RV_OK;
+}
+int rv_stitch_close(rv_handle h, rv_stitch sb) {
+  if (!h) return RV_EINVAL;
+  RvStitchBuf* k = find_stitch_buf(h, sb);
+  if (!k) return fail(h, RV_EINVAL, "rv_stitch_close: not a stitch buffer of this handle");
+  if (k->tickets > 0) return fail(h, RV_ESTATE, "rv_stitch_close: %d uncollected ticket(s) write into this stitch buffer: collect them first", k->tickets);
+  h->stitch_bufs.erase(std::find(h->stitch_bufs.begin(), h->stitch_bufs.end(), k));
+  hipSetDevice(h->cfg.device);
+  free_stitch_buf(k);
+  return RV_OK;
+}
+int rv_beam_search_submit_windows_stitch(rv_handle h, const int32_t* win, int32_t B, int32_t T_r, int32_t T_e, int32_t W, int32_t L,
+                                         const uint8_t* lut, rv_stitch sb, int32_t row0, int32_t* ticket) {
+  if (!lut) return h ? fail(h, RV_EINVAL, "null lut") : RV_EINVAL;
+  std::vector<RecWindow> rows; std::vector<int> ids; Call c;
+  TRY(windows_call(h, win, B, T_r, T_e, W, L, rows, ids, c));
+  RvStitchBuf* k = find_stitch_buf(h, sb);
+  if (!k) return fail(h, RV_EINVAL, "rv_beam_search_submit_windows_stitch: not a stitch buffer of this handle");
+  if (L != k->L) return fail(h, RV_EINVAL, "max_output_len=%d, but the stitch buffer was opened for %d", L, k->L);
+  if (row0 < 0 || (long long)row0 + B > (long long)k->n)
+    return fail(h, RV_EINVAL, "rows [%d,%lld) lie outside the stitch buffer's %d rows", row0, (long long)row0 + B, k->n);
+  c.lut = lut; c.want_call_moves = true; c.stitch = k; c.stitch_row0 = row0;
+  TRY(submit(h, c, ticket));
+  hold_reads(h, *ticket, ids);
+  h->stitch_tickets[*ticket] = k;
+  k->tickets += 1;
+  if (B > 0) memcpy(k->win.data() + (size_t)row0 * 5, win, sizeof(int32_t) * 5 * (size_t)B);
+  return RV_OK;
+}
+int rv_beam_search_collect_stitch(rv_handle h, int32_t ticket, int32_t* S_out) {
+  if (!h) return RV_EINVAL;
+  return collect(h, ticket, nullptr, nullptr, nullptr, S_out, nullptr, nullptr, nullptr, true);
+}
+int rv_stitch_run(rv_handle h, rv_stitch sb, int32_t n_reads, const int32_t* read_rows, const RvStitchOut* out) {
+  if (!h) return RV_EINVAL;
+  RvStitchBuf* k = find_stitch_buf(h, sb);
+  if (!k) return fail(h, RV_EINVAL, "rv_stitch_run: not a stitch buffer of this handle");
+  if (k->tickets > 0) return fail(h, RV_ESTATE, "rv_stitch_run: %d uncollected ticket(s) write into this stitch buffer: collect them first", k->tickets);
+  StIn d{k->bases, k->probs, k->lens, k->mv[0], k->mv[1], k->mv[2], k->mv[3], k->n, k->steps, 0};
+  return stitch_core(h, d, k->win.data(), n_reads, read_rows, out, "rv_stitch_run");
 }
 
 // ---- forced alignment: the forced decode with its records kept, k_forced_moves behind the finalize
